@@ -2,17 +2,24 @@
 """bench.py -- ADMM iterations/sec of the HIP engine on BASELINE.json's workload.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rand-1e6|rand-1e5|lasso-5e5|control-1e6|mpc-batch]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one ADMM iteration of the hot path (rhs build, KKT solve by the back-end the workload needs, fused
 x/z/y update, residual evaluation every `check_termination` = 25 iterations) on a synthetic QP generated in HBM
 before the timed region.  Protocol: W untimed warm-up iterations from the cold start, then exactly K timed ones
 between barrier + synchronize, MAX over ranks, one JSON line from rank 0.
 
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (`--dump-outputs DIR`: what the timed
+path computed in its last step -- the iterate x, y in the caller's units, or the packed x / y / info rows of the
+batch -- as DIR/<name>.npy in float64; inputs are seeded, so two builds can be compared output for output) and the
+line.  Everything else -- the time-to-eps solve, the single-QP roofline and PMC traffic, the CPU baselines, the other
+workloads beside rand-1e6 and, at N > 1, the `batch` / `sharded` legs below -- runs with `--full` only.
+
 Launch.  One process per GPU.  Under `torch.distributed.run` (RANK / WORLD_SIZE in the environment) this process is
 one rank.  Started plainly with `--gpus N`, N > 1, it SPAWNS the N ranks itself (one child per device, RCCL
 rendezvous on 127.0.0.1, a free port) and relays rank 0's line -- `python bench.py --gpus 8` is an 8-GPU run.
 
-At N > 1 the line carries three multi-GPU legs:
+At N > 1 a `--full` line carries three multi-GPU legs:
   * headline `value`: replicas -- every rank owns an independent QP (seed 1 + rank), no data-path collective, one
     final gather of the per-instance results (weak scaling);
   * `batch`: BASELINE.json config 5 -- 4096 MPC QPs (n = 100, m = 200) cut into contiguous blocks
@@ -26,9 +33,9 @@ At N > 1 the line carries three multi-GPU legs:
   processes of their own (their own process groups on the next ports, a time limit) so that neither an exception nor a
   hang in a transport can take the headline numbers with it.  `--mode sharded|batch` promotes a leg to the headline.
 
-The line carries `roofline` for the dominant kernel (measured live with HIP events on the engine's stream; `traffic`
-from FETCH_SIZE / WRITE_SIZE collected live by two rocprofv3 --pmc passes over a child of this script) and
-`cpu_baseline` (the CPU oracle on the host cores).
+A `--full` line carries `roofline` for the dominant kernel (measured live with HIP events on the engine's stream;
+`traffic` from FETCH_SIZE / WRITE_SIZE collected live by two rocprofv3 --pmc passes over a child of this script) and
+`cpu_baseline` (the CPU oracle on the host cores; `--cpu-full` re-measures rand-1e6 itself, about 10 minutes).
 """
 import argparse
 import glob
@@ -98,6 +105,26 @@ def protocol_sha16(workload, warm, iters):
     return hashlib.sha256(blob.encode()).hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 60 << 20  # under 64 MB with room for the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64.  Past DUMP_LIMIT_BYTES in all, every array is cut to the same
+    fixed, seeded sample of its flat entries (and <name>_index.npy says which)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    share = sum(a.nbytes for a in arrays.values()) / DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        if share > 1.0:
+            keep = int(a.size / share) // 2  # the index file takes as much room as the values
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -116,17 +143,27 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-full", action="store_true",
                     help="re-measure the CPU oracle on rand-1e6 itself at the driver's window (W = 5, K = 20) in a child process and rewrite "
-                         "the committed record (about 10 minutes and 46 GiB of host memory)")
+                         "the committed record (about 10 minutes and 46 GiB of host memory); implies --full")
     ap.add_argument("--mode", choices=["replicas", "sharded", "batch"], default=os.environ.get("OSQP_AMD_BENCH_MODE", "replicas"),
                     help="which multi-GPU leg is the headline value (all are measured when N > 1)")
     ap.add_argument("--no-sharded", action="store_true", help="skip the row-sharded leg")
     ap.add_argument("--no-batch", action="store_true", help="skip the sharded mpc-batch leg at N > 1")
     ap.add_argument("--traffic", choices=["live", "file", "off"], default=os.environ.get("OSQP_AMD_BENCH_TRAFFIC", "live"),
                     help="roofline.traffic: two live rocprofv3 --pmc passes (default), the committed profiles/pmc_traffic.json, or none")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps: time-to-eps solve, the single-QP roofline + PMC traffic, CPU baselines, "
+                         "other workloads, the batch / sharded legs at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--child", choices=["sharded", "batch", "pmc"], default=None, help=argparse.SUPPRESS)  # internal legs
     ap.add_argument("--one-gpu-its", type=float, default=0.0, help=argparse.SUPPRESS)
     ap.add_argument("--spawn-check", action="store_true", help=argparse.SUPPRESS)  # launch logic only (no GPU): CPU test hook
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.cpu_full:
+        args.full = True  # the CPU record is part of the --full line
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -228,7 +265,7 @@ def main():
         return
 
     if args.workload == "mpc-batch":
-        rec = batch_leg(ctx, want_cpu=(not args.no_cpu and world == 1))
+        rec = batch_leg(ctx, want_cpu=(args.full and not args.no_cpu and world == 1))
         if rank == 0:
             line = batch_line(args, world, rec)
             line["device"] = device_identity(torch, local_rank)
@@ -295,11 +332,12 @@ def build_model(oq, lib, workload, seed, oracle=False):
 def start_cpu_full(args, rank, world):
     """The CPU oracle on the headline workload ITSELF, in this run: started as a child process before the GPU legs (one host
     thread and ~46 GiB against the GPU's work: different resources), collected by cpu_leg with a 20-minute cap.  Only when
-    the host can afford it (>= 64 GiB available) and OSQP_AMD_BENCH_CPU_FULL is not 0; otherwise the committed record."""
+    asked for (--cpu-full or OSQP_AMD_BENCH_CPU_FULL=1: about 10 minutes) and the host can afford it (>= 64 GiB
+    available); otherwise the committed record."""
     if rank != 0 or world != 1 or args.no_cpu or args.child is not None or args.workload not in CPU_RECORDS:
         return None
-    if os.environ.get("OSQP_AMD_BENCH_CPU_FULL", "1") == "0" and not getattr(args, "cpu_full", False):
-        return {"proc": None, "reason": "OSQP_AMD_BENCH_CPU_FULL=0"}
+    if os.environ.get("OSQP_AMD_BENCH_CPU_FULL", "0") != "1" and not getattr(args, "cpu_full", False):
+        return {"proc": None, "reason": "not asked for (--cpu-full)"}
     try:
         avail = [int(l.split()[1]) for l in open("/proc/meminfo") if l.startswith("MemAvailable")][0] / 1048576.0
     except Exception:
@@ -322,7 +360,7 @@ def start_cpu_full(args, rank, world):
 
 def replica_bench(ctx):
     args, oq, lib, torch, dist, rank, world = (ctx[k] for k in ("args", "oq", "lib", "torch", "dist", "rank", "world"))
-    ctx["cpu_full"] = start_cpu_full(args, rank, world)
+    ctx["cpu_full"] = start_cpu_full(args, rank, world) if args.full else None
     model, n, setup_s = build_model(oq, lib, args.workload, 1 + rank)
     ws = model.workspace
 
@@ -350,87 +388,42 @@ def replica_bench(ctx):
         dist.all_reduce(ones)  # how many ranks the collective library really connected
         collective_ranks_seen = int(ones.item())
     cg_per_admm = (st1[6] - st0[6]) / max(args.steps, 1)
-
-    # time-to-eps: a full cold-start solve to eps_abs = eps_rel = 1e-4
-    oq.update_settings(model, warm_start=0)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = oq.solve(model)
-    torch.cuda.synchronize()
-    solve_s = time.perf_counter() - t0
-    st2 = oq.stats(model)
-
-    # roofline of the dominant kernel, measured live with HIP events on the engine's stream
-    st = st2
-    nnzA, nnzPf = st[1], st[2]
-    pmc_names = []
-    if st[0] == 2:   # indirect back-end: SpMV y = A x
-        variant = int(st[12]) if len(st) > 12 else 0
-        kname = ["k_spmv<G> (CSR, y = A x)", "k_spmv_panel (LDS-staged x panels, y = A x)", "k_spmv_sell + k_panel_reduce (LDS-staged x panels, sliced-ELL tiles, y = A x)",
-                 "k_spmv_sell + k_panel_reduce (wide x panels through L2, sliced-ELL tiles, y = A x)"][variant]
-        pmc_names = ["k_spmv_sell", "k_panel_reduce"] if variant >= 2 else ["k_spmv"]
-        which, abytes = 0, st[10]
-    else:            # direct back-end: the kernels of one iteration (right-hand side | triangular solves | update, fused as the factor allows)
-        kname, which = "direct ADMM iteration: rhs + forward | backward + update around the LDL' factor (k_direct2_fwd + k_direct2_bwd_update on a two-level factor)", 5
-        abytes = st[11] + 8.0 * (6 * n + 12 * int(oq.dimensions(model)[1]))  # trisolve bytes + the vector updates
-        pmc_names = ["k_direct2_fwd", "k_direct2_bwd_update"]  # the two-launch iteration of a two-level factor
-        if int(st[19]) > 0:  # supernodal solves: right-hand side | level 0 | tree (forward, backward) | level 0 | update
-            kname = ("direct ADMM iteration on a supernodal factor: k_direct_rhs | k_sn_level_w / _wf / _f forward (levels below the tree launch) | "
-                     "k_sn_tree forward | k_sn_tree backward | k_sn_level_f / _wf / _w + k_sn_single_bwd backward | k_direct_update")
-            pmc_names = {"sum": ["k_direct_rhs", "k_sn_level", "k_sn_single", "k_sn_tree", "k_direct_update"], "per": "k_direct_rhs"}
-    ms = float(lib.osqp_amd_time_kernel(ws, which, 20))
-    achieved = abytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    roofline = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "traffic_source": None, "ms_per_launch": round(ms, 4),
-                "algorithmic_bytes_per_launch": abytes}
-    # the whole step against the same peak: SURVEY.md 8d bytes of one ADMM iteration / measured time per step
-    step_bytes = step_algorithmic_bytes(st, n, int(oq.dimensions(model)[1]), cg_per_admm)
-    roofline["step"] = {"algorithmic_bytes_per_step": step_bytes, "achieved": round(step_bytes / (elapsed / args.steps) / 1e9, 1),
-                        "frac": round(step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                        "formula": "SURVEY.md 8d B_iter with the measured CG iterations per ADMM iteration"}
-
-    # final gather of per-instance results (the only collective of the replica leg)
-    summary = torch.tensor([float(res.info.iter), float(res.info.status_val), res.info.pri_res, res.info.dua_res,
-                            res.info.obj_val, solve_s], dtype=torch.float64, device="cuda")
-    if world > 1:
-        gathered = [torch.zeros_like(summary) for _ in range(world)]
-        dist.all_gather(gathered, summary)
-        summaries = [g.cpu().tolist() for g in gathered]
-    else:
-        summaries = [summary.cpu().tolist()]
+    m = int(oq.dimensions(model)[1])
+    if args.dump_outputs and rank == 0 and (world == 1 or args.mode == "replicas"):  # rank 0's instance after the last timed step
+        dump_outputs(args.dump_outputs, dict(zip(("x", "y"), get_iterate(oq, lib, model))))
 
     its_per_s = args.steps * world / elapsed
     out = None
     if rank == 0:
+        st = st1
         out = {
             "metric": "ADMM iterations/sec", "value": round(its_per_s, 3), "unit": "iterations/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": args.workload, "n": n, "m": int(oq.dimensions(model)[1]), "nnz_A": int(nnzA),
-                       "nnz_P_full": int(nnzPf), "nnz_P_triu": int(st[3]), "backend": "pcg" if st[0] == 2 else "direct-ldl",
+            "config": {"workload": args.workload, "n": n, "m": m, "nnz_A": int(st[1]),
+                       "nnz_P_full": int(st[2]), "nnz_P_triu": int(st[3]), "backend": "pcg" if st[0] == 2 else "direct-ldl",
                        "eps_abs": 1e-4, "eps_rel": 1e-4, "check_termination": 25, "adaptive_rho_interval": 50,
                        "instances": world, "sharding": "one independent QP per GPU, final gather of the per-instance results"},
             "cg_iters_per_admm_iter": round(cg_per_admm, 3),
-            "time_to_eps_s": round(solve_s, 4), "iters_to_eps": int(res.info.iter), "status": res.info.status,
-            "cg_iters_to_eps": int(st2[6] - st1[6]),
-            "pri_res": res.info.pri_res, "dua_res": res.info.dua_res, "rho_updates": int(res.info.rho_updates),
             "setup_s": round(setup_s, 3), "device_gb": round(st[9] / 1e9, 2), "device_peak_gb": round(st[20] / 1e9, 2),
-            # the reference reports run_time = setup + solve [REF src/types.jl:92-96]: the same solve priced on that clock
-            "run_time_s": round(setup_s + solve_s, 4), "iterations_per_s_incl_setup": round(res.info.iter / (setup_s + solve_s), 3),
-            "per_rank": summaries, "collective_ranks_seen": collective_ranks_seen, "collective_backend": ctx["backend"] if world > 1 else None, "launch": "self-spawned" if os.environ.get("OSQP_AMD_BENCH_SPAWNED") == "1" else ("torchrun" if world > 1 else "single process"),
-            "roofline": roofline, "cpu_baseline": None,
+            "collective_ranks_seen": collective_ranks_seen, "collective_backend": ctx["backend"] if world > 1 else None, "launch": "self-spawned" if os.environ.get("OSQP_AMD_BENCH_SPAWNED") == "1" else ("torchrun" if world > 1 else "single process"),
         }
+    st, pmc_names = st1, []
+    if args.full:
+        full, st, pmc_names = replica_full(ctx, model, n, m, setup_s, elapsed, cg_per_admm, st1)
+        if rank == 0:
+            out.update(full)
 
     oq.clean(model)  # the replica's memory goes before any other leg is built
     del model
 
     if rank == 0:
         out["device"] = device_identity(torch, ctx["local_rank"])
-    if rank == 0 and world == 1 and args.child is None and args.workload == "rand-1e6" and os.environ.get("OSQP_AMD_BENCH_OTHERS", "1") != "0":
+    if args.full and rank == 0 and world == 1 and args.child is None and args.workload == "rand-1e6" and os.environ.get("OSQP_AMD_BENCH_OTHERS", "1") != "0":
         out["other_workloads"] = other_workloads(ctx)
 
-    if rank == 0 and world == 1 and args.traffic != "off" and pmc_names:
+    if args.full and rank == 0 and world == 1 and args.traffic != "off" and pmc_names:
         tr, src = (None, None)
         if args.traffic == "live":
             tr, src = live_traffic(args, pmc_names)
@@ -438,15 +431,15 @@ def replica_bench(ctx):
             tr, src = file_traffic(args)
         out["roofline"]["traffic"], out["roofline"]["traffic_source"] = tr, src
 
-    if rank == 0 and not args.no_cpu and world == 1:  # the CPU leg belongs to the 1-GPU line only
+    if args.full and rank == 0 and not args.no_cpu and world == 1:  # the CPU leg belongs to the 1-GPU line only
         out["cpu_baseline"] = cpu_leg(oq, args, ctx.get("cpu_full"))
         out["cpu_baseline"]["all_cores_bandwidth_bound"] = all_cores_bound(out["roofline"]["step"]["algorithmic_bytes_per_step"])
 
     if world > 1:
         legs = []
-        if not args.no_batch:
+        if not args.no_batch and (args.full or args.mode == "batch"):
             legs.append(("batch", 1))
-        if st[0] == 2 and not args.no_sharded:
+        if st[0] == 2 and not args.no_sharded and (args.full or args.mode == "sharded"):
             legs.append(("sharded", 2))
         for name, port_offset in legs:
             rec = run_child_leg(args, rank, name, port_offset, its_per_s / world)
@@ -468,6 +461,83 @@ def replica_bench(ctx):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def get_iterate(oq, lib, model):
+    """The current iterate (x, y) in the caller's units, without touching it (osqp_amd_get_iterate)."""
+    import ctypes
+    import numpy as np
+
+    n, m = (int(v) for v in oq.dimensions(model))
+    x, y = np.empty(n), np.empty(m)
+    ptr = ctypes.POINTER(ctypes.c_double)
+    assert lib.osqp_amd_get_iterate(model.workspace, x.ctypes.data_as(ptr), y.ctypes.data_as(ptr)) == 0
+    return x, y
+
+
+def replica_full(ctx, model, n, m, setup_s, elapsed, cg_per_admm, st1):
+    """--full on the replica leg: the time-to-eps solve, the roofline of the dominant kernel and the per-rank summaries.
+    Returns (fields for rank 0's line, the stats after the solve, the kernel names of the PMC passes)."""
+    args, oq, lib, torch, dist, world = (ctx[k] for k in ("args", "oq", "lib", "torch", "dist", "world"))
+    ws = model.workspace
+
+    # time-to-eps: a full cold-start solve to eps_abs = eps_rel = 1e-4
+    oq.update_settings(model, warm_start=0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = oq.solve(model)
+    torch.cuda.synchronize()
+    solve_s = time.perf_counter() - t0
+    st2 = oq.stats(model)
+
+    # roofline of the dominant kernel, measured live with HIP events on the engine's stream
+    st = st2
+    pmc_names = []
+    if st[0] == 2:   # indirect back-end: SpMV y = A x
+        variant = int(st[12]) if len(st) > 12 else 0
+        kname = ["k_spmv<G> (CSR, y = A x)", "k_spmv_panel (LDS-staged x panels, y = A x)", "k_spmv_sell + k_panel_reduce (LDS-staged x panels, sliced-ELL tiles, y = A x)",
+                 "k_spmv_sell + k_panel_reduce (wide x panels through L2, sliced-ELL tiles, y = A x)"][variant]
+        pmc_names = ["k_spmv_sell", "k_panel_reduce"] if variant >= 2 else ["k_spmv"]
+        which, abytes = 0, st[10]
+    else:            # direct back-end: the kernels of one iteration (right-hand side | triangular solves | update, fused as the factor allows)
+        kname, which = "direct ADMM iteration: rhs + forward | backward + update around the LDL' factor (k_direct2_fwd + k_direct2_bwd_update on a two-level factor)", 5
+        abytes = st[11] + 8.0 * (6 * n + 12 * m)  # SURVEY.md 8d: trisolve bytes + the vector updates
+        pmc_names = ["k_direct2_fwd", "k_direct2_bwd_update"]  # the two-launch iteration of a two-level factor
+        if int(st[19]) > 0:  # supernodal solves: right-hand side | level 0 | tree (forward, backward) | level 0 | update
+            kname = ("direct ADMM iteration on a supernodal factor: k_direct_rhs | k_sn_level_w / _wf / _f forward (levels below the tree launch) | "
+                     "k_sn_tree forward | k_sn_tree backward | k_sn_level_f / _wf / _w + k_sn_single_bwd backward | k_direct_update")
+            pmc_names = {"sum": ["k_direct_rhs", "k_sn_level", "k_sn_single", "k_sn_tree", "k_direct_update"], "per": "k_direct_rhs"}
+    ms = float(lib.osqp_amd_time_kernel(ws, which, 20))
+    achieved = abytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+    roofline = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "traffic_source": None, "ms_per_launch": round(ms, 4),
+                "algorithmic_bytes_per_launch": abytes}
+    # the whole step against the same peak: SURVEY.md 8d bytes of one ADMM iteration / measured time per step
+    step_bytes = step_algorithmic_bytes(st, n, m, cg_per_admm)
+    roofline["step"] = {"algorithmic_bytes_per_step": step_bytes, "achieved": round(step_bytes / (elapsed / args.steps) / 1e9, 1),
+                        "frac": round(step_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                        "formula": "SURVEY.md 8d B_iter with the measured CG iterations per ADMM iteration"}
+
+    # final gather of per-instance results (the only collective of the replica leg)
+    summary = torch.tensor([float(res.info.iter), float(res.info.status_val), res.info.pri_res, res.info.dua_res,
+                            res.info.obj_val, solve_s], dtype=torch.float64, device="cuda")
+    if world > 1:
+        gathered = [torch.zeros_like(summary) for _ in range(world)]
+        dist.all_gather(gathered, summary)
+        summaries = [g.cpu().tolist() for g in gathered]
+    else:
+        summaries = [summary.cpu().tolist()]
+
+    full = {
+        "time_to_eps_s": round(solve_s, 4), "iters_to_eps": int(res.info.iter), "status": res.info.status,
+        "cg_iters_to_eps": int(st2[6] - st1[6]),
+        "pri_res": res.info.pri_res, "dua_res": res.info.dua_res, "rho_updates": int(res.info.rho_updates),
+        "device_gb": round(st[9] / 1e9, 2), "device_peak_gb": round(st[20] / 1e9, 2),
+        # the reference reports run_time = setup + solve [REF src/types.jl:92-96]: the same solve priced on that clock
+        "run_time_s": round(setup_s + solve_s, 4), "iterations_per_s_incl_setup": round(res.info.iter / (setup_s + solve_s), 3),
+        "per_rank": summaries, "roofline": roofline, "cpu_baseline": None,
+    }
+    return full, st, pmc_names
 
 
 def kernel_roofline(oq, lib, model, n, st):
@@ -527,7 +597,7 @@ def other_workloads(ctx):
             continue
         try:
             if name == "mpc-batch":
-                rec = batch_leg(ctx, want_cpu=False, traffic=False)
+                rec = batch_leg(ctx, want_cpu=False, traffic=False, dump=False)
                 out[name] = {k: rec[k] for k in ("value", "unit", "ms_per_step", "instances", "instances_per_s", "mean_iters_per_instance", "solved")}
                 out[name]["roofline"] = {"bound": "lds", "frac": rec["roofline"]["frac"], "fp64_tflops": rec["roofline"]["fp64"]["achieved_tflops"]}
             else:
@@ -684,6 +754,8 @@ def run_child_leg(args, rank, leg, port_offset, one_gpu_its, limit_s=300.0):
     env["MASTER_PORT"] = str(int(os.environ.get("MASTER_PORT", "29500")) + port_offset)
     cmd = [sys.executable, os.path.abspath(__file__), "--child", leg, "--one-gpu-its", repr(float(one_gpu_its)), "--workload", args.workload,
            "--steps", str(args.steps), "--warmup", str(args.warmup), "--gpus", str(args.gpus), "--no-cpu"]
+    if args.dump_outputs and args.mode == leg:  # the headline's outputs come from this leg
+        cmd += ["--dump-outputs", args.dump_outputs]
     try:
         p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=limit_s)
     except subprocess.TimeoutExpired:
@@ -752,6 +824,10 @@ def sharded_leg(ctx, kind, n, per_row, one_gpu_its):
     tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed = float(tt.item())
+    if args.dump_outputs:  # every rank takes part in assembling the full iterate; rank 0 writes it
+        x, y = get_iterate(oq, lib, model)
+        if ctx["rank"] == 0:
+            dump_outputs(args.dump_outputs, {"x": x, "y": y})
     oq.update_settings(model, warm_start=0)
     barrier()
     t0 = time.perf_counter()
@@ -782,7 +858,7 @@ def sharded_leg(ctx, kind, n, per_row, one_gpu_its):
     return rec
 
 
-def batch_leg(ctx, want_cpu, traffic=True):
+def batch_leg(ctx, want_cpu, traffic=True, dump=True):
     """BASELINE.json config 5: 4096 independent MPC QPs (n = 100, m = 200) cut into contiguous blocks over the ranks
     (instance i -> rank floor(i / (4096 / N))), resident in HBM; a step = one solve of the whole batch: every rank its
     block, one workgroup per QP, then ONE in-place all-gather of the packed [x | y | info] rows on the library's own
@@ -800,8 +876,8 @@ def batch_leg(ctx, want_cpu, traffic=True):
             dist.barrier()
         torch.cuda.synchronize()
 
-    steps, warm = max(args.steps, 1), max(args.warmup, 1)
-    for _ in range(min(warm, 5)):
+    steps = args.steps
+    for _ in range(args.warmup):
         b.solve(packed)
     barrier()
     t0 = time.perf_counter()
@@ -814,6 +890,8 @@ def batch_leg(ctx, want_cpu, traffic=True):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     x, y, info = batch.split_packed(packed.numpy())  # the packed array is the library's own allocation (no torch on this path)
+    if dump and args.dump_outputs and rank == 0:  # the whole gathered batch after the last timed solve
+        dump_outputs(args.dump_outputs, {"x": x, "y": y, "info": info})
     iters = float(info[:, 0].sum())
     import hashlib
     packed_sha16 = hashlib.sha256(packed.numpy().tobytes()).hexdigest()[:16]  # the gathered batch, bit for bit (equal for every world size)
@@ -858,7 +936,7 @@ def batch_leg(ctx, want_cpu, traffic=True):
     if want_cpu:
         rec["cpu_baseline"] = batch_cpu_leg(oq, args)
     b.close()
-    if traffic and rank == 0 and world == 1 and args.child is None and args.traffic == "live":  # HBM bytes of one launch, two --pmc passes over a child
+    if traffic and args.full and rank == 0 and world == 1 and args.child is None and args.traffic == "live":  # HBM bytes of one launch, two --pmc passes over a child
         tr, src = live_traffic(args, ["k_batch_solve" if os.environ.get("OSQP_AMD_BATCH_QUAD") == "0" else "k_batch_quad"])
         rec["roofline"]["traffic"], rec["roofline"]["traffic_source"] = tr, src
     if comm is not None:
@@ -909,7 +987,8 @@ def batch_cpu_leg(oq, args):
            "instances_per_s": round(k / spent, 2)}
     cores = usable_cores()[0]
     try:
-        with mp.get_context("fork").Pool(cores) as pool:
+        # fresh worker processes: forked ones would each inherit this process's open GPU device
+        with mp.get_context("spawn").Pool(cores) as pool:
             res = pool.map(_batch_cpu_worker, [(r, cores, args.cpu_seconds / 2.0, opts) for r in range(cores)])
         kk, ii, tmax = sum(r[0] for r in res), sum(r[1] for r in res), max(r[2] for r in res)
         out["all_cores"] = {"cores": cores, "host_cores": os.cpu_count(), "cgroup_cpu_quota": usable_cores()[1],
@@ -1022,7 +1101,8 @@ def host_stream_gbs(cores=None, n=8_000_000, reps=12):
 
     cores = cores or usable_cores()[0]
     try:
-        with mp.get_context("fork").Pool(cores) as pool:
+        # fresh worker processes: forked ones would each inherit this process's open GPU device
+        with mp.get_context("spawn").Pool(cores) as pool:
             res = pool.map(_stream_worker, [(n, reps)] * cores)
         return sum(r[0] for r in res) / max(r[1] for r in res) / 1e9, cores
     except Exception:

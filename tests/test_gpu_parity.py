@@ -16,8 +16,6 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("linsys", ["qdldl", "pcg"])
 @pytest.mark.parametrize("case", qp_cases.ALL_CASES, ids=lambda f: f.__name__)
 def test_product_case(product_lib, case, linsys):
-    if linsys == "pcg" and case.__name__ in qp_cases.DIRECT_ONLY:
-        pytest.skip("inertia is only checked by a factorisation")
     case(oq, product_lib, linsys)
 
 

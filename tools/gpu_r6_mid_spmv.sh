@@ -9,7 +9,7 @@ export TMPDIR=/tmp OSQP_AMD_BENCH_CPU_FULL=0 OSQP_AMD_BENCH_OTHERS=0
 for shift in 14 13; do
   for tile in auto 46000 32768 24576 16384; do
     if [ $tile = auto ]; then unset OSQP_AMD_PANEL_TILE_NNZ; else export OSQP_AMD_PANEL_TILE_NNZ=$tile; fi
-    OSQP_AMD_PANEL_SHIFT=$shift timeout 300 python bench.py --workload rand-1e5 --no-cpu --traffic off --steps 20 --warmup 5 2>/dev/null | python -c "
+    OSQP_AMD_PANEL_SHIFT=$shift timeout 300 python bench.py --full --workload rand-1e5 --no-cpu --traffic off --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('shift=$shift tile_nnz=$tile: %.1f it/s  %.4f ms/step  spmv %.4f ms (frac %.3f)  to eps %.4f s' % (d['value'], d['ms_per_step'], d['roofline']['ms_per_launch'], d['roofline']['frac'], d['time_to_eps_s']))"

@@ -7,7 +7,7 @@ for v in 1 0; do
   REFACTOR_GRID=1 OSQP_AMD_MF_REGPIV=$v timeout 600 python tools/refactor_time.py --child 700 2>&1 | grep "T=" | sed "s/^/regpiv=$v grid /"
 done
 for v in 1 0; do
-OSQP_AMD_MF_REGPIV=$v timeout 900 python bench.py --workload control-1e6 --no-cpu --traffic off --steps 100 --warmup 25 2>/dev/null | python -c "
+OSQP_AMD_MF_REGPIV=$v timeout 900 python bench.py --full --workload control-1e6 --no-cpu --traffic off --steps 100 --warmup 25 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('regpiv=$v control-1e6: %.1f it/s  to eps %.4f s  setup %.2f' % (d['value'], d['time_to_eps_s'], d['setup_s']))"
