@@ -415,6 +415,9 @@ struct LdlFactor {
       }
       if (top_end - sn_tree_L0 < 2) sn_tree = false;  // a single level (or none) left: nothing to fuse
     }
+    if (getenv("OSQP_AMD_SETUP_TRACE"))
+      fprintf(stderr, "[supernodes] one-launch tree %s: from level %d of %d, %d threads, %d persistent workgroups (0: one per supernode)\n",
+              sn_tree ? "on" : "off", sn_tree_L0, T.nlev, sn_tree_threads, sn_tree_grid);
     // the split of the forward rows: where the entries that point at the first level of the one-launch tree (level 1
     // without it) begin -- children below that level have finished in earlier launches (not waited for), entries that
     // point below it are read through the caches
