@@ -430,6 +430,40 @@ c_int osqp_amd_batch_mpc_create(osqp_amd_batch **out, c_int total, unsigned long
 c_int osqp_amd_batch_mpc_solve(osqp_amd_batch *batch, c_float *packed_dev);
 c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
 
+/* A resident batch of the caller's own QPs (one shared sparsity pattern): set up once, then the life cycle of
+ * osqp_setup / osqp_update_* / osqp_warm_start / osqp_solve, instance by instance, without leaving HBM.
+ *   setup():  arguments and validation as osqp_amd_batch_solve (host pointers; return codes 1 = data, 2 = settings).  The
+ *             handle keeps the RAW data and, per instance, a state record [c, rho, flag, - | D[n] | x[n] | E[m] | z[m] | y[m]]:
+ *             the Ruiz factors D, E, c are computed HERE from the setup data and kept; no solve is run.
+ *   update_lin_cost() / update_bounds(): replace q / l and-or u of every instance ([count x n] / [count x m]); the stored
+ *             factors are applied to the new vectors, nothing is re-equilibrated.  update_bounds refuses l > u in any instance
+ *             (return 1, "lower bound greater than upper bound") and then leaves the handle unchanged.
+ *   update_matrices(): replace the values of P and-or A ([count x nnz], the pattern stays) and re-run the equilibration from
+ *             scratch on the raw data with the current q, l, u; the stored (scaled) iterate is left as it is, as
+ *             osqp_update_P_A leaves it.
+ *   warm_start(): x [count x n] and-or y [count x m] in the caller's units, stored as x / D, c y / E, z = A x; x alone sets
+ *             y = 0, y alone sets x = 0 and z = 0; switches the handle's warm_start setting on.
+ *   resolve(): solves every instance.  With settings.warm_start = 1 (the default) a solve starts from the iterate the last
+ *             one ended on (the first from zero; so does the solve after one that ended without a solution -- primal / dual
+ *             infeasible, non-convex -- as osqp_solve resets the iterate then); with 0 every solve starts from zero.  rho is kept per
+ *             instance: a solve that adapted it hands the adapted value on.  The constraint classes are derived from the
+ *             current bounds at the start of each solve.  x_out [count x n], y_out [count x m] (NaN rows for instances
+ *             without a solution), info_out [count x 6] doubles: iter, status_val, pri_res, dua_res, obj_val, rho_updates.
+ * where: 0 = the array arguments are host pointers, 1 = device pointers on the handle's device (no host hop: a controller
+ * whose state estimate lives in HBM).  A NULL array means "keep" (update_*) / "none" (warm_start).  Every call blocks until
+ * done.  Single rank.  The handle is freed by osqp_amd_batch_destroy; it is not interchangeable with the handle of
+ * osqp_amd_batch_mpc_create: each family's calls return 1 with a message on the other's handle. */
+c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m,
+                           const c_int *Pp, const c_int *Pi, const c_float *Px_all,
+                           const c_int *Ap, const c_int *Ai, const c_float *Ax_all,
+                           const c_float *q_all, const c_float *l_all, const c_float *u_all,
+                           const OSQPSettings *settings, c_int device);
+c_int osqp_amd_batch_update_lin_cost(osqp_amd_batch *batch, const c_float *q_all, c_int where);
+c_int osqp_amd_batch_update_bounds(osqp_amd_batch *batch, const c_float *l_all, const c_float *u_all, c_int where);
+c_int osqp_amd_batch_update_matrices(osqp_amd_batch *batch, const c_float *Px_all, const c_float *Ax_all, c_int where);
+c_int osqp_amd_batch_warm_start(osqp_amd_batch *batch, const c_float *x_all, const c_float *y_all, c_int where);
+c_int osqp_amd_batch_resolve(osqp_amd_batch *batch, c_float *x_out, c_float *y_out, c_float *info_out, c_int where);
+
 /* Device memory for callers without an allocator of their own (the packed result array above): plain hipMalloc / hipFree /
  * hipMemcpy on `device`.  copy kind: 0 device -> host, 1 host -> device, 2 device -> device; blocking. */
 void *osqp_amd_device_alloc(c_int bytes, c_int device);
@@ -438,9 +472,11 @@ c_int osqp_amd_device_copy(void *dst, const void *src, c_int bytes, c_int kind, 
 
 /* Differences between the batched path and osqp_setup / osqp_solve: instances share one sparsity pattern, n <= 128,
  * fewer than 65536 rows and non-zeros, everything must fit 160 KB of LDS; `adaptive_rho_interval` = 0 (automatic) means
- * every 100 iterations (there is no per-instance clock); `polish`, `time_limit`, `warm_start`, `verbose` and
- * `linsys_solver` are ignored (always a cold start, the reduced KKT system factorised in LDS); data and settings are
- * validated as by osqp_setup (1 = data, 2 = settings). */
+ * every 100 iterations (there is no per-instance clock); `polish`, `time_limit`, `verbose` and `linsys_solver` are
+ * ignored (the reduced KKT system is factorised on chip); data and settings are validated as by osqp_setup (1 = data,
+ * 2 = settings).  The one-shot entries (osqp_amd_batch_solve, _solve_generated, _mpc_create / _mpc_solve) also ignore
+ * `warm_start`: they equilibrate and start from zero every time.  The resident handle (osqp_amd_batch_setup) honours it
+ * and keeps scaling, iterate and rho between solves, as described above. */
 
 /* Select the HIP device for workspaces created afterwards by this process
  * (one process per GPU: pass LOCAL_RANK). */

@@ -119,6 +119,15 @@ class DeviceArray:
             raise OSQPError("device copy failed: " + self.lib.osqp_amd_last_error().decode())
         return out
 
+    def upload(self, host):
+        """Fill the array from a host array of the same shape; returns self."""
+        host = _as_f64(host)
+        if host.shape != self.shape:
+            raise ValueError(f"expected shape {self.shape}, got {host.shape}")
+        if self.lib.osqp_amd_device_copy(self.ptr, host.ctypes.data_as(C.c_void_p), self.nbytes, 1, self.device) != 0:
+            raise OSQPError("device copy failed: " + self.lib.osqp_amd_last_error().decode())
+        return self
+
     def clone(self):
         other = DeviceArray(self.lib, self.shape[0], self.shape[1], self.device)
         if self.lib.osqp_amd_device_copy(other.ptr, self.ptr, self.nbytes, 2, self.device) != 0:
@@ -166,6 +175,141 @@ class MpcBatch:
 
     def close(self):
         if self.handle:
+            self.lib.osqp_amd_batch_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _batch_array(name, a, shape):
+    """(address, device form?) of an array argument of `ResidentBatch`: a numpy array (host form; anything array-like is
+    converted) or an object with `data_ptr()` and `shape` -- `DeviceArray`, a torch tensor on the handle's device -- (device
+    form).  Shape and element type are checked here, before the library sees the pointer."""
+    if hasattr(a, "data_ptr"):
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(a.shape)}")
+        dt = getattr(a, "dtype", None)
+        if dt is not None and "float64" not in str(dt):
+            raise ValueError(f"{name}: device arrays must be float64, got {dt}")
+        if hasattr(a, "is_contiguous") and not a.is_contiguous():
+            raise ValueError(f"{name}: device arrays must be contiguous")
+        if getattr(a, "is_cuda", True) is False:
+            raise ValueError(f"{name}: a tensor with data_ptr() must live on the device; pass host data as a numpy array")
+        return a, a.data_ptr(), 1
+    arr = np.asarray(a)
+    if arr.dtype.kind not in "fiu":
+        raise ValueError(f"{name}: expected a real numeric array, got dtype {arr.dtype}")
+    if arr.shape != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {arr.shape}")
+    arr = _as_f64(arr)
+    return arr, arr.ctypes.data, 0
+
+
+class ResidentBatch:
+    """`count` QPs of the caller's own that share one sparsity pattern, resident in HBM (osqp_amd_batch_setup): the life
+    cycle of a single model -- setup, `update`, `warm_start`, `solve`, again and again -- instance by instance.  Scaling is
+    computed once from the setup data; every solve starts from the iterate and the rho the last one ended on (with
+    `warm_start=False` in the settings: from zero).  P (upper triangle) and A are scipy matrices giving the pattern; the
+    *_all arrays are [count x .] as for `solve_batch`.  Array arguments of `update` / `warm_start` and the `out` of `solve`
+    may be numpy arrays (host form) or device arrays (`DeviceArray`, torch tensors: no host hop)."""
+
+    def __init__(self, lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, **settings):
+        import scipy.sparse as sp
+
+        P = sp.csc_matrix(sp.triu(P)); P.sort_indices()
+        A = sp.csc_matrix(A); A.sort_indices()
+        self.n, self.m, self.nnzP, self.nnzA = A.shape[1], A.shape[0], P.nnz, A.nnz
+        if P.shape != (self.n, self.n):
+            raise ValueError(f"P: expected shape {(self.n, self.n)}, got {P.shape}")
+        q0 = np.asarray(q_all)
+        if q0.ndim != 2:
+            raise ValueError(f"q_all: expected a [count x {self.n}] array, got shape {q0.shape}")
+        self.count = count = q0.shape[0]
+        if count == 0:
+            raise ValueError("q_all: the batch is empty")
+        arrays = []
+        for name, a, k in (("Px_all", Px_all, self.nnzP), ("Ax_all", Ax_all, self.nnzA), ("q_all", q_all, self.n),
+                           ("l_all", l_all, self.m), ("u_all", u_all, self.m)):
+            if hasattr(a, "data_ptr"):
+                raise ValueError(f"{name}: the setup data are host arrays (numpy); device arrays are for update / warm_start / solve")
+            arrays.append(_batch_array(name, a, (count, k))[0])
+        Px, Ax, q, l, u = arrays
+        self.lib, self.device, self.handle = lib, int(device), C.c_void_p()
+        Pp, Pi = np.ascontiguousarray(P.indptr, dtype=np.int64), np.ascontiguousarray(P.indices, dtype=np.int64)
+        Ap, Ai = np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int64)
+        stgs = make_settings(lib, settings)
+        rc = lib.osqp_amd_batch_setup(C.byref(self.handle), count, self.n, self.m, _iptr(Pp), _iptr(Pi), _fptr(Px), _iptr(Ap), _iptr(Ai),
+                                      _fptr(Ax), _fptr(q), _fptr(l), _fptr(u), C.byref(stgs), self.device)
+        if rc != 0:
+            self.handle = C.c_void_p()
+            raise OSQPError("Error in batched setup: " + lib.osqp_amd_last_error().decode())
+
+    def _call(self, what, rc):
+        if rc != 0:
+            raise OSQPError(f"Error in batched {what}: " + self.lib.osqp_amd_last_error().decode())
+
+    def _pair(self, names, values, cols):
+        """The two optional arrays of one library call: both in the same form (host or device); None stays NULL."""
+        got = [None if v is None else _batch_array(nm, v, (self.count, k)) for nm, v, k in zip(names, values, cols)]
+        forms = {g[2] for g in got if g is not None}
+        if len(forms) > 1:
+            raise ValueError(f"{names[0]} and {names[1]} must both be host arrays or both device arrays")
+        return got, [None if g is None else g[1] for g in got], (forms.pop() if forms else 0)
+
+    def update(self, q=None, l=None, u=None, Px=None, Ax=None):
+        """New q / bounds / matrix values for every instance, in the order of `osqp.update!`: q, then the bounds (scaled with
+        the stored factors), then the matrices (which re-equilibrate, with the q, l, u just given).  Nothing is changed by a
+        call whose arguments fail the checks; `l > u` in any instance raises and leaves the bounds as they were."""
+        qa = None if q is None else _batch_array("q", q, (self.count, self.n))
+        keep_b, bounds, where_b = self._pair(("l", "u"), (l, u), (self.m, self.m))
+        keep_m, mats, where_m = self._pair(("Px", "Ax"), (Px, Ax), (self.nnzP, self.nnzA))
+        if keep_b[0] is not None and keep_b[1] is not None and not where_b and np.any(keep_b[0][0] > keep_b[1][0]):
+            raise OSQPError("Error in batched update: lower bound greater than upper bound")
+        if qa is not None:
+            self._call("update", self.lib.osqp_amd_batch_update_lin_cost(self.handle, qa[1], qa[2]))
+        if bounds[0] is not None or bounds[1] is not None:
+            self._call("update", self.lib.osqp_amd_batch_update_bounds(self.handle, bounds[0], bounds[1], where_b))
+        if mats[0] is not None or mats[1] is not None:
+            self._call("update", self.lib.osqp_amd_batch_update_matrices(self.handle, mats[0], mats[1], where_m))
+
+    def warm_start(self, x=None, y=None):
+        """Start the next solve from x and / or y (caller's units, [count x n] / [count x m]); a missing one is zero."""
+        keep, ptrs, where = self._pair(("x", "y"), (x, y), (self.n, self.m))
+        if ptrs[0] is not None or ptrs[1] is not None:
+            self._call("warm start", self.lib.osqp_amd_batch_warm_start(self.handle, ptrs[0], ptrs[1], where))
+
+    def solve(self, out=None):
+        """Solve every instance -> (x [count x n], y [count x m], info [count x 6]: iter, status_val, pri_res, dua_res,
+        obj_val, rho_updates).  out=None: numpy arrays; out=(x, y, info) of device arrays: written in place and returned."""
+        if out is None:
+            x, y, info = np.empty((self.count, self.n)), np.empty((self.count, self.m)), np.empty((self.count, 6))
+            self._call("solve", self.lib.osqp_amd_batch_resolve(self.handle, x.ctypes.data, y.ctypes.data, info.ctypes.data, 0))
+            return x, y, info
+        if len(out) != 3:
+            raise ValueError("out: expected (x, y, info)")
+        ptrs = []
+        for name, a, k in (("out[0]", out[0], self.n), ("out[1]", out[1], self.m), ("out[2]", out[2], 6)):
+            if a is None and k == 0:
+                ptrs.append(None)
+                continue
+            if not hasattr(a, "data_ptr"):
+                raise ValueError(f"{name}: expected a device array (DeviceArray, torch tensor); omit `out` for numpy results")
+            ptrs.append(_batch_array(name, a, (self.count, k))[1])
+        self._call("solve", self.lib.osqp_amd_batch_resolve(self.handle, ptrs[0], ptrs[1], ptrs[2], 1))
+        return out
+
+    def alloc(self):
+        """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints."""
+        return (DeviceArray(self.lib, self.count, self.n, self.device),
+                DeviceArray(self.lib, self.count, self.m, self.device) if self.m else None,
+                DeviceArray(self.lib, self.count, 6, self.device))
+
+    def close(self):
+        if getattr(self, "handle", None):
             self.lib.osqp_amd_batch_destroy(self.handle)
             self.handle = C.c_void_p()
 

@@ -26,6 +26,9 @@
 // packed word (two instructions per entry), short columns / rows are padded with a zero-valued entry instead of
 // branching, nothing the loop needs lives in spilled registers.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
+// Both kernels also run in RESIDENT mode (osqp_amd_batch_setup ... _resolve, "the state record" below): scaling, iterate
+// and rho of every instance live in HBM between launches; a branch of the prologue and of the epilogue on a kernel argument,
+// the ADMM loop is the same code.
 // There is no communication between instances: the multi-GPU path shards the
 // instance range over ranks and gathers the packed results once (batch.py).
 #include <algorithm>
@@ -602,7 +605,7 @@ struct Ops6 { double a, b, c, d, e, f; };
 // the nrm[] block: the 14 norms (Slot order of the large-problem path), then pri_res, dua_res, obj and the status code
 // (0: keep iterating).
 // ---------------------------------------------------------------------------------------------------------
-enum { N_PRI = 14, N_DUA = 15, N_OBJ = 16, N_STATUS = 17, N_COUNT = 24 };
+enum { N_PRI = 14, N_DUA = 15, N_OBJ = 16, N_STATUS = 17, N_RECORD = 18, N_COUNT = 24 };  // N_RECORD: the four-wavefront kernel only (here 18 .. 23 are scratch)
 struct CheckArgs {
   int n, m, nnzA, nnzF, swapped, uns, passes, last, words;
   double ea, er, epi, edi, c, cinv;
@@ -757,6 +760,32 @@ __device__ __noinline__ void residual_phase(CheckArgs a) {
   __syncthreads();
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Resident mode (osqp_amd_batch_setup ... _resolve): the state of an instance that outlives a launch, one contiguous row
+// of doubles per instance in HBM (an even number of them: every row starts on a 16-byte boundary):
+//   [ c | rho | flag | - | D[n] | x[n] | E[m] | z[m] | y[m] ]       x, z, y: the SCALED iterate; caller's numbering
+// flag: 1 the factors are valid, 3 a solve has left its iterate.  The handle keeps the caller's RAW data; a solve applies
+// D, E, c in one pass of its prologue.  res_mode is a kernel argument, uniform over the grid: 0 = the one-shot entry
+// points (nothing of this is touched), otherwise bits:
+//   RES_SCALE_ONLY  run the Ruiz passes on the raw data, write D, E, c to the record, return (setup, matrix updates);
+//   RES_SOLVE       load D, E, c, rho and apply them instead of the Ruiz passes; leave x, z, y (zeros when the instance has
+//                   no solution, as the oracle cold-starts it) and rho behind at the end;
+//   RES_WARM        (with RES_SOLVE) start from the record's x, z, y instead of zero.
+// ---------------------------------------------------------------------------------------------------------
+enum { RES_SOLVE = 1, RES_WARM = 2, RES_SCALE_ONLY = 4 };
+enum { REC_C = 0, REC_RHO = 1, REC_FLAG = 2, REC_HDR = 4 };
+__host__ __device__ constexpr int rec_D(int, int) { return REC_HDR; }
+__host__ __device__ constexpr int rec_x(int n, int) { return REC_HDR + n; }
+__host__ __device__ constexpr int rec_E(int n, int) { return REC_HDR + 2 * n; }
+__host__ __device__ constexpr int rec_z(int n, int m) { return REC_HDR + 2 * n + m; }
+__host__ __device__ constexpr int rec_y(int n, int m) { return REC_HDR + 2 * n + 2 * m; }
+__host__ __device__ constexpr int rec_doubles(int n, int m) { return (REC_HDR + 2 * n + 3 * m + 1) & ~1; }
+// a pointer parked in LDS by the prologue, back as a wave-uniform value
+typedef __attribute__((address_space(3))) unsigned long long lu64;
+__device__ __forceinline__ double *parked_ptr(unsigned long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return (double *)(((unsigned long long)hi << 32) | lo);
+}
 
 #include "batch_quad.hpp"
 
@@ -770,9 +799,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                                                     const double *__restrict__ l_all, const double *__restrict__ u_all,
                                                     double *__restrict__ x_out, double *__restrict__ y_out,
                                                     double *__restrict__ info_out, int x_stride, int y_stride, int info_stride,
-                                                    int info_cols) {
+                                                    int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
   const int inst = blockIdx.x;
   if (inst >= count) return;
+  const bool res_solve = (res_mode & RES_SOLVE) != 0, res_warm = (res_mode & RES_WARM) != 0;
+  double *const rec = res_mode ? rec_all + (size_t)inst * rec_stride : nullptr;  // the instance's state record (resident mode)
   Pattern P = Pin;
   if (CN > 0) { P.n = CN; P.m = CM; P.nnzA = CA; P.nnzF = CF; }
   constexpr bool EXACT = CN > 0 && PARTS * NCT == CN;
@@ -790,18 +821,26 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   for (int k = tid; k < P.nnzA; k += NT) s.Av[k] = Ax_all[(size_t)inst * P.nnzA + k];
   if (tid == 0) s.Av[P.nnzA] = 0.0;  // what padded entries of the packed words point at
   for (int k = tid; k < P.nnzF; k += NT) s.Pv[k] = Px_all[(size_t)inst * P.nnzP + P.Fmap[k]];
-  for (int j = tid; j < n; j += NT) { s.q[j] = q_all[(size_t)inst * n + j]; s.D[j] = 1.0; s.x[j] = 0.0; s.xp[j] = 0.0; s.dx[j] = 0.0; }
+  for (int j = tid; j < n; j += NT) {
+    const double x0 = res_warm ? rec[rec_x(n, m) + j] : 0.0;  // the scaled iterate the last solve left (or warm_start wrote)
+    s.q[j] = q_all[(size_t)inst * n + j]; s.D[j] = res_solve ? rec[rec_D(n, m) + j] : 1.0; s.x[j] = x0; s.xp[j] = x0; s.dx[j] = 0.0;
+  }
   for (int i = tid; i < m; i += NT) {
     s.l[i] = fmax(l_all[(size_t)inst * m + i], -OSQP_INFTY); s.u[i] = fmin(u_all[(size_t)inst * m + i], OSQP_INFTY);
-    s.E[i] = 1.0; s.z[i] = 0.0; s.y[i] = 0.0; s.zp[i] = 0.0; s.dy[i] = 0.0;
+    const double z0 = res_warm ? rec[rec_z(n, m) + i] : 0.0;
+    s.E[i] = res_solve ? rec[rec_E(n, m) + i] : 1.0; s.z[i] = z0; s.y[i] = res_warm ? rec[rec_y(n, m) + i] : 0.0; s.zp[i] = z0; s.dy[i] = 0.0;
   }
+  // where the epilogue finds the record (0: nothing to leave behind): parked behind the pivot buffers of the inversion
+  // instead of scalar registers that would stay live across the whole ADMM loop
+  if (tid == 0) *(lu64 *)(s.gjc + 2 * 4 * 128 + 56) = res_solve ? (unsigned long long)rec : 0ull;
   __syncthreads();
   PROF(0)
   // ---- K0: Ruiz equilibration + cost scaling --------------------------------
   if (regs) store_sparse(P, s);
   __syncthreads();
   double c = 1.0;
-  for (int it = 0; it < st.scaling; it++) {
+  const int nscale = res_solve ? 0 : (int)st.scaling;  // a resident solve applies the factors of its record instead (below)
+  for (int it = 0; it < nscale; it++) {
     if (regs) {
       const ColWords cwd = col_words(s);
       double mx = 0.0;
@@ -889,12 +928,32 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     c *= c_temp;
     __syncthreads();
   }
+  if (res_mode & RES_SCALE_ONLY) {  // setup / after a matrix update: D, E, c of this data into the record, no solve
+    for (int j = tid; j < n; j += NT) rec[rec_D(n, m) + j] = s.D[j];
+    for (int i = tid; i < m; i += NT) rec[rec_E(n, m) + i] = s.E[i];
+    if (tid == 0) { rec[REC_C] = c; rec[REC_FLAG] = 1.0; }
+    return;
+  }
+  if (res_solve) {  // the stored factors in one pass over the raw data: P <- c D P D, A <- E A D, q <- c D q
+    c = uni(rec[REC_C]);
+    for (int r = tid; r < n; r += NT)
+      for (int q = s.Fp[r]; q < s.Fp[r + 1]; q++) {
+        const int cc = s.Fc[q];
+        const int lo = cc < r ? cc : r, hi = cc < r ? r : cc;
+        s.Pv[q] = c * ((s.Pv[q] * s.D[lo]) * s.D[hi]);
+      }
+    for (int j = tid; j < n; j += NT) {
+      for (int k = s.Ap[j]; k < s.Ap[j + 1]; k++) s.Av[k] = (s.Av[k] * s.E[s.Ai[k]]) * s.D[j];
+      s.q[j] = c * (s.q[j] * s.D[j]);
+    }
+    __syncthreads();
+  }
   const double cinv = 1.0 / c;
   for (int i = tid; i < m; i += NT) { s.l[i] *= s.E[i]; s.u[i] *= s.E[i]; }
   __syncthreads();
   PROF(1)
-  // ---- K1, K2 ----------------------------------------------------------------
-  double rho = uni(fmin(fmax(st.rho, B_RHO_MIN), B_RHO_MAX));
+  // ---- K1, K2 (a resident solve goes on with the rho its last solve ended on) ---
+  double rho = uni(fmin(fmax(res_solve ? rec[REC_RHO] : st.rho, B_RHO_MIN), B_RHO_MAX));
   set_rho(P, s, rho, true);
   int status = OSQP_UNSOLVED;
   double *scratch = scratch_all + (size_t)inst * n * n;
@@ -1006,6 +1065,38 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     o[0] = (double)iter; o[1] = (double)status; o[2] = pri_res; o[3] = dua_res;
     if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)rho_updates; }
   }
+  if (double *const rec = parked_ptr(*(const lu64 *)(s.gjc + 2 * 4 * 128 + 56))) {  // the scaled iterate and rho stay: the next solve starts from them
+    // (an instance without a solution -- infeasible, non-convex -- starts its next solve from zero, as the oracle's
+    // store_solution cold-starts it; rho stays)
+    for (int j = tid; j < n; j += NT) rec[rec_x(n, m) + j] = has_sol ? x[j] : 0.0;
+    for (int i = tid; i < m; i += NT) { rec[rec_z(n, m) + i] = has_sol ? z[i] : 0.0; rec[rec_y(n, m) + i] = has_sol ? s.y[i] : 0.0; }
+    if (tid == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; }
+  }
+}
+
+// the iterate of osqp_amd_batch_warm_start, caller's units in, the record's scaled units out: x <- x / D, y <- c y / E,
+// z <- A x in scaled units = E (A_raw x_raw); a missing vector is zero (and z with x).  One workgroup per instance.
+__global__ __launch_bounds__(256) void k_batch_warm(Pattern P, int count, const double *__restrict__ Ax_all, const double *__restrict__ x_all,
+                                                    const double *__restrict__ y_all, double *__restrict__ rec_all, int rec_stride) {
+  const int inst = blockIdx.x, n = P.n, m = P.m;
+  if (inst >= count) return;
+  double *rec = rec_all + (size_t)inst * rec_stride;
+  const double c = rec[REC_C];
+  for (int j = threadIdx.x; j < n; j += 256) rec[rec_x(n, m) + j] = x_all ? x_all[(size_t)inst * n + j] / rec[rec_D(n, m) + j] : 0.0;
+  for (int i = threadIdx.x; i < m; i += 256) {
+    const double e = rec[rec_E(n, m) + i];
+    double ax = 0.0;
+    if (x_all)
+      for (int q = P.Rp[i]; q < P.Rp[i + 1]; q++) ax += Ax_all[(size_t)inst * P.nnzA + P.Rmap[q]] * x_all[(size_t)inst * n + P.Rc[q]];
+    rec[rec_z(n, m) + i] = e * ax;
+    rec[rec_y(n, m) + i] = y_all ? c * y_all[(size_t)inst * m + i] / e : 0.0;
+  }
+}
+
+// rows with l > u, counted per launch (osqp_amd_batch_update_bounds refuses the update when there is one)
+__global__ __launch_bounds__(256) void k_batch_check_bounds(size_t total, const double *__restrict__ l, const double *__restrict__ u, int *bad) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < total && l[i] > u[i]) atomicAdd(bad, 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -1352,7 +1443,7 @@ struct DevicePattern {
 // outputs: row i of x / y / info at x + i * x_stride etc. (packed layouts put all three in one row); info_cols 4 or 6
 void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, const double *Px, const double *Ax, const double *q,
                   const double *l, const double *u, double *x, double *y, double *info, int x_stride, int y_stride, int info_stride,
-                  int info_cols, hipStream_t s) {
+                  int info_cols, hipStream_t s, double *rec = nullptr, int rec_stride = 0, int res_mode = 0) {
   const Pattern &P = dp.P;
   size_t bytes = lds_bytes(P.n, P.m, P.nnzA, P.nnzF, sparse_fits(P));
   if (P.n > 128 || P.m > 65535 || P.nnzA > 65535 || P.nnzF > 65535) throw Error(1, "the batched path supports n <= 128 and fewer than 65536 rows / non-zeros");
@@ -1365,7 +1456,7 @@ void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, co
   do {                                                                                                                                 \
     HIP_CHECK(hipFuncSetAttribute((const void *)k_batch_solve<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));  \
     OQ_LAUNCH((k_batch_solve<__VA_ARGS__>), dim3(count), dim3(NT), bytes, s, P, st, count, dp.scratch.get(), Px, Ax, q, l, u, x, y, info, \
-              x_stride, y_stride, info_stride, info_cols);                                                                             \
+              x_stride, y_stride, info_stride, info_cols, rec, rec_stride, res_mode);                                                    \
   } while (0)
   // shapes compiled in (same source, constants folded): the MPC family of BASELINE.json config 5
   const bool mpc = P.n == MPC_N && P.m == MPC_M && P.nnzA == kMpcNnzA && P.nnzF == MPC_N;
@@ -1379,7 +1470,7 @@ void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, co
     auto kern = quad::KERN<__VA_ARGS__>;                                                                                               \
     HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));                           \
     OQ_LAUNCH(kern, dim3(count), dim3(quad::QT), (size_t)L.total, s, dp.QS, st, count, Px, Ax, q, l, u, x, y, info, x_stride, y_stride, \
-              info_stride, info_cols);                                                                                                 \
+              info_stride, info_cols, rec, rec_stride, res_mode);                                                         \
   } while (0)
     g_batch_last_kernel = dp.quad_cfg;
     switch (dp.quad_cfg) {
@@ -1417,7 +1508,66 @@ struct BatchPlan {
   DevicePattern dp;
   DevBuf<double> Px, Ax, q, l, u;
   static constexpr int kRow = MPC_N + MPC_M + 4;
+  // osqp_amd_batch_setup: the caller's own QPs (raw values in Px .. u above), their state records, staging for host-pointer
+  // calls (updates and warm starts come in through in_a / in_b, results leave through x_out / y_out / info_out)
+  bool resident = false;
+  int n = 0, m = 0, nnzA = 0, nnzP = 0, rec_stride = 0;
+  DevBuf<double> rec, in_a, in_b, x_out, y_out, info_out;
+  DevBuf<int> bad;
 };
+
+// The checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings], shared by the
+// one-shot osqp_amd_batch_solve and osqp_amd_batch_setup.  outputs_ok: what the caller checked of its own output
+// pointers.  0 = fine; otherwise the return code, the message is set.
+c_int validate_batch_data(c_int count, c_int n, c_int m, const c_int *Pp, const c_int *Pi, const c_float *Px_all, const c_int *Ap,
+                          const c_int *Ai, const c_float *Ax_all, const c_float *q_all, const c_float *l_all, const c_float *u_all,
+                          const OSQPSettings *settings, bool outputs_ok) {
+  if (count <= 0 || n <= 0 || m < 0 || !Pp || !Pi || !Ap || !Ai || !q_all || (m > 0 && (!l_all || !u_all)) || !settings || !outputs_ok) {
+    set_last_error("invalid batch data"); return 1;
+  }
+  if (validate_settings(settings)) { set_last_error("invalid settings"); return 2; }
+  if (n > 128 || m > 65535 || Pp[0] != 0 || Ap[0] != 0 || Pp[n] < 0 || Ap[n] < 0 || Pp[n] > 65535 || Ap[n] > 65535) {
+    set_last_error("the batched path supports n <= 128 and fewer than 65536 rows / non-zeros"); return 1;
+  }
+  for (c_int j = 0; j < n; j++) {
+    if (Pp[j + 1] < Pp[j] || Ap[j + 1] < Ap[j]) { set_last_error("column pointers must not decrease"); return 1; }
+    for (c_int k = Pp[j]; k < Pp[j + 1]; k++) if (Pi[k] < 0 || Pi[k] > j) { set_last_error("P must be upper triangular with row indices in range"); return 1; }
+    for (c_int k = Ap[j]; k < Ap[j + 1]; k++) if (Ai[k] < 0 || Ai[k] >= m) { set_last_error("row index of A out of range"); return 1; }
+    // the term lists of A' rho A are built by merging sorted columns (DevicePattern::build): unsorted or repeated rows
+    // would silently drop terms
+    for (c_int k = Ap[j] + 1; k < Ap[j + 1]; k++) if (Ai[k] <= Ai[k - 1]) { set_last_error("the rows of every column of A must be sorted and unique"); return 1; }
+    for (c_int k = Pp[j] + 1; k < Pp[j + 1]; k++) if (Pi[k] <= Pi[k - 1]) { set_last_error("the rows of every column of P must be sorted and unique"); return 1; }
+  }
+  if ((Pp[n] > 0 && !Px_all) || (Ap[n] > 0 && !Ax_all)) { set_last_error("invalid batch data"); return 1; }
+  for (c_int i = 0; i < count * m; i++) if (l_all[i] > u_all[i]) { set_last_error("lower bound greater than upper bound"); return 1; }
+  return 0;
+}
+
+// the handle of a resident call, or nullptr with the message set
+BatchPlan *resident_plan(osqp_amd_batch *handle) {
+  if (!handle) { set_last_error("null batch handle"); return nullptr; }
+  BatchPlan *b = (BatchPlan *)handle;
+  if (!b->resident) { set_last_error("this batch handle was not created by osqp_amd_batch_setup"); return nullptr; }
+  return b;
+}
+// `src` ([len] doubles, host or device pointer by `where`) as a device pointer: host data goes through `stage`
+const double *device_ptr(const c_float *src, size_t len, c_int where, DevBuf<double> &stage, hipStream_t s) {
+  if (where) return src;
+  if (stage.n < len) stage.alloc(len);
+  stage.upload(src, len, s);
+  return stage.get();
+}
+void copy_d2d(double *dst, const double *src, size_t len, hipStream_t s) {
+  HIP_CHECK(hipMemcpyAsync(dst, src, len * sizeof(double), hipMemcpyDeviceToDevice, s));
+}
+// D, E, c of the handle's current raw data into the records (one launch of the solve kernel in its scale-only mode)
+void resident_equilibrate(BatchPlan &b, hipStream_t s) {
+  launch_batch(b.dp, b.st, b.count, b.Px.get(), b.Ax.get(), b.q.get(), b.l.get(), b.u.get(), nullptr, nullptr, nullptr, 0, 0, 0, 0, s,
+               b.rec.get(), b.rec_stride, RES_SCALE_ONLY);
+}
+#define OQ_BATCH_CATCH                                                                          \
+  catch (const Error &er) { set_last_error(er.what()); return er.code ? er.code : 6; }         \
+  catch (const std::exception &ex) { set_last_error(ex.what()); return 6; }
 
 }  // namespace
 }  // namespace oq
@@ -1432,24 +1582,8 @@ c_int osqp_amd_batch_solve(c_int count, c_int n, c_int m, const c_int *Pp, const
                            const c_int *Ai, const c_float *Ax_all, const c_float *q_all, const c_float *l_all, const c_float *u_all,
                            const OSQPSettings *settings, c_float *x_out, c_float *y_out, OSQPInfo *info_out, c_int device) {
   try {
-    // the same checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings]
-    if (count <= 0 || n <= 0 || m < 0 || !Pp || !Pi || !Ap || !Ai || !q_all || (m > 0 && (!l_all || !u_all)) || !settings || !x_out ||
-        !info_out || (m > 0 && !y_out)) { set_last_error("invalid batch data"); return 1; }
-    if (validate_settings(settings)) { set_last_error("invalid settings"); return 2; }
-    if (n > 128 || m > 65535 || Pp[0] != 0 || Ap[0] != 0 || Pp[n] < 0 || Ap[n] < 0 || Pp[n] > 65535 || Ap[n] > 65535) {
-      set_last_error("the batched path supports n <= 128 and fewer than 65536 rows / non-zeros"); return 1;
-    }
-    for (c_int j = 0; j < n; j++) {
-      if (Pp[j + 1] < Pp[j] || Ap[j + 1] < Ap[j]) { set_last_error("column pointers must not decrease"); return 1; }
-      for (c_int k = Pp[j]; k < Pp[j + 1]; k++) if (Pi[k] < 0 || Pi[k] > j) { set_last_error("P must be upper triangular with row indices in range"); return 1; }
-      for (c_int k = Ap[j]; k < Ap[j + 1]; k++) if (Ai[k] < 0 || Ai[k] >= m) { set_last_error("row index of A out of range"); return 1; }
-      // the term lists of A' rho A are built by merging sorted columns (DevicePattern::build): unsorted or repeated rows
-      // would silently drop terms
-      for (c_int k = Ap[j] + 1; k < Ap[j + 1]; k++) if (Ai[k] <= Ai[k - 1]) { set_last_error("the rows of every column of A must be sorted and unique"); return 1; }
-      for (c_int k = Pp[j] + 1; k < Pp[j + 1]; k++) if (Pi[k] <= Pi[k - 1]) { set_last_error("the rows of every column of P must be sorted and unique"); return 1; }
-    }
-    if ((Pp[n] > 0 && !Px_all) || (Ap[n] > 0 && !Ax_all)) { set_last_error("invalid batch data"); return 1; }
-    for (c_int i = 0; i < count * m; i++) if (l_all[i] > u_all[i]) { set_last_error("lower bound greater than upper bound"); return 1; }
+    if (c_int bad = validate_batch_data(count, n, m, Pp, Pi, Px_all, Ap, Ai, Ax_all, q_all, l_all, u_all, settings,
+                                        x_out && info_out && (m <= 0 || y_out))) return bad;
     DeviceScope on_device((int)device);
     hipStream_t s = nullptr;
     std::vector<int> hPp(Pp, Pp + n + 1), hAp(Ap, Ap + n + 1);
@@ -1567,6 +1701,7 @@ c_int osqp_amd_batch_mpc_create(osqp_amd_batch **out, c_int total, unsigned long
 c_int osqp_amd_batch_mpc_solve(osqp_amd_batch *handle, c_float *packed_dev) {
   if (!handle || !packed_dev) return 1;
   BatchPlan &b = *(BatchPlan *)handle;
+  if (b.resident) { set_last_error("this batch handle was not created by osqp_amd_batch_mpc_create"); return 1; }
   try {
     DeviceScope on_device(b.device);
     hipStream_t s = nullptr;
@@ -1583,6 +1718,127 @@ c_int osqp_amd_batch_mpc_solve(osqp_amd_batch *handle, c_float *packed_dev) {
     set_last_error(ex.what());
     return 6;
   }
+}
+
+// ---- resident batch of the caller's own QPs: setup once, update vectors / values in place, re-solve warm ---------------------
+c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, const c_int *Pp, const c_int *Pi, const c_float *Px_all,
+                           const c_int *Ap, const c_int *Ai, const c_float *Ax_all, const c_float *q_all, const c_float *l_all,
+                           const c_float *u_all, const OSQPSettings *settings, c_int device) {
+  if (!out) { set_last_error("invalid batch data"); return 1; }
+  *out = nullptr;
+  try {
+    if (c_int bad = validate_batch_data(count, n, m, Pp, Pi, Px_all, Ap, Ai, Ax_all, q_all, l_all, u_all, settings, true)) return bad;
+    DeviceScope on_device((int)device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<BatchPlan> b(new BatchPlan());
+    b->resident = true; b->device = (int)device; b->total = b->count = (int)count; b->st = *settings;
+    b->n = (int)n; b->m = (int)m; b->nnzP = (int)Pp[n]; b->nnzA = (int)Ap[n]; b->rec_stride = rec_doubles((int)n, (int)m);
+    std::vector<int> hPp(Pp, Pp + n + 1), hAp(Ap, Ap + n + 1), hPi(Pi, Pi + Pp[n]), hAi(Ai, Ai + Ap[n]);
+    b->dp.build(b->n, b->m, hPp, hPi, hAp, hAi, s);
+    const size_t cnt = (size_t)count;
+    b->Px.alloc(cnt * b->nnzP); b->Ax.alloc(cnt * b->nnzA); b->q.alloc(cnt * n); b->l.alloc(cnt * m); b->u.alloc(cnt * m);
+    b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6); b->bad.alloc(1);
+    b->Px.upload(Px_all, cnt * b->nnzP, s); b->Ax.upload(Ax_all, cnt * b->nnzA, s);
+    b->q.upload(q_all, cnt * n, s); b->l.upload(l_all, cnt * m, s); b->u.upload(u_all, cnt * m, s);
+    // the records: a zero iterate (the first solve starts from zero either way), the rho of the settings
+    std::vector<double> hrec(cnt * b->rec_stride, 0.0);
+    for (size_t i = 0; i < cnt; i++) hrec[i * b->rec_stride + REC_RHO] = settings->rho;
+    b->rec.alloc(hrec.size()); b->rec.upload(hrec.data(), hrec.size(), s);
+    resident_equilibrate(*b, s);  // D, E, c come from the setup data and stay until the matrices change
+    HIP_CHECK(hipDeviceSynchronize());
+    *out = (osqp_amd_batch *)b.release();
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_update_lin_cost(osqp_amd_batch *handle, const c_float *q_all, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!q_all) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const size_t len = (size_t)b->count * b->n;
+    if (where) copy_d2d(b->q.get(), q_all, len, s); else b->q.upload(q_all, len, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_update_bounds(osqp_amd_batch *handle, const c_float *l_all, const c_float *u_all, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (b->m == 0 || (!l_all && !u_all)) return 0;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const size_t len = (size_t)b->count * b->m;
+    // checked on the device against the bound that stays, before anything of the handle changes
+    const double *ln = l_all ? device_ptr(l_all, len, where, b->in_a, s) : b->l.get();
+    const double *un = u_all ? device_ptr(u_all, len, where, b->in_b, s) : b->u.get();
+    int bad = 0;
+    HIP_CHECK(hipMemsetAsync(b->bad.get(), 0, sizeof(int), s));
+    OQ_LAUNCH(k_batch_check_bounds, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, len, ln, un, b->bad.get());
+    b->bad.download(&bad, 1, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (bad) { set_last_error("lower bound greater than upper bound"); return 1; }
+    if (l_all) copy_d2d(b->l.get(), ln, len, s);
+    if (u_all) copy_d2d(b->u.get(), un, len, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_update_matrices(osqp_amd_batch *handle, const c_float *Px_all, const c_float *Ax_all, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!Px_all && !Ax_all) return 0;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const size_t lp = (size_t)b->count * b->nnzP, la = (size_t)b->count * b->nnzA;
+    if (Px_all && lp) { if (where) copy_d2d(b->Px.get(), Px_all, lp, s); else b->Px.upload(Px_all, lp, s); }
+    if (Ax_all && la) { if (where) copy_d2d(b->Ax.get(), Ax_all, la, s); else b->Ax.upload(Ax_all, la, s); }
+    resident_equilibrate(*b, s);  // from scratch on the raw data with the current q, l, u; the scaled iterate stays as it is
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_warm_start(osqp_amd_batch *handle, const c_float *x_all, const c_float *y_all, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!x_all && !y_all) return 0;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const double *xd = x_all ? device_ptr(x_all, (size_t)b->count * b->n, where, b->in_a, s) : nullptr;
+    const double *yd = y_all && b->m ? device_ptr(y_all, (size_t)b->count * b->m, where, b->in_b, s) : nullptr;
+    OQ_LAUNCH(k_batch_warm, dim3(b->count), dim3(256), 0, s, b->dp.P, b->count, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride);
+    HIP_CHECK(hipStreamSynchronize(s));
+    b->st.warm_start = 1;  // as osqp_warm_start does
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_out, c_float *info_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!x_out || !info_out || (b->m > 0 && !y_out)) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    double *xd = where ? x_out : b->x_out.get(), *yd = where ? y_out : b->y_out.get(), *id = where ? info_out : b->info_out.get();
+    launch_batch(b->dp, b->st, b->count, b->Px.get(), b->Ax.get(), b->q.get(), b->l.get(), b->u.get(), xd, yd, id, b->n, b->m, 6, 6, s,
+                 b->rec.get(), b->rec_stride, RES_SOLVE | (b->st.warm_start ? RES_WARM : 0));
+    if (!where) {
+      b->x_out.download(x_out, (size_t)b->count * b->n, s);
+      if (b->m) b->y_out.download(y_out, (size_t)b->count * b->m, s);
+      b->info_out.download(info_out, (size_t)b->count * 6, s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
 }
 
 c_int osqp_amd_batch_destroy(osqp_amd_batch *handle) {

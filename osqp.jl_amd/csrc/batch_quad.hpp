@@ -334,10 +334,13 @@ __device__ __forceinline__ void quad_body(
     const Sched &S, const OSQPSettings &st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,
     const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,
     double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,
-    int info_stride, int info_cols) {
+    int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
   const int inst = blockIdx.x;
   if (inst >= count) return;
   const int n = CN ? CN : S.n, m = CN ? CM : S.m, nnzA = CN ? CA : S.nnzA, nnzF = CN ? CF : S.nnzF;
+  // resident mode (batch.hip, "the state record"): a workgroup-uniform branch of the prologue and the epilogue
+  const bool res_solve = (res_mode & RES_SOLVE) != 0, res_warm = (res_mode & RES_WARM) != 0;
+  double *const rec = res_mode ? rec_all + (size_t)inst * rec_stride : nullptr;
   const Layout L = make_layout(n, m, nnzA, nnzF, NH, KC, KE, CH);
   constexpr int NB = (NH + 15) / 16;       // broadcast registers of a row half
   constexpr int NHP = NB * 16;             // a row half, padded
@@ -371,15 +374,23 @@ __device__ __forceinline__ void quad_body(
     for (int i = t; i <= m; i += QT) {
       const unsigned r = (unsigned)i * RECB;
       const bool real = i < m;
-      st2at(lds, L.rec + r + F_Z, 0.0, 0.0);
+      const bool keep = res_warm && real;  // the scaled iterate the last solve left (or warm_start wrote)
+      st2at(lds, L.rec + r + F_Z, keep ? rec[rec_z(n, m) + i] : 0.0, keep ? rec[rec_y(n, m) + i] : 0.0);
       st2at(lds, L.rec + r + F_L, real ? fmax(l_all[(size_t)inst * m + i], -OSQP_INFTY) : 0.0, real ? fmin(u_all[(size_t)inst * m + i], OSQP_INFTY) : 0.0);
       st2at(lds, L.rec + r + F_RHO, 0.0, 0.0);
-      st2at(lds, L.rec + r + F_ZT, 0.0, real ? 1.0 : 0.0);
+      st2at(lds, L.rec + r + F_ZT, 0.0, real ? (res_solve ? rec[rec_E(n, m) + i] : 1.0) : 0.0);
       if (real) { sd(lds, L.dy + i * 8, 0.0); sd(lds, L.ax + i * 8, 0.0); }
     }
     // x_j, q_j, D_j, delta_x_j live in LDS, not in registers of the column's owner: they are touched once or twice per
     // iteration, and every register next to the inverse counts
-    if (me.owner) { sd(lds, L.cx + me.j * 8, 0.0); sd(lds, L.cq + me.j * 8, q_all[(size_t)inst * n + S.perm[me.j]]); sd(lds, L.cD + me.j * 8, 1.0); sd(lds, L.cdx + me.j * 8, 0.0); }
+    if (me.owner) {
+      const int jo = S.perm[me.j];  // the record is in the caller's numbering
+      sd(lds, L.cx + me.j * 8, res_warm ? rec[rec_x(n, m) + jo] : 0.0); sd(lds, L.cq + me.j * 8, q_all[(size_t)inst * n + jo]);
+      sd(lds, L.cD + me.j * 8, res_solve ? rec[rec_D(n, m) + jo] : 1.0); sd(lds, L.cdx + me.j * 8, 0.0);
+    }
+    // where the epilogue finds the record (0: nothing to leave behind): parked in a spare slot of nrm[] instead of
+    // scalar registers that would stay live, next to the inverse, across the whole ADMM loop
+    if (t == 0) *(lu64 *)(lds + L.nrm + 8 * N_RECORD) = res_solve ? (unsigned long long)rec : 0ull;
   }
   auto stage_words = [&]() {
     const int t = tid();
@@ -488,8 +499,10 @@ __device__ __forceinline__ void quad_body(
 
   QPROF(0)
   // ---- K0: Ruiz equilibration + cost scaling (the arithmetic of batch.hip / oracle scale_data, element for element) ----
+  // (a resident solve applies the factors its record holds instead: below)
   double c = 1.0;
-  for (int it = 0; it < st.scaling; it++) {
+  const int nscale = res_solve ? 0 : (int)st.scaling;
+  for (int it = 0; it < nscale; it++) {
     ME;
     const unsigned myrec = my_rec(me);
     const bool hasrow = myrec != 0xFFFFFFFFu;
@@ -532,9 +545,37 @@ __device__ __forceinline__ void quad_body(
     c = uni(c * c_temp);
     __syncthreads();
   }
+  if (res_mode & RES_SCALE_ONLY) {  // setup / after a matrix update: D, E, c of this data into the record, no solve
+    ME;
+    if (me.owner) rec[rec_D(n, m) + S.perm[me.j]] = ld(lds, L.cD + me.j * 8);
+    for (int i = me.t; i < m; i += QT) rec[rec_E(n, m) + i] = ld(lds, L.rec + (unsigned)i * RECB + F_E);
+    if (me.t == 0) { rec[REC_C] = c; rec[REC_FLAG] = 1.0; }
+    return;
+  }
+  if (res_solve) {  // the stored factors in one pass over the raw data: P <- c D P D, A <- E A D, q <- c D q
+    ME;
+    c = uni(rec[REC_C]);
+    const int j = me.j;
+    if (me.owner) {
+      const int q0 = *(const lshort *)(lds + L.Fp + 2 * j), q1 = *(const lshort *)(lds + L.Fp + 2 * j + 2);
+      for (int q = q0; q < q1; q++) {
+        const int cc = *(const lshort *)(lds + L.Fc + 2 * q);
+        const int lo = cc < j ? cc : j, hi = cc < j ? j : cc;
+        sd(lds, L.Pv + q * 8, c * ((ld(lds, L.Pv + q * 8) * ld(lds, L.cD + lo * 8)) * ld(lds, L.cD + hi * 8)));
+      }
+      sd(lds, L.cq + j * 8, c * (ld(lds, L.cq + j * 8) * ld(lds, L.cD + j * 8)));
+    }
+    if (me.col) {
+      const double dj = ld(lds, L.cD + j * 8);
+      col_walk(me, [&](int e, unsigned voff, unsigned ro) {
+        if (ro != ZREC) sd(lds, voff, (ld(lds, voff) * ld(lds, L.rec + ro + F_E)) * dj);
+      });
+    }
+    __syncthreads();
+  }
   const double cinv = uni(1.0 / c);
-  // ---- scaled bounds, K1: classes and rho ------------------------------------------------------------------------
-  double rho = uni(fmin(fmax(st.rho, B_RHO_MIN), B_RHO_MAX));
+  // ---- scaled bounds, K1: classes and rho (a resident solve goes on with the rho its last solve ended on) -------------
+  double rho = uni(fmin(fmax(res_solve ? rec[REC_RHO] : st.rho, B_RHO_MIN), B_RHO_MAX));
   auto set_rho = [&](bool classify) {
     for (int i = tid(); i < m; i += QT) {
       const unsigned r = (unsigned)i * RECB;
@@ -1073,6 +1114,16 @@ __device__ __forceinline__ void quad_body(
       o[0] = (double)iter; o[1] = (double)status; o[2] = pri_res; o[3] = dua_res;
       if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)rho_updates; }
     }
+    if (double *const rec = parked_ptr(*(const lu64 *)(lds + L.nrm + 8 * N_RECORD))) {  // the scaled iterate and rho stay: the next solve starts from them
+      // (an instance without a solution -- infeasible, non-convex -- starts its next solve from zero, as the oracle's
+      // store_solution cold-starts it; rho stays)
+      if (me.owner) rec[rec_x(n, m) + S.perm[me.j]] = has_sol ? ld(lds, L.cx + me.j * 8) : 0.0;
+      for (int i = me.t; i < m; i += QT) {
+        const d2_t zy = ld2at(lds, L.rec + (unsigned)i * RECB + F_Z);
+        rec[rec_z(n, m) + i] = has_sol ? zy.x : 0.0; rec[rec_y(n, m) + i] = has_sol ? zy.y : 0.0;
+      }
+      if (me.t == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; }
+    }
   }
 #undef ME
 }
@@ -1084,18 +1135,18 @@ __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(3, 3))) void
     Sched S, OSQPSettings st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,
     const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,
     double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,
-    int info_stride, int info_cols) {
+    int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
   quad_body<NH, KC, KE, CH, CN, CM, CA, CF>(S, st, count, Px_all, Ax_all, q_all, l_all, u_all, x_out, y_out, info_out, x_stride, y_stride,
-                                            info_stride, info_cols);
+                                            info_stride, info_cols, rec_all, rec_stride, res_mode);
 }
 template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF>
 __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_batch_quad2(
     Sched S, OSQPSettings st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,
     const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,
     double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,
-    int info_stride, int info_cols) {
+    int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
   quad_body<NH, KC, KE, CH, CN, CM, CA, CF>(S, st, count, Px_all, Ax_all, q_all, l_all, u_all, x_out, y_out, info_out, x_stride, y_stride,
-                                            info_stride, info_cols);
+                                            info_stride, info_cols, rec_all, rec_stride, res_mode);
 }
 
 }  // namespace quad

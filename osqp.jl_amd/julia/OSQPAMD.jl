@@ -244,6 +244,96 @@ function batch_mpc_solve!(b::MpcBatch, packed::Ptr{Cdouble})
     return nothing
 end
 
+# ---------------------------------------------------------------------------------------------------------
+# The resident batch of the caller's own QPs (include/osqp_amd.h: osqp_amd_batch_setup ... _resolve): `count` QPs sharing
+# one sparsity pattern, set up once, then `batch_update!` / `batch_warm_start!` / `batch_solve!` as often as wanted -- the
+# life cycle of `OSQP.setup!` / `update!` / `warm_start!` / `solve!`, instance by instance, without leaving HBM.  P (upper
+# triangle) and A give the pattern; the value arrays are `count` columns of a Julia matrix (column i = instance i: the
+# row-major [count x .] layout of the C side).  Array arguments are host `Matrix{Float64}` (where = 0) or device
+# pointers `Ptr{Cdouble}` (where = 1, e.g. from AMDGPU.jl).  (Not executed by the test suite, like the rest of this file;
+# the Python mirror `batch.ResidentBatch` is what the tests drive.)
+# ---------------------------------------------------------------------------------------------------------
+mutable struct ResidentBatch
+    handle::Ptr{Cvoid}
+    count::Int
+    n::Int
+    m::Int
+end
+
+function batch_setup(P::SparseMatrixCSC, A::SparseMatrixCSC, Px::Matrix{Float64}, Ax::Matrix{Float64}, q::Matrix{Float64},
+                     l::Matrix{Float64}, u::Matrix{Float64}; device::Integer = 0, settings...)
+    Pu = triu(P)
+    n, m, count = size(A, 2), size(A, 1), size(q, 2)
+    size(Px) == (nnz(Pu), count) || error("Px: expected $(nnz(Pu)) x $(count)")
+    size(Ax) == (nnz(A), count) || error("Ax: expected $(nnz(A)) x $(count)")
+    size(q, 1) == n || error("q: expected $(n) x $(count)")
+    size(l) == (m, count) && size(u) == (m, count) || error("l, u: expected $(m) x $(count)")
+    stgs = OSQP.Settings(Dict{Symbol,Any}(settings))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    Pp, Pi = Vector{Cc_int}(Pu.colptr .- 1), Vector{Cc_int}(Pu.rowval .- 1)
+    Ap, Ai = Vector{Cc_int}(A.colptr .- 1), Vector{Cc_int}(A.rowval .- 1)
+    flag = ccall((:osqp_amd_batch_setup, lib), Cc_int,
+                 (Ptr{Ptr{Cvoid}}, Cc_int, Cc_int, Cc_int, Ptr{Cc_int}, Ptr{Cc_int}, Ptr{Cdouble}, Ptr{Cc_int}, Ptr{Cc_int}, Ptr{Cdouble},
+                  Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{OSQP.Settings}, Cc_int),
+                 h, count, n, m, Pp, Pi, Px, Ap, Ai, Ax, q, l, u, Ref(stgs), device)
+    flag == 0 || error("Error in batched setup: $(last_error())")
+    b = ResidentBatch(h[], count, n, m)
+    finalizer(x -> ccall((:osqp_amd_batch_destroy, lib), Cc_int, (Ptr{Cvoid},), x.handle), b)
+    return b
+end
+
+const BatchArg = Union{Nothing,Matrix{Float64},Ptr{Cdouble}}
+_batch_ptr(a::Nothing) = Ptr{Cdouble}(C_NULL)
+_batch_ptr(a::Matrix{Float64}) = pointer(a)
+_batch_ptr(a::Ptr{Cdouble}) = a
+_batch_where(args...) = any(a -> a isa Ptr{Cdouble}, args) ? 1 : 0
+
+"New q / l / u / values of P / values of A for every instance, in the order of `OSQP.update!`; `nothing` keeps what is there."
+function batch_update!(b::ResidentBatch; q::BatchArg = nothing, l::BatchArg = nothing, u::BatchArg = nothing,
+                       Px::BatchArg = nothing, Ax::BatchArg = nothing)
+    GC.@preserve q l u Px Ax begin
+        if q !== nothing
+            flag = ccall((:osqp_amd_batch_update_lin_cost, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), b.handle, _batch_ptr(q), _batch_where(q))
+            flag == 0 || error("Error in batched update: $(last_error())")
+        end
+        if l !== nothing || u !== nothing
+            flag = ccall((:osqp_amd_batch_update_bounds, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                         b.handle, _batch_ptr(l), _batch_ptr(u), _batch_where(l, u))
+            flag == 0 || error("Error in batched update: $(last_error())")
+        end
+        if Px !== nothing || Ax !== nothing
+            flag = ccall((:osqp_amd_batch_update_matrices, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                         b.handle, _batch_ptr(Px), _batch_ptr(Ax), _batch_where(Px, Ax))
+            flag == 0 || error("Error in batched update: $(last_error())")
+        end
+    end
+    return nothing
+end
+
+function batch_warm_start!(b::ResidentBatch; x::BatchArg = nothing, y::BatchArg = nothing)
+    GC.@preserve x y begin
+        flag = ccall((:osqp_amd_batch_warm_start, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, _batch_ptr(x), _batch_ptr(y), _batch_where(x, y))
+    end
+    flag == 0 || error("Error in batched warm start: $(last_error())")
+    return nothing
+end
+
+"Solve every instance -> (x [n x count], y [m x count], info [6 x count]: iter, status_val, pri_res, dua_res, obj_val, rho_updates)."
+function batch_solve!(b::ResidentBatch)
+    x, y, info = Matrix{Float64}(undef, b.n, b.count), Matrix{Float64}(undef, b.m, b.count), Matrix{Float64}(undef, 6, b.count)
+    flag = ccall((:osqp_amd_batch_resolve, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int), b.handle, x, y, info, 0)
+    flag == 0 || error("Error in batched solve: $(last_error())")
+    return x, y, info
+end
+
+"The same into device arrays (pointers to n * count, m * count, 6 * count doubles on the handle's device)."
+function batch_solve!(b::ResidentBatch, x::Ptr{Cdouble}, y::Ptr{Cdouble}, info::Ptr{Cdouble})
+    flag = ccall((:osqp_amd_batch_resolve, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int), b.handle, x, y, info, 1)
+    flag == 0 || error("Error in batched solve: $(last_error())")
+    return nothing
+end
+
 "In-place all-gather of `count` doubles per rank on a device buffer, on the library's communicator."
 function comm_all_gather!(comm::Ptr{Cvoid}, buf::Ptr{Cdouble}, count::Integer)
     flag = ccall((:osqp_amd_comm_all_gather, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), comm, buf, count)

@@ -202,6 +202,17 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_mpc_create": (c_int, [C.POINTER(C.c_void_p), c_int, C.c_ulonglong, C.POINTER(Settings), C.c_void_p, c_int]),
     "osqp_amd_batch_mpc_solve": (c_int, [C.c_void_p, C.c_void_p]),
     "osqp_amd_batch_destroy": (c_int, [C.c_void_p]),
+    # the resident batch (include/osqp_amd.h: osqp_amd_batch_setup ...): array arguments are host or device addresses by `where`
+    "osqp_amd_batch_setup": (
+        c_int,
+        [C.POINTER(C.c_void_p), c_int, c_int, c_int, c_int_p, c_int_p, c_float_p, c_int_p, c_int_p, c_float_p,
+         c_float_p, c_float_p, c_float_p, C.POINTER(Settings), c_int],
+    ),
+    "osqp_amd_batch_update_lin_cost": (c_int, [C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_update_bounds": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_update_matrices": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_warm_start": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_resolve": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_last_kernel": (c_int, []),
     "osqp_amd_device_alloc": (C.c_void_p, [c_int, c_int]),
     "osqp_amd_device_free": (c_int, [C.c_void_p, c_int]),
