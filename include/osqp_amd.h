@@ -392,7 +392,7 @@ c_int osqp_amd_apply(OSQPWorkspace *work, c_int op, const c_float *in, c_float *
 
 /* Which kernel the last batched solve of this process ran (tests, benchmarks): -1 the 512-thread kernel (one QP per eight
  * wavefronts, the factorisation through an n x n scratch in global memory), k >= 0 entry k of the table of instantiations of
- * the four-wavefront kernel (csrc/batch.hip DevicePattern::kQuadCfg; 0 = the MPC family with its shape compiled in), -2 none yet. */
+ * the four-wavefront kernel (csrc/batch_common.hpp OQ_QUAD_ENTRIES; 0 = the MPC family with its shape compiled in), -2 none yet. */
 c_int osqp_amd_batch_last_kernel(void);
 
 /* Batched path: `count` independent QPs that

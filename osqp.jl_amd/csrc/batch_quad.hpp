@@ -1,8 +1,9 @@
 // batch_quad.hpp -- the batched small-QP kernel, round 4: ONE QP PER FOUR WAVEFRONTS, THE INVERSE IN REGISTERS AS FOUR
-// QUADRANTS (row K11 of SURVEY.md section 8a).  Included by batch.hip inside namespace oq::{anonymous} (it uses the LDS
-// pointer types and the small helpers defined there).
+// QUADRANTS (row K11 of SURVEY.md section 8a).  Stands on batch_common.hpp (LDS pointer types, small helpers, the state
+// record, the table of its instantiations); its host-side schedule is built in batch_sched.hpp, launch_batch (batch.hip)
+// dispatches to it.
 //
-// Why a second decomposition (the 512-thread kernel in batch.hip stays for the patterns this one does not take): with one
+// Why a second decomposition (the 512-thread kernel in batch_solve.hpp stays for the patterns this one does not take): with one
 // QP per 512 threads every phase of an ADMM iteration gives a wavefront ~20 useful multiply-adds between two
 // eight-wavefront barriers, two QPs fit a compute unit, and the factorisation goes through an n x n scratch in global
 // memory (5.5 GB of HBM / L2 traffic per 4096 QPs).  Here a QP is a 256-thread workgroup, THREE are resident per compute
@@ -34,6 +35,10 @@
 #include <type_traits>
 #include <utility>
 
+#include "batch_common.hpp"
+
+namespace oq {
+namespace {
 namespace quad {
 
 #ifdef OQ_BATCH_PROFILE  // experiment build (make prof): clock64() stamps per phase, printed by instance 0
@@ -56,7 +61,7 @@ struct Sched {  // device pointers, shared by all instances (built on the host f
   int ns;                           // term slots per thread and window (a multiple of 4)
   // two-ended sweeps (round 6): the first p1_top pivots (0, 1, ...) fill in only inside the quadrant (0, 0), the last p1_bot
   // (n - 1, n - 2, ...) only inside (1, 1) -- found on the host by symbolic elimination of the pattern of M; bw: its half
-  // bandwidth (the MPC family: 19, two stages)
+  // bandwidth (the MPC family: kQuadFixedBW, two stages)
   int p1_top, p1_bot, bw;
   int rot;                          // > 0: the roles of the four wavefronts rotate with (workgroup id >> rot) & 3 (which SIMD carries the one-wavefront sweeps)
   const unsigned short *perm;       // [n]: the caller's index of the kernel's variable j (identity, or row half 1 reversed)
@@ -338,7 +343,7 @@ __device__ __forceinline__ void quad_body(
   const int inst = blockIdx.x;
   if (inst >= count) return;
   const int n = CN ? CN : S.n, m = CN ? CM : S.m, nnzA = CN ? CA : S.nnzA, nnzF = CN ? CF : S.nnzF;
-  // resident mode (batch.hip, "the state record"): a workgroup-uniform branch of the prologue and the epilogue
+  // resident mode (batch_common.hpp, "the state record"): a workgroup-uniform branch of the prologue and the epilogue
   const bool res_solve = (res_mode & RES_SOLVE) != 0, res_warm = (res_mode & RES_WARM) != 0;
   double *const rec = res_mode ? rec_all + (size_t)inst * rec_stride : nullptr;
   const Layout L = make_layout(n, m, nnzA, nnzF, NH, KC, KE, CH);
@@ -498,7 +503,7 @@ __device__ __forceinline__ void quad_body(
   };
 
   QPROF(0)
-  // ---- K0: Ruiz equilibration + cost scaling (the arithmetic of batch.hip / oracle scale_data, element for element) ----
+  // ---- K0: Ruiz equilibration + cost scaling (the arithmetic of batch_solve.hpp / oracle scale_data, element for element) ----
   // (a resident solve applies the factors its record holds instead: below)
   double c = 1.0;
   const int nscale = res_solve ? 0 : (int)st.scaling;
@@ -684,7 +689,7 @@ __device__ __forceinline__ void quad_body(
       // column beyond the quadrant (0, 0), and the pivots taken from the top of row half 1 (NH, NH + 1, ... -- the host numbers
       // the variables of that half in REVERSE, S.perm, so that these are the LAST variables of a banded pattern) none outside
       // (1, 1), the two sweeps touch disjoint registers of ONE wavefront each (pivots of a sweep commute; the swept array of
-      // a banded M -- the MPC family: two stages, half bandwidth 19 -- stays zero outside the reach of the pivots taken so
+      // a banded M -- the MPC family: two stages, half bandwidth kQuadFixedBW -- stays zero outside the reach of the pivots taken so
       // far).  Wavefront 0 takes the pivots of half 0, wavefront 3 those of half 1, at the same time and through the same
       // code, each with its own pivot-row buffer and WITHOUT a workgroup barrier (the LDS operations of one wavefront
       // complete in order); the other two wait at the hand-over.  With the half bandwidth compiled in (BWC) a step also skips
@@ -692,7 +697,7 @@ __device__ __forceinline__ void quad_body(
       // pattern of M (0: a pattern without such pivots, the phase is skipped).
       const int T1 = uni(S.p1_top), B1 = uni(S.p1_bot);
       if (T1 + B1 > 0) {
-        constexpr int BWC = CN ? 19 : 0;  // the half bandwidth compiled in (the host leaves the phase out when the pattern's is larger)
+        constexpr int BWC = CN ? kQuadFixedBW : 0;  // the half bandwidth compiled in (the host leaves the phase out when the pattern's is larger)
         ME;
         const unsigned slot8 = (me.cb * NHP + me.cl) * 8, brow8 = (me.hb * NHP + me.lane16) * 8;
         const bool inpad = NHP == 64 || me.cl < NHP;
@@ -1130,23 +1135,21 @@ __device__ __forceinline__ void quad_body(
 
 // Two occupancies: quadrants of at most 50 columns keep three QPs per compute unit (168 vector registers a lane), larger
 // ones (NH = 64: 128 registers of inverse alone) two.
-template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF>
-__global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_batch_quad(
-    Sched S, OSQPSettings st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,
-    const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,
-    double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,
-    int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
-  quad_body<NH, KC, KE, CH, CN, CM, CA, CF>(S, st, count, Px_all, Ax_all, q_all, l_all, u_all, x_out, y_out, info_out, x_stride, y_stride,
-                                            info_stride, info_cols, rec_all, rec_stride, res_mode);
-}
-template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF>
-__global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_batch_quad2(
-    Sched S, OSQPSettings st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,
-    const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,
-    double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,
-    int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
-  quad_body<NH, KC, KE, CH, CN, CM, CA, CF>(S, st, count, Px_all, Ax_all, q_all, l_all, u_all, x_out, y_out, info_out, x_stride, y_stride,
-                                            info_stride, info_cols, rec_all, rec_stride, res_mode);
-}
+// (the last column of OQ_QUAD_ENTRIES names one of the two; the arguments are BatchIO's members in its order)
+#define OQ_QUAD_KERNEL(NAME, WAVES)                                                                                            \
+  template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF>                                                    \
+  __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void NAME(                               \
+      Sched S, OSQPSettings st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,               \
+      const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,                    \
+      double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,       \
+      int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {                            \
+    quad_body<NH, KC, KE, CH, CN, CM, CA, CF>(S, st, count, Px_all, Ax_all, q_all, l_all, u_all, x_out, y_out, info_out, x_stride, \
+                                              y_stride, info_stride, info_cols, rec_all, rec_stride, res_mode);                \
+  }
+OQ_QUAD_KERNEL(k_batch_quad, 3)
+OQ_QUAD_KERNEL(k_batch_quad2, 2)
+#undef OQ_QUAD_KERNEL
 
 }  // namespace quad
+}  // namespace
+}  // namespace oq

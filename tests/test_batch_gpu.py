@@ -85,7 +85,7 @@ def test_batch_generic_shapes_match_oracle(product_lib, oracle_lib, n, m):
     x, y, info = batch.solve_batch(product_lib, pat_P, pat_A, np.array(Px), np.array(Ax).reshape(count, pat_A.nnz), np.array(qs),
                                    np.array(ls).reshape(count, m), np.array(us).reshape(count, m), **OPTS)
     # round 5: every pattern the four-wavefront kernel's schedule can hold runs it (an instantiation per quadrant size and
-    # column / row bound, csrc/batch.hip DevicePattern::kQuadCfg) -- the 512-thread kernel with its global scratch is left
+    # column / row bound, csrc/batch_common.hpp OQ_QUAD_ENTRIES) -- the 512-thread kernel with its global scratch is left
     # with what does not fit (no constraint rows, more than 256 rows, columns / rows beyond 32 entries)
     kernel = product_lib.osqp_amd_batch_last_kernel()
     assert kernel >= 1 if m > 0 else kernel == -1, kernel
