@@ -449,6 +449,19 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             instance: a solve that adapted it hands the adapted value on.  The constraint classes are derived from the
  *             current bounds at the start of each solve.  x_out [count x n], y_out [count x m] (NaN rows for instances
  *             without a solution), info_out [count x 6] doubles: iter, status_val, pri_res, dua_res, obj_val, rho_updates.
+ *             With settings.polish = 1 a second launch then polishes every instance whose status is Solved, as osqp_solve
+ *             does (settings.delta, settings.polish_refine_iter): an accepted polish overwrites the instance's x, y, pri_res,
+ *             dua_res, obj_val and the stored iterate (the next warm solve starts from the polished point); a refused one
+ *             and every instance that is not Solved keep exactly what the solve left.  With where = 0 the results are
+ *             downloaded after the polish launch.
+ *   polish_status(): status_out [count] doubles, status_polish of every instance from the handle's last resolve: 1 accepted,
+ *             -1 refused (the acceptance rule of osqp_solve, or a failed factorisation), 0 not polished (not Solved, or
+ *             polish off).  All 0 before the first resolve.
+ *   update_polish(): the batch form of osqp_update_polish + osqp_update_polish_refine_iter: polish_new in {0, 1},
+ *             polish_refine_iter_new >= 0, otherwise return 1 and the handle is unchanged.  A pattern whose polish working
+ *             set (the n x n condensed KKT matrix as a packed triangle, the values of A and P, 5 n + 6 m doubles) exceeds
+ *             160 KB of LDS is refused with return 1 and a message naming the bytes -- here and by setup() with polish = 1;
+ *             polish is never skipped silently.
  * where: 0 = the array arguments are host pointers, 1 = device pointers on the handle's device (no host hop: a controller
  * whose state estimate lives in HBM).  A NULL array means "keep" (update_*) / "none" (warm_start).  Every call blocks until
  * done.  Single rank.  The handle is freed by osqp_amd_batch_destroy; it is not interchangeable with the handle of
@@ -463,6 +476,11 @@ c_int osqp_amd_batch_update_bounds(osqp_amd_batch *batch, const c_float *l_all, 
 c_int osqp_amd_batch_update_matrices(osqp_amd_batch *batch, const c_float *Px_all, const c_float *Ax_all, c_int where);
 c_int osqp_amd_batch_warm_start(osqp_amd_batch *batch, const c_float *x_all, const c_float *y_all, c_int where);
 c_int osqp_amd_batch_resolve(osqp_amd_batch *batch, c_float *x_out, c_float *y_out, c_float *info_out, c_int where);
+c_int osqp_amd_batch_polish_status(osqp_amd_batch *batch, c_float *status_out, c_int where);
+c_int osqp_amd_batch_update_polish(osqp_amd_batch *batch, c_int polish_new, c_int polish_refine_iter_new);
+/* Diagnostic, like osqp_amd_batch_last_kernel: how many polish launches this process has made so far.  A resolve with
+ * polish = 0 makes none -- its launch sequence is the one of a library without the polish kernel. */
+c_int osqp_amd_batch_polish_launches(void);
 
 /* Device memory for callers without an allocator of their own (the packed result array above): plain hipMalloc / hipFree /
  * hipMemcpy on `device`.  copy kind: 0 device -> host, 1 host -> device, 2 device -> device; blocking. */
@@ -472,11 +490,13 @@ c_int osqp_amd_device_copy(void *dst, const void *src, c_int bytes, c_int kind, 
 
 /* Differences between the batched path and osqp_setup / osqp_solve: instances share one sparsity pattern, n <= 128,
  * fewer than 65536 rows and non-zeros, everything must fit 160 KB of LDS; `adaptive_rho_interval` = 0 (automatic) means
- * every 100 iterations (there is no per-instance clock); `polish`, `time_limit`, `verbose` and `linsys_solver` are
- * ignored (the reduced KKT system is factorised on chip); data and settings are validated as by osqp_setup (1 = data,
- * 2 = settings).  The one-shot entries (osqp_amd_batch_solve, _solve_generated, _mpc_create / _mpc_solve) also ignore
- * `warm_start`: they equilibrate and start from zero every time.  The resident handle (osqp_amd_batch_setup) honours it
- * and keeps scaling, iterate and rho between solves, as described above. */
+ * every 100 iterations (there is no per-instance clock); `time_limit`, `verbose` and `linsys_solver` are ignored (the
+ * reduced KKT system is factorised on chip); data and settings are validated as by osqp_setup (1 = data, 2 = settings).
+ * The one-shot entries (osqp_amd_batch_solve, _solve_generated, _mpc_create / _mpc_solve) also ignore `warm_start` and
+ * `polish` (with `polish_refine_iter` and `delta`): they equilibrate, start from zero every time and return the ADMM
+ * iterate.  The resident handle (osqp_amd_batch_setup) honours all of them: it keeps scaling, iterate and rho between
+ * solves and polishes the Solved instances after the ADMM launch when `polish` = 1, as described above; the per-instance
+ * status_polish is read with osqp_amd_batch_polish_status (the six info columns do not change). */
 
 /* Select the HIP device for workspaces created afterwards by this process
  * (one process per GPU: pass LOCAL_RANK). */

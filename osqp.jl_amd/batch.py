@@ -242,6 +242,7 @@ class ResidentBatch:
         Pp, Pi = np.ascontiguousarray(P.indptr, dtype=np.int64), np.ascontiguousarray(P.indices, dtype=np.int64)
         Ap, Ai = np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int64)
         stgs = make_settings(lib, settings)
+        self.polish_refine_iter = int(stgs.polish_refine_iter)
         rc = lib.osqp_amd_batch_setup(C.byref(self.handle), count, self.n, self.m, _iptr(Pp), _iptr(Pi), _fptr(Px), _iptr(Ap), _iptr(Ai),
                                       _fptr(Ax), _fptr(q), _fptr(l), _fptr(u), C.byref(stgs), self.device)
         if rc != 0:
@@ -301,6 +302,34 @@ class ResidentBatch:
             ptrs.append(_batch_array(name, a, (self.count, k))[1])
         self._call("solve", self.lib.osqp_amd_batch_resolve(self.handle, ptrs[0], ptrs[1], ptrs[2], 1))
         return out
+
+    def polish_status(self, out=None):
+        """status_polish of every instance from the last `solve()`: 1 accepted, -1 refused, 0 not polished (the instance was
+        not Solved, or `polish` is off).  out=None: a numpy int array [count]; out = a device array [count x 1] of float64:
+        filled in place and returned."""
+        if out is None:
+            st = np.empty(self.count)
+            self._call("polish status", self.lib.osqp_amd_batch_polish_status(self.handle, st.ctypes.data, 0))
+            return st.astype(np.int64)
+        if not hasattr(out, "data_ptr"):
+            raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
+        ptr = _batch_array("out", out, (self.count, 1))[1]
+        self._call("polish status", self.lib.osqp_amd_batch_polish_status(self.handle, ptr, 1))
+        return out
+
+    def update_polish(self, polish, polish_refine_iter=None):
+        """Switch polishing of the following solves on (1 / True) or off (0 / False), as `update_settings(polish=...)` does
+        for a single model; `polish_refine_iter` (>= 0) is kept when None.  Anything else raises and changes nothing."""
+        if isinstance(polish, (bool, np.bool_)):
+            polish = int(polish)
+        if not isinstance(polish, (int, np.integer)) or polish not in (0, 1):
+            raise ValueError(f"polish: expected 0 or 1, got {polish!r}")
+        if polish_refine_iter is None:
+            polish_refine_iter = getattr(self, "polish_refine_iter", 3)
+        if not isinstance(polish_refine_iter, (int, np.integer)) or isinstance(polish_refine_iter, bool) or polish_refine_iter < 0:
+            raise ValueError(f"polish_refine_iter: expected a nonnegative integer, got {polish_refine_iter!r}")
+        self._call("update", self.lib.osqp_amd_batch_update_polish(self.handle, int(polish), int(polish_refine_iter)))
+        self.polish_refine_iter = int(polish_refine_iter)
 
     def alloc(self):
         """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints."""

@@ -11,6 +11,8 @@
 //                     pattern with n <= 128 (run-time shapes, dense P, long rows);
 //   batch_sched.hpp   host side: the analysis of the shared pattern (HostPattern), its device copy and the schedule of the
 //                     four-wavefront kernel for the first table entry it fits (DevicePattern);
+//   batch_polish.hpp  k_batch_polish -- solution polishing for the resident batch, a launch of its own after the ADMM launch
+//                     when the handle's settings.polish is 1; the solve kernels know nothing of it;
 //   this file         the small kernels (warm start, bound check, MPC generator), the launcher (launch_batch), the handle
 //                     (BatchPlan) and the C ABI.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
@@ -22,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "batch_polish.hpp"
 #include "batch_quad.hpp"
 #include "batch_sched.hpp"
 #include "batch_solve.hpp"
@@ -30,6 +33,7 @@
 namespace oq {
 namespace {
 
+int g_batch_polish_launches = 0;  // launches of k_batch_polish by this process (osqp_amd_batch_polish_launches)
 int g_batch_last_kernel = -2;  // what launch_batch launched last: -1 the 512-thread kernel, >= 0 the number of the entry of OQ_QUAD_ENTRIES
 inline bool batch_quad_enabled() {  // OSQP_AMD_BATCH_QUAD=0: the MPC family on the 512-thread kernel (A/B runs, tests)
   const char *e = getenv("OSQP_AMD_BATCH_QUAD");
@@ -237,6 +241,10 @@ struct BatchPlan : BatchData {
   int n = 0, m = 0, nnzA = 0, nnzP = 0, rec_stride = 0;
   DevBuf<double> rec, in_a, in_b, x_out, y_out, info_out;
   DevBuf<int> bad;
+  // polish (settings.polish = 1): status_polish of every instance from the last resolve (1, -1, 0); pstat_live = 0: the
+  // last resolve did not polish (or there was none) and all are 0, whatever the buffer holds
+  DevBuf<double> pstat;
+  bool pstat_live = false;
 };
 
 // The checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings], shared by the
@@ -290,6 +298,29 @@ void resident_equilibrate(BatchPlan &b, hipStream_t s) {
   io.rec = b.rec.get(); io.rec_stride = b.rec_stride; io.res_mode = RES_SCALE_ONLY;
   launch_batch(b.dp, b.st, b.count, io, s);
 }
+// the LDS a polish launch of this pattern needs; a pattern it cannot serve is refused where polish is asked for (setup,
+// osqp_amd_batch_update_polish), never skipped
+void polish_check_fits(const Pattern &P) {
+  const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
+  if (L.total > polish::kLdsLimit)
+    throw Error(1, "instance too large to polish on the LDS-resident batched path (needs " + std::to_string(L.total) + " bytes of LDS, " +
+                       std::to_string(polish::kLdsLimit) + " available); set polish = 0");
+}
+// polish() of the oracle on every Solved instance of the launch that has just written io.x / io.y / io.info and the records
+void launch_polish(BatchPlan &b, const BatchIO &io, hipStream_t s) {
+  const Pattern &P = b.dp.P;
+  polish_check_fits(P);
+  const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
+  polish::Args a;
+  a.Px = io.Px; a.Ax = io.Ax; a.q = io.q; a.l = io.l; a.u = io.u;
+  a.x = io.x; a.y = io.y; a.info = io.info; a.rec = io.rec; a.status = b.pstat.get();
+  a.x_stride = io.x_stride; a.y_stride = io.y_stride; a.info_stride = io.info_stride; a.rec_stride = io.rec_stride;
+  a.refine = (int)b.st.polish_refine_iter; a.unscaled = b.st.scaling && !b.st.scaled_termination;
+  a.delta = b.st.delta;
+  HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_polish, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+  g_batch_polish_launches++;
+  OQ_LAUNCH(polish::k_batch_polish, dim3(b.count), dim3(polish::PT), (size_t)L.total, s, P, b.count, L, a);
+}
 #define OQ_BATCH_CATCH                                                                          \
   catch (const Error &er) { set_last_error(er.what()); return er.code ? er.code : 6; }         \
   catch (const std::exception &ex) { set_last_error(ex.what()); return 6; }
@@ -302,6 +333,7 @@ using namespace oq;
 extern "C" {
 
 c_int osqp_amd_batch_last_kernel(void) { return g_batch_last_kernel; }
+c_int osqp_amd_batch_polish_launches(void) { return g_batch_polish_launches; }
 
 c_int osqp_amd_batch_solve(c_int count, c_int n, c_int m, const c_int *Pp, const c_int *Pi, const c_float *Px_all, const c_int *Ap,
                            const c_int *Ai, const c_float *Ax_all, const c_float *q_all, const c_float *l_all, const c_float *u_all,
@@ -417,9 +449,10 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, 
     b->resident = true; b->device = (int)device; b->total = b->count = (int)count; b->st = *settings;
     b->n = (int)n; b->m = (int)m; b->nnzP = (int)Pp[n]; b->nnzA = (int)Ap[n]; b->rec_stride = rec_doubles((int)n, (int)m);
     b->dp.build(host_pattern(prob), s);
+    if (settings->polish) polish_check_fits(b->dp.P);
     const size_t cnt = (size_t)count;
     b->upload(prob, b->dp.P, s);
-    b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6); b->bad.alloc(1);
+    b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6); b->bad.alloc(1); b->pstat.alloc(cnt);
     // the records: a zero iterate (the first solve starts from zero either way), the rho of the settings
     std::vector<double> hrec(cnt * b->rec_stride, 0.0);
     for (size_t i = 0; i < cnt; i++) hrec[i * b->rec_stride + REC_RHO] = settings->rho;
@@ -513,12 +546,44 @@ c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_
     io.x_stride = b->n; io.y_stride = b->m; io.info_stride = io.info_cols = 6;
     io.rec = b->rec.get(); io.rec_stride = b->rec_stride; io.res_mode = RES_SOLVE | (b->st.warm_start ? RES_WARM : 0);
     launch_batch(b->dp, b->st, b->count, io, s);
+    b->pstat_live = b->st.polish != 0;
+    if (b->pstat_live) launch_polish(*b, io, s);
     if (!where) {
       b->x_out.download(x_out, (size_t)b->count * b->n, s);
       if (b->m) b->y_out.download(y_out, (size_t)b->count * b->m, s);
       b->info_out.download(info_out, (size_t)b->count * 6, s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_polish_status(osqp_amd_batch *handle, c_float *status_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!status_out) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const size_t len = (size_t)b->count;
+    if (!b->pstat_live) {  // no resolve yet, or the last one did not polish: all 0
+      if (where) HIP_CHECK(hipMemsetAsync(status_out, 0, len * sizeof(double), s));
+      else std::fill(status_out, status_out + len, 0.0);
+    } else if (where) copy_d2d(status_out, b->pstat.get(), len, s);
+    else b->pstat.download(status_out, len, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_update_polish(osqp_amd_batch *handle, c_int polish_new, c_int polish_refine_iter_new) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (polish_new != 0 && polish_new != 1) { set_last_error("polish must be 0 or 1"); return 1; }
+  if (polish_refine_iter_new < 0) { set_last_error("polish_refine_iter must be nonnegative"); return 1; }
+  try {
+    if (polish_new) polish_check_fits(b->dp.P);
+    b->st.polish = polish_new; b->st.polish_refine_iter = polish_refine_iter_new;
     return 0;
   } OQ_BATCH_CATCH
 }

@@ -1,0 +1,249 @@
+// batch_polish.hpp -- solution polishing for the resident batch (osqp_amd_batch_resolve with settings.polish = 1): a kernel
+// of its own, launched after the ADMM launch.  The semantics are polish() / form_Ared() of oracle/osqp_oracle.c, instance by
+// instance, in the SCALED space: the record row (batch_common.hpp) holds c, D, E and the scaled x, z, y the solve left, the
+// handle holds the raw data, and D, E, c are applied on the fly exactly as the solve kernels' prologue applies them.
+//
+// One workgroup (PT threads) per instance; only instances whose ADMM status is Solved do anything.  The regularised KKT
+// system [P + delta I, Aa'; Aa, -delta I] (Aa: the active rows) is solved in its condensed form -- the constraint block
+// eliminated exactly:
+//     M = P + delta I + (1 / delta) Aa' Aa     (n x n, symmetric positive definite)
+//     d_x = M^-1 (r_x + Aa' r_y / delta),   d_y = (Aa d_x - r_y) / delta
+// which is the matrix the batched path assembles for ADMM with sigma -> delta and rho_i -> 1 / delta on the active rows, 0
+// elsewhere: the term lists of A' diag(.) A and the full-P CSR of the shared pattern are reused.  The full (n + m_act)-square
+// matrix would not fit the LDS (the MPC family has >= 60 active rows on n = 100); M does for every n <= 128.
+//
+// LDS (doubles; make_layout): M as a packed lower triangle, row-major (entry (i, j), i >= j, at i (i + 1) / 2 + j: a row of
+// the factor is contiguous -- the backward substitution and the trailing update walk rows with consecutive lanes on
+// consecutive words), the scaled values of A and of the full P, 1 / pivot [n], the pivot column [n], q, x, t (right-hand side
+// / correction) [n each], l, u, y, r_y, z, act [m each], and a small block for reductions.  Nothing of an instance touches
+// global scratch.  tests/batch_polish_ref.py is the numpy model of this file.
+#pragma once
+#include "batch_common.hpp"
+
+namespace oq {
+namespace {
+namespace polish {
+
+constexpr int PT = 256;  // threads per workgroup
+constexpr int PW = PT / 64;
+
+struct Layout { int M, Av, Pv, rdg, col, q, x, t, l, u, y, ry, z, act, red, total; };  // offsets in doubles; total in bytes
+inline Layout make_layout(int n, int m, int nnzA, int nnzF) {
+  Layout L;
+  int o = 0;
+  auto take = [&o](int k) { const int at = o; o += (k + 1) & ~1; return at; };
+  L.M = take(n * (n + 1) / 2); L.Av = take(nnzA); L.Pv = take(nnzF);
+  L.rdg = take(n); L.col = take(n); L.q = take(n); L.x = take(n); L.t = take(n);
+  L.l = take(m); L.u = take(m); L.y = take(m); L.ry = take(m); L.z = take(m); L.act = take(m);
+  L.red = take(4 * PW);
+  L.total = o * (int)sizeof(double);
+  return L;
+}
+constexpr int kLdsLimit = 160 * 1024;
+
+struct Args {
+  const double *Px, *Ax, *q, *l, *u;
+  double *x, *y, *info, *rec, *status;
+  int x_stride, y_stride, info_stride, rec_stride;
+  int refine, unscaled;  // unscaled: scaling on and scaled_termination off (residuals in the caller's units)
+  double delta;
+};
+
+__device__ __forceinline__ int tri(int i, int j) { return ((i * (i + 1)) >> 1) + j; }  // i >= j
+
+// max / max / sum over the workgroup of (a, b, c); every thread gets the results.  NaN propagates through the maxima.
+__device__ __forceinline__ void reduce3(ldouble *red, double &a, double &b, double &c) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { a = nmax(a, __shfl_xor(a, o, 64)); b = nmax(b, __shfl_xor(b, o, 64)); c += __shfl_xor(c, o, 64); }
+  __syncthreads();  // whoever still reads the block of an earlier reduction
+  if ((tid & 63) == 0) { red[3 * (tid >> 6)] = a; red[3 * (tid >> 6) + 1] = b; red[3 * (tid >> 6) + 2] = c; }
+  __syncthreads();
+  a = red[0]; b = red[1]; c = red[2];
+#pragma unroll
+  for (int w = 1; w < PW; w++) { a = nmax(a, red[3 * w]); b = nmax(b, red[3 * w + 1]); c += red[3 * w + 2]; }
+}
+
+// t <- M^-1 t through the Cholesky factor in LDS, by the first wavefront: lane L holds entries L and L + 64 of the vector in
+// registers; step k hands the finished entry round (one cross-lane read) and takes one column (forward: L w = t) or one row
+// (backward: L' x = w) of the factor out of the rest.  The other wavefronts wait at the caller's barrier.
+__device__ __forceinline__ void factor_solve(int n, const ldouble *M, const ldouble *rdg, ldouble *t) {
+  const int lane = threadIdx.x;
+  if (lane >= 64) return;
+  const int i0 = lane, i1 = lane + 64;
+  double b0 = i0 < n ? t[i0] : 0.0, b1 = i1 < n ? t[i1] : 0.0;
+  for (int k = 0; k < n; k++) {
+    const double m0 = (i0 > k && i0 < n) ? M[tri(i0, k)] : 0.0, m1 = (i1 > k && i1 < n) ? M[tri(i1, k)] : 0.0;
+    const double wk = __shfl(k < 64 ? b0 : b1, k & 63, 64) * rdg[k];
+    if (lane == (k & 63)) { if (k < 64) b0 = wk; else b1 = wk; }
+    b0 -= m0 * wk; b1 -= m1 * wk;
+  }
+  for (int k = n - 1; k >= 0; k--) {
+    const double m0 = i0 < k ? M[tri(k, i0)] : 0.0, m1 = i1 < k ? M[tri(k, i1)] : 0.0;
+    const double xk = __shfl(k < 64 ? b0 : b1, k & 63, 64) * rdg[k];
+    if (lane == (k & 63)) { if (k < 64) b0 = xk; else b1 = xk; }
+    b0 -= m0 * xk; b1 -= m1 * xk;
+  }
+  if (i0 < n) t[i0] = b0;
+  if (i1 < n) t[i1] = b1;
+}
+
+__global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layout L, Args a) {
+  const int inst = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
+  if (inst >= count) return;
+  double *const info = a.info + (size_t)inst * a.info_stride;
+  if ((int)info[1] != OSQP_SOLVED) {  // nothing to polish: x, y, info and the record stay as the solve left them
+    if (tid == 0) a.status[inst] = 0.0;
+    return;
+  }
+  ldouble *const lds = (ldouble *)lds_raw;
+  ldouble *const M = lds + L.M, *const Av = lds + L.Av, *const Pv = lds + L.Pv, *const rdg = lds + L.rdg, *const col = lds + L.col;
+  ldouble *const q = lds + L.q, *const x = lds + L.x, *const t = lds + L.t, *const l = lds + L.l, *const u = lds + L.u;
+  ldouble *const y = lds + L.y, *const ry = lds + L.ry, *const z = lds + L.z, *const act = lds + L.act, *const red = lds + L.red;
+  double *const rec = a.rec + (size_t)inst * a.rec_stride;
+  const double *const D = rec + rec_D(n, m), *const E = rec + rec_E(n, m);
+  const double c = rec[REC_C], cinv = 1.0 / c, delta = a.delta;
+  const double pri0 = info[2], dua0 = info[3];
+
+  // ---- the scaled data (as the solve prologue forms them), the iterate of the record, the active sets ----
+  const double *const Axi = a.Ax + (size_t)inst * P.nnzA, *const Pxi = a.Px + (size_t)inst * P.nnzP;
+  for (int j = tid; j < n; j += PT) {
+    const double dj = D[j];
+    for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) Av[k] = (Axi[k] * E[P.Ai[k]]) * dj;
+    for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) {
+      const int cc = P.Fc[f];
+      const int lo = cc < j ? cc : j, hi = cc < j ? j : cc;
+      Pv[f] = c * ((Pxi[P.Fmap[f]] * D[lo]) * D[hi]);
+    }
+    q[j] = c * (a.q[(size_t)inst * n + j] * dj);
+    x[j] = rec[rec_x(n, m) + j];
+  }
+  for (int i = tid; i < m; i += PT) {
+    const double e = E[i];
+    const double li = fmax(a.l[(size_t)inst * m + i], -OSQP_INFTY) * e, ui = fmin(a.u[(size_t)inst * m + i], OSQP_INFTY) * e;
+    const double zi = rec[rec_z(n, m) + i], yi = rec[rec_y(n, m) + i];
+    l[i] = li; u[i] = ui;
+    const double on = (zi - li < -yi) ? -1.0 : ((ui - zi < yi) ? 1.0 : 0.0);  // lower first, as form_Ared
+    act[i] = on;
+    ry[i] = on < 0.0 ? li : (on > 0.0 ? ui : 0.0);  // the right-hand side of the first solve: [-q; l_low; u_upp]
+    y[i] = 0.0;
+  }
+  for (int e = tid; e < n * (n + 1) / 2; e += PT) M[e] = 0.0;
+  __syncthreads();
+
+  // ---- M = P + delta I + Aa' Aa / delta, lower triangle ----
+  for (int p = tid; p < P.npair; p += PT) {
+    double acc = 0.0;
+    for (int s = P.Tp[p]; s < P.Tp[p + 1]; s++) acc += (act[P.Tr[s]] != 0.0 ? 1.0 : 0.0) * Av[P.Ta[s]] * Av[P.Tb[s]];
+    M[tri(P.Ti[p], P.Tj[p])] = acc / delta;
+  }
+  __syncthreads();
+  for (int r = tid; r < n; r += PT) {
+    for (int f = P.Fp[r]; f < P.Fp[r + 1]; f++) {
+      const int cc = P.Fc[f];
+      if (cc <= r) M[tri(r, cc)] += Pv[f];
+    }
+    M[tri(r, r)] += delta;
+  }
+  __syncthreads();
+
+  // ---- Cholesky, right-looking, in place (the diagonal of M keeps the pivot's square; 1 / pivot goes to rdg) ----
+  bool pd = true;
+  {
+    const int tx = tid & 15, ty = tid >> 4;
+    for (int k = 0; k < n; k++) {
+      const double d = M[tri(k, k)];  // final since the barrier that ended step k - 1; not written in step k
+      if (!(d > 0.0)) { pd = false; break; }  // the same value in every thread: a uniform exit
+      const double piv = sqrt(d);
+      if (tid == 0) rdg[k] = 1.0 / piv;
+      for (int i = k + 1 + tid; i < n; i += PT) { const double v = M[tri(i, k)] / piv; M[tri(i, k)] = v; col[i] = v; }
+      __syncthreads();
+      for (int i = k + 1 + ty; i < n; i += 16) {
+        const double ci = col[i];
+        for (int j = k + 1 + tx; j <= i; j += 16) M[tri(i, j)] -= ci * col[j];
+      }
+      __syncthreads();
+    }
+  }
+  if (!pd) {  // as a failed direct_init in the oracle
+    if (tid == 0) a.status[inst] = -1.0;
+    return;
+  }
+
+  // ---- solve with [-q; b_act], then `refine` steps against the unregularised [P, Aa'; Aa, 0] ----
+  for (int it = 0; it <= a.refine; it++) {
+    if (it > 0) {  // r_y = b - Aa x on the active rows (zero elsewhere, so the column walks need no mask)
+      for (int i = tid; i < m; i += PT) {
+        const double on = act[i];
+        double ax = 0.0;
+        if (on != 0.0) for (int s = P.Rp[i]; s < P.Rp[i + 1]; s++) ax += Av[P.Rmap[s]] * x[P.Rc[s]];
+        ry[i] = on != 0.0 ? (on < 0.0 ? l[i] : u[i]) - ax : 0.0;
+      }
+      __syncthreads();
+    }
+    for (int j = tid; j < n; j += PT) {  // t = r_x + Aa' r_y / delta,  r_x = -q - P x - Aa' y (first solve: -q)
+      double rx = -q[j], ar = 0.0;
+      if (it > 0) {
+        double px = 0.0, ay = 0.0;
+        for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) px += Pv[f] * x[P.Fc[f]];
+        for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) ay += Av[k] * y[P.Ai[k]];
+        rx = (rx - px) - ay;
+      }
+      for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) ar += Av[k] * ry[P.Ai[k]];
+      t[j] = rx + ar / delta;
+    }
+    __syncthreads();
+    factor_solve(n, M, rdg, t);
+    __syncthreads();
+    for (int i = tid; i < m; i += PT) {  // d_y = (Aa d_x - r_y) / delta
+      if (act[i] == 0.0) continue;
+      double ad = 0.0;
+      for (int s = P.Rp[i]; s < P.Rp[i + 1]; s++) ad += Av[P.Rmap[s]] * t[P.Rc[s]];
+      const double dy = (ad - ry[i]) / delta;
+      y[i] = it > 0 ? y[i] + dy : dy;
+    }
+    for (int j = tid; j < n; j += PT) x[j] = it > 0 ? x[j] + t[j] : t[j];
+    __syncthreads();
+  }
+
+  // ---- z = A x, (z, y) onto the normal cone of [l, u]; residuals and objective as the termination check defines them ----
+  double pri = 0.0, dua = 0.0, obj = 0.0;
+  for (int i = tid; i < m; i += PT) {
+    double ax = 0.0;
+    for (int s = P.Rp[i]; s < P.Rp[i + 1]; s++) ax += Av[P.Rmap[s]] * x[P.Rc[s]];
+    const double sum = ax + y[i];
+    const double zc = fmin(fmax(sum, l[i]), u[i]);
+    z[i] = zc; y[i] = sum - zc;
+    const double rp = ax - zc;
+    pri = nmax(pri, fabs(a.unscaled ? rp / E[i] : rp));
+  }
+  __syncthreads();
+  for (int j = tid; j < n; j += PT) {
+    double px = 0.0, ay = 0.0;
+    for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) px += Pv[f] * x[P.Fc[f]];
+    for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) ay += Av[k] * y[P.Ai[k]];
+    const double rd = (px + q[j]) + ay;
+    dua = nmax(dua, fabs(a.unscaled ? rd / D[j] : rd));
+    obj += x[j] * (0.5 * px + q[j]);
+  }
+  reduce3(red, pri, dua, obj);
+  if (a.unscaled) dua *= cinv;
+  obj *= cinv;
+
+  // ---- acceptance: lines 635-637 of the oracle ----
+  const bool ok = (pri < pri0 && dua < dua0) || (pri < pri0 && dua0 < 1e-10) || (dua < dua0 && pri0 < 1e-10);
+  if (!ok) {
+    if (tid == 0) a.status[inst] = -1.0;
+    return;
+  }
+  for (int j = tid; j < n; j += PT) { a.x[(size_t)inst * a.x_stride + j] = D[j] * x[j]; rec[rec_x(n, m) + j] = x[j]; }
+  for (int i = tid; i < m; i += PT) {
+    a.y[(size_t)inst * a.y_stride + i] = cinv * E[i] * y[i];
+    rec[rec_z(n, m) + i] = z[i]; rec[rec_y(n, m) + i] = y[i];
+  }
+  if (tid == 0) { info[2] = pri; info[3] = dua; info[4] = obj; a.status[inst] = 1.0; }
+}
+
+}  // namespace polish
+}  // namespace
+}  // namespace oq

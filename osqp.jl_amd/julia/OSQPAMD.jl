@@ -334,6 +334,28 @@ function batch_solve!(b::ResidentBatch, x::Ptr{Cdouble}, y::Ptr{Cdouble}, info::
     return nothing
 end
 
+"status_polish of every instance from the last `batch_solve!`: 1 accepted, -1 refused, 0 not polished (not Solved, or polish off)."
+function batch_polish_status(b::ResidentBatch)
+    st = Vector{Float64}(undef, b.count)
+    flag = ccall((:osqp_amd_batch_polish_status, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), b.handle, st, 0)
+    flag == 0 || error("Error in batched polish status: $(last_error())")
+    return Int.(st)
+end
+
+"The same into a device array (a pointer to `count` doubles on the handle's device)."
+function batch_polish_status(b::ResidentBatch, st::Ptr{Cdouble})
+    flag = ccall((:osqp_amd_batch_polish_status, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), b.handle, st, 1)
+    flag == 0 || error("Error in batched polish status: $(last_error())")
+    return nothing
+end
+
+"Polishing of the following solves on / off and its number of refinement steps: `OSQP.update_settings!(polish = ..., polish_refine_iter = ...)` for the batch."
+function batch_update_polish!(b::ResidentBatch, polish::Bool; polish_refine_iter::Integer = 3)
+    flag = ccall((:osqp_amd_batch_update_polish, lib), Cc_int, (Ptr{Cvoid}, Cc_int, Cc_int), b.handle, polish ? 1 : 0, polish_refine_iter)
+    flag == 0 || error("Error in batched update: $(last_error())")
+    return nothing
+end
+
 "In-place all-gather of `count` doubles per rank on a device buffer, on the library's communicator."
 function comm_all_gather!(comm::Ptr{Cvoid}, buf::Ptr{Cdouble}, count::Integer)
     flag = ccall((:osqp_amd_comm_all_gather, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), comm, buf, count)

@@ -213,7 +213,10 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_update_matrices": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_warm_start": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_resolve": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_polish_status": (c_int, [C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_update_polish": (c_int, [C.c_void_p, c_int, c_int]),
     "osqp_amd_batch_last_kernel": (c_int, []),
+    "osqp_amd_batch_polish_launches": (c_int, []),
     "osqp_amd_device_alloc": (C.c_void_p, [c_int, c_int]),
     "osqp_amd_device_free": (c_int, [C.c_void_p, c_int]),
     "osqp_amd_device_copy": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int]),

@@ -9,7 +9,10 @@ inside one process, each ending in a device synchronise (every library call bloc
   D  ResidentBatch, warm, device-pointer updates and device outputs (the period's q, l, u are already in HBM).
 One JSON line per leg: ms per period (median and mean over the timed periods), ADMM iterations per period, ms per 1000
 instance-iterations.  The library has no per-kernel event timer for the batched path, so the kernel's share is not reported.
-usage: python tools/batch_closed_loop.py [count] [K] [W]"""
+--polish: the resident legs B, C, D run with settings.polish = 1 (a second launch per period polishes the Solved instances);
+leg A, the one-shot entry, ignores the setting.  Their lines then carry `polished_fraction`: accepted polishes per
+instance-period.
+usage: python tools/batch_closed_loop.py [--polish] [count] [K] [W]"""
 import json
 import os
 import sys
@@ -24,12 +27,14 @@ import osqp_jl_amd as oq  # noqa: E402
 from osqp_jl_amd import batch  # noqa: E402
 import batch_resident_ref as ref  # noqa: E402
 
-count = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-K = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-W = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+POLISH = "--polish" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != "--polish"]
+count = int(argv[0]) if len(argv) > 0 else 4096
+K = int(argv[1]) if len(argv) > 1 else 10
+W = int(argv[2]) if len(argv) > 2 else 2
 lib = oq.load_library()
 olib = oq.load_library(oq.ORACLE_LIB_PATH)  # the host generator only
-OPTS = dict(verbose=False, eps_abs=1e-5, eps_rel=1e-5, adaptive_rho_interval=50, max_iter=4000)
+OPTS = dict(verbose=False, eps_abs=1e-5, eps_rel=1e-5, adaptive_rho_interval=50, max_iter=4000, polish=POLISH)
 
 args = ref.stack(ref.mpc_instances(olib, 0, count, 5))
 P0, A0, Px, Ax, q, l, u = args
@@ -43,6 +48,7 @@ for h in handles.values():  # period 0: the data as set up
 times = {k: [] for k in "ABCD"}
 iters = {k: [] for k in "ABCD"}
 solved = {k: 0 for k in "ABCD"}
+polished = {k: 0 for k in "ABCD"}
 for k in range(1, W + K + 1):
     qk, lk, uk = steps[k]
     dq, dl, du = dev(qk), dev(lk), dev(uk)  # leg D's inputs live in HBM before its period starts
@@ -59,6 +65,8 @@ for k in range(1, W + K + 1):
         dt = time.perf_counter() - t0
         if leg == "D":
             info = out_d[2].numpy()  # outside the timed stretch: a controller would consume it on the device
+        if POLISH and leg != "A" and k > W:
+            polished[leg] += int(np.sum(handles[leg].polish_status() == 1))  # outside the timed stretch too
         if k > W:
             times[leg].append(1e3 * dt); iters[leg].append(float(np.sum(info[:, 0]))); solved[leg] += int(np.sum(info[:, 1] == 1))
     for a in (dq, dl, du):
@@ -70,6 +78,7 @@ for leg in "ABCD":
     print(json.dumps(dict(leg=leg, what=what[leg], instances=count, periods=K, warmup=W, kernel=int(lib.osqp_amd_batch_last_kernel()),
                           ms_per_period_median=ms, ms_per_period_mean=float(np.mean(times[leg])), ms_per_period_min=float(np.min(times[leg])),
                           iterations_per_period=it, ms_per_1000_instance_iterations=1e3 * float(np.mean(times[leg])) / it,
-                          solved_fraction=solved[leg] / (count * K))))
+                          solved_fraction=solved[leg] / (count * K),
+                          **(dict(polish=1, polished_fraction=polished[leg] / (count * K)) if POLISH and leg != "A" else {}))))
 for h in handles.values():
     h.close()
