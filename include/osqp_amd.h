@@ -462,6 +462,30 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             set (the n x n condensed KKT matrix as a packed triangle, the values of A and P, 5 n + 6 m doubles) exceeds
  *             160 KB of LDS is refused with return 1 and a message naming the bytes -- here and by setup() with polish = 1;
  *             polish is never skipped silently.
+ *   adjoint(): derivatives of a scalar loss through the solutions of the last resolve.  dx [count x n], dy [count x m]: the
+ *             gradients of the loss with respect to x and y as resolve returned them (NULL = zero; both NULL: return 1).
+ *             Per instance, with L / U the rows active at the lower / upper bound, a = L u U and K = [P, Aa'; Aa, 0], one solve
+ *             K [r_x; r_a] = [dx; dy restricted to a] (dy on inactive rows does not enter: the multiplier there is locally
+ *             constant at 0), r_y = r_a scattered to length m, gives
+ *               dq [count x n] = -r_x;  dl, du [count x m]: r_y,i on the rows of L (dl) / U (du), 0 elsewhere;
+ *               dPx [count x nnz(P upper)], in the setup's pattern order: -r_x,i x_i for a stored diagonal entry (i, i),
+ *                   -(r_x,i x_j + r_x,j x_i) for a stored entry (i, j), i < j (it stands for both halves of P);
+ *               dAx [count x nnz(A)]: -(y_i r_x,j + r_y,i x_j) for entry (i, j);
+ *               act_out [count x m] doubles: -1 lower, 1 upper, 0 inactive;  status_out [count] doubles.
+ *             Any output may be NULL (not wanted); a y-sized or A-sized pointer is ignored when m = 0 or nnz(A) = 0.
+ *             The active rows are those the polish step takes from the stored iterate (lower if z - l < -y, else upper if
+ *             u - z < y, scaled space), and a row with l == u is always active and counts as lower: for such a row only
+ *             dl + du is meaningful (the derivative with respect to moving both bounds together), and it is returned in dl.
+ *             The solve is the polish solve with another right-hand side, in its own kernel launch: the condensed matrix
+ *             regularised with settings.delta, a Cholesky factor, settings.polish_refine_iter refinement steps against the
+ *             unregularised K (polish itself need not be on).  Where K is singular -- dependent active rows, more active
+ *             rows than variables -- the derivative does not exist; the call does not detect this and returns the refined
+ *             regularised answer.  status: 1 differentiated; 0 the instance had no solution at the last resolve (its
+ *             gradient rows and its act_out row are zeros); -1 the Cholesky factor met a non-positive pivot (zeros).
+ *             Refused with return 1 and a message: a handle that has not been resolved, or whose data or iterate changed
+ *             since (any update_* or warm_start; update_polish does not count), and a pattern whose working set exceeds
+ *             the polish LDS limit.  The call changes nothing on the handle: a resolve after it is bit-identical to one
+ *             without it.
  * where: 0 = the array arguments are host pointers, 1 = device pointers on the handle's device (no host hop: a controller
  * whose state estimate lives in HBM).  A NULL array means "keep" (update_*) / "none" (warm_start).  Every call blocks until
  * done.  Single rank.  The handle is freed by osqp_amd_batch_destroy; it is not interchangeable with the handle of
@@ -478,9 +502,14 @@ c_int osqp_amd_batch_warm_start(osqp_amd_batch *batch, const c_float *x_all, con
 c_int osqp_amd_batch_resolve(osqp_amd_batch *batch, c_float *x_out, c_float *y_out, c_float *info_out, c_int where);
 c_int osqp_amd_batch_polish_status(osqp_amd_batch *batch, c_float *status_out, c_int where);
 c_int osqp_amd_batch_update_polish(osqp_amd_batch *batch, c_int polish_new, c_int polish_refine_iter_new);
+c_int osqp_amd_batch_adjoint(osqp_amd_batch *batch, const c_float *dx, const c_float *dy,
+                             c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
+                             c_float *act_out, c_float *status_out, c_int where);
 /* Diagnostic, like osqp_amd_batch_last_kernel: how many polish launches this process has made so far.  A resolve with
  * polish = 0 makes none -- its launch sequence is the one of a library without the polish kernel. */
 c_int osqp_amd_batch_polish_launches(void);
+/* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint that passed its checks, none otherwise. */
+c_int osqp_amd_batch_adjoint_launches(void);
 
 /* Device memory for callers without an allocator of their own (the packed result array above): plain hipMalloc / hipFree /
  * hipMemcpy on `device`.  copy kind: 0 device -> host, 1 host -> device, 2 device -> device; blocking. */

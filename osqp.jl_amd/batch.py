@@ -331,6 +331,59 @@ class ResidentBatch:
         self._call("update", self.lib.osqp_amd_batch_update_polish(self.handle, int(polish), int(polish_refine_iter)))
         self.polish_refine_iter = int(polish_refine_iter)
 
+    ADJOINT_WANT = ("q", "l", "u", "Px", "Ax")
+
+    def _adjoint_cols(self):
+        return dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA, act=self.m, status=1)
+
+    def adjoint(self, dx=None, dy=None, want=ADJOINT_WANT, out=None):
+        """Gradients of a scalar loss with respect to the data, through the solutions of the last `solve()`
+        (osqp_amd_batch_adjoint): dx [count x n], dy [count x m] are the loss's gradients with respect to x and y (None: zero;
+        not both).  Returns a dict with the entries of `want` -- "q" [count x n], "l", "u" [count x m], "Px" [count x nnz(P
+        upper)], "Ax" [count x nnz(A)] -- plus "act" [count x m] (-1 lower, 1 upper, 0 inactive) and "status" (1
+        differentiated, 0 no solution, -1 factorisation failed; rows with status != 1 are zeros).  Entries of width 0 (m = 0)
+        are left out.  Host form: numpy dx / dy, out=None, numpy results ("act" and "status" [count] as integers).  Device
+        form: dx / dy device arrays and `out` a dict of float64 device arrays for the entries of `want` and, optionally,
+        "act" and "status" ([count x 1]); they are filled in place and `out` is returned.  The handle must hold the solution
+        of its current data: a `solve()` since the last `update` / `warm_start`.  Where the active constraints of an instance
+        are dependent the derivative does not exist and the regularised answer is returned (see include/osqp_amd.h)."""
+        cols = self._adjoint_cols()
+        want = tuple(want)
+        for w in want:
+            if w not in self.ADJOINT_WANT:
+                raise ValueError(f"want: unknown gradient {w!r}; expected a subset of {self.ADJOINT_WANT}")
+        if dx is None and dy is None:
+            raise ValueError("dx and dy: at least one incoming gradient is needed")
+        keep, ptrs, where = self._pair(("dx", "dy"), (dx, dy), (self.n, self.m))
+        names = [k for k in self.ADJOINT_WANT + ("act", "status") if cols[k] > 0]
+        if not where:
+            if out is not None:
+                raise ValueError("out: host gradients (numpy dx / dy) return numpy arrays; pass device arrays for dx / dy to fill `out`")
+            res = {k: np.empty((self.count, cols[k])) for k in names if k in want or k in ("act", "status")}
+            addr = {k: v.ctypes.data for k, v in res.items()}
+        else:
+            if not isinstance(out, dict):
+                raise ValueError("out: device gradients need a dict of device arrays to fill, one per entry of `want`")
+            for k in out:
+                if k not in cols:
+                    raise ValueError(f"out: unknown entry {k!r}")
+            addr = {}
+            for k in names:
+                if k in out and (k in want or k in ("act", "status")):
+                    if not hasattr(out[k], "data_ptr"):
+                        raise ValueError(f"out[{k!r}]: expected a device array (DeviceArray, torch tensor)")
+                    addr[k] = _batch_array(f"out[{k!r}]", out[k], (self.count, cols[k]))[1]
+                elif k in want:
+                    raise ValueError(f"out: no array for the wanted gradient {k!r}")
+            res = out
+        self._call("adjoint", self.lib.osqp_amd_batch_adjoint(self.handle, ptrs[0], ptrs[1], *[addr.get(k) for k in self.ADJOINT_WANT],
+                                                              addr.get("act"), addr.get("status"), where))
+        if not where:
+            if "act" in res:
+                res["act"] = res["act"].astype(np.int64)
+            res["status"] = res["status"].ravel().astype(np.int64)
+        return res
+
     def alloc(self):
         """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints."""
         return (DeviceArray(self.lib, self.count, self.n, self.device),

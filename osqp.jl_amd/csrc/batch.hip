@@ -13,6 +13,8 @@
 //                     four-wavefront kernel for the first table entry it fits (DevicePattern);
 //   batch_polish.hpp  k_batch_polish -- solution polishing for the resident batch, a launch of its own after the ADMM launch
 //                     when the handle's settings.polish is 1; the solve kernels know nothing of it;
+//   batch_adjoint.hpp k_batch_adjoint -- adjoint derivatives of the solutions of the resident batch, a launch of its own on
+//                     request (osqp_amd_batch_adjoint); shares the factorisation and the solves of the polish kernel;
 //   this file         the small kernels (warm start, bound check, MPC generator), the launcher (launch_batch), the handle
 //                     (BatchPlan) and the C ABI.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
@@ -24,6 +26,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "batch_adjoint.hpp"
 #include "batch_polish.hpp"
 #include "batch_quad.hpp"
 #include "batch_sched.hpp"
@@ -34,6 +37,7 @@ namespace oq {
 namespace {
 
 int g_batch_polish_launches = 0;  // launches of k_batch_polish by this process (osqp_amd_batch_polish_launches)
+int g_batch_adjoint_launches = 0;  // launches of k_batch_adjoint by this process (osqp_amd_batch_adjoint_launches)
 int g_batch_last_kernel = -2;  // what launch_batch launched last: -1 the 512-thread kernel, >= 0 the number of the entry of OQ_QUAD_ENTRIES
 inline bool batch_quad_enabled() {  // OSQP_AMD_BATCH_QUAD=0: the MPC family on the 512-thread kernel (A/B runs, tests)
   const char *e = getenv("OSQP_AMD_BATCH_QUAD");
@@ -245,6 +249,11 @@ struct BatchPlan : BatchData {
   // last resolve did not polish (or there was none) and all are 0, whatever the buffer holds
   DevBuf<double> pstat;
   bool pstat_live = false;
+  // adjoint (osqp_amd_batch_adjoint): sol_current = the records and info_out hold the solution of the handle's current data
+  // (set by a resolve, cleared by every update_* and warm_start); info_out keeps the info rows of the last resolve also when
+  // the caller's went to device pointers.  Staging of host-pointer calls: gradients in through in_a / in_b, out through adj_out
+  bool sol_current = false;
+  DevBuf<double> adj_out;
 };
 
 // The checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings], shared by the
@@ -334,6 +343,7 @@ extern "C" {
 
 c_int osqp_amd_batch_last_kernel(void) { return g_batch_last_kernel; }
 c_int osqp_amd_batch_polish_launches(void) { return g_batch_polish_launches; }
+c_int osqp_amd_batch_adjoint_launches(void) { return g_batch_adjoint_launches; }
 
 c_int osqp_amd_batch_solve(c_int count, c_int n, c_int m, const c_int *Pp, const c_int *Pi, const c_float *Px_all, const c_int *Ap,
                            const c_int *Ai, const c_float *Ax_all, const c_float *q_all, const c_float *l_all, const c_float *u_all,
@@ -472,6 +482,7 @@ c_int osqp_amd_batch_update_lin_cost(osqp_amd_batch *handle, const c_float *q_al
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
     const size_t len = (size_t)b->count * b->n;
+    b->sol_current = false;
     if (where) copy_d2d(b->q.get(), q_all, len, s); else b->q.upload(q_all, len, s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
@@ -495,6 +506,7 @@ c_int osqp_amd_batch_update_bounds(osqp_amd_batch *handle, const c_float *l_all,
     b->bad.download(&bad, 1, s);
     HIP_CHECK(hipStreamSynchronize(s));
     if (bad) { set_last_error("lower bound greater than upper bound"); return 1; }
+    b->sol_current = false;
     if (l_all) copy_d2d(b->l.get(), ln, len, s);
     if (u_all) copy_d2d(b->u.get(), un, len, s);
     HIP_CHECK(hipStreamSynchronize(s));
@@ -510,6 +522,7 @@ c_int osqp_amd_batch_update_matrices(osqp_amd_batch *handle, const c_float *Px_a
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
     const size_t lp = (size_t)b->count * b->nnzP, la = (size_t)b->count * b->nnzA;
+    b->sol_current = false;
     if (Px_all && lp) { if (where) copy_d2d(b->Px.get(), Px_all, lp, s); else b->Px.upload(Px_all, lp, s); }
     if (Ax_all && la) { if (where) copy_d2d(b->Ax.get(), Ax_all, la, s); else b->Ax.upload(Ax_all, la, s); }
     resident_equilibrate(*b, s);  // from scratch on the raw data with the current q, l, u; the scaled iterate stays as it is
@@ -525,6 +538,7 @@ c_int osqp_amd_batch_warm_start(osqp_amd_batch *handle, const c_float *x_all, co
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
+    b->sol_current = false;
     const double *xd = x_all ? device_ptr(x_all, (size_t)b->count * b->n, where, b->in_a, s) : nullptr;
     const double *yd = y_all && b->m ? device_ptr(y_all, (size_t)b->count * b->m, where, b->in_b, s) : nullptr;
     OQ_LAUNCH(k_batch_warm, dim3(b->count), dim3(256), 0, s, b->dp.P, b->count, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride);
@@ -548,11 +562,60 @@ c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_
     launch_batch(b->dp, b->st, b->count, io, s);
     b->pstat_live = b->st.polish != 0;
     if (b->pstat_live) launch_polish(*b, io, s);
+    if (where) copy_d2d(b->info_out.get(), info_out, (size_t)b->count * 6, s);  // the statuses, for osqp_amd_batch_adjoint
     if (!where) {
       b->x_out.download(x_out, (size_t)b->count * b->n, s);
       if (b->m) b->y_out.download(y_out, (size_t)b->count * b->m, s);
       b->info_out.download(info_out, (size_t)b->count * 6, s);
     }
+    HIP_CHECK(hipStreamSynchronize(s));
+    b->sol_current = true;
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_adjoint(osqp_amd_batch *handle, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
+                             c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
+  if (!b->sol_current) {
+    set_last_error("the batch holds no current solution: call osqp_amd_batch_resolve after the last update or warm start");
+    return 1;
+  }
+  try {
+    const Pattern &P = b->dp.P;
+    polish_check_fits(P);
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const size_t cnt = (size_t)b->count, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    if (!lm) { dy = nullptr; dl = du = act_out = nullptr; }
+    if (!la) dAx = nullptr;
+    if (!lp) dPx = nullptr;
+    // host pointers: the wanted outputs share one staging buffer, in this order
+    c_float *const host[7] = {dq, dl, du, dPx, dAx, act_out, status_out};
+    const size_t len[7] = {ln, lm, lm, lp, la, lm, cnt};
+    double *dev[7];
+    size_t total = 0;
+    for (int k = 0; k < 7; k++) if (host[k]) total += len[k];
+    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
+    size_t at = 0;
+    for (int k = 0; k < 7; k++) {
+      dev[k] = !host[k] ? nullptr : (where ? host[k] : b->adj_out.get() + at);
+      if (host[k] && !where) at += len[k];
+    }
+    polish::AdjointArgs a;
+    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_out.get(); a.rec = b->rec.get();
+    a.gx = dx ? device_ptr(dx, ln, where, b->in_a, s) : nullptr;
+    a.gy = dy ? device_ptr(dy, lm, where, b->in_b, s) : nullptr;
+    a.dq = dev[0]; a.dl = dev[1]; a.du = dev[2]; a.dPx = dev[3]; a.dAx = dev[4]; a.act = dev[5]; a.status = dev[6];
+    a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
+    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
+    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+    g_batch_adjoint_launches++;
+    OQ_LAUNCH(polish::k_batch_adjoint, dim3(b->count), dim3(polish::PT), (size_t)L.total, s, P, b->count, L, a);
+    if (!where)
+      for (int k = 0; k < 7; k++) if (host[k]) HIP_CHECK(hipMemcpyAsync(host[k], dev[k], len[k] * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH

@@ -88,6 +88,114 @@ __device__ __forceinline__ void factor_solve(int n, const ldouble *M, const ldou
   if (i1 < n) t[i1] = b1;
 }
 
+// ---- what k_batch_polish and k_batch_adjoint (batch_adjoint.hpp) share: the views of the LDS slots, the scaled matrices, the
+// classification of a row, the assembly of M, its factorisation and one solve / refinement step ----
+struct Slots { ldouble *M, *Av, *Pv, *rdg, *col, *q, *x, *t, *l, *u, *y, *ry, *z, *act, *red; };
+__device__ __forceinline__ Slots make_slots(const Layout &L) {
+  ldouble *const lds = (ldouble *)lds_raw;
+  return Slots{lds + L.M, lds + L.Av, lds + L.Pv, lds + L.rdg, lds + L.col, lds + L.q, lds + L.x, lds + L.t,
+               lds + L.l, lds + L.u, lds + L.y, lds + L.ry, lds + L.z, lds + L.act, lds + L.red};
+}
+
+// column j of the scaled A and row j of the scaled full P (as the solve prologue forms them) into Av / Pv
+__device__ __forceinline__ void stage_matrices(const Pattern &P, const Slots &S, int j, const double *Axi, const double *Pxi, const double *D,
+                                               const double *E, double c) {
+  const double dj = D[j];
+  for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) S.Av[k] = (Axi[k] * E[P.Ai[k]]) * dj;
+  for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) {
+    const int cc = P.Fc[f];
+    const int lo = cc < j ? cc : j, hi = cc < j ? j : cc;
+    S.Pv[f] = c * ((Pxi[P.Fmap[f]] * D[lo]) * D[hi]);
+  }
+}
+// -1 lower, 1 upper, 0 inactive, on the scaled iterate: lower first, as form_Ared
+__device__ __forceinline__ double classify(double zi, double yi, double li, double ui) {
+  return (zi - li < -yi) ? -1.0 : ((ui - zi < yi) ? 1.0 : 0.0);
+}
+
+// M = P + delta I + Aa' Aa / delta, lower triangle; Av, Pv and act are written but not yet synchronised on entry
+__device__ __forceinline__ void assemble_M(const Pattern &P, const Slots &S, double delta) {
+  const int tid = threadIdx.x, n = P.n;
+  ldouble *const M = S.M;
+  for (int e = tid; e < n * (n + 1) / 2; e += PT) M[e] = 0.0;
+  __syncthreads();
+  for (int p = tid; p < P.npair; p += PT) {
+    double acc = 0.0;
+    for (int s = P.Tp[p]; s < P.Tp[p + 1]; s++) acc += (S.act[P.Tr[s]] != 0.0 ? 1.0 : 0.0) * S.Av[P.Ta[s]] * S.Av[P.Tb[s]];
+    M[tri(P.Ti[p], P.Tj[p])] = acc / delta;
+  }
+  __syncthreads();
+  for (int r = tid; r < n; r += PT) {
+    for (int f = P.Fp[r]; f < P.Fp[r + 1]; f++) {
+      const int cc = P.Fc[f];
+      if (cc <= r) M[tri(r, cc)] += S.Pv[f];
+    }
+    M[tri(r, r)] += delta;
+  }
+  __syncthreads();
+}
+
+// Cholesky, right-looking, in place (the diagonal of M keeps the pivot's square; 1 / pivot goes to rdg); false: a
+// non-positive pivot (the same value in every thread: a uniform exit)
+__device__ __forceinline__ bool cholesky(int n, ldouble *M, ldouble *rdg, ldouble *col) {
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  for (int k = 0; k < n; k++) {
+    const double d = M[tri(k, k)];  // final since the barrier that ended step k - 1; not written in step k
+    if (!(d > 0.0)) return false;
+    const double piv = sqrt(d);
+    if (tid == 0) rdg[k] = 1.0 / piv;
+    for (int i = k + 1 + tid; i < n; i += PT) { const double v = M[tri(i, k)] / piv; M[tri(i, k)] = v; col[i] = v; }
+    __syncthreads();
+    for (int i = k + 1 + ty; i < n; i += 16) {
+      const double ci = col[i];
+      for (int j = k + 1 + tx; j <= i; j += 16) M[tri(i, j)] -= ci * col[j];
+    }
+    __syncthreads();
+  }
+  return true;
+}
+
+// One solve with the factor: step `it` = 0 solves [P + delta I, Aa'; Aa, -delta I] [x; y] = [g; b] from the ry the caller
+// staged (b on the active rows, zero elsewhere); a step it > 0 refines x, y against the unregularised [P, Aa'; Aa, 0].
+// POLISH: g = -q and b = l on the lower rows, u on the upper ones; otherwise (the adjoint) g = q and b = l on every active row.
+template <bool POLISH>
+__device__ __forceinline__ void kkt_step(const Pattern &P, const Slots &S, int it, double delta) {
+  const int tid = threadIdx.x, n = P.n, m = P.m;
+  ldouble *const Av = S.Av, *const Pv = S.Pv, *const x = S.x, *const y = S.y, *const t = S.t, *const ry = S.ry, *const act = S.act;
+  if (it > 0) {  // r_y = b - Aa x on the active rows (zero elsewhere, so the column walks need no mask)
+    for (int i = tid; i < m; i += PT) {
+      const double on = act[i];
+      double ax = 0.0;
+      if (on != 0.0) for (int s = P.Rp[i]; s < P.Rp[i + 1]; s++) ax += Av[P.Rmap[s]] * x[P.Rc[s]];
+      ry[i] = on != 0.0 ? ((on < 0.0 || !POLISH) ? S.l[i] : S.u[i]) - ax : 0.0;
+    }
+    __syncthreads();
+  }
+  for (int j = tid; j < n; j += PT) {  // t = r_x + Aa' r_y / delta,  r_x = g - P x - Aa' y (first solve: g)
+    double rx = POLISH ? -S.q[j] : S.q[j], ar = 0.0;
+    if (it > 0) {
+      double px = 0.0, ay = 0.0;
+      for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) px += Pv[f] * x[P.Fc[f]];
+      for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) ay += Av[k] * y[P.Ai[k]];
+      rx = (rx - px) - ay;
+    }
+    for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) ar += Av[k] * ry[P.Ai[k]];
+    t[j] = rx + ar / delta;
+  }
+  __syncthreads();
+  factor_solve(n, S.M, S.rdg, t);
+  __syncthreads();
+  for (int i = tid; i < m; i += PT) {  // d_y = (Aa d_x - r_y) / delta
+    if (act[i] == 0.0) continue;
+    double ad = 0.0;
+    for (int s = P.Rp[i]; s < P.Rp[i + 1]; s++) ad += Av[P.Rmap[s]] * t[P.Rc[s]];
+    const double dy = (ad - ry[i]) / delta;
+    y[i] = it > 0 ? y[i] + dy : dy;
+  }
+  for (int j = tid; j < n; j += PT) x[j] = it > 0 ? x[j] + t[j] : t[j];
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layout L, Args a) {
   const int inst = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
   if (inst >= count) return;
@@ -96,10 +204,9 @@ __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layou
     if (tid == 0) a.status[inst] = 0.0;
     return;
   }
-  ldouble *const lds = (ldouble *)lds_raw;
-  ldouble *const M = lds + L.M, *const Av = lds + L.Av, *const Pv = lds + L.Pv, *const rdg = lds + L.rdg, *const col = lds + L.col;
-  ldouble *const q = lds + L.q, *const x = lds + L.x, *const t = lds + L.t, *const l = lds + L.l, *const u = lds + L.u;
-  ldouble *const y = lds + L.y, *const ry = lds + L.ry, *const z = lds + L.z, *const act = lds + L.act, *const red = lds + L.red;
+  const Slots S = make_slots(L);
+  ldouble *const Av = S.Av, *const Pv = S.Pv, *const q = S.q, *const x = S.x, *const l = S.l, *const u = S.u;
+  ldouble *const y = S.y, *const ry = S.ry, *const z = S.z, *const act = S.act, *const red = S.red;
   double *const rec = a.rec + (size_t)inst * a.rec_stride;
   const double *const D = rec + rec_D(n, m), *const E = rec + rec_E(n, m);
   const double c = rec[REC_C], cinv = 1.0 / c, delta = a.delta;
@@ -108,14 +215,8 @@ __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layou
   // ---- the scaled data (as the solve prologue forms them), the iterate of the record, the active sets ----
   const double *const Axi = a.Ax + (size_t)inst * P.nnzA, *const Pxi = a.Px + (size_t)inst * P.nnzP;
   for (int j = tid; j < n; j += PT) {
-    const double dj = D[j];
-    for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) Av[k] = (Axi[k] * E[P.Ai[k]]) * dj;
-    for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) {
-      const int cc = P.Fc[f];
-      const int lo = cc < j ? cc : j, hi = cc < j ? j : cc;
-      Pv[f] = c * ((Pxi[P.Fmap[f]] * D[lo]) * D[hi]);
-    }
-    q[j] = c * (a.q[(size_t)inst * n + j] * dj);
+    stage_matrices(P, S, j, Axi, Pxi, D, E, c);
+    q[j] = c * (a.q[(size_t)inst * n + j] * D[j]);
     x[j] = rec[rec_x(n, m) + j];
   }
   for (int i = tid; i < m; i += PT) {
@@ -123,88 +224,19 @@ __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layou
     const double li = fmax(a.l[(size_t)inst * m + i], -OSQP_INFTY) * e, ui = fmin(a.u[(size_t)inst * m + i], OSQP_INFTY) * e;
     const double zi = rec[rec_z(n, m) + i], yi = rec[rec_y(n, m) + i];
     l[i] = li; u[i] = ui;
-    const double on = (zi - li < -yi) ? -1.0 : ((ui - zi < yi) ? 1.0 : 0.0);  // lower first, as form_Ared
+    const double on = classify(zi, yi, li, ui);
     act[i] = on;
     ry[i] = on < 0.0 ? li : (on > 0.0 ? ui : 0.0);  // the right-hand side of the first solve: [-q; l_low; u_upp]
     y[i] = 0.0;
   }
-  for (int e = tid; e < n * (n + 1) / 2; e += PT) M[e] = 0.0;
-  __syncthreads();
-
-  // ---- M = P + delta I + Aa' Aa / delta, lower triangle ----
-  for (int p = tid; p < P.npair; p += PT) {
-    double acc = 0.0;
-    for (int s = P.Tp[p]; s < P.Tp[p + 1]; s++) acc += (act[P.Tr[s]] != 0.0 ? 1.0 : 0.0) * Av[P.Ta[s]] * Av[P.Tb[s]];
-    M[tri(P.Ti[p], P.Tj[p])] = acc / delta;
-  }
-  __syncthreads();
-  for (int r = tid; r < n; r += PT) {
-    for (int f = P.Fp[r]; f < P.Fp[r + 1]; f++) {
-      const int cc = P.Fc[f];
-      if (cc <= r) M[tri(r, cc)] += Pv[f];
-    }
-    M[tri(r, r)] += delta;
-  }
-  __syncthreads();
-
-  // ---- Cholesky, right-looking, in place (the diagonal of M keeps the pivot's square; 1 / pivot goes to rdg) ----
-  bool pd = true;
-  {
-    const int tx = tid & 15, ty = tid >> 4;
-    for (int k = 0; k < n; k++) {
-      const double d = M[tri(k, k)];  // final since the barrier that ended step k - 1; not written in step k
-      if (!(d > 0.0)) { pd = false; break; }  // the same value in every thread: a uniform exit
-      const double piv = sqrt(d);
-      if (tid == 0) rdg[k] = 1.0 / piv;
-      for (int i = k + 1 + tid; i < n; i += PT) { const double v = M[tri(i, k)] / piv; M[tri(i, k)] = v; col[i] = v; }
-      __syncthreads();
-      for (int i = k + 1 + ty; i < n; i += 16) {
-        const double ci = col[i];
-        for (int j = k + 1 + tx; j <= i; j += 16) M[tri(i, j)] -= ci * col[j];
-      }
-      __syncthreads();
-    }
-  }
-  if (!pd) {  // as a failed direct_init in the oracle
+  assemble_M(P, S, delta);
+  if (!cholesky(n, S.M, S.rdg, S.col)) {  // as a failed direct_init in the oracle
     if (tid == 0) a.status[inst] = -1.0;
     return;
   }
 
   // ---- solve with [-q; b_act], then `refine` steps against the unregularised [P, Aa'; Aa, 0] ----
-  for (int it = 0; it <= a.refine; it++) {
-    if (it > 0) {  // r_y = b - Aa x on the active rows (zero elsewhere, so the column walks need no mask)
-      for (int i = tid; i < m; i += PT) {
-        const double on = act[i];
-        double ax = 0.0;
-        if (on != 0.0) for (int s = P.Rp[i]; s < P.Rp[i + 1]; s++) ax += Av[P.Rmap[s]] * x[P.Rc[s]];
-        ry[i] = on != 0.0 ? (on < 0.0 ? l[i] : u[i]) - ax : 0.0;
-      }
-      __syncthreads();
-    }
-    for (int j = tid; j < n; j += PT) {  // t = r_x + Aa' r_y / delta,  r_x = -q - P x - Aa' y (first solve: -q)
-      double rx = -q[j], ar = 0.0;
-      if (it > 0) {
-        double px = 0.0, ay = 0.0;
-        for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) px += Pv[f] * x[P.Fc[f]];
-        for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) ay += Av[k] * y[P.Ai[k]];
-        rx = (rx - px) - ay;
-      }
-      for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) ar += Av[k] * ry[P.Ai[k]];
-      t[j] = rx + ar / delta;
-    }
-    __syncthreads();
-    factor_solve(n, M, rdg, t);
-    __syncthreads();
-    for (int i = tid; i < m; i += PT) {  // d_y = (Aa d_x - r_y) / delta
-      if (act[i] == 0.0) continue;
-      double ad = 0.0;
-      for (int s = P.Rp[i]; s < P.Rp[i + 1]; s++) ad += Av[P.Rmap[s]] * t[P.Rc[s]];
-      const double dy = (ad - ry[i]) / delta;
-      y[i] = it > 0 ? y[i] + dy : dy;
-    }
-    for (int j = tid; j < n; j += PT) x[j] = it > 0 ? x[j] + t[j] : t[j];
-    __syncthreads();
-  }
+  for (int it = 0; it <= a.refine; it++) kkt_step<true>(P, S, it, delta);
 
   // ---- z = A x, (z, y) onto the normal cone of [l, u]; residuals and objective as the termination check defines them ----
   double pri = 0.0, dua = 0.0, obj = 0.0;

@@ -356,6 +356,33 @@ function batch_update_polish!(b::ResidentBatch, polish::Bool; polish_refine_iter
     return nothing
 end
 
+"""
+    batch_adjoint!(b; dx = nothing, dy = nothing, dq = nothing, dl = nothing, du = nothing, dPx = nothing, dAx = nothing,
+                   act = nothing, status = nothing)
+
+Gradients of a scalar loss through the solutions of the last `batch_solve!` (osqp_amd_batch_adjoint in include/osqp_amd.h):
+`dx` [n x count] and `dy` [m x count] are the loss's gradients with respect to x and y (`nothing` = zero, not both); every
+output that is given is filled in place -- `dq` [n x count], `dl`, `du`, `act` [m x count], `dPx` [nnz(triu(P)) x count],
+`dAx` [nnz(A) x count], `status` [1 x count] -- and `nothing` means not wanted.  All arrays are host matrices or all are
+device pointers, as for `batch_update!`.  The handle must have been solved since its last update or warm start.
+"""
+function batch_adjoint!(b::ResidentBatch; dx::BatchArg = nothing, dy::BatchArg = nothing, dq::BatchArg = nothing,
+                        dl::BatchArg = nothing, du::BatchArg = nothing, dPx::BatchArg = nothing, dAx::BatchArg = nothing,
+                        act::BatchArg = nothing, status::BatchArg = nothing)
+    all_args = (dx, dy, dq, dl, du, dPx, dAx, act, status)
+    given = filter(a -> a !== nothing, collect(all_args))
+    all(a -> a isa Ptr{Cdouble}, given) || all(a -> a isa Matrix{Float64}, given) ||
+        error("batch_adjoint!: the arrays must all be host matrices or all device pointers")
+    GC.@preserve dx dy dq dl du dPx dAx act status begin
+        flag = ccall((:osqp_amd_batch_adjoint, lib), Cc_int,
+                     (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                      Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, map(_batch_ptr, all_args)..., _batch_where(all_args...))
+    end
+    flag == 0 || error("Error in batched adjoint: $(last_error())")
+    return nothing
+end
+
 "In-place all-gather of `count` doubles per rank on a device buffer, on the library's communicator."
 function comm_all_gather!(comm::Ptr{Cvoid}, buf::Ptr{Cdouble}, count::Integer)
     flag = ccall((:osqp_amd_comm_all_gather, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), comm, buf, count)

@@ -1,0 +1,77 @@
+"""A resident batch as a differentiable torch layer: `BatchQPFunction` solves `count` QPs in its forward
+(`ResidentBatch.update` + `solve`, device pointers, no host hop) and differentiates their solutions in its backward
+(`ResidentBatch.adjoint`: one launch of k_batch_adjoint).  torch is plumbing only: tensors are passed to the library by
+address and nothing is computed in torch.
+
+    rb = batch.ResidentBatch(lib, P, A, Px, Ax, q, l, u, polish=True)
+    layer = BatchQPLayer(rb)
+    x, y = layer(q=q_t, l=l_t, u=u_t)          # float64 CUDA tensors [count x .]; None keeps the handle's data
+    loss(x, y).backward()                       # q_t.grad, l_t.grad, u_t.grad
+
+Three rules.  The library runs on its own stream and blocks, so torch's current stream is synchronised before every library
+call.  The handle holds ONE solution: every forward stamps the handle, and a backward whose stamp is no longer the handle's
+raises RuntimeError.  Instances whose adjoint status is not 1 (no solution, failed factorisation) get zero gradients; where
+an instance's active constraints are dependent the derivative does not exist and the regularised answer is returned
+(include/osqp_amd.h, osqp_amd_batch_adjoint)."""
+import torch
+
+NAMES = ("q", "l", "u", "Px", "Ax")
+
+
+def _sync(t):
+    torch.cuda.current_stream(t.device).synchronize()
+
+
+class BatchQPFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rb, q, l, u, Px, Ax):
+        given = dict(zip(NAMES, (q, l, u, Px, Ax)))
+        tensors = [t for t in given.values() if t is not None]
+        if not tensors:
+            raise ValueError("BatchQPFunction: at least one of q, l, u, Px, Ax must be a tensor")
+        for name, t in given.items():
+            if t is not None and (not t.is_cuda or t.dtype != torch.float64):
+                raise ValueError(f"{name}: expected a float64 CUDA tensor")
+        ref = tensors[0]
+        _sync(ref)
+        rb.update(**{k: t.detach().contiguous() for k, t in given.items() if t is not None})
+        x = torch.empty((rb.count, rb.n), dtype=torch.float64, device=ref.device)
+        y = torch.empty((rb.count, rb.m), dtype=torch.float64, device=ref.device)
+        info = torch.empty((rb.count, 6), dtype=torch.float64, device=ref.device)
+        rb.solve(out=(x, y if rb.m else None, info))
+        rb._qp_layer_stamp = getattr(rb, "_qp_layer_stamp", 0) + 1
+        rb._qp_layer_info = info
+        ctx.rb, ctx.stamp = rb, rb._qp_layer_stamp
+        return x, y
+
+    @staticmethod
+    def backward(ctx, gx, gy):
+        rb = ctx.rb
+        if getattr(rb, "_qp_layer_stamp", None) != ctx.stamp:
+            raise RuntimeError("BatchQPFunction: the batch has been solved again since this forward; its handle holds one "
+                               "solution, so backward must run before the next forward")
+        need = dict(zip(NAMES, ctx.needs_input_grad[1:]))
+        cols = dict(q=rb.n, l=rb.m, u=rb.m, Px=rb.nnzP, Ax=rb.nnzA)
+        want = tuple(k for k in NAMES if need[k] and cols[k] > 0)
+        if gx is None and gy is None:
+            return (None,) * 6
+        dev = gx.device if gx is not None else gy.device
+        out = {k: torch.empty((rb.count, cols[k]), dtype=torch.float64, device=dev) for k in want}
+        _sync(gx if gx is not None else gy)
+        rb.adjoint(dx=None if gx is None else gx.contiguous(), dy=None if gy is None or rb.m == 0 else gy.contiguous(), want=want, out=out)
+        grads = {k: (out[k] if k in out else (torch.zeros((rb.count, 0), dtype=torch.float64, device=dev) if need[k] else None)) for k in NAMES}
+        return (None,) + tuple(grads[k] for k in NAMES)
+
+
+class BatchQPLayer(torch.nn.Module):
+    """`layer(q=None, l=None, u=None, Px=None, Ax=None) -> (x, y)` on the resident batch `rb`; `layer.info` is the info
+    array [count x 6] of the last forward."""
+
+    def __init__(self, rb):
+        super().__init__()
+        self.rb, self.info = rb, None
+
+    def forward(self, q=None, l=None, u=None, Px=None, Ax=None):
+        x, y = BatchQPFunction.apply(self.rb, q, l, u, Px, Ax)
+        self.info = self.rb._qp_layer_info
+        return x, y

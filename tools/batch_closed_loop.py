@@ -12,7 +12,13 @@ instance-iterations.  The library has no per-kernel event timer for the batched 
 --polish: the resident legs B, C, D run with settings.polish = 1 (a second launch per period polishes the Solved instances);
 leg A, the one-shot entry, ignores the setting.  Their lines then carry `polished_fraction`: accepted polishes per
 instance-period.
-usage: python tools/batch_closed_loop.py [--polish] [count] [K] [W]"""
+--adjoint: instead of the four legs, the cost of differentiating the loop.  Two leg-D handles (device pointers) take the same
+updates, one with polish = 0 and one with polish = 1; per period, alternated, each call timed on its own (every call blocks):
+the resolve of the first, the resolve + polish launch of the second, then on the second `adjoint` with all five gradients
+and with dq, dl, du only (device inputs and outputs).  One JSON line: the median over the timed periods of each, the mean
+iterations of the two resolves, and the polish launch estimated as the second resolve minus the first scaled by their
+iteration counts (the two handles warm-start from different points, so their ADMM launches are not the same work).
+usage: python tools/batch_closed_loop.py [--polish | --adjoint] [count] [K] [W]"""
 import json
 import os
 import sys
@@ -28,7 +34,8 @@ from osqp_jl_amd import batch  # noqa: E402
 import batch_resident_ref as ref  # noqa: E402
 
 POLISH = "--polish" in sys.argv[1:]
-argv = [a for a in sys.argv[1:] if a != "--polish"]
+ADJOINT = "--adjoint" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a not in ("--polish", "--adjoint")]
 count = int(argv[0]) if len(argv) > 0 else 4096
 K = int(argv[1]) if len(argv) > 1 else 10
 W = int(argv[2]) if len(argv) > 2 else 2
@@ -40,6 +47,50 @@ args = ref.stack(ref.mpc_instances(olib, 0, count, 5))
 P0, A0, Px, Ax, q, l, u = args
 steps = ref.closed_loop_steps(q, l, u, steps=W + K + 1)
 dev = lambda a: batch.DeviceArray(lib, *a.shape).upload(a)
+
+
+def adjoint_legs():
+    h0, h1 = batch.ResidentBatch(lib, *args, **dict(OPTS, polish=False)), batch.ResidentBatch(lib, *args, **dict(OPTS, polish=True))
+    out0, out1 = h0.alloc(), h1.alloc()
+    h0.solve(out=out0); h1.solve(out=out1)
+    rng = np.random.default_rng(0)
+    gx, gy = dev(rng.standard_normal((count, h1.n))), dev(rng.standard_normal((count, h1.m)))
+    cols = dict(q=h1.n, l=h1.m, u=h1.m, Px=h1.nnzP, Ax=h1.nnzA, act=h1.m, status=1)
+    outs = {k: batch.DeviceArray(lib, count, c) for k, c in cols.items()}
+    t = {k: [] for k in ("resolve", "resolve_polish", "adjoint_all", "adjoint_qlu")}
+    its, differentiated = {"resolve": [], "resolve_polish": []}, 0
+    for k in range(1, W + K + 1):
+        dq, dl, du = (dev(a) for a in steps[k])
+        for name, h, out in (("resolve", h0, out0), ("resolve_polish", h1, out1)):
+            h.update(q=dq, l=dl, u=du)
+            t0 = time.perf_counter()
+            h.solve(out=out)
+            t[name].append(1e3 * (time.perf_counter() - t0))
+            its[name].append(float(np.sum(out[2].numpy()[:, 0])))
+        for name, want in (("adjoint_all", ("q", "l", "u", "Px", "Ax")), ("adjoint_qlu", ("q", "l", "u"))):
+            t0 = time.perf_counter()
+            h1.adjoint(dx=gx, dy=gy, want=want, out=outs)
+            t[name].append(1e3 * (time.perf_counter() - t0))
+        if k > W:
+            differentiated += int(np.sum(outs["status"].numpy() == 1))
+        for a in (dq, dl, du):
+            a.free()
+    med = {k: float(np.median(v[W:])) for k, v in t.items()}
+    it = {k: float(np.mean(v[W:])) for k, v in its.items()}
+    print(json.dumps(dict(what="adjoint of the closed loop, device pointers", instances=count, periods=K, warmup=W,
+                          kernel=int(lib.osqp_amd_batch_last_kernel()), ms_resolve_median=med["resolve"],
+                          ms_resolve_with_polish_median=med["resolve_polish"], iterations_resolve=it["resolve"],
+                          iterations_resolve_with_polish=it["resolve_polish"],
+                          ms_polish_launch_estimate=med["resolve_polish"] - med["resolve"] * it["resolve_polish"] / it["resolve"],
+                          ms_adjoint_all_median=med["adjoint_all"], ms_adjoint_qlu_median=med["adjoint_qlu"],
+                          ms_adjoint_all_min=float(np.min(t["adjoint_all"][W:])), ms_adjoint_qlu_min=float(np.min(t["adjoint_qlu"][W:])),
+                          differentiated_fraction=differentiated / (count * K))))
+    h0.close(); h1.close()
+
+
+if ADJOINT:
+    adjoint_legs()
+    sys.exit(0)
 handles = {"B": batch.ResidentBatch(lib, *args, **dict(OPTS, warm_start=False)), "C": batch.ResidentBatch(lib, *args, **OPTS),
            "D": batch.ResidentBatch(lib, *args, **OPTS)}
 out_d = handles["D"].alloc()
