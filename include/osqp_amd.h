@@ -395,6 +395,14 @@ c_int osqp_amd_apply(OSQPWorkspace *work, c_int op, const c_float *in, c_float *
  * the four-wavefront kernel (csrc/batch_common.hpp OQ_QUAD_ENTRIES; 0 = the MPC family with its shape compiled in), -2 none yet. */
 c_int osqp_amd_batch_last_kernel(void);
 
+/* The schedule of that launch (tests, diagnostics): fills out[0 .. min(count, 11)) with, in this order, the entry number as
+ * osqp_amd_batch_last_kernel gives it, the pivots of the two-ended first phase taken from the top and from the bottom
+ * (p1_top, p1_bot), the furthest such a pivot reaches (bw), the term slots per thread and assembly window (ns), the longest
+ * row held by each of the four wavefronts (kew[0 .. 3]), the bytes of LDS of a workgroup, and the instances launched.  For the
+ * 512-thread kernel the schedule numbers are 0 and the bytes are that kernel's; before any launch out[0] = -2 and the rest
+ * is 0.  Returns the number of entries written. */
+c_int osqp_amd_batch_last_schedule(c_int *out, c_int count);
+
 /* Batched path: `count` independent QPs that
  * share one sparsity pattern.  P (upper triangle) and A are given once as
  * patterns; values are [count x nnz] row-major; q,l,u are [count x n|m].

@@ -47,6 +47,22 @@ def solve_batch(lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, **sett
     return x, y, info
 
 
+SCHEDULE_FIELDS = ("entry", "p1_top", "p1_bot", "bw", "ns", "kew0", "kew1", "kew2", "kew3", "lds_bytes", "instances")
+
+
+def last_schedule(lib):
+    """The schedule of the last batched launch of this process (osqp_amd_batch_last_schedule) as a dict: `entry` (-1 the
+    512-thread kernel, -2 none yet), `p1_top`, `p1_bot`, `bw`, `ns`, `kew` (the four wavefronts' longest rows), `lds_bytes`,
+    `instances`."""
+    out = np.zeros(len(SCHEDULE_FIELDS), dtype=np.int64)
+    got = lib.osqp_amd_batch_last_schedule(out.ctypes.data, len(out))
+    if got != len(out):
+        raise OSQPError(f"osqp_amd_batch_last_schedule wrote {got} of {len(out)} entries")
+    d = {k: int(v) for k, v in zip(SCHEDULE_FIELDS, out)}
+    d["kew"] = [d.pop("kew%d" % i) for i in range(4)]
+    return d
+
+
 def shard_range(count, rank, world):
     """Contiguous equal blocks: instance i -> rank floor(i / (count / world))."""
     if count % world != 0:

@@ -39,6 +39,9 @@ namespace {
 int g_batch_polish_launches = 0;  // launches of k_batch_polish by this process (osqp_amd_batch_polish_launches)
 int g_batch_adjoint_launches = 0;  // launches of k_batch_adjoint by this process (osqp_amd_batch_adjoint_launches)
 int g_batch_last_kernel = -2;  // what launch_batch launched last: -1 the 512-thread kernel, >= 0 the number of the entry of OQ_QUAD_ENTRIES
+// the schedule of that launch (osqp_amd_batch_last_schedule): entry, p1_top, p1_bot, bw, ns, kew[0..3], LDS bytes, instances
+constexpr int kSchedWords = 11;
+int g_batch_last_schedule[kSchedWords] = {-2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 inline bool batch_quad_enabled() {  // OSQP_AMD_BATCH_QUAD=0: the MPC family on the 512-thread kernel (A/B runs, tests)
   const char *e = getenv("OSQP_AMD_BATCH_QUAD");
   return !e || atoi(e) != 0;
@@ -184,6 +187,12 @@ void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, co
     // was built for.  FIXED entries get the shape of the MPC family as template arguments (DevicePattern::build tries
     // them for that family only).
     g_batch_last_kernel = dp.quad->number;
+    {
+      const quad::Sched &q = dp.QS;
+      const int sched[kSchedWords] = {dp.quad->number, q.p1_top, q.p1_bot, q.bw, q.ns, q.kew[0], q.kew[1], q.kew[2], q.kew[3],
+                                      quad::make_layout(P.n, P.m, P.nnzA, P.nnzF, dp.quad->NH, dp.quad->KC, dp.quad->KE, dp.quad->CH).total, count};
+      std::copy(sched, sched + kSchedWords, g_batch_last_schedule);
+    }
     switch (dp.quad->number) {
 #define OQ_QUAD_CASE(NUMBER, NH, KC, KE, CH, FIXED, KERNEL)                                                                    \
   case NUMBER: {                                                                                                               \
@@ -201,6 +210,10 @@ void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, co
   if (dp.scratch.n < need) { HIP_CHECK(hipStreamSynchronize(s)); dp.scratch.alloc(need); }
   const int nc = (P.n + PARTS - 1) / PARTS;  // columns of the inverse per thread: the register tile is sized at compile time
   g_batch_last_kernel = -1;
+  {
+    const int sched[kSchedWords] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, (int)bytes, count};  // no schedule: the LDS bytes are this kernel's
+    std::copy(sched, sched + kSchedWords, g_batch_last_schedule);
+  }
   // shapes compiled in (same source, constants folded): the MPC family of BASELINE.json config 5
   if (dp.mpc) launch_kernel_solve(k_batch_solve<25, MPC_N, MPC_M, kMpcNnzA, MPC_N>, bytes, dp, st, count, io, s);
   else if (nc <= 16) launch_kernel_solve(k_batch_solve<16, 0, 0, 0, 0>, bytes, dp, st, count, io, s);
@@ -342,6 +355,12 @@ using namespace oq;
 extern "C" {
 
 c_int osqp_amd_batch_last_kernel(void) { return g_batch_last_kernel; }
+c_int osqp_amd_batch_last_schedule(c_int *out, c_int count) {
+  if (!out || count <= 0) return 0;
+  const c_int k = std::min<c_int>(count, kSchedWords);
+  for (c_int i = 0; i < k; i++) out[i] = g_batch_last_schedule[i];
+  return k;
+}
 c_int osqp_amd_batch_polish_launches(void) { return g_batch_polish_launches; }
 c_int osqp_amd_batch_adjoint_launches(void) { return g_batch_adjoint_launches; }
 

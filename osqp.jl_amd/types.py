@@ -216,6 +216,7 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_polish_status": (c_int, [C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_update_polish": (c_int, [C.c_void_p, c_int, c_int]),
     "osqp_amd_batch_last_kernel": (c_int, []),
+    "osqp_amd_batch_last_schedule": (c_int, [C.c_void_p, c_int]),
     "osqp_amd_batch_adjoint": (c_int, [C.c_void_p] + [C.c_void_p] * 9 + [c_int]),
     "osqp_amd_batch_polish_launches": (c_int, []),
     "osqp_amd_batch_adjoint_launches": (c_int, []),

@@ -49,6 +49,10 @@ def test_batch_host_api_matches_oracle(product_lib, oracle_lib):
         assert abs(info[i, 4] - r.info.obj_val) <= 1e-4 * max(1.0, abs(r.info.obj_val))
 
 
+# the entry of OQ_QUAD_ENTRIES each shape's random pattern takes (the first it fits, in the order of the table); no rows: none
+GENERIC_SHAPE_ENTRY = {(3, 2): 1, (16, 40): 1, (17, 0): -1, (40, 25): 2, (64, 100): 2, (65, 30): 3, (100, 60): 10, (113, 20): 5, (128, 90): 5}
+
+
 @pytest.mark.parametrize("n,m", [(3, 2), (16, 40), (17, 0), (40, 25), (64, 100), (65, 30), (100, 60), (113, 20), (128, 90)])
 def test_batch_generic_shapes_match_oracle(product_lib, oracle_lib, n, m):
     """Shapes other than the MPC family go through the run-time-sized instantiations (register tiles of 16 / 25 / 32
@@ -88,7 +92,8 @@ def test_batch_generic_shapes_match_oracle(product_lib, oracle_lib, n, m):
     # column / row bound, csrc/batch_common.hpp OQ_QUAD_ENTRIES) -- the 512-thread kernel with its global scratch is left
     # with what does not fit (no constraint rows, more than 256 rows, columns / rows beyond 32 entries)
     kernel = product_lib.osqp_amd_batch_last_kernel()
-    assert kernel >= 1 if m > 0 else kernel == -1, kernel
+    sched = batch.last_schedule(product_lib)
+    assert kernel == sched["entry"] == GENERIC_SHAPE_ENTRY[(n, m)] and sched["instances"] == count, (kernel, sched)
     ref = _oracle_solutions(oracle_lib, probs)
     for i, r in enumerate(ref):
         assert r.info.status == "Solved" and int(info[i, 1]) == 1, (i, r.info.status, info[i])
