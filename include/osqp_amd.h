@@ -494,6 +494,27 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             since (any update_* or warm_start; update_polish does not count), and a pattern whose working set exceeds
  *             the polish LDS limit.  The call changes nothing on the handle: a resolve after it is bit-identical to one
  *             without it.
+ *   certificates(): the directions that prove the infeasibilities of the handle's last resolve -- results.prim_inf_cert /
+ *             dual_inf_cert of a single model.  Row i of prim_inf_cert_out [count x m], for an instance whose status is
+ *             primal infeasible (or its inaccurate form), is the projected delta_y of the terminating check, multiplied
+ *             element-wise by E when scaling is on and scaled_termination off, then divided by its infinity norm: its largest
+ *             entry is exactly +-1.  Row i of dual_inf_cert_out [count x n] is the same with delta_x and D for the two dual
+ *             infeasible statuses.  Every other row is NaN; before the first resolve all rows are.  Like polish_status they
+ *             are results of the last resolve: update_* and warm_start leave them readable, the next resolve replaces them.
+ *             Either pointer may be NULL (not wanted; both NULL: return 1); with m = 0 the first is ignored.  The call only
+ *             copies: every resolve makes one extra small launch (k_batch_cert) after its ADMM launch, which normalises
+ *             the directions that launch left in the records and puts the records back as they were -- the one-shot
+ *             entries and the MPC handle make none and have no certificates.
+ *   update_setting(): the batch form of osqp_update_<name>, by name: max_iter, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf,
+ *             time_limit, rho, alpha, delta, polish, polish_refine_iter, verbose, scaled_termination, check_termination,
+ *             warm_start.  The value must pass the rule of the single-model function of that name, and an integer setting
+ *             must be given an integral value; otherwise return 1 with a message naming the setting, and the handle is
+ *             unchanged.  Any other name (sigma, scaling, adaptive_rho*, linsys_solver, ...) returns 1 with "<name> cannot
+ *             be updated or is not recognized".  The value acts from the next resolve.  rho also replaces the stored rho of
+ *             EVERY instance, adapted or not, as osqp_update_rho rebuilds rho_vec (the iterate stays); polish and
+ *             polish_refine_iter go the way of update_polish, with its LDS refusal; time_limit and verbose are stored and
+ *             have no effect (below).  No setting change makes the stored solution stale for adjoint(), and the certificates
+ *             and polish_status of the last resolve stay as they are.
  * where: 0 = the array arguments are host pointers, 1 = device pointers on the handle's device (no host hop: a controller
  * whose state estimate lives in HBM).  A NULL array means "keep" (update_*) / "none" (warm_start).  Every call blocks until
  * done.  Single rank.  The handle is freed by osqp_amd_batch_destroy; it is not interchangeable with the handle of
@@ -510,6 +531,9 @@ c_int osqp_amd_batch_warm_start(osqp_amd_batch *batch, const c_float *x_all, con
 c_int osqp_amd_batch_resolve(osqp_amd_batch *batch, c_float *x_out, c_float *y_out, c_float *info_out, c_int where);
 c_int osqp_amd_batch_polish_status(osqp_amd_batch *batch, c_float *status_out, c_int where);
 c_int osqp_amd_batch_update_polish(osqp_amd_batch *batch, c_int polish_new, c_int polish_refine_iter_new);
+c_int osqp_amd_batch_update_setting(osqp_amd_batch *batch, const char *name, c_float value);
+c_int osqp_amd_batch_certificates(osqp_amd_batch *batch, c_float *prim_inf_cert_out /* [count x m] */,
+                                  c_float *dual_inf_cert_out /* [count x n] */, c_int where);
 c_int osqp_amd_batch_adjoint(osqp_amd_batch *batch, const c_float *dx, const c_float *dy,
                              c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
                              c_float *act_out, c_float *status_out, c_int where);
@@ -518,6 +542,9 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *batch, const c_float *dx, const c_f
 c_int osqp_amd_batch_polish_launches(void);
 /* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint that passed its checks, none otherwise. */
 c_int osqp_amd_batch_adjoint_launches(void);
+/* The same for the certificate kernel: one launch per osqp_amd_batch_resolve, none by osqp_amd_batch_certificates or by the
+ * one-shot entries. */
+c_int osqp_amd_batch_cert_launches(void);
 
 /* Device memory for callers without an allocator of their own (the packed result array above): plain hipMalloc / hipFree /
  * hipMemcpy on `device`.  copy kind: 0 device -> host, 1 host -> device, 2 device -> device; blocking. */
@@ -533,7 +560,9 @@ c_int osqp_amd_device_copy(void *dst, const void *src, c_int bytes, c_int kind, 
  * `polish` (with `polish_refine_iter` and `delta`): they equilibrate, start from zero every time and return the ADMM
  * iterate.  The resident handle (osqp_amd_batch_setup) honours all of them: it keeps scaling, iterate and rho between
  * solves and polishes the Solved instances after the ADMM launch when `polish` = 1, as described above; the per-instance
- * status_polish is read with osqp_amd_batch_polish_status (the six info columns do not change). */
+ * status_polish is read with osqp_amd_batch_polish_status (the six info columns do not change).  Only the resident handle
+ * returns infeasibility certificates (osqp_amd_batch_certificates) and takes settings updates after setup
+ * (osqp_amd_batch_update_setting: the names of osqp_update_*; `time_limit` and `verbose` are stored and ignored as above). */
 
 /* Select the HIP device for workspaces created afterwards by this process
  * (one process per GPU: pass LOCAL_RANK). */

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import types as T
 from .interface import _as_f64, _fptr, _iptr, make_settings, OSQPError
-from .constants import status_map
+from .constants import UPDATABLE_SETTINGS, status_map
 
 MPC_N, MPC_M = 100, 200
 INFO_COLS = 4  # iter, status_val, pri_res, dua_res
@@ -346,6 +346,52 @@ class ResidentBatch:
             raise ValueError(f"polish_refine_iter: expected a nonnegative integer, got {polish_refine_iter!r}")
         self._call("update", self.lib.osqp_amd_batch_update_polish(self.handle, int(polish), int(polish_refine_iter)))
         self.polish_refine_iter = int(polish_refine_iter)
+
+    # what `update_settings` takes: the list of a single model, and scaled_termination, for which the C ABI has a symbol too
+    SETTINGS = tuple(UPDATABLE_SETTINGS) + ("scaled_termination",)
+
+    def update_settings(self, **kw):
+        """New values for settings of the following solves, as `update_settings` does for a single model: the names of
+        `constants.UPDATABLE_SETTINGS` and `scaled_termination`, each checked by the rule of the single-model function
+        (osqp_amd_batch_update_setting).  Any other name raises before the library is called; values of None are skipped.
+        `rho` also replaces the rho of every instance, adapted or not; the iterate stays.  The calls are issued in the order
+        of the list; one that is refused raises and leaves its setting (and those after it) unchanged."""
+        for key in kw:
+            if key not in self.SETTINGS:
+                raise OSQPError(f"{key} cannot be updated or is not recognized")
+        for key in self.SETTINGS:
+            value = kw.get(key)
+            if value is None:
+                continue
+            self._call("settings update", self.lib.osqp_amd_batch_update_setting(self.handle, key.encode(), float(value)))
+            if key == "polish_refine_iter":
+                self.polish_refine_iter = int(value)
+
+    def certificates(self, out=None):
+        """(prim_inf_cert [count x m], dual_inf_cert [count x n]) of the last `solve()`: row i of the first is the direction
+        that proves instance i primal infeasible (status -3 or 3), of the second dual infeasible (-4 or 4), each with
+        largest entry +-1 as a single model's results carry them; every other row is NaN, and all rows before the first
+        solve.  out=None: numpy arrays; out=(p, d) of device arrays, either may be None: filled in place and returned.
+        With m = 0 the first element is None."""
+        if out is None:
+            p = np.empty((self.count, self.m)) if self.m else None
+            d = np.empty((self.count, self.n))
+            self._call("certificates", self.lib.osqp_amd_batch_certificates(self.handle, None if p is None else p.ctypes.data, d.ctypes.data, 0))
+            return p, d
+        if len(out) != 2:
+            raise ValueError("out: expected (prim_inf_cert, dual_inf_cert)")
+        ptrs = []
+        for name, a, k in (("out[0]", out[0], self.m), ("out[1]", out[1], self.n)):
+            if a is None:
+                ptrs.append(None)
+                continue
+            if not hasattr(a, "data_ptr"):
+                raise ValueError(f"{name}: expected a device array (DeviceArray, torch tensor); omit `out` for numpy results")
+            ptrs.append(_batch_array(name, a, (self.count, k))[1])
+        if ptrs[1] is None and (ptrs[0] is None or self.m == 0):
+            raise ValueError("out: no certificate was asked for")
+        self._call("certificates", self.lib.osqp_amd_batch_certificates(self.handle, ptrs[0], ptrs[1], 1))
+        return (None if self.m == 0 else out[0]), out[1]
 
     ADJOINT_WANT = ("q", "l", "u", "Px", "Ax")
 

@@ -581,7 +581,7 @@ c_int osqp_update_P_A(OSQPWorkspace *w, const c_float *Px_new, const c_int *Px_n
 c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  if (rho_new <= 0) return 1;
+  if (!setting_ok_rho(rho_new)) return 1;
   return guarded([&]() {
     Engine &e = *E(w);
     e.begin_update();
@@ -592,10 +592,11 @@ c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
   });
 }
 
-#define OQ_SETTING(fn, type, field, cond)                 \
+// the rule of every setting is setting_ok_<field> (engine.hpp, OQ_UPDATABLE_SETTINGS: shared with the resident batch)
+#define OQ_SETTING(fn, type, field)                       \
   c_int fn(OSQPWorkspace *w, type v) {                    \
     if (!w) return 7;                                     \
-    if (!(cond)) return 1;                                \
+    if (!setting_ok_##field(v)) return 1;                 \
     OQ_ON_DEVICE(w);                                      \
     return guarded([&]() {                                \
       E(w)->st.field = v;                                 \
@@ -604,26 +605,24 @@ c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
       return 0;                                           \
     });                                                   \
   }
-OQ_SETTING(osqp_update_max_iter, c_int, max_iter, v > 0)
-OQ_SETTING(osqp_update_eps_abs, c_float, eps_abs, v >= 0.)
-OQ_SETTING(osqp_update_eps_rel, c_float, eps_rel, v >= 0.)
-// libosqp's update functions reject only negative values here (the > 0 rule is the setup validation's): a caller's
-// update_settings!(eps_prim_inf = 0) [REF src/interface.jl:506-530] stays legal
-OQ_SETTING(osqp_update_eps_prim_inf, c_float, eps_prim_inf, v >= 0.)
-OQ_SETTING(osqp_update_eps_dual_inf, c_float, eps_dual_inf, v >= 0.)
-OQ_SETTING(osqp_update_alpha, c_float, alpha, v > 0. && v < 2.)
-OQ_SETTING(osqp_update_delta, c_float, delta, v > 0.)
-OQ_SETTING(osqp_update_polish_refine_iter, c_int, polish_refine_iter, v >= 0)
-OQ_SETTING(osqp_update_verbose, c_int, verbose, v == 0 || v == 1)
-OQ_SETTING(osqp_update_scaled_termination, c_int, scaled_termination, v == 0 || v == 1)
-OQ_SETTING(osqp_update_check_termination, c_int, check_termination, v >= 0)
-OQ_SETTING(osqp_update_warm_start, c_int, warm_start, v == 0 || v == 1)
-OQ_SETTING(osqp_update_time_limit, c_float, time_limit, v >= 0.)
+OQ_SETTING(osqp_update_max_iter, c_int, max_iter)
+OQ_SETTING(osqp_update_eps_abs, c_float, eps_abs)
+OQ_SETTING(osqp_update_eps_rel, c_float, eps_rel)
+OQ_SETTING(osqp_update_eps_prim_inf, c_float, eps_prim_inf)
+OQ_SETTING(osqp_update_eps_dual_inf, c_float, eps_dual_inf)
+OQ_SETTING(osqp_update_alpha, c_float, alpha)
+OQ_SETTING(osqp_update_delta, c_float, delta)
+OQ_SETTING(osqp_update_polish_refine_iter, c_int, polish_refine_iter)
+OQ_SETTING(osqp_update_verbose, c_int, verbose)
+OQ_SETTING(osqp_update_scaled_termination, c_int, scaled_termination)
+OQ_SETTING(osqp_update_check_termination, c_int, check_termination)
+OQ_SETTING(osqp_update_warm_start, c_int, warm_start)
+OQ_SETTING(osqp_update_time_limit, c_float, time_limit)
 
 c_int osqp_update_polish(OSQPWorkspace *w, c_int v) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  if (v != 0 && v != 1) return 1;
+  if (!setting_ok_polish(v)) return 1;
   return guarded([&]() {
     E(w)->st.polish = v;
     w->settings->polish = v;

@@ -15,7 +15,9 @@
 //                     when the handle's settings.polish is 1; the solve kernels know nothing of it;
 //   batch_adjoint.hpp k_batch_adjoint -- adjoint derivatives of the solutions of the resident batch, a launch of its own on
 //                     request (osqp_amd_batch_adjoint); shares the factorisation and the solves of the polish kernel;
-//   this file         the small kernels (warm start, bound check, MPC generator), the launcher (launch_batch), the handle
+//   batch_cert.hpp    k_batch_cert -- the infeasibility certificates of the resident batch, a launch of its own after every
+//                     ADMM launch of osqp_amd_batch_resolve: normalises the directions that launch left in the records (RES_CERT);
+//   this file         the small kernels (warm start, rho fill, bound check, MPC generator), the launcher (launch_batch), the handle
 //                     (BatchPlan) and the C ABI.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
 // Both kernels also run in RESIDENT mode (osqp_amd_batch_setup ... _resolve, "the state record" in batch_common.hpp):
@@ -25,8 +27,11 @@
 // instance range over ranks and gathers the packed results once (batch.py).
 #include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <type_traits>
 
 #include "batch_adjoint.hpp"
+#include "batch_cert.hpp"
 #include "batch_polish.hpp"
 #include "batch_quad.hpp"
 #include "batch_sched.hpp"
@@ -38,6 +43,7 @@ namespace {
 
 int g_batch_polish_launches = 0;  // launches of k_batch_polish by this process (osqp_amd_batch_polish_launches)
 int g_batch_adjoint_launches = 0;  // launches of k_batch_adjoint by this process (osqp_amd_batch_adjoint_launches)
+int g_batch_cert_launches = 0;  // launches of k_batch_cert by this process (osqp_amd_batch_cert_launches)
 int g_batch_last_kernel = -2;  // what launch_batch launched last: -1 the 512-thread kernel, >= 0 the number of the entry of OQ_QUAD_ENTRIES
 // the schedule of that launch (osqp_amd_batch_last_schedule): entry, p1_top, p1_bot, bw, ns, kew[0..3], LDS bytes, instances
 constexpr int kSchedWords = 11;
@@ -64,6 +70,12 @@ __global__ __launch_bounds__(256) void k_batch_warm(Pattern P, int count, const 
     rec[rec_z(n, m) + i] = e * ax;
     rec[rec_y(n, m) + i] = y_all ? c * y_all[(size_t)inst * m + i] / e : 0.0;
   }
+}
+
+// the rho of osqp_amd_batch_update_setting("rho") into every record, as osqp_update_rho rebuilds rho_vec; the iterate stays
+__global__ __launch_bounds__(256) void k_batch_fill_rho(int count, double rho, double *__restrict__ rec_all, int rec_stride) {
+  const int inst = blockIdx.x * 256 + threadIdx.x;
+  if (inst < count) rec_all[(size_t)inst * rec_stride + REC_RHO] = rho;
 }
 
 // rows with l > u, counted per launch (osqp_amd_batch_update_bounds refuses the update when there is one)
@@ -267,6 +279,10 @@ struct BatchPlan : BatchData {
   // the caller's went to device pointers.  Staging of host-pointer calls: gradients in through in_a / in_b, out through adj_out
   bool sol_current = false;
   DevBuf<double> adj_out;
+  // certificates (osqp_amd_batch_certificates): [count x m] and [count x n], NaN from setup, then written by k_batch_cert
+  // after every resolve
+  DevBuf<double> pcert, dcert;
+  bool rec_raw = false;  // a solve launched with RES_CERT whose k_batch_cert has not been launched (osqp_amd_batch_resolve)
 };
 
 // The checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings], shared by the
@@ -343,6 +359,20 @@ void launch_polish(BatchPlan &b, const BatchIO &io, hipStream_t s) {
   g_batch_polish_launches++;
   OQ_LAUNCH(polish::k_batch_polish, dim3(b.count), dim3(polish::PT), (size_t)L.total, s, P, b.count, L, a);
 }
+// the certificates of the launch that has just written io.info and, under RES_CERT, left the directions in the records
+void launch_cert(BatchPlan &b, const BatchIO &io, hipStream_t s) {
+  cert::Args a;
+  a.info = io.info; a.rec = io.rec; a.prim = b.m ? b.pcert.get() : nullptr; a.dual = b.dcert.get();
+  a.info_stride = io.info_stride; a.rec_stride = io.rec_stride; a.unscaled = b.st.scaling && !b.st.scaled_termination;
+  g_batch_cert_launches++;
+  OQ_LAUNCH(cert::k_batch_cert, dim3(b.count), dim3(cert::CT), 0, s, b.n, b.m, b.count, a);
+}
+// polish / polish_refine_iter of a resident handle (osqp_amd_batch_update_polish, osqp_amd_batch_update_setting); the values
+// have passed their rules
+void set_polish(BatchPlan &b, c_int polish_new, c_int refine_new) {
+  if (polish_new) polish_check_fits(b.dp.P);
+  b.st.polish = polish_new; b.st.polish_refine_iter = refine_new;
+}
 #define OQ_BATCH_CATCH                                                                          \
   catch (const Error &er) { set_last_error(er.what()); return er.code ? er.code : 6; }         \
   catch (const std::exception &ex) { set_last_error(ex.what()); return 6; }
@@ -363,6 +393,7 @@ c_int osqp_amd_batch_last_schedule(c_int *out, c_int count) {
 }
 c_int osqp_amd_batch_polish_launches(void) { return g_batch_polish_launches; }
 c_int osqp_amd_batch_adjoint_launches(void) { return g_batch_adjoint_launches; }
+c_int osqp_amd_batch_cert_launches(void) { return g_batch_cert_launches; }
 
 c_int osqp_amd_batch_solve(c_int count, c_int n, c_int m, const c_int *Pp, const c_int *Pi, const c_float *Px_all, const c_int *Ap,
                            const c_int *Ai, const c_float *Ax_all, const c_float *q_all, const c_float *l_all, const c_float *u_all,
@@ -482,6 +513,12 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, 
     const size_t cnt = (size_t)count;
     b->upload(prob, b->dp.P, s);
     b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6); b->bad.alloc(1); b->pstat.alloc(cnt);
+    {
+      const std::vector<double> nan(cnt * std::max(n, m), NAN);
+      b->pcert.alloc(cnt * m); b->dcert.alloc(cnt * n);
+      b->pcert.upload(nan.data(), cnt * m, s); b->dcert.upload(nan.data(), cnt * n, s);
+      HIP_CHECK(hipStreamSynchronize(s));  // nan leaves scope
+    }
     // the records: a zero iterate (the first solve starts from zero either way), the rho of the settings
     std::vector<double> hrec(cnt * b->rec_stride, 0.0);
     for (size_t i = 0; i < cnt; i++) hrec[i * b->rec_stride + REC_RHO] = settings->rho;
@@ -577,8 +614,14 @@ c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_
     BatchIO io = b->inputs();
     io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : b->info_out.get();
     io.x_stride = b->n; io.y_stride = b->m; io.info_stride = io.info_cols = 6;
-    io.rec = b->rec.get(); io.rec_stride = b->rec_stride; io.res_mode = RES_SOLVE | (b->st.warm_start ? RES_WARM : 0);
+    // (a resolve that failed between its solve launch and k_batch_cert may have left directions where the records of
+    // infeasible instances hold zeros: the next one starts every instance from zero and rewrites every record)
+    io.rec = b->rec.get(); io.rec_stride = b->rec_stride;
+    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0);
+    b->rec_raw = true;
     launch_batch(b->dp, b->st, b->count, io, s);
+    launch_cert(*b, io, s);  // before anything else reads the records: it puts them back as a solve without RES_CERT leaves them
+    b->rec_raw = false;
     b->pstat_live = b->st.polish != 0;
     if (b->pstat_live) launch_polish(*b, io, s);
     if (where) copy_d2d(b->info_out.get(), info_out, (size_t)b->count * 6, s);  // the statuses, for osqp_amd_batch_adjoint
@@ -661,11 +704,61 @@ c_int osqp_amd_batch_polish_status(osqp_amd_batch *handle, c_float *status_out, 
 c_int osqp_amd_batch_update_polish(osqp_amd_batch *handle, c_int polish_new, c_int polish_refine_iter_new) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
-  if (polish_new != 0 && polish_new != 1) { set_last_error("polish must be 0 or 1"); return 1; }
-  if (polish_refine_iter_new < 0) { set_last_error("polish_refine_iter must be nonnegative"); return 1; }
+  if (!setting_ok_polish(polish_new)) { set_last_error("polish must be 0 or 1"); return 1; }
+  if (!setting_ok_polish_refine_iter(polish_refine_iter_new)) { set_last_error("polish_refine_iter must be nonnegative"); return 1; }
   try {
-    if (polish_new) polish_check_fits(b->dp.P);
-    b->st.polish = polish_new; b->st.polish_refine_iter = polish_refine_iter_new;
+    set_polish(*b, polish_new, polish_refine_iter_new);
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_update_setting(osqp_amd_batch *handle, const char *name, c_float value) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!name) { set_last_error("invalid batch data"); return 1; }
+  try {
+    // the rule of the name from the table of the single-model updates (engine.hpp); an integer setting takes integral values
+    OSQPSettings st = b->st;
+    bool known = false, ok = false;
+#define OQ_BATCH_SETTING(field, type, cond)                                                                       \
+    if (!known && !strcmp(name, #field)) {                                                                          \
+      known = true;                                                                                                 \
+      const bool whole = std::is_floating_point<type>::value || (value == std::floor(value) && std::fabs(value) <= 9007199254740992.0); \
+      if (whole && setting_ok_##field((type)value)) { st.field = (type)value; ok = true; }                          \
+    }
+    OQ_UPDATABLE_SETTINGS(OQ_BATCH_SETTING)
+#undef OQ_BATCH_SETTING
+    if (!known) { set_last_error(std::string(name) + " cannot be updated or is not recognized"); return 1; }
+    if (!ok) { set_last_error(std::string("invalid value for the setting ") + name); return 1; }
+    if (!strcmp(name, "polish") || !strcmp(name, "polish_refine_iter")) { set_polish(*b, st.polish, st.polish_refine_iter); return 0; }
+    if (!strcmp(name, "rho")) {  // also the stored rho of every instance, as osqp_update_rho rebuilds rho_vec from it
+      DeviceScope on_dev(b->device);
+      hipStream_t s = nullptr;
+      st.rho = std::min(std::max(st.rho, (c_float)B_RHO_MIN), (c_float)B_RHO_MAX);
+      OQ_LAUNCH(k_batch_fill_rho, dim3(blocks_for(b->count, 256)), dim3(256), 0, s, b->count, (double)st.rho, b->rec.get(), b->rec_stride);
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    b->st = st;  // acts from the next resolve; data and iterate are unchanged: sol_current, the certificates and polish_status stay
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_certificates(osqp_amd_batch *handle, c_float *prim_inf_cert_out, c_float *dual_inf_cert_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (b->m == 0) prim_inf_cert_out = nullptr;
+  if (!prim_inf_cert_out && !dual_inf_cert_out) { set_last_error("invalid batch data: no certificate was asked for"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    c_float *const out[2] = {prim_inf_cert_out, dual_inf_cert_out};
+    DevBuf<double> *const src[2] = {&b->pcert, &b->dcert};
+    const size_t len[2] = {(size_t)b->count * b->m, (size_t)b->count * b->n};
+    for (int k = 0; k < 2; k++) {
+      if (!out[k]) continue;
+      if (where) copy_d2d(out[k], src[k]->get(), len[k], s); else src[k]->download(out[k], len[k], s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
 }

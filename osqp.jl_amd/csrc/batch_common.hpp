@@ -116,9 +116,17 @@ extern __shared__ __attribute__((aligned(16))) double lds_raw[];
 //   RES_SCALE_ONLY  run the Ruiz passes on the raw data, write D, E, c to the record, return (setup, matrix updates);
 //   RES_SOLVE       load D, E, c, rho and apply them instead of the Ruiz passes; leave x, z, y (zeros when the instance has
 //                   no solution, as the oracle cold-starts it) and rho behind at the end;
-//   RES_WARM        (with RES_SOLVE) start from the record's x, z, y instead of zero.
+//   RES_WARM        (with RES_SOLVE) start from the record's x, z, y instead of zero;
+//   RES_CERT        (with RES_SOLVE; osqp_amd_batch_resolve only) an instance that ends primal infeasible leaves the scaled,
+//                   projected delta_y in the y slot of its record instead of zeros, one that ends dual infeasible the scaled
+//                   delta_x in the x slot: k_batch_cert (batch_cert.hpp), launched next on the same stream, turns them into
+//                   the certificates and puts the zeros back.  No kernel argument and nothing before or inside the ADMM loop
+//                   of k_batch_quad / k_batch_quad2: their epilogue tests the bit of res_mode itself, which the compiler
+//                   loads again from the kernel arguments there, so a launch without the bit runs the code it ran before up
+//                   to the store.  In k_batch_solve, whose certificate store is a call that takes everything from LDS, the
+//                   bit travels in bit 0 of the parked record pointer (records are 16-byte aligned).
 // ---------------------------------------------------------------------------------------------------------
-enum { RES_SOLVE = 1, RES_WARM = 2, RES_SCALE_ONLY = 4 };
+enum { RES_SOLVE = 1, RES_WARM = 2, RES_SCALE_ONLY = 4, RES_CERT = 8 };
 enum { REC_C = 0, REC_RHO = 1, REC_FLAG = 2, REC_HDR = 4 };
 __host__ __device__ constexpr int rec_D(int, int) { return REC_HDR; }
 __host__ __device__ constexpr int rec_x(int n, int) { return REC_HDR + n; }
@@ -126,12 +134,18 @@ __host__ __device__ constexpr int rec_E(int n, int) { return REC_HDR + 2 * n; }
 __host__ __device__ constexpr int rec_z(int n, int m) { return REC_HDR + 2 * n + m; }
 __host__ __device__ constexpr int rec_y(int n, int m) { return REC_HDR + 2 * n + 2 * m; }
 __host__ __device__ constexpr int rec_doubles(int n, int m) { return (REC_HDR + 2 * n + 3 * m + 1) & ~1; }
-// a pointer parked in LDS by the prologue, back as a wave-uniform value
+// a pointer parked in LDS by the prologue, back as a wave-uniform value; k_batch_solve parks RES_CERT in bit 0 (park_rec)
 typedef __attribute__((address_space(3))) unsigned long long lu64;
+__device__ __forceinline__ unsigned long long park_rec(const double *rec, int res_mode) {
+  return (res_mode & RES_SOLVE) ? ((unsigned long long)rec | ((res_mode & RES_CERT) ? 1ull : 0ull)) : 0ull;
+}
 __device__ __forceinline__ double *parked_ptr(unsigned long long v) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return (double *)(((unsigned long long)hi << 32) | lo);
+  return (double *)(((unsigned long long)hi << 32) | (lo & ~7u));
 }
+__device__ __forceinline__ bool parked_cert(unsigned long long v) { return (__builtin_amdgcn_readfirstlane((int)(unsigned)v) & 1) != 0; }
+__host__ __device__ inline bool status_prim_inf(int s) { return s == OSQP_PRIMAL_INFEASIBLE || s == OSQP_PRIMAL_INFEASIBLE_INACCURATE; }
+__host__ __device__ inline bool status_dual_inf(int s) { return s == OSQP_DUAL_INFEASIBLE || s == OSQP_DUAL_INFEASIBLE_INACCURATE; }
 
 // the shape of the MPC family (BASELINE.json config 5; the generator is mpc_fill in batch.hip): both kernels have an
 // instantiation with it compiled in

@@ -1119,13 +1119,17 @@ __device__ __forceinline__ void quad_body(
       o[0] = (double)iter; o[1] = (double)status; o[2] = pri_res; o[3] = dua_res;
       if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)rho_updates; }
     }
-    if (double *const rec = parked_ptr(*(const lu64 *)(lds + L.nrm + 8 * N_RECORD))) {  // the scaled iterate and rho stay: the next solve starts from them
+    const unsigned long long parked = *(const lu64 *)(lds + L.nrm + 8 * N_RECORD);
+    if (double *const rec = parked_ptr(parked)) {  // the scaled iterate and rho stay: the next solve starts from them
       // (an instance without a solution -- infeasible, non-convex -- starts its next solve from zero, as the oracle's
-      // store_solution cold-starts it; rho stays)
-      if (me.owner) rec[rec_x(n, m) + S.perm[me.j]] = has_sol ? ld(lds, L.cx + me.j * 8) : 0.0;
+      // store_solution cold-starts it; rho stays.  RES_CERT: the direction that proves an infeasibility passes through the
+      // slot it belongs to on its way to k_batch_cert, which puts the zero back; res_mode is read here for the first time
+      // since the prologue, from the kernel arguments: the prologue and the ADMM loop know nothing of the bit)
+      const bool cert = (res_mode & RES_CERT) != 0, pcert = cert && status_prim_inf(status), dcert = cert && status_dual_inf(status);
+      if (me.owner) rec[rec_x(n, m) + S.perm[me.j]] = has_sol ? ld(lds, L.cx + me.j * 8) : (dcert ? ld(lds, L.cdx + me.j * 8) : 0.0);
       for (int i = me.t; i < m; i += QT) {
         const d2_t zy = ld2at(lds, L.rec + (unsigned)i * RECB + F_Z);
-        rec[rec_z(n, m) + i] = has_sol ? zy.x : 0.0; rec[rec_y(n, m) + i] = has_sol ? zy.y : 0.0;
+        rec[rec_z(n, m) + i] = has_sol ? zy.x : 0.0; rec[rec_y(n, m) + i] = has_sol ? zy.y : (pcert ? ld(lds, L.dy + i * 8) : 0.0);
       }
       if (me.t == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; }
     }

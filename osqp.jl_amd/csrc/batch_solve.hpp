@@ -625,6 +625,25 @@ __device__ __noinline__ void residual_phase(CheckArgs a) {
   __syncthreads();
 }
 
+// RES_CERT (batch_common.hpp), the last step of the epilogue: the direction that proves an infeasibility passes through the
+// record slot it belongs to on its way to k_batch_cert, which puts the zero back.  Every thread overwrites the zeros it has
+// just written itself (the same thread-to-entry map as the store before it).  A call like residual_phase, and for its
+// reason: everything it needs is in LDS -- the parked record pointer with the RES_CERT bit, the status code where the
+// residual phase left it (a loop that ended on a failed factorisation left 0 there: no certificate), delta_y and delta_x --
+// so the kernel keeps no register for it and its own code stays what it was.
+template <int CN, int CM, int CA, int CF>
+__device__ __noinline__ void leave_certificate(int n_, int m_, int nnzA, int nnzF, int words) {
+  Pattern P;
+  P.n = CN ? CN : n_; P.m = CN ? CM : m_; P.nnzA = CN ? CA : nnzA; P.nnzF = CN ? CF : nnzF;
+  const Lds s = carve((ldouble *)lds_raw, P, words != 0);
+  const unsigned long long parked = *(const lu64 *)(s.gjc + 2 * 4 * 128 + 56);
+  if (!parked_cert(parked)) return;
+  double *const rec = parked_ptr(parked);
+  const int n = P.n, m = P.m, code = uni((int)s.nrm[N_STATUS]);
+  if (status_prim_inf(code)) for (int i = mytid(); i < m; i += NT) rec[rec_y(n, m) + i] = s.dy[i];
+  else if (status_dual_inf(code)) for (int j = mytid(); j < n; j += NT) rec[rec_x(n, m) + j] = s.dx[j];
+}
+
 // CN > 0: the instance shape (n, m, nnz(A), nnz(P full)) = (CN, CM, CA, CF) is known at compile time -- every LDS address
 // becomes an immediate and every vector loop a fixed trip count (the registers otherwise spent on ~35 LDS pointers are
 // what the inverse needs); CN = 0: the same source with the shape read from the pattern at run time.
@@ -668,7 +687,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   }
   // where the epilogue finds the record (0: nothing to leave behind): parked behind the pivot buffers of the inversion
   // instead of scalar registers that would stay live across the whole ADMM loop
-  if (tid == 0) *(lu64 *)(s.gjc + 2 * 4 * 128 + 56) = res_solve ? (unsigned long long)rec : 0ull;
+  // (and a defined status code for the RES_CERT block of the epilogue, should the loop end before its first residual phase)
+  if (tid == 0) { *(lu64 *)(s.gjc + 2 * 4 * 128 + 56) = park_rec(rec, res_mode); s.nrm[N_STATUS] = 0.0; }
   __syncthreads();
   PROF(0)
   // ---- K0: Ruiz equilibration + cost scaling --------------------------------
@@ -908,6 +928,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     for (int i = tid; i < m; i += NT) { rec[rec_z(n, m) + i] = has_sol ? z[i] : 0.0; rec[rec_y(n, m) + i] = has_sol ? s.y[i] : 0.0; }
     if (tid == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; }
   }
+  leave_certificate<CN, CM, CA, CF>(n, m, P.nnzA, P.nnzF, regs);
 }
 
 }  // namespace

@@ -252,6 +252,31 @@ int validate_data(const OSQPData *d);
 int validate_settings(const OSQPSettings *s);
 void set_last_error(const std::string &m);
 
+// The settings that can change after setup, each with its type and the rule its new value `v` must pass: stated HERE and
+// nowhere else.  osqp_update_<name> of a single model (abi.hip) and osqp_amd_batch_update_setting (batch.hip) both check
+// through setting_ok_<name>, generated below.  libosqp's update functions reject only negative eps_prim_inf / eps_dual_inf
+// (the > 0 rule is the setup validation's): a caller's update_settings!(eps_prim_inf = 0) [REF src/interface.jl:506-530]
+// stays legal.
+#define OQ_UPDATABLE_SETTINGS(X)                      \
+  X(max_iter, c_int, v > 0)                           \
+  X(eps_abs, c_float, v >= 0.)                        \
+  X(eps_rel, c_float, v >= 0.)                        \
+  X(eps_prim_inf, c_float, v >= 0.)                   \
+  X(eps_dual_inf, c_float, v >= 0.)                   \
+  X(time_limit, c_float, v >= 0.)                     \
+  X(rho, c_float, v > 0.)                             \
+  X(alpha, c_float, v > 0. && v < 2.)                 \
+  X(delta, c_float, v > 0.)                           \
+  X(polish, c_int, v == 0 || v == 1)                  \
+  X(polish_refine_iter, c_int, v >= 0)                \
+  X(verbose, c_int, v == 0 || v == 1)                 \
+  X(scaled_termination, c_int, v == 0 || v == 1)      \
+  X(check_termination, c_int, v >= 0)                 \
+  X(warm_start, c_int, v == 0 || v == 1)
+#define OQ_SETTING_RULE(name, type, cond) inline bool setting_ok_##name(type v) { return cond; }
+OQ_UPDATABLE_SETTINGS(OQ_SETTING_RULE)
+#undef OQ_SETTING_RULE
+
 // runs the enclosing scope on `device` and puts the caller's current device back on exit
 struct DeviceScope {
   int prev = -1;

@@ -356,6 +356,53 @@ function batch_update_polish!(b::ResidentBatch, polish::Bool; polish_refine_iter
     return nothing
 end
 
+const BATCH_UPDATABLE_SETTINGS = (OSQP.UPDATABLE_SETTINGS..., :scaled_termination)
+
+"""
+    batch_update_settings!(b; settings...)
+
+`OSQP.update_settings!` for the batch (osqp_amd_batch_update_setting): the names of `OSQP.UPDATABLE_SETTINGS` and
+`scaled_termination`, each checked by the rule of the single-model update; any other name is an error before the library is
+called, `nothing` values are skipped.  `rho` also replaces the rho of every instance; the iterate stays.
+"""
+function batch_update_settings!(b::ResidentBatch; settings...)
+    for (key, _) in settings
+        key in BATCH_UPDATABLE_SETTINGS || error("$(key) cannot be updated or is not recognized")
+    end
+    given = Dict{Symbol,Any}(settings)
+    for key in BATCH_UPDATABLE_SETTINGS
+        value = get(given, key, nothing)
+        value === nothing && continue
+        flag = ccall((:osqp_amd_batch_update_setting, lib), Cc_int, (Ptr{Cvoid}, Cstring, Cdouble), b.handle, String(key), Float64(value))
+        flag == 0 || error("Error in batched settings update: $(last_error())")
+    end
+    return nothing
+end
+
+"""
+    batch_certificates(b) -> (prim_inf_cert [m x count], dual_inf_cert [n x count])
+
+The infeasibility certificates of the last `batch_solve!` (osqp_amd_batch_certificates): column i of the first is the
+direction that proves instance i primal infeasible, of the second dual infeasible, each with largest entry +-1; every other
+column is NaN, and all columns before the first solve.  With m = 0 the first is `nothing`.
+"""
+function batch_certificates(b::ResidentBatch)
+    p = b.m > 0 ? Matrix{Float64}(undef, b.m, b.count) : nothing
+    d = Matrix{Float64}(undef, b.n, b.count)
+    GC.@preserve p d begin
+        flag = ccall((:osqp_amd_batch_certificates, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int), b.handle, _batch_ptr(p), _batch_ptr(d), 0)
+    end
+    flag == 0 || error("Error in batched certificates: $(last_error())")
+    return p, d
+end
+
+"The same into device arrays (pointers to m * count and n * count doubles on the handle's device; `C_NULL`: not wanted)."
+function batch_certificates(b::ResidentBatch, p::Ptr{Cdouble}, d::Ptr{Cdouble})
+    flag = ccall((:osqp_amd_batch_certificates, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int), b.handle, p, d, 1)
+    flag == 0 || error("Error in batched certificates: $(last_error())")
+    return nothing
+end
+
 """
     batch_adjoint!(b; dx = nothing, dy = nothing, dq = nothing, dl = nothing, du = nothing, dPx = nothing, dAx = nothing,
                    act = nothing, status = nothing)
