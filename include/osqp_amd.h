@@ -515,6 +515,21 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             polish_refine_iter go the way of update_polish, with its LDS refusal; time_limit and verbose are stored and
  *             have no effect (below).  No setting change makes the stored solution stale for adjoint(), and the certificates
  *             and polish_status of the last resolve stay as they are.
+ *   *_rows(): update_lin_cost, update_bounds, update_matrices, warm_start and resolve for a SELECTION of the instances.
+ *             rows [k]: k distinct instance numbers in [0, count), 1 <= k <= count, in any order; always a HOST pointer.  The
+ *             array arguments and results are compact, [k x .]: row j belongs to instance rows[j].  A selected instance
+ *             behaves exactly as under the whole-batch call of the same name, bit for bit (x, y, info, record, certificates,
+ *             polish status).  An instance that is not selected is neither read nor written nor launched: its data, its
+ *             record (D, E, c, rho, iterate), its certificate rows, its polish status and its info row stay as they were.
+ *             update_bounds_rows compares a new bound with the stored other bound of the same instance when only one is
+ *             given; update_matrices_rows re-equilibrates the selected instances only; resolve_rows launches k workgroups
+ *             in its ADMM launch, in k_batch_cert and (polish = 1) in k_batch_polish; x_out [k x n], y_out [k x m],
+ *             info_out [k x 6].  A bad selection -- k < 1, k > count, an entry out of range, a repeated entry (the message
+ *             names it) -- returns 1 with a message and leaves the handle unchanged.
+ *             polish_status(), certificates() and adjoint() stay whole-batch calls: their row i is of instance i's OWN last
+ *             resolve, whole or selected (polish status 0 when polish was off at that resolve).  adjoint() needs every
+ *             instance current: a *_rows update or warm start makes its rows stale, resolve_rows makes them current, and
+ *             the refusal names the first stale instance.
  * where: 0 = the array arguments are host pointers, 1 = device pointers on the handle's device (no host hop: a controller
  * whose state estimate lives in HBM).  A NULL array means "keep" (update_*) / "none" (warm_start).  Every call blocks until
  * done.  Single rank.  The handle is freed by osqp_amd_batch_destroy; it is not interchangeable with the handle of
@@ -529,6 +544,15 @@ c_int osqp_amd_batch_update_bounds(osqp_amd_batch *batch, const c_float *l_all, 
 c_int osqp_amd_batch_update_matrices(osqp_amd_batch *batch, const c_float *Px_all, const c_float *Ax_all, c_int where);
 c_int osqp_amd_batch_warm_start(osqp_amd_batch *batch, const c_float *x_all, const c_float *y_all, c_int where);
 c_int osqp_amd_batch_resolve(osqp_amd_batch *batch, c_float *x_out, c_float *y_out, c_float *info_out, c_int where);
+c_int osqp_amd_batch_update_lin_cost_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, const c_float *q_rows, c_int where);
+c_int osqp_amd_batch_update_bounds_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, const c_float *l_rows,
+                                        const c_float *u_rows, c_int where);
+c_int osqp_amd_batch_update_matrices_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, const c_float *Px_rows,
+                                          const c_float *Ax_rows, c_int where);
+c_int osqp_amd_batch_warm_start_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, const c_float *x_rows,
+                                     const c_float *y_rows, c_int where);
+c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *x_out, c_float *y_out,
+                                  c_float *info_out, c_int where);
 c_int osqp_amd_batch_polish_status(osqp_amd_batch *batch, c_float *status_out, c_int where);
 c_int osqp_amd_batch_update_polish(osqp_amd_batch *batch, c_int polish_new, c_int polish_refine_iter_new);
 c_int osqp_amd_batch_update_setting(osqp_amd_batch *batch, const char *name, c_float value);
@@ -542,7 +566,7 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *batch, const c_float *dx, const c_f
 c_int osqp_amd_batch_polish_launches(void);
 /* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint that passed its checks, none otherwise. */
 c_int osqp_amd_batch_adjoint_launches(void);
-/* The same for the certificate kernel: one launch per osqp_amd_batch_resolve, none by osqp_amd_batch_certificates or by the
+/* The same for the certificate kernel: one launch per osqp_amd_batch_resolve / _resolve_rows, none by osqp_amd_batch_certificates or by the
  * one-shot entries. */
 c_int osqp_amd_batch_cert_launches(void);
 

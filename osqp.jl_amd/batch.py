@@ -225,13 +225,52 @@ def _batch_array(name, a, shape):
     return arr, arr.ctypes.data, 0
 
 
+def selection(rows, count):
+    """The instance numbers of a `rows=` argument of `ResidentBatch` as a contiguous int64 array [k], in the order given: an
+    integer sequence or array (distinct entries in [0, count)), or a boolean mask of length `count` (the numbers of its True
+    entries, ascending).  Checked here, before the library is called: dtype, dimension, range, duplicates, an empty
+    selection, more than `count` entries -- each a ValueError."""
+    count = int(count)
+    arr = np.asarray(rows)
+    if arr.ndim == 1 and arr.size == 0:
+        raise ValueError("rows: the selection is empty")
+    if arr.dtype == object or arr.dtype.kind not in "biu":
+        raise ValueError(f"rows: expected integers or a boolean mask, got dtype {arr.dtype}")
+    if arr.ndim != 1:
+        raise ValueError(f"rows: expected a one-dimensional selection, got shape {arr.shape}")
+    if arr.dtype.kind == "b":
+        if arr.shape[0] != count:
+            raise ValueError(f"rows: a boolean mask must have length {count}, got {arr.shape[0]}")
+        arr = np.flatnonzero(arr)
+    if arr.size == 0:
+        raise ValueError("rows: the selection is empty")
+    if arr.size > count:
+        raise ValueError(f"rows: {arr.size} entries for a batch of {count} instances")
+    if arr.dtype.kind == "u" and arr.max() > np.iinfo(np.int64).max:
+        raise ValueError(f"rows: instance {int(arr.max())} is out of range [0, {count})")
+    arr = np.ascontiguousarray(arr, dtype=np.int64)
+    out_of_range = (arr < 0) | (arr >= count)
+    if out_of_range.any():
+        raise ValueError(f"rows: instance {int(arr[out_of_range][0])} is out of range [0, {count})")
+    seen = np.zeros(count, dtype=bool)
+    for i in arr:
+        if seen[i]:
+            raise ValueError(f"rows: instance {int(i)} is repeated")
+        seen[i] = True
+    return arr
+
+
 class ResidentBatch:
     """`count` QPs of the caller's own that share one sparsity pattern, resident in HBM (osqp_amd_batch_setup): the life
     cycle of a single model -- setup, `update`, `warm_start`, `solve`, again and again -- instance by instance.  Scaling is
     computed once from the setup data; every solve starts from the iterate and the rho the last one ended on (with
     `warm_start=False` in the settings: from zero).  P (upper triangle) and A are scipy matrices giving the pattern; the
     *_all arrays are [count x .] as for `solve_batch`.  Array arguments of `update` / `warm_start` and the `out` of `solve`
-    may be numpy arrays (host form) or device arrays (`DeviceArray`, torch tensors: no host hop)."""
+    may be numpy arrays (host form) or device arrays (`DeviceArray`, torch tensors: no host hop).
+    `update`, `warm_start` and `solve` take `rows=`: a selection of the instances (`selection` above: integers in any order,
+    or a boolean mask; always host data).  Their arrays are then compact, [k x .], row j for instance rows[j]; a selected
+    instance gets the bits of the whole-batch call, every other instance is left exactly as it was -- data, record,
+    certificates, polish status (include/osqp_amd.h, "*_rows")."""
 
     def __init__(self, lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, **settings):
         import scipy.sparse as sp
@@ -269,23 +308,37 @@ class ResidentBatch:
         if rc != 0:
             raise OSQPError(f"Error in batched {what}: " + self.lib.osqp_amd_last_error().decode())
 
-    def _pair(self, names, values, cols):
-        """The two optional arrays of one library call: both in the same form (host or device); None stays NULL."""
-        got = [None if v is None else _batch_array(nm, v, (self.count, k)) for nm, v, k in zip(names, values, cols)]
+    def _pair(self, names, values, cols, rows=None):
+        """The two optional arrays of one library call: both in the same form (host or device); None stays NULL.  `rows`:
+        the number of rows they must have (None: count)."""
+        rows = self.count if rows is None else rows
+        got = [None if v is None else _batch_array(nm, v, (rows, k)) for nm, v, k in zip(names, values, cols)]
         forms = {g[2] for g in got if g is not None}
         if len(forms) > 1:
             raise ValueError(f"{names[0]} and {names[1]} must both be host arrays or both device arrays")
         return got, [None if g is None else g[1] for g in got], (forms.pop() if forms else 0)
 
-    def update(self, q=None, l=None, u=None, Px=None, Ax=None):
+    def update(self, q=None, l=None, u=None, Px=None, Ax=None, rows=None):
         """New q / bounds / matrix values for every instance, in the order of `osqp.update!`: q, then the bounds (scaled with
         the stored factors), then the matrices (which re-equilibrate, with the q, l, u just given).  Nothing is changed by a
-        call whose arguments fail the checks; `l > u` in any instance raises and leaves the bounds as they were."""
-        qa = None if q is None else _batch_array("q", q, (self.count, self.n))
-        keep_b, bounds, where_b = self._pair(("l", "u"), (l, u), (self.m, self.m))
-        keep_m, mats, where_m = self._pair(("Px", "Ax"), (Px, Ax), (self.nnzP, self.nnzA))
+        call whose arguments fail the checks; `l > u` in any instance raises and leaves the bounds as they were.
+        rows: a selection (`selection`); the arrays are then [k x .] and only those instances change and re-equilibrate."""
+        sel = None if rows is None else selection(rows, self.count)
+        k = self.count if sel is None else len(sel)
+        qa = None if q is None else _batch_array("q", q, (k, self.n))
+        keep_b, bounds, where_b = self._pair(("l", "u"), (l, u), (self.m, self.m), k)
+        keep_m, mats, where_m = self._pair(("Px", "Ax"), (Px, Ax), (self.nnzP, self.nnzA), k)
         if keep_b[0] is not None and keep_b[1] is not None and not where_b and np.any(keep_b[0][0] > keep_b[1][0]):
             raise OSQPError("Error in batched update: lower bound greater than upper bound")
+        if sel is not None:
+            lib, h, sp = self.lib, self.handle, _iptr(sel)
+            if qa is not None:
+                self._call("update", lib.osqp_amd_batch_update_lin_cost_rows(h, sp, k, qa[1], qa[2]))
+            if bounds[0] is not None or bounds[1] is not None:
+                self._call("update", lib.osqp_amd_batch_update_bounds_rows(h, sp, k, bounds[0], bounds[1], where_b))
+            if mats[0] is not None or mats[1] is not None:
+                self._call("update", lib.osqp_amd_batch_update_matrices_rows(h, sp, k, mats[0], mats[1], where_m))
+            return
         if qa is not None:
             self._call("update", self.lib.osqp_amd_batch_update_lin_cost(self.handle, qa[1], qa[2]))
         if bounds[0] is not None or bounds[1] is not None:
@@ -293,34 +346,50 @@ class ResidentBatch:
         if mats[0] is not None or mats[1] is not None:
             self._call("update", self.lib.osqp_amd_batch_update_matrices(self.handle, mats[0], mats[1], where_m))
 
-    def warm_start(self, x=None, y=None):
-        """Start the next solve from x and / or y (caller's units, [count x n] / [count x m]); a missing one is zero."""
-        keep, ptrs, where = self._pair(("x", "y"), (x, y), (self.n, self.m))
+    def warm_start(self, x=None, y=None, rows=None):
+        """Start the next solve from x and / or y (caller's units, [count x n] / [count x m]); a missing one is zero.
+        rows: a selection (`selection`); x / y are then [k x .] and only the iterates of those instances change."""
+        sel = None if rows is None else selection(rows, self.count)
+        keep, ptrs, where = self._pair(("x", "y"), (x, y), (self.n, self.m), None if sel is None else len(sel))
+        if sel is not None:
+            if ptrs[0] is not None or ptrs[1] is not None:
+                self._call("warm start", self.lib.osqp_amd_batch_warm_start_rows(self.handle, _iptr(sel), len(sel), ptrs[0], ptrs[1], where))
+            return
         if ptrs[0] is not None or ptrs[1] is not None:
             self._call("warm start", self.lib.osqp_amd_batch_warm_start(self.handle, ptrs[0], ptrs[1], where))
 
-    def solve(self, out=None):
+    def solve(self, out=None, rows=None):
         """Solve every instance -> (x [count x n], y [count x m], info [count x 6]: iter, status_val, pri_res, dua_res,
-        obj_val, rho_updates).  out=None: numpy arrays; out=(x, y, info) of device arrays: written in place and returned."""
+        obj_val, rho_updates).  out=None: numpy arrays; out=(x, y, info) of device arrays: written in place and returned.
+        rows: a selection (`selection`): only those instances are launched, the results are [k x .] (`alloc(k)`), and every
+        other instance keeps its iterate, rho, certificates, polish status and info row."""
+        sel = None if rows is None else selection(rows, self.count)
+        k = self.count if sel is None else len(sel)
+
+        def resolve(xp, yp, ip, where):
+            if sel is None:
+                return self.lib.osqp_amd_batch_resolve(self.handle, xp, yp, ip, where)
+            return self.lib.osqp_amd_batch_resolve_rows(self.handle, _iptr(sel), k, xp, yp, ip, where)
+
         if out is None:
-            x, y, info = np.empty((self.count, self.n)), np.empty((self.count, self.m)), np.empty((self.count, 6))
-            self._call("solve", self.lib.osqp_amd_batch_resolve(self.handle, x.ctypes.data, y.ctypes.data, info.ctypes.data, 0))
+            x, y, info = np.empty((k, self.n)), np.empty((k, self.m)), np.empty((k, 6))
+            self._call("solve", resolve(x.ctypes.data, y.ctypes.data, info.ctypes.data, 0))
             return x, y, info
         if len(out) != 3:
             raise ValueError("out: expected (x, y, info)")
         ptrs = []
-        for name, a, k in (("out[0]", out[0], self.n), ("out[1]", out[1], self.m), ("out[2]", out[2], 6)):
-            if a is None and k == 0:
+        for name, a, cols in (("out[0]", out[0], self.n), ("out[1]", out[1], self.m), ("out[2]", out[2], 6)):
+            if a is None and cols == 0:
                 ptrs.append(None)
                 continue
             if not hasattr(a, "data_ptr"):
                 raise ValueError(f"{name}: expected a device array (DeviceArray, torch tensor); omit `out` for numpy results")
-            ptrs.append(_batch_array(name, a, (self.count, k))[1])
-        self._call("solve", self.lib.osqp_amd_batch_resolve(self.handle, ptrs[0], ptrs[1], ptrs[2], 1))
+            ptrs.append(_batch_array(name, a, (k, cols))[1])
+        self._call("solve", resolve(ptrs[0], ptrs[1], ptrs[2], 1))
         return out
 
     def polish_status(self, out=None):
-        """status_polish of every instance from the last `solve()`: 1 accepted, -1 refused, 0 not polished (the instance was
+        """status_polish of every instance from its own last `solve()` (whole or `rows=`): 1 accepted, -1 refused, 0 not polished (the instance was
         not Solved, or `polish` is off).  out=None: a numpy int array [count]; out = a device array [count x 1] of float64:
         filled in place and returned."""
         if out is None:
@@ -368,7 +437,7 @@ class ResidentBatch:
                 self.polish_refine_iter = int(value)
 
     def certificates(self, out=None):
-        """(prim_inf_cert [count x m], dual_inf_cert [count x n]) of the last `solve()`: row i of the first is the direction
+        """(prim_inf_cert [count x m], dual_inf_cert [count x n]) of every instance's own last `solve()` (whole or `rows=`): row i of the first is the direction
         that proves instance i primal infeasible (status -3 or 3), of the second dual infeasible (-4 or 4), each with
         largest entry +-1 as a single model's results carry them; every other row is NaN, and all rows before the first
         solve.  out=None: numpy arrays; out=(p, d) of device arrays, either may be None: filled in place and returned.
@@ -407,7 +476,8 @@ class ResidentBatch:
         are left out.  Host form: numpy dx / dy, out=None, numpy results ("act" and "status" [count] as integers).  Device
         form: dx / dy device arrays and `out` a dict of float64 device arrays for the entries of `want` and, optionally,
         "act" and "status" ([count x 1]); they are filled in place and `out` is returned.  The handle must hold the solution
-        of its current data: a `solve()` since the last `update` / `warm_start`.  Where the active constraints of an instance
+        of its current data, for EVERY instance: a `solve()` that served it since its last `update` / `warm_start` (`rows=` calls
+        count per instance; the refusal names the first stale one).  Where the active constraints of an instance
         are dependent the derivative does not exist and the regularised answer is returned (see include/osqp_amd.h)."""
         cols = self._adjoint_cols()
         want = tuple(want)
@@ -446,11 +516,15 @@ class ResidentBatch:
             res["status"] = res["status"].ravel().astype(np.int64)
         return res
 
-    def alloc(self):
-        """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints."""
-        return (DeviceArray(self.lib, self.count, self.n, self.device),
-                DeviceArray(self.lib, self.count, self.m, self.device) if self.m else None,
-                DeviceArray(self.lib, self.count, 6, self.device))
+    def alloc(self, k=None):
+        """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints.  k: the number of
+        rows, for a solve of a selection of k instances (None: count)."""
+        k = self.count if k is None else int(k)
+        if not 1 <= k <= self.count:
+            raise ValueError(f"k: expected 1 <= k <= {self.count}, got {k}")
+        return (DeviceArray(self.lib, k, self.n, self.device),
+                DeviceArray(self.lib, k, self.m, self.device) if self.m else None,
+                DeviceArray(self.lib, k, 6, self.device))
 
     def close(self):
         if getattr(self, "handle", None):

@@ -17,8 +17,8 @@
 //                     request (osqp_amd_batch_adjoint); shares the factorisation and the solves of the polish kernel;
 //   batch_cert.hpp    k_batch_cert -- the infeasibility certificates of the resident batch, a launch of its own after every
 //                     ADMM launch of osqp_amd_batch_resolve: normalises the directions that launch left in the records (RES_CERT);
-//   this file         the small kernels (warm start, rho fill, bound check, MPC generator), the launcher (launch_batch), the handle
-//                     (BatchPlan) and the C ABI.
+//   this file         the small kernels (warm start, rho fill, bound check, the row scatter of a selection, MPC generator), the
+//                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
 // Both kernels also run in RESIDENT mode (osqp_amd_batch_setup ... _resolve, "the state record" in batch_common.hpp):
 // scaling, iterate and rho of every instance live in HBM between launches; a branch of the prologue and of the epilogue on
@@ -54,21 +54,24 @@ inline bool batch_quad_enabled() {  // OSQP_AMD_BATCH_QUAD=0: the MPC family on 
 }
 
 // the iterate of osqp_amd_batch_warm_start, caller's units in, the record's scaled units out: x <- x / D, y <- c y / E,
-// z <- A x in scaled units = E (A_raw x_raw); a missing vector is zero (and z with x).  One workgroup per instance.
+// z <- A x in scaled units = E (A_raw x_raw); a missing vector is zero (and z with x).  One workgroup per instance: the one
+// at position p serves instance sel[p] (sel nullptr: p) with row p of x_all / y_all, as BatchIO::sel has it.
 __global__ __launch_bounds__(256) void k_batch_warm(Pattern P, int count, const double *__restrict__ Ax_all, const double *__restrict__ x_all,
-                                                    const double *__restrict__ y_all, double *__restrict__ rec_all, int rec_stride) {
-  const int inst = blockIdx.x, n = P.n, m = P.m;
-  if (inst >= count) return;
+                                                    const double *__restrict__ y_all, double *__restrict__ rec_all, int rec_stride,
+                                                    const int *__restrict__ sel) {
+  const int pos = blockIdx.x, n = P.n, m = P.m;
+  if (pos >= count) return;
+  const int inst = sel ? sel[pos] : pos;
   double *rec = rec_all + (size_t)inst * rec_stride;
   const double c = rec[REC_C];
-  for (int j = threadIdx.x; j < n; j += 256) rec[rec_x(n, m) + j] = x_all ? x_all[(size_t)inst * n + j] / rec[rec_D(n, m) + j] : 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) rec[rec_x(n, m) + j] = x_all ? x_all[(size_t)pos * n + j] / rec[rec_D(n, m) + j] : 0.0;
   for (int i = threadIdx.x; i < m; i += 256) {
     const double e = rec[rec_E(n, m) + i];
     double ax = 0.0;
     if (x_all)
-      for (int q = P.Rp[i]; q < P.Rp[i + 1]; q++) ax += Ax_all[(size_t)inst * P.nnzA + P.Rmap[q]] * x_all[(size_t)inst * n + P.Rc[q]];
+      for (int q = P.Rp[i]; q < P.Rp[i + 1]; q++) ax += Ax_all[(size_t)inst * P.nnzA + P.Rmap[q]] * x_all[(size_t)pos * n + P.Rc[q]];
     rec[rec_z(n, m) + i] = e * ax;
-    rec[rec_y(n, m) + i] = y_all ? c * y_all[(size_t)inst * m + i] / e : 0.0;
+    rec[rec_y(n, m) + i] = y_all ? c * y_all[(size_t)pos * m + i] / e : 0.0;
   }
 }
 
@@ -82,6 +85,33 @@ __global__ __launch_bounds__(256) void k_batch_fill_rho(int count, double rho, d
 __global__ __launch_bounds__(256) void k_batch_check_bounds(size_t total, const double *__restrict__ l, const double *__restrict__ u, int *bad) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < total && l[i] > u[i]) atomicAdd(bad, 1);
+}
+
+// ---- a selection of instances (osqp_amd_batch_*_rows): sel[0 .. k) distinct instance numbers, checked on the host ----------
+// row p of src [k x cols] into row sel[p] of dst [count x cols]: q, l, u, Px, Ax of an update, the info rows of a resolve.
+// One workgroup per selected row.
+__global__ __launch_bounds__(256) void k_batch_scatter_rows(const int *__restrict__ sel, int k, int cols, const double *__restrict__ src,
+                                                            double *__restrict__ dst) {
+  const int pos = blockIdx.x;
+  if (pos >= k) return;
+  const double *from = src + (size_t)pos * cols;
+  double *to = dst + (size_t)sel[pos] * cols;
+  for (int c = threadIdx.x; c < cols; c += 256) to[c] = from[c];
+}
+// dst[sel[p]] = value (the polish status of instances re-solved without polish)
+__global__ __launch_bounds__(256) void k_batch_fill_rows(const int *__restrict__ sel, int k, double value, double *__restrict__ dst) {
+  const int pos = blockIdx.x * 256 + threadIdx.x;
+  if (pos < k) dst[sel[pos]] = value;
+}
+// k_batch_check_bounds over the selected rows: a bound that is not given ([k x m], nullptr) is the stored one of the instance
+__global__ __launch_bounds__(256) void k_batch_check_bounds_rows(const int *__restrict__ sel, int k, int m, const double *__restrict__ l_rows,
+                                                                 const double *__restrict__ u_rows, const double *__restrict__ l_all,
+                                                                 const double *__restrict__ u_all, int *bad) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)k * m) return;
+  const size_t pos = i / m, at = (size_t)sel[pos] * m + (i - pos * m);
+  const double l = l_rows ? l_rows[i] : l_all[at], u = u_rows ? u_rows[i] : u_all[at];
+  if (l > u) atomicAdd(bad, 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -178,7 +208,7 @@ template <typename K>
 void launch_kernel_solve(K kern, size_t bytes, const DevicePattern &dp, const OSQPSettings &st, int count, const BatchIO &io, hipStream_t s) {
   HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   OQ_LAUNCH(kern, dim3(count), dim3(NT), bytes, s, dp.P, st, count, dp.scratch.get(), io.Px, io.Ax, io.q, io.l, io.u, io.x, io.y, io.info,
-            io.x_stride, io.y_stride, io.info_stride, io.info_cols, io.rec, io.rec_stride, io.res_mode);
+            io.x_stride, io.y_stride, io.info_stride, io.info_cols, io.rec, io.rec_stride, io.res_mode, io.sel);
 }
 template <typename K>
 void launch_kernel_quad(K kern, const DevicePattern &dp, const OSQPSettings &st, int count, const BatchIO &io, hipStream_t s) {
@@ -186,7 +216,7 @@ void launch_kernel_quad(K kern, const DevicePattern &dp, const OSQPSettings &st,
   const quad::Layout L = quad::make_layout(P.n, P.m, P.nnzA, P.nnzF, dp.quad->NH, dp.quad->KC, dp.quad->KE, dp.quad->CH);
   HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
   OQ_LAUNCH(kern, dim3(count), dim3(quad::QT), (size_t)L.total, s, dp.QS, st, count, io.Px, io.Ax, io.q, io.l, io.u, io.x, io.y, io.info,
-            io.x_stride, io.y_stride, io.info_stride, io.info_cols, io.rec, io.rec_stride, io.res_mode);
+            io.x_stride, io.y_stride, io.info_stride, io.info_cols, io.rec, io.rec_stride, io.res_mode, io.sel);
 }
 
 void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, const BatchIO &io, hipStream_t s) {
@@ -210,7 +240,8 @@ void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, co
   case NUMBER: {                                                                                                               \
     constexpr int CN = FIXED ? MPC_N : 0, CM = FIXED ? MPC_M : 0, CA = FIXED ? kMpcNnzA : 0, CF = FIXED ? MPC_N : 0;           \
     static_assert(quad_entry(NUMBER)->fixed == (CN > 0), "shape compiled in <=> CN > 0: the kernel's BWC and the host's guard"); \
-    launch_kernel_quad(quad::KERNEL<NH, KC, KE, CH, CN, CM, CA, CF>, dp, st, count, io, s);                                   \
+    if (io.sel) launch_kernel_quad(quad::KERNEL<NH, KC, KE, CH, CN, CM, CA, CF, true>, dp, st, count, io, s);                 \
+    else launch_kernel_quad(quad::KERNEL<NH, KC, KE, CH, CN, CM, CA, CF, false>, dp, st, count, io, s);                       \
   } break;
       OQ_QUAD_ENTRIES(OQ_QUAD_CASE)
 #undef OQ_QUAD_CASE
@@ -227,10 +258,17 @@ void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, co
     std::copy(sched, sched + kSchedWords, g_batch_last_schedule);
   }
   // shapes compiled in (same source, constants folded): the MPC family of BASELINE.json config 5
-  if (dp.mpc) launch_kernel_solve(k_batch_solve<25, MPC_N, MPC_M, kMpcNnzA, MPC_N>, bytes, dp, st, count, io, s);
-  else if (nc <= 16) launch_kernel_solve(k_batch_solve<16, 0, 0, 0, 0>, bytes, dp, st, count, io, s);
-  else if (nc <= 25) launch_kernel_solve(k_batch_solve<25, 0, 0, 0, 0>, bytes, dp, st, count, io, s);
-  else launch_kernel_solve(k_batch_solve<32, 0, 0, 0, 0>, bytes, dp, st, count, io, s);
+  // (the last argument: a launch over a selection, io.sel, has instantiations of its own)
+#define OQ_SOLVE_LAUNCH(...)                                                                              \
+  do {                                                                                                    \
+    if (io.sel) launch_kernel_solve(k_batch_solve<__VA_ARGS__, true>, bytes, dp, st, count, io, s);       \
+    else launch_kernel_solve(k_batch_solve<__VA_ARGS__, false>, bytes, dp, st, count, io, s);             \
+  } while (0)
+  if (dp.mpc) OQ_SOLVE_LAUNCH(25, MPC_N, MPC_M, kMpcNnzA, MPC_N);
+  else if (nc <= 16) OQ_SOLVE_LAUNCH(16, 0, 0, 0, 0);
+  else if (nc <= 25) OQ_SOLVE_LAUNCH(25, 0, 0, 0, 0);
+  else OQ_SOLVE_LAUNCH(32, 0, 0, 0, 0);
+#undef OQ_SOLVE_LAUNCH
 }
 
 // the five data arrays of `count` instances of pattern P on the device: allocated and filled in one step
@@ -274,11 +312,18 @@ struct BatchPlan : BatchData {
   // last resolve did not polish (or there was none) and all are 0, whatever the buffer holds
   DevBuf<double> pstat;
   bool pstat_live = false;
-  // adjoint (osqp_amd_batch_adjoint): sol_current = the records and info_out hold the solution of the handle's current data
-  // (set by a resolve, cleared by every update_* and warm_start); info_out keeps the info rows of the last resolve also when
-  // the caller's went to device pointers.  Staging of host-pointer calls: gradients in through in_a / in_b, out through adj_out
-  bool sol_current = false;
-  DevBuf<double> adj_out;
+  // adjoint (osqp_amd_batch_adjoint): current[i] = the record and the info row of instance i hold the solution of its current
+  // data (set by a resolve that served it, cleared by every update_* and warm_start that touched it; host bookkeeping).
+  // info_all [count x 6]: the info row of every instance's own last resolve, wherever the caller's went -- not the staging of
+  // a host-pointer resolve of a selection, which is compact (info_out).  Staging of host-pointer calls: gradients in through
+  // in_a / in_b, out through adj_out
+  std::vector<char> current;
+  DevBuf<double> info_all, adj_out;
+  void mark(bool is_current) { std::fill(current.begin(), current.end(), (char)is_current); }
+  void mark_rows(bool is_current) { for (int i : sel_host) current[(size_t)i] = (char)is_current; }
+  // the selection of the running *_rows call, uploaded once per call (BatchIO::sel)
+  std::vector<int> sel_host;
+  DevBuf<int> sel;
   // certificates (osqp_amd_batch_certificates): [count x m] and [count x n], NaN from setup, then written by k_batch_cert
   // after every resolve
   DevBuf<double> pcert, dcert;
@@ -331,10 +376,37 @@ void copy_d2d(double *dst, const double *src, size_t len, hipStream_t s) {
   HIP_CHECK(hipMemcpyAsync(dst, src, len * sizeof(double), hipMemcpyDeviceToDevice, s));
 }
 // D, E, c of the handle's current raw data into the records (one launch of the solve kernel in its scale-only mode)
-void resident_equilibrate(BatchPlan &b, hipStream_t s) {
+// (`count` workgroups, instance by `sel`: nullptr = all of them)
+void resident_equilibrate(BatchPlan &b, int count, const int *sel, hipStream_t s) {
   BatchIO io = b.inputs();
-  io.rec = b.rec.get(); io.rec_stride = b.rec_stride; io.res_mode = RES_SCALE_ONLY;
-  launch_batch(b.dp, b.st, b.count, io, s);
+  io.rec = b.rec.get(); io.rec_stride = b.rec_stride; io.res_mode = RES_SCALE_ONLY; io.sel = sel;
+  launch_batch(b.dp, b.st, count, io, s);
+}
+// The selection of a *_rows call, checked on the host before anything of the handle changes and uploaded into the handle's
+// buffer: false with the message set when it is bad.
+bool select_rows(BatchPlan &b, const c_int *rows, c_int k, hipStream_t s) {
+  if (!rows) { set_last_error("invalid selection: rows is NULL"); return false; }
+  if (k < 1 || k > b.count) {
+    set_last_error("invalid selection: " + std::to_string(k) + " rows of a batch of " + std::to_string(b.count) + " instances (1 <= k <= count)");
+    return false;
+  }
+  std::vector<char> seen((size_t)b.count, 0);
+  for (c_int j = 0; j < k; j++) {
+    const c_int i = rows[j];
+    if (i < 0 || i >= b.count) {
+      set_last_error("invalid selection: rows[" + std::to_string(j) + "] = " + std::to_string(i) + " is out of range [0, " + std::to_string(b.count) + ")");
+      return false;
+    }
+    if (seen[(size_t)i]) { set_last_error("invalid selection: instance " + std::to_string(i) + " is repeated"); return false; }
+    seen[(size_t)i] = 1;
+  }
+  b.sel_host.assign(rows, rows + k);
+  if (b.sel.n < (size_t)b.count) b.sel.alloc((size_t)b.count);
+  b.sel.upload(b.sel_host.data(), (size_t)k, s);
+  return true;
+}
+void scatter_rows(const BatchPlan &b, int k, int cols, const double *src, double *dst, hipStream_t s) {
+  if (cols) OQ_LAUNCH(k_batch_scatter_rows, dim3(k), dim3(256), 0, s, b.sel.get(), k, cols, src, dst);
 }
 // the LDS a polish launch of this pattern needs; a pattern it cannot serve is refused where polish is asked for (setup,
 // osqp_amd_batch_update_polish), never skipped
@@ -345,7 +417,8 @@ void polish_check_fits(const Pattern &P) {
                        std::to_string(polish::kLdsLimit) + " available); set polish = 0");
 }
 // polish() of the oracle on every Solved instance of the launch that has just written io.x / io.y / io.info and the records
-void launch_polish(BatchPlan &b, const BatchIO &io, hipStream_t s) {
+// (`count` workgroups, instance by io.sel)
+void launch_polish(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
   const Pattern &P = b.dp.P;
   polish_check_fits(P);
   const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
@@ -354,18 +427,19 @@ void launch_polish(BatchPlan &b, const BatchIO &io, hipStream_t s) {
   a.x = io.x; a.y = io.y; a.info = io.info; a.rec = io.rec; a.status = b.pstat.get();
   a.x_stride = io.x_stride; a.y_stride = io.y_stride; a.info_stride = io.info_stride; a.rec_stride = io.rec_stride;
   a.refine = (int)b.st.polish_refine_iter; a.unscaled = b.st.scaling && !b.st.scaled_termination;
-  a.delta = b.st.delta;
+  a.delta = b.st.delta; a.sel = io.sel;
   HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_polish, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
   g_batch_polish_launches++;
-  OQ_LAUNCH(polish::k_batch_polish, dim3(b.count), dim3(polish::PT), (size_t)L.total, s, P, b.count, L, a);
+  OQ_LAUNCH(polish::k_batch_polish, dim3(count), dim3(polish::PT), (size_t)L.total, s, P, count, L, a);
 }
 // the certificates of the launch that has just written io.info and, under RES_CERT, left the directions in the records
-void launch_cert(BatchPlan &b, const BatchIO &io, hipStream_t s) {
+void launch_cert(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
   cert::Args a;
   a.info = io.info; a.rec = io.rec; a.prim = b.m ? b.pcert.get() : nullptr; a.dual = b.dcert.get();
   a.info_stride = io.info_stride; a.rec_stride = io.rec_stride; a.unscaled = b.st.scaling && !b.st.scaled_termination;
+  a.sel = io.sel;
   g_batch_cert_launches++;
-  OQ_LAUNCH(cert::k_batch_cert, dim3(b.count), dim3(cert::CT), 0, s, b.n, b.m, b.count, a);
+  OQ_LAUNCH(cert::k_batch_cert, dim3(count), dim3(cert::CT), 0, s, b.n, b.m, count, a);
 }
 // polish / polish_refine_iter of a resident handle (osqp_amd_batch_update_polish, osqp_amd_batch_update_setting); the values
 // have passed their rules
@@ -513,6 +587,7 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, 
     const size_t cnt = (size_t)count;
     b->upload(prob, b->dp.P, s);
     b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6); b->bad.alloc(1); b->pstat.alloc(cnt);
+    b->info_all.alloc(cnt * 6); b->current.assign(cnt, 0);
     {
       const std::vector<double> nan(cnt * std::max(n, m), NAN);
       b->pcert.alloc(cnt * m); b->dcert.alloc(cnt * n);
@@ -523,7 +598,7 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, 
     std::vector<double> hrec(cnt * b->rec_stride, 0.0);
     for (size_t i = 0; i < cnt; i++) hrec[i * b->rec_stride + REC_RHO] = settings->rho;
     b->rec.alloc(hrec.size()); b->rec.upload(hrec.data(), hrec.size(), s);
-    resident_equilibrate(*b, s);  // D, E, c come from the setup data and stay until the matrices change
+    resident_equilibrate(*b, b->count, nullptr, s);  // D, E, c come from the setup data and stay until the matrices change
     HIP_CHECK(hipDeviceSynchronize());
     *out = (osqp_amd_batch *)b.release();
     return 0;
@@ -538,7 +613,7 @@ c_int osqp_amd_batch_update_lin_cost(osqp_amd_batch *handle, const c_float *q_al
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
     const size_t len = (size_t)b->count * b->n;
-    b->sol_current = false;
+    b->mark(false);
     if (where) copy_d2d(b->q.get(), q_all, len, s); else b->q.upload(q_all, len, s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
@@ -562,7 +637,7 @@ c_int osqp_amd_batch_update_bounds(osqp_amd_batch *handle, const c_float *l_all,
     b->bad.download(&bad, 1, s);
     HIP_CHECK(hipStreamSynchronize(s));
     if (bad) { set_last_error("lower bound greater than upper bound"); return 1; }
-    b->sol_current = false;
+    b->mark(false);
     if (l_all) copy_d2d(b->l.get(), ln, len, s);
     if (u_all) copy_d2d(b->u.get(), un, len, s);
     HIP_CHECK(hipStreamSynchronize(s));
@@ -578,10 +653,10 @@ c_int osqp_amd_batch_update_matrices(osqp_amd_batch *handle, const c_float *Px_a
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
     const size_t lp = (size_t)b->count * b->nnzP, la = (size_t)b->count * b->nnzA;
-    b->sol_current = false;
+    b->mark(false);
     if (Px_all && lp) { if (where) copy_d2d(b->Px.get(), Px_all, lp, s); else b->Px.upload(Px_all, lp, s); }
     if (Ax_all && la) { if (where) copy_d2d(b->Ax.get(), Ax_all, la, s); else b->Ax.upload(Ax_all, la, s); }
-    resident_equilibrate(*b, s);  // from scratch on the raw data with the current q, l, u; the scaled iterate stays as it is
+    resident_equilibrate(*b, b->count, nullptr, s);  // from scratch on the raw data with the current q, l, u; the scaled iterate stays as it is
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
@@ -594,10 +669,10 @@ c_int osqp_amd_batch_warm_start(osqp_amd_batch *handle, const c_float *x_all, co
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    b->sol_current = false;
+    b->mark(false);
     const double *xd = x_all ? device_ptr(x_all, (size_t)b->count * b->n, where, b->in_a, s) : nullptr;
     const double *yd = y_all && b->m ? device_ptr(y_all, (size_t)b->count * b->m, where, b->in_b, s) : nullptr;
-    OQ_LAUNCH(k_batch_warm, dim3(b->count), dim3(256), 0, s, b->dp.P, b->count, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride);
+    OQ_LAUNCH(k_batch_warm, dim3(b->count), dim3(256), 0, s, b->dp.P, b->count, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride, (const int *)nullptr);
     HIP_CHECK(hipStreamSynchronize(s));
     b->st.warm_start = 1;  // as osqp_warm_start does
     return 0;
@@ -612,7 +687,7 @@ c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
     BatchIO io = b->inputs();
-    io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : b->info_out.get();
+    io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : b->info_all.get();
     io.x_stride = b->n; io.y_stride = b->m; io.info_stride = io.info_cols = 6;
     // (a resolve that failed between its solve launch and k_batch_cert may have left directions where the records of
     // infeasible instances hold zeros: the next one starts every instance from zero and rewrites every record)
@@ -620,18 +695,138 @@ c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_
     io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0);
     b->rec_raw = true;
     launch_batch(b->dp, b->st, b->count, io, s);
-    launch_cert(*b, io, s);  // before anything else reads the records: it puts them back as a solve without RES_CERT leaves them
+    launch_cert(*b, io, b->count, s);  // before anything else reads the records: it puts them back as a solve without RES_CERT leaves them
     b->rec_raw = false;
     b->pstat_live = b->st.polish != 0;
-    if (b->pstat_live) launch_polish(*b, io, s);
-    if (where) copy_d2d(b->info_out.get(), info_out, (size_t)b->count * 6, s);  // the statuses, for osqp_amd_batch_adjoint
+    if (b->pstat_live) launch_polish(*b, io, b->count, s);
+    if (where) copy_d2d(b->info_all.get(), info_out, (size_t)b->count * 6, s);  // the statuses, for osqp_amd_batch_adjoint
     if (!where) {
       b->x_out.download(x_out, (size_t)b->count * b->n, s);
       if (b->m) b->y_out.download(y_out, (size_t)b->count * b->m, s);
-      b->info_out.download(info_out, (size_t)b->count * 6, s);
+      b->info_all.download(info_out, (size_t)b->count * 6, s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
-    b->sol_current = true;
+    b->mark(true);
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+// ---- the same five calls for a selection of the instances (include/osqp_amd.h, "*_rows") -------------------------------------
+c_int osqp_amd_batch_update_lin_cost_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *q_rows, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!q_rows) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (!select_rows(*b, rows, k, s)) return 1;
+    b->mark_rows(false);
+    scatter_rows(*b, (int)k, b->n, device_ptr(q_rows, (size_t)k * b->n, where, b->in_a, s), b->q.get(), s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_update_bounds_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *l_rows, const c_float *u_rows,
+                                        c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (!select_rows(*b, rows, k, s)) return 1;
+    if (b->m == 0 || (!l_rows && !u_rows)) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
+    const size_t len = (size_t)k * b->m;
+    // checked on the device against the stored bound of the same instance where one is kept, before anything changes
+    const double *ln = l_rows ? device_ptr(l_rows, len, where, b->in_a, s) : nullptr;
+    const double *un = u_rows ? device_ptr(u_rows, len, where, b->in_b, s) : nullptr;
+    int bad = 0;
+    HIP_CHECK(hipMemsetAsync(b->bad.get(), 0, sizeof(int), s));
+    OQ_LAUNCH(k_batch_check_bounds_rows, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, b->sel.get(), (int)k, b->m, ln, un, b->l.get(),
+              b->u.get(), b->bad.get());
+    b->bad.download(&bad, 1, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (bad) { set_last_error("lower bound greater than upper bound"); return 1; }
+    b->mark_rows(false);
+    if (ln) scatter_rows(*b, (int)k, b->m, ln, b->l.get(), s);
+    if (un) scatter_rows(*b, (int)k, b->m, un, b->u.get(), s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_update_matrices_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *Px_rows, const c_float *Ax_rows,
+                                          c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (!select_rows(*b, rows, k, s)) return 1;
+    if (!Px_rows && !Ax_rows) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
+    b->mark_rows(false);
+    if (Px_rows && b->nnzP) scatter_rows(*b, (int)k, b->nnzP, device_ptr(Px_rows, (size_t)k * b->nnzP, where, b->in_a, s), b->Px.get(), s);
+    if (Ax_rows && b->nnzA) scatter_rows(*b, (int)k, b->nnzA, device_ptr(Ax_rows, (size_t)k * b->nnzA, where, b->in_b, s), b->Ax.get(), s);
+    resident_equilibrate(*b, (int)k, b->sel.get(), s);  // the selected instances only: k workgroups
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_warm_start_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *x_rows, const c_float *y_rows,
+                                     c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (!select_rows(*b, rows, k, s)) return 1;
+    if (!x_rows && !y_rows) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
+    b->mark_rows(false);
+    const double *xd = x_rows ? device_ptr(x_rows, (size_t)k * b->n, where, b->in_a, s) : nullptr;
+    const double *yd = y_rows && b->m ? device_ptr(y_rows, (size_t)k * b->m, where, b->in_b, s) : nullptr;
+    OQ_LAUNCH(k_batch_warm, dim3((unsigned)k), dim3(256), 0, s, b->dp.P, (int)k, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride,
+              (const int *)b->sel.get());
+    HIP_CHECK(hipStreamSynchronize(s));
+    b->st.warm_start = 1;  // a setting of the handle, as in osqp_amd_batch_warm_start
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *x_out, c_float *y_out, c_float *info_out,
+                                  c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!x_out || !info_out || (b->m > 0 && !y_out)) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (!select_rows(*b, rows, k, s)) return 1;
+    const int cnt = (int)k;
+    // compact outputs: row j of x / y / info is of instance rows[j] (host pointers: through the first k rows of the staging)
+    BatchIO io = b->inputs();
+    io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : b->info_out.get();
+    io.x_stride = b->n; io.y_stride = b->m; io.info_stride = io.info_cols = 6;
+    io.rec = b->rec.get(); io.rec_stride = b->rec_stride; io.sel = b->sel.get();
+    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0);  // rec_raw: as osqp_amd_batch_resolve
+    b->rec_raw = true;
+    launch_batch(b->dp, b->st, cnt, io, s);
+    launch_cert(*b, io, cnt, s);
+    b->rec_raw = false;
+    // the polish status is of every instance's own last resolve: the others keep theirs (all 0 while the buffer is not live)
+    const bool was_live = b->pstat_live;
+    if (!was_live) b->pstat.zero(s);
+    b->pstat_live = true;
+    if (b->st.polish) launch_polish(*b, io, cnt, s);
+    else if (was_live) OQ_LAUNCH(k_batch_fill_rows, dim3(blocks_for(cnt, 256)), dim3(256), 0, s, b->sel.get(), cnt, 0.0, b->pstat.get());
+    scatter_rows(*b, cnt, 6, io.info, b->info_all.get(), s);  // after the polish launch, which rewrites the residuals
+    if (!where) {
+      b->x_out.download(x_out, (size_t)cnt * b->n, s);
+      if (b->m) b->y_out.download(y_out, (size_t)cnt * b->m, s);
+      b->info_out.download(info_out, (size_t)cnt * 6, s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    b->mark_rows(true);
     return 0;
   } OQ_BATCH_CATCH
 }
@@ -641,10 +836,12 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *handle, const c_float *dx, const c_
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
   if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
-  if (!b->sol_current) {
-    set_last_error("the batch holds no current solution: call osqp_amd_batch_resolve after the last update or warm start");
-    return 1;
-  }
+  for (size_t i = 0; i < b->current.size(); i++)
+    if (!b->current[i]) {
+      set_last_error("instance " + std::to_string(i) + " of the batch holds no current solution: call osqp_amd_batch_resolve (or _resolve_rows "
+                     "with this instance) after its last update or warm start");
+      return 1;
+    }
   try {
     const Pattern &P = b->dp.P;
     polish_check_fits(P);
@@ -667,7 +864,7 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *handle, const c_float *dx, const c_
       if (host[k] && !where) at += len[k];
     }
     polish::AdjointArgs a;
-    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_out.get(); a.rec = b->rec.get();
+    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
     a.gx = dx ? device_ptr(dx, ln, where, b->in_a, s) : nullptr;
     a.gy = dy ? device_ptr(dy, lm, where, b->in_b, s) : nullptr;
     a.dq = dev[0]; a.dl = dev[1]; a.du = dev[2]; a.dPx = dev[3]; a.dAx = dev[4]; a.act = dev[5]; a.status = dev[6];
@@ -738,7 +935,7 @@ c_int osqp_amd_batch_update_setting(osqp_amd_batch *handle, const char *name, c_
       OQ_LAUNCH(k_batch_fill_rho, dim3(blocks_for(b->count, 256)), dim3(256), 0, s, b->count, (double)st.rho, b->rec.get(), b->rec_stride);
       HIP_CHECK(hipStreamSynchronize(s));
     }
-    b->st = st;  // acts from the next resolve; data and iterate are unchanged: sol_current, the certificates and polish_status stay
+    b->st = st;  // acts from the next resolve; data and iterate are unchanged: `current`, the certificates and polish_status stay
     return 0;
   } OQ_BATCH_CATCH
 }

@@ -22,6 +22,7 @@ struct Args {
   double *rec;         // the records
   double *prim, *dual; // [count x m], [count x n] of the handle (prim nullptr when m = 0)
   int info_stride, rec_stride, unscaled;
+  const int *sel;      // the instance of each workgroup (nullptr: its own number); the info rows are the workgroups'
 };
 
 // max over the workgroup, the same value in every thread; `red` holds one double per wavefront
@@ -51,9 +52,10 @@ __device__ __forceinline__ void normalise_row(double *slot, const double *scale,
 
 __global__ __launch_bounds__(CT) void k_batch_cert(int n, int m, int count, Args a) {
   __shared__ double red[CT / 64];
-  const int inst = blockIdx.x;
-  if (inst >= count) return;
-  const int status = (int)a.info[(size_t)inst * a.info_stride + 1];
+  const int pos = blockIdx.x;
+  if (pos >= count) return;
+  const int inst = a.sel ? a.sel[pos] : pos;
+  const int status = (int)a.info[(size_t)pos * a.info_stride + 1];
   double *const rec = a.rec + (size_t)inst * a.rec_stride;
   double *const prim = a.prim ? a.prim + (size_t)inst * m : nullptr, *const dual = a.dual + (size_t)inst * n;
   if (prim) {

@@ -159,13 +159,16 @@ constexpr int kMpcNnzA = mpc_nnzA();
 
 // The argument block of a batched launch: the instances' data (nnzP / nnzA / n / m / m doubles per instance), where row i
 // of x / y / info goes (x + i * x_stride etc.: packed layouts put all three in one row; info_cols 4 or 6), and for resident
-// mode the state records.  launch_batch takes it; its callers fill it by name.
+// mode the state records.  sel (resident handles only): the workgroup at position p of the launch serves instance sel[p] --
+// its data and its record -- and writes row p of x / y / info; nullptr: position = instance.  launch_batch takes it; its
+// callers fill it by name.
 struct BatchIO {
   const double *Px = nullptr, *Ax = nullptr, *q = nullptr, *l = nullptr, *u = nullptr;
   double *x = nullptr, *y = nullptr, *info = nullptr;
   int x_stride = 0, y_stride = 0, info_stride = 0, info_cols = 0;
   double *rec = nullptr;
   int rec_stride = 0, res_mode = 0;
+  const int *sel = nullptr;
 };
 
 // ---- the instantiations of the four-wavefront kernel: stated HERE and nowhere else -----------------------------------------

@@ -47,6 +47,7 @@ struct Args {
   int x_stride, y_stride, info_stride, rec_stride;
   int refine, unscaled;  // unscaled: scaling on and scaled_termination off (residuals in the caller's units)
   double delta;
+  const int *sel;  // the instance of each workgroup (nullptr: its own number); the x / y / info rows are the workgroups'
 };
 
 __device__ __forceinline__ int tri(int i, int j) { return ((i * (i + 1)) >> 1) + j; }  // i >= j
@@ -197,9 +198,10 @@ __device__ __forceinline__ void kkt_step(const Pattern &P, const Slots &S, int i
 }
 
 __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layout L, Args a) {
-  const int inst = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
-  if (inst >= count) return;
-  double *const info = a.info + (size_t)inst * a.info_stride;
+  const int pos = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
+  if (pos >= count) return;
+  const int inst = a.sel ? a.sel[pos] : pos;
+  double *const info = a.info + (size_t)pos * a.info_stride;
   if ((int)info[1] != OSQP_SOLVED) {  // nothing to polish: x, y, info and the record stay as the solve left them
     if (tid == 0) a.status[inst] = 0.0;
     return;
@@ -268,9 +270,9 @@ __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layou
     if (tid == 0) a.status[inst] = -1.0;
     return;
   }
-  for (int j = tid; j < n; j += PT) { a.x[(size_t)inst * a.x_stride + j] = D[j] * x[j]; rec[rec_x(n, m) + j] = x[j]; }
+  for (int j = tid; j < n; j += PT) { a.x[(size_t)pos * a.x_stride + j] = D[j] * x[j]; rec[rec_x(n, m) + j] = x[j]; }
   for (int i = tid; i < m; i += PT) {
-    a.y[(size_t)inst * a.y_stride + i] = cinv * E[i] * y[i];
+    a.y[(size_t)pos * a.y_stride + i] = cinv * E[i] * y[i];
     rec[rec_z(n, m) + i] = z[i]; rec[rec_y(n, m) + i] = y[i];
   }
   if (tid == 0) { info[2] = pri; info[3] = dua; info[4] = obj; a.status[inst] = 1.0; }

@@ -334,14 +334,20 @@ __device__ __forceinline__ Me make_me(int n, int wvs) {  // wvs: the wavefront's
   return me;
 }
 
-template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF>
+template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF, bool SEL>
 __device__ __forceinline__ void quad_body(
     const Sched &S, const OSQPSettings &st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,
     const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,
     double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,
-    int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
-  const int inst = blockIdx.x;
-  if (inst >= count) return;
+    int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode, const int *__restrict__ sel) {
+  // the workgroup's position in the launch and the instance it serves (BatchIO::sel): the data and the record are the
+  // instance's, the x / y / info rows the position's.  Read here, once; the store takes the position from blockIdx.x again.
+  // SEL is a template argument, not a test of the pointer: a launch without a selection runs the code it ran before there
+  // was one, instruction for instruction (profiles/batch_subset_resources.md) -- the extra scalar code of the prologue
+  // moved the ADMM loop to other addresses, and the benchmark saw it
+  const int pos = blockIdx.x;
+  if (pos >= count) return;
+  const int inst = SEL ? uni(sel[pos]) : pos;
   const int n = CN ? CN : S.n, m = CN ? CM : S.m, nnzA = CN ? CA : S.nnzA, nnzF = CN ? CF : S.nnzF;
   // resident mode (batch_common.hpp, "the state record"): a workgroup-uniform branch of the prologue and the epilogue
   const bool res_solve = (res_mode & RES_SOLVE) != 0, res_warm = (res_mode & RES_WARM) != 0;
@@ -1109,13 +1115,14 @@ __device__ __forceinline__ void quad_body(
   {
     ME;
     const bool has_sol = status == OSQP_SOLVED || status == OSQP_SOLVED_INACCURATE || status == OSQP_MAX_ITER_REACHED;
-    if (me.owner) x_out[(size_t)inst * x_stride + S.perm[me.j]] = has_sol ? ld(lds, L.cD + me.j * 8) * ld(lds, L.cx + me.j * 8) : NAN;
+    const int row = SEL ? (int)blockIdx.x : inst;  // the position (without a selection the same number, and the code as it was)
+    if (me.owner) x_out[(size_t)row * x_stride + S.perm[me.j]] = has_sol ? ld(lds, L.cD + me.j * 8) * ld(lds, L.cx + me.j * 8) : NAN;
     for (int i = me.t; i < m; i += QT) {
       const unsigned r = (unsigned)i * RECB;
-      y_out[(size_t)inst * y_stride + i] = has_sol ? cinv * ld(lds, L.rec + r + F_E) * ld(lds, L.rec + r + F_Y) : NAN;
+      y_out[(size_t)row * y_stride + i] = has_sol ? cinv * ld(lds, L.rec + r + F_E) * ld(lds, L.rec + r + F_Y) : NAN;
     }
     if (me.t == 0) {
-      double *o = info_out + (size_t)inst * info_stride;
+      double *o = info_out + (size_t)row * info_stride;
       o[0] = (double)iter; o[1] = (double)status; o[2] = pri_res; o[3] = dua_res;
       if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)rho_updates; }
     }
@@ -1141,14 +1148,15 @@ __device__ __forceinline__ void quad_body(
 // ones (NH = 64: 128 registers of inverse alone) two.
 // (the last column of OQ_QUAD_ENTRIES names one of the two; the arguments are BatchIO's members in its order)
 #define OQ_QUAD_KERNEL(NAME, WAVES)                                                                                            \
-  template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF>                                                    \
+  template <int NH, int KC, int KE, int CH, int CN, int CM, int CA, int CF, bool SEL>                                          \
   __global__ __launch_bounds__(QT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void NAME(                               \
       Sched S, OSQPSettings st, int count, const double *__restrict__ Px_all, const double *__restrict__ Ax_all,               \
       const double *__restrict__ q_all, const double *__restrict__ l_all, const double *__restrict__ u_all,                    \
       double *__restrict__ x_out, double *__restrict__ y_out, double *__restrict__ info_out, int x_stride, int y_stride,       \
-      int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {                            \
-    quad_body<NH, KC, KE, CH, CN, CM, CA, CF>(S, st, count, Px_all, Ax_all, q_all, l_all, u_all, x_out, y_out, info_out, x_stride, \
-                                              y_stride, info_stride, info_cols, rec_all, rec_stride, res_mode);                \
+      int info_stride, int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode,                              \
+      const int *__restrict__ sel) {                                                                                           \
+    quad_body<NH, KC, KE, CH, CN, CM, CA, CF, SEL>(S, st, count, Px_all, Ax_all, q_all, l_all, u_all, x_out, y_out, info_out, x_stride, \
+                                              y_stride, info_stride, info_cols, rec_all, rec_stride, res_mode, sel);           \
   }
 OQ_QUAD_KERNEL(k_batch_quad, 3)
 OQ_QUAD_KERNEL(k_batch_quad2, 2)

@@ -647,16 +647,21 @@ __device__ __noinline__ void leave_certificate(int n_, int m_, int nnzA, int nnz
 // CN > 0: the instance shape (n, m, nnz(A), nnz(P full)) = (CN, CM, CA, CF) is known at compile time -- every LDS address
 // becomes an immediate and every vector loop a fixed trip count (the registers otherwise spent on ~35 LDS pointers are
 // what the inverse needs); CN = 0: the same source with the shape read from the pattern at run time.
-template <int NCT, int CN, int CM, int CA, int CF>
+template <int NCT, int CN, int CM, int CA, int CF, bool SEL>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_batch_solve(Pattern Pin, OSQPSettings st, int count, double *__restrict__ scratch_all,
                                                     const double *__restrict__ Px_all,
                                                     const double *__restrict__ Ax_all, const double *__restrict__ q_all,
                                                     const double *__restrict__ l_all, const double *__restrict__ u_all,
                                                     double *__restrict__ x_out, double *__restrict__ y_out,
                                                     double *__restrict__ info_out, int x_stride, int y_stride, int info_stride,
-                                                    int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode) {
-  const int inst = blockIdx.x;
-  if (inst >= count) return;
+                                                    int info_cols, double *__restrict__ rec_all, int rec_stride, int res_mode,
+                                                    const int *__restrict__ sel) {
+  // the workgroup's position in the launch and the instance it serves (BatchIO::sel): the data and the record are the
+  // instance's; the x / y / info rows and the scratch are the position's, taken from blockIdx.x again where they are used.
+  // SEL: a template argument, as in k_batch_quad -- without a selection the kernel is the code it was before there was one
+  const int pos = blockIdx.x;
+  if (pos >= count) return;
+  const int inst = SEL ? uni(sel[pos]) : pos;
   const bool res_solve = (res_mode & RES_SOLVE) != 0, res_warm = (res_mode & RES_WARM) != 0;
   double *const rec = res_mode ? rec_all + (size_t)inst * rec_stride : nullptr;  // the instance's state record (resident mode)
   Pattern P = Pin;
@@ -812,7 +817,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   double rho = uni(fmin(fmax(res_solve ? rec[REC_RHO] : st.rho, B_RHO_MIN), B_RHO_MAX));
   set_rho(P, s, rho, true);
   int status = OSQP_UNSOLVED;
-  double *scratch = scratch_all + (size_t)inst * n * n;
+  double *scratch = scratch_all + (size_t)(SEL ? (int)blockIdx.x : inst) * n * n;
   MTile<NCT> Minv;
   // y = A v / y = A' v through whichever walk of A applies
   auto a_rows = [&](const ldouble *v, auto pre, auto finish) {
@@ -914,10 +919,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   PROF_PRINT
   // ---- store -----------------------------------------------------
   const bool has_sol = status == OSQP_SOLVED || status == OSQP_SOLVED_INACCURATE || status == OSQP_MAX_ITER_REACHED;
-  for (int j = tid; j < n; j += NT) x_out[(size_t)inst * x_stride + j] = has_sol ? s.D[j] * x[j] : NAN;
-  for (int i = tid; i < m; i += NT) y_out[(size_t)inst * y_stride + i] = has_sol ? cinv * s.E[i] * s.y[i] : NAN;
+  const int row = SEL ? (int)blockIdx.x : inst;  // the position (without a selection the same number, and the code as it was)
+  for (int j = tid; j < n; j += NT) x_out[(size_t)row * x_stride + j] = has_sol ? s.D[j] * x[j] : NAN;
+  for (int i = tid; i < m; i += NT) y_out[(size_t)row * y_stride + i] = has_sol ? cinv * s.E[i] * s.y[i] : NAN;
   if (tid == 0) {
-    double *o = info_out + (size_t)inst * info_stride;
+    double *o = info_out + (size_t)row * info_stride;
     o[0] = (double)iter; o[1] = (double)status; o[2] = pri_res; o[3] = dua_res;
     if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)rho_updates; }
   }

@@ -334,6 +334,67 @@ function batch_solve!(b::ResidentBatch, x::Ptr{Cdouble}, y::Ptr{Cdouble}, info::
     return nothing
 end
 
+# ---- the same calls for a selection of the instances (osqp_amd_batch_*_rows) ----------------------------------------------
+# `rows`: distinct 1-based instance numbers, in any order; the arrays then have one COLUMN per selected instance, column j for
+# instance rows[j].  A selected instance gets the bits of the whole-batch call; every other instance -- data, record,
+# certificates, polish status -- stays as it was.  The library checks the selection (range, repeats, 1 <= k <= count).
+_batch_rows(rows::AbstractVector{<:Integer}) = Vector{Cc_int}(rows .- 1)
+
+"`batch_update!` for the instances `rows` only; only they are re-equilibrated when Px / Ax are given."
+function batch_update!(b::ResidentBatch, rows::AbstractVector{<:Integer}; q::BatchArg = nothing, l::BatchArg = nothing,
+                       u::BatchArg = nothing, Px::BatchArg = nothing, Ax::BatchArg = nothing)
+    r = _batch_rows(rows)
+    k = length(r)
+    GC.@preserve q l u Px Ax begin
+        if q !== nothing
+            flag = ccall((:osqp_amd_batch_update_lin_cost_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Cc_int),
+                         b.handle, r, k, _batch_ptr(q), _batch_where(q))
+            flag == 0 || error("Error in batched update: $(last_error())")
+        end
+        if l !== nothing || u !== nothing
+            flag = ccall((:osqp_amd_batch_update_bounds_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                         b.handle, r, k, _batch_ptr(l), _batch_ptr(u), _batch_where(l, u))
+            flag == 0 || error("Error in batched update: $(last_error())")
+        end
+        if Px !== nothing || Ax !== nothing
+            flag = ccall((:osqp_amd_batch_update_matrices_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                         b.handle, r, k, _batch_ptr(Px), _batch_ptr(Ax), _batch_where(Px, Ax))
+            flag == 0 || error("Error in batched update: $(last_error())")
+        end
+    end
+    return nothing
+end
+
+function batch_warm_start!(b::ResidentBatch, rows::AbstractVector{<:Integer}; x::BatchArg = nothing, y::BatchArg = nothing)
+    r = _batch_rows(rows)
+    GC.@preserve x y begin
+        flag = ccall((:osqp_amd_batch_warm_start_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, r, length(r), _batch_ptr(x), _batch_ptr(y), _batch_where(x, y))
+    end
+    flag == 0 || error("Error in batched warm start: $(last_error())")
+    return nothing
+end
+
+"Solve the instances `rows` only -> (x [n x k], y [m x k], info [6 x k]); k workgroups per launch."
+function batch_solve!(b::ResidentBatch, rows::AbstractVector{<:Integer})
+    r = _batch_rows(rows)
+    k = length(r)
+    x, y, info = Matrix{Float64}(undef, b.n, k), Matrix{Float64}(undef, b.m, k), Matrix{Float64}(undef, 6, k)
+    flag = ccall((:osqp_amd_batch_resolve_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                 b.handle, r, k, x, y, info, 0)
+    flag == 0 || error("Error in batched solve: $(last_error())")
+    return x, y, info
+end
+
+"The same into device arrays (pointers to n * k, m * k, 6 * k doubles on the handle's device)."
+function batch_solve!(b::ResidentBatch, rows::AbstractVector{<:Integer}, x::Ptr{Cdouble}, y::Ptr{Cdouble}, info::Ptr{Cdouble})
+    r = _batch_rows(rows)
+    flag = ccall((:osqp_amd_batch_resolve_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                 b.handle, r, length(r), x, y, info, 1)
+    flag == 0 || error("Error in batched solve: $(last_error())")
+    return nothing
+end
+
 "status_polish of every instance from the last `batch_solve!`: 1 accepted, -1 refused, 0 not polished (not Solved, or polish off)."
 function batch_polish_status(b::ResidentBatch)
     st = Vector{Float64}(undef, b.count)

@@ -12,7 +12,8 @@ Three rules.  The library runs on its own stream and blocks, so torch's current 
 call.  The handle holds ONE solution: every forward stamps the handle, and a backward whose stamp is no longer the handle's
 raises RuntimeError.  Instances whose adjoint status is not 1 (no solution, failed factorisation) get zero gradients; where
 an instance's active constraints are dependent the derivative does not exist and the regularised answer is returned
-(include/osqp_amd.h, osqp_amd_batch_adjoint)."""
+(include/osqp_amd.h, osqp_amd_batch_adjoint).  The layer works on the whole batch: the `rows=` forms of
+`ResidentBatch.update` / `solve` are not offered here."""
 import torch
 
 NAMES = ("q", "l", "u", "Px", "Ax")

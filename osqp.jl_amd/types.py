@@ -213,6 +213,12 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_update_matrices": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_warm_start": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_resolve": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    # the same for a selection of the instances: rows (a host array of k instance numbers) and k after the handle
+    "osqp_amd_batch_update_lin_cost_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, c_int]),
+    "osqp_amd_batch_update_bounds_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_update_matrices_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_warm_start_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_resolve_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_polish_status": (c_int, [C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_update_polish": (c_int, [C.c_void_p, c_int, c_int]),
     "osqp_amd_batch_last_kernel": (c_int, []),
