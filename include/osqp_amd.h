@@ -494,6 +494,30 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             since (any update_* or warm_start; update_polish does not count), and a pattern whose working set exceeds
  *             the polish LDS limit.  The call changes nothing on the handle: a resolve after it is bit-identical to one
  *             without it.
+ *   jvp():    forward sensitivities (Jacobian-vector products) of the solutions of the last resolve: the transpose of
+ *             adjoint().  A direction of the data is (tq [n], tl, tu [m], tPx [nnz(P upper)], tAx [nnz(A)]) per instance, in
+ *             the setup's pattern order; tP is the symmetric matrix of tPx (a stored off-diagonal entry stands for both
+ *             halves of P).  With the active rows a = L u U and K = [P, Aa'; Aa, 0] of adjoint(), one solve per direction
+ *               K [tx; ty_a] = [-(tq + tP x + tA' y); (tb - tA x) restricted to a],   tb_i = tl_i on L, tu_i on U,
+ *             gives tx_out (the tangent of x) and ty_out = ty_a scattered to length m, zero on the inactive rows.  On a row
+ *             with l == u (always active, counts as lower) only tl is read -- the mirror of "returned in dl" of adjoint();
+ *             a tangent of an inactive bound has no effect.  x, y are the values resolve returned.
+ *             ndir >= 1 directions per call, direction-major: every tangent is [ndir x count x cols] and so are tx_out
+ *             [ndir x count x n] and ty_out [ndir x count x m]; direction d of every array is a contiguous [count x cols]
+ *             block.  act_out [count x m] and status_out [count], once per call, are those of adjoint().  The matrix is
+ *             assembled and factorised ONCE per instance and solved once per direction (the polish solve: regularised with
+ *             settings.delta, settings.polish_refine_iter refinement steps against the unregularised K); nothing is carried
+ *             from one direction to the next, so direction d of an ndir-direction call has the bits of a one-direction call
+ *             with that tangent, and a NULL tangent gives the bits of a tangent of zeros.
+ *             A NULL tangent is zero and never read (all five NULL: return 1); tx_out or ty_out may be NULL (not wanted;
+ *             both NULL: return 1), as may act_out and status_out.  With m = 0, tl / tu / tAx / ty_out / act_out are
+ *             ignored, and a zero-width tPx or tAx is ignored.  status: 1 differentiated; 0 the instance had no solution at
+ *             the last resolve (its rows of every direction and its act_out row are zeros); -1 non-positive pivot (zeros).
+ *             Refused with return 1 and a message, without a launch and with the handle unchanged: ndir < 1, a handle that
+ *             has not been resolved or whose data or iterate changed since (the rules and the message of adjoint(): every
+ *             instance must be current, the first stale one is named; setting changes do not count), and a pattern whose
+ *             working set exceeds the polish LDS limit.  Singular K: as adjoint().  The call only reads the handle: a
+ *             resolve after it is bit-identical to one without it.
  *   certificates(): the directions that prove the infeasibilities of the handle's last resolve -- results.prim_inf_cert /
  *             dual_inf_cert of a single model.  Row i of prim_inf_cert_out [count x m], for an instance whose status is
  *             primal infeasible (or its inaccurate form), is the projected delta_y of the terminating check, multiplied
@@ -526,8 +550,8 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             in its ADMM launch, in k_batch_cert and (polish = 1) in k_batch_polish; x_out [k x n], y_out [k x m],
  *             info_out [k x 6].  A bad selection -- k < 1, k > count, an entry out of range, a repeated entry (the message
  *             names it) -- returns 1 with a message and leaves the handle unchanged.
- *             polish_status(), certificates() and adjoint() stay whole-batch calls: their row i is of instance i's OWN last
- *             resolve, whole or selected (polish status 0 when polish was off at that resolve).  adjoint() needs every
+ *             polish_status(), certificates(), adjoint() and jvp() stay whole-batch calls: their row i is of instance i's OWN last
+ *             resolve, whole or selected (polish status 0 when polish was off at that resolve).  adjoint() and jvp() need every
  *             instance current: a *_rows update or warm start makes its rows stale, resolve_rows makes them current, and
  *             the refusal names the first stale instance.
  * where: 0 = the array arguments are host pointers, 1 = device pointers on the handle's device (no host hop: a controller
@@ -561,11 +585,16 @@ c_int osqp_amd_batch_certificates(osqp_amd_batch *batch, c_float *prim_inf_cert_
 c_int osqp_amd_batch_adjoint(osqp_amd_batch *batch, const c_float *dx, const c_float *dy,
                              c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
                              c_float *act_out, c_float *status_out, c_int where);
+c_int osqp_amd_batch_jvp(osqp_amd_batch *batch, c_int ndir,
+                         const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx, const c_float *tAx,
+                         c_float *tx_out, c_float *ty_out, c_float *act_out, c_float *status_out, c_int where);
 /* Diagnostic, like osqp_amd_batch_last_kernel: how many polish launches this process has made so far.  A resolve with
  * polish = 0 makes none -- its launch sequence is the one of a library without the polish kernel. */
 c_int osqp_amd_batch_polish_launches(void);
 /* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint that passed its checks, none otherwise. */
 c_int osqp_amd_batch_adjoint_launches(void);
+/* The same for the sensitivity kernel: one launch per osqp_amd_batch_jvp that passed its checks, whatever ndir, none otherwise. */
+c_int osqp_amd_batch_jvp_launches(void);
 /* The same for the certificate kernel: one launch per osqp_amd_batch_resolve / _resolve_rows, none by osqp_amd_batch_certificates or by the
  * one-shot entries. */
 c_int osqp_amd_batch_cert_launches(void);

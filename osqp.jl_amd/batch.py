@@ -516,6 +516,70 @@ class ResidentBatch:
             res["status"] = res["status"].ravel().astype(np.int64)
         return res
 
+    JVP_TANGENTS = ("q", "l", "u", "Px", "Ax")
+
+    def jvp(self, q=None, l=None, u=None, Px=None, Ax=None, out=None):
+        """Forward sensitivities of the solutions of the last `solve()` along directions of the data (osqp_amd_batch_jvp): the
+        tangents q [count x n], l, u [count x m], Px [count x nnz(P upper)], Ax [count x nnz(A)] (None: zero; not all), or
+        each with a leading axis [ndir x count x .] for several directions at once -- one launch, one factorisation per
+        instance, one solve per direction, and direction d has the bits of a call with that direction alone.  All tangents
+        have the same number of dimensions and the same ndir.  Returns a dict: "x" (tangent of the solution), "y" (of the
+        multipliers; zero on inactive rows), shaped like the tangents, "act" [count x m] (-1 lower, 1 upper, 0 inactive) and
+        "status" (1 differentiated, 0 no solution, -1 factorisation failed; rows with status != 1 are zeros).  "y" and "act"
+        are left out when m = 0.  On a row with l == u only the tangent `l` is read; a tangent of an inactive bound has no
+        effect.  Host form: numpy tangents, out=None, numpy results ("act" and "status" [count] as integers).  Device form:
+        device arrays and `out` a dict of float64 device arrays -- "x" and (m > 0) "y", optionally "act" [count x m] and
+        "status" [count x 1] -- filled in place and returned.  The handle must hold the solution of its current data for
+        EVERY instance, as for `adjoint`."""
+        cols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA)
+        given = {k: v for k, v in zip(self.JVP_TANGENTS, (q, l, u, Px, Ax)) if v is not None}
+        if not given:
+            raise ValueError("q, l, u, Px, Ax: at least one tangent is needed")
+        dims = {k: len(tuple(v.shape)) if hasattr(v, "data_ptr") else np.asarray(v).ndim for k, v in given.items()}
+        if len(set(dims.values())) > 1 or next(iter(dims.values())) not in (2, 3):
+            raise ValueError(f"tangents: expected all [count x cols] or all [ndir x count x cols], got dimensions {dims}")
+        many = next(iter(dims.values())) == 3
+        first = next(iter(given.values()))
+        ndir = int((first.shape if hasattr(first, "data_ptr") else np.asarray(first).shape)[0]) if many else 1
+        if ndir < 1:
+            raise ValueError("tangents: ndir must be at least 1")
+        lead = (ndir, self.count) if many else (self.count,)
+        got = {k: _batch_array(k, v, lead + (cols[k],)) for k, v in given.items()}
+        forms = {g[2] for g in got.values()}
+        if len(forms) > 1:
+            raise ValueError("tangents: they must all be host arrays or all device arrays")
+        where = forms.pop()
+        ocols = dict(x=self.n, y=self.m, act=self.m, status=1)
+        oshape = dict(x=lead + (self.n,), y=lead + (self.m,), act=(self.count, self.m), status=(self.count, 1))
+        names = [k for k in ("x", "y", "act", "status") if ocols[k] > 0]
+        if not where:
+            if out is not None:
+                raise ValueError("out: host tangents (numpy) return numpy arrays; pass device arrays for the tangents to fill `out`")
+            res = {k: np.empty(oshape[k]) for k in names}
+            addr = {k: v.ctypes.data for k, v in res.items()}
+        else:
+            if not isinstance(out, dict):
+                raise ValueError("out: device tangents need a dict of device arrays to fill: x, y")
+            for k in out:
+                if k not in ocols:
+                    raise ValueError(f"out: unknown entry {k!r}")
+            addr = {}
+            for k in names:
+                if k in out:
+                    if not hasattr(out[k], "data_ptr"):
+                        raise ValueError(f"out[{k!r}]: expected a device array (DeviceArray, torch tensor)")
+                    addr[k] = _batch_array(f"out[{k!r}]", out[k], oshape[k])[1]
+                elif k in ("x", "y"):
+                    raise ValueError(f"out: no array for {k!r}")
+            res = out
+        self._call("jvp", self.lib.osqp_amd_batch_jvp(self.handle, ndir, *[got[k][1] if k in got else None for k in self.JVP_TANGENTS],
+                                                      addr.get("x"), addr.get("y"), addr.get("act"), addr.get("status"), where))
+        if not where:
+            if "act" in res:
+                res["act"] = res["act"].astype(np.int64)
+            res["status"] = res["status"].ravel().astype(np.int64)
+        return res
+
     def alloc(self, k=None):
         """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints.  k: the number of
         rows, for a solve of a selection of k instances (None: count)."""

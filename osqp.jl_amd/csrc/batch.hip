@@ -15,6 +15,8 @@
 //                     when the handle's settings.polish is 1; the solve kernels know nothing of it;
 //   batch_adjoint.hpp k_batch_adjoint -- adjoint derivatives of the solutions of the resident batch, a launch of its own on
 //                     request (osqp_amd_batch_adjoint); shares the factorisation and the solves of the polish kernel;
+//   batch_jvp.hpp     k_batch_jvp -- forward sensitivities of the solutions of the resident batch along directions of the data, a
+//                     launch of its own on request (osqp_amd_batch_jvp): one factorisation per instance, one solve per direction;
 //   batch_cert.hpp    k_batch_cert -- the infeasibility certificates of the resident batch, a launch of its own after every
 //                     ADMM launch of osqp_amd_batch_resolve: normalises the directions that launch left in the records (RES_CERT);
 //   this file         the small kernels (warm start, rho fill, bound check, the row scatter of a selection, MPC generator), the
@@ -31,6 +33,7 @@
 #include <type_traits>
 
 #include "batch_adjoint.hpp"
+#include "batch_jvp.hpp"
 #include "batch_cert.hpp"
 #include "batch_polish.hpp"
 #include "batch_quad.hpp"
@@ -42,6 +45,7 @@ namespace oq {
 namespace {
 
 int g_batch_polish_launches = 0;  // launches of k_batch_polish by this process (osqp_amd_batch_polish_launches)
+int g_batch_jvp_launches = 0;      // launches of k_batch_jvp by this process (osqp_amd_batch_jvp_launches)
 int g_batch_adjoint_launches = 0;  // launches of k_batch_adjoint by this process (osqp_amd_batch_adjoint_launches)
 int g_batch_cert_launches = 0;  // launches of k_batch_cert by this process (osqp_amd_batch_cert_launches)
 int g_batch_last_kernel = -2;  // what launch_batch launched last: -1 the 512-thread kernel, >= 0 the number of the entry of OQ_QUAD_ENTRIES
@@ -319,6 +323,9 @@ struct BatchPlan : BatchData {
   // in_a / in_b, out through adj_out
   std::vector<char> current;
   DevBuf<double> info_all, adj_out;
+  // forward sensitivities (osqp_amd_batch_jvp): the staging of host-pointer calls -- the five tangents come in through in_a,
+  // in_b and these three, the wanted outputs leave through adj_out
+  DevBuf<double> in_c, in_d, in_e;
   void mark(bool is_current) { std::fill(current.begin(), current.end(), (char)is_current); }
   void mark_rows(bool is_current) { for (int i : sel_host) current[(size_t)i] = (char)is_current; }
   // the selection of the running *_rows call, uploaded once per call (BatchIO::sel)
@@ -467,6 +474,7 @@ c_int osqp_amd_batch_last_schedule(c_int *out, c_int count) {
 }
 c_int osqp_amd_batch_polish_launches(void) { return g_batch_polish_launches; }
 c_int osqp_amd_batch_adjoint_launches(void) { return g_batch_adjoint_launches; }
+c_int osqp_amd_batch_jvp_launches(void) { return g_batch_jvp_launches; }
 c_int osqp_amd_batch_cert_launches(void) { return g_batch_cert_launches; }
 
 c_int osqp_amd_batch_solve(c_int count, c_int n, c_int m, const c_int *Pp, const c_int *Pi, const c_float *Px_all, const c_int *Ap,
@@ -875,6 +883,60 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *handle, const c_float *dx, const c_
     OQ_LAUNCH(polish::k_batch_adjoint, dim3(b->count), dim3(polish::PT), (size_t)L.total, s, P, b->count, L, a);
     if (!where)
       for (int k = 0; k < 7; k++) if (host[k]) HIP_CHECK(hipMemcpyAsync(host[k], dev[k], len[k] * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_jvp(osqp_amd_batch *handle, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,
+                         const c_float *tAx, c_float *tx_out, c_float *ty_out, c_float *act_out, c_float *status_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (ndir < 1) { set_last_error("invalid batch data: the sensitivities need ndir >= 1"); return 1; }
+  if (!tq && !tl && !tu && !tPx && !tAx) { set_last_error("invalid batch data: the sensitivities need a tangent"); return 1; }
+  if (!tx_out && !ty_out) { set_last_error("invalid batch data: the sensitivities need tx_out or ty_out"); return 1; }
+  for (size_t i = 0; i < b->current.size(); i++)
+    if (!b->current[i]) {
+      set_last_error("instance " + std::to_string(i) + " of the batch holds no current solution: call osqp_amd_batch_resolve (or _resolve_rows "
+                     "with this instance) after its last update or warm start");
+      return 1;
+    }
+  try {
+    const Pattern &P = b->dp.P;
+    polish_check_fits(P);
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const size_t cnt = (size_t)b->count, nd = (size_t)ndir, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    if (!lm) { tl = tu = nullptr; ty_out = act_out = nullptr; }
+    if (!la) tAx = nullptr;
+    if (!lp) tPx = nullptr;
+    // host pointers: the wanted outputs share one staging buffer, in this order
+    c_float *const host[4] = {tx_out, ty_out, act_out, status_out};
+    const size_t len[4] = {nd * ln, nd * lm, lm, cnt};
+    double *dev[4];
+    size_t total = 0;
+    for (int k = 0; k < 4; k++) if (host[k]) total += len[k];
+    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
+    size_t at = 0;
+    for (int k = 0; k < 4; k++) {
+      dev[k] = !host[k] ? nullptr : (where ? host[k] : b->adj_out.get() + at);
+      if (host[k] && !where) at += len[k];
+    }
+    polish::JvpArgs a;
+    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
+    a.tq = tq ? device_ptr(tq, nd * ln, where, b->in_a, s) : nullptr;
+    a.tl = tl ? device_ptr(tl, nd * lm, where, b->in_b, s) : nullptr;
+    a.tu = tu ? device_ptr(tu, nd * lm, where, b->in_c, s) : nullptr;
+    a.tPx = tPx ? device_ptr(tPx, nd * lp, where, b->in_d, s) : nullptr;
+    a.tAx = tAx ? device_ptr(tAx, nd * la, where, b->in_e, s) : nullptr;
+    a.tx = dev[0]; a.ty = dev[1]; a.act = dev[2]; a.status = dev[3];
+    a.ndir = (int)ndir; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
+    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
+    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_jvp, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+    g_batch_jvp_launches++;
+    OQ_LAUNCH(polish::k_batch_jvp, dim3(b->count), dim3(polish::PT), (size_t)L.total, s, P, b->count, L, a);
+    if (!where)
+      for (int k = 0; k < 4; k++) if (host[k]) HIP_CHECK(hipMemcpyAsync(host[k], dev[k], len[k] * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH

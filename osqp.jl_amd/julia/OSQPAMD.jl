@@ -491,6 +491,50 @@ function batch_adjoint!(b::ResidentBatch; dx::BatchArg = nothing, dy::BatchArg =
     return nothing
 end
 
+const JvpArg = Union{Nothing,Matrix{Float64},Array{Float64,3},Ptr{Cdouble}}
+_batch_ptr(a::Array{Float64,3}) = pointer(a)
+
+"""
+    batch_jvp!(b; tq = nothing, tl = nothing, tu = nothing, tPx = nothing, tAx = nothing, tx = nothing, ty = nothing,
+               act = nothing, status = nothing, ndir = nothing)
+
+Forward sensitivities of the solutions of the last `batch_solve!` along directions of the data (osqp_amd_batch_jvp in
+include/osqp_amd.h): the tangents `tq` [n x count], `tl`, `tu` [m x count], `tPx` [nnz(triu(P)) x count], `tAx`
+[nnz(A) x count] (`nothing` = zero, not all five), or each with a third axis [. x count x ndir] for several directions in one
+launch (one factorisation per instance, one solve per direction).  `tx` [n x count (x ndir)] and `ty` [m x count (x ndir)]
+are filled in place (`nothing` = not wanted, not both), as are `act` [m x count] and `status` [1 x count], once per call.  All
+arrays are host arrays or all are device pointers, as for `batch_adjoint!`; with device pointers `ndir` gives the number of
+directions (default 1), with host arrays it is read from the third axis and all arrays must agree.  The handle must have
+been solved since its last update or warm start.  Julia is not installed in the build image: like the rest of this file
+this function is not executed by the test suite; the Python mirror (`ResidentBatch.jvp`) is.
+"""
+function batch_jvp!(b::ResidentBatch; tq::JvpArg = nothing, tl::JvpArg = nothing, tu::JvpArg = nothing, tPx::JvpArg = nothing,
+                    tAx::JvpArg = nothing, tx::JvpArg = nothing, ty::JvpArg = nothing, act::BatchArg = nothing,
+                    status::BatchArg = nothing, ndir::Union{Nothing,Integer} = nothing)
+    dirs = (tq, tl, tu, tPx, tAx, tx, ty)
+    all_args = (dirs..., act, status)
+    given = filter(a -> a !== nothing, collect(all_args))
+    all(a -> a isa Ptr{Cdouble}, given) || all(a -> a isa Array{Float64}, given) ||
+        error("batch_jvp!: the arrays must all be host arrays or all device pointers")
+    host = filter(a -> a isa Array{Float64}, collect(dirs))
+    if !isempty(host)
+        counts = unique(map(a -> size(a, 3), host))
+        length(counts) == 1 && length(unique(map(ndims, host))) == 1 ||
+            error("batch_jvp!: the tangents and tx, ty must all have the same number of directions")
+        ndir === nothing || ndir == counts[1] || error("batch_jvp!: ndir does not match the arrays")
+        ndir = counts[1]
+    end
+    nd = ndir === nothing ? 1 : Int(ndir)
+    GC.@preserve tq tl tu tPx tAx tx ty act status begin
+        flag = ccall((:osqp_amd_batch_jvp, lib), Cc_int,
+                     (Ptr{Cvoid}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                      Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, nd, map(_batch_ptr, all_args)..., _batch_where(all_args...))
+    end
+    flag == 0 || error("Error in batched sensitivities: $(last_error())")
+    return nothing
+end
+
 "In-place all-gather of `count` doubles per rank on a device buffer, on the library's communicator."
 function comm_all_gather!(comm::Ptr{Cvoid}, buf::Ptr{Cdouble}, count::Integer)
     flag = ccall((:osqp_amd_comm_all_gather, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), comm, buf, count)

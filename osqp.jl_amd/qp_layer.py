@@ -1,18 +1,22 @@
 """A resident batch as a differentiable torch layer: `BatchQPFunction` solves `count` QPs in its forward
 (`ResidentBatch.update` + `solve`, device pointers, no host hop) and differentiates their solutions in its backward
-(`ResidentBatch.adjoint`: one launch of k_batch_adjoint).  torch is plumbing only: tensors are passed to the library by
-address and nothing is computed in torch.
+(`ResidentBatch.adjoint`: one launch of k_batch_adjoint); under forward-mode differentiation (`torch.autograd.forward_ad`,
+`torch.func.jvp`) its `jvp` pushes the tangents of the inputs forward to the solutions (`ResidentBatch.jvp`: one launch of
+k_batch_jvp).  torch is plumbing only: tensors are passed to the library by address and nothing is computed in torch.
 
     rb = batch.ResidentBatch(lib, P, A, Px, Ax, q, l, u, polish=True)
     layer = BatchQPLayer(rb)
     x, y = layer(q=q_t, l=l_t, u=u_t)          # float64 CUDA tensors [count x .]; None keeps the handle's data
     loss(x, y).backward()                       # q_t.grad, l_t.grad, u_t.grad
+    with forward_ad.dual_level():               # forward mode: the tangents of x, y along a tangent of q
+        x, y = layer(q=forward_ad.make_dual(q_t, tq_t))
+        tx = forward_ad.unpack_dual(x).tangent
 
 Three rules.  The library runs on its own stream and blocks, so torch's current stream is synchronised before every library
 call.  The handle holds ONE solution: every forward stamps the handle, and a backward whose stamp is no longer the handle's
-raises RuntimeError.  Instances whose adjoint status is not 1 (no solution, failed factorisation) get zero gradients; where
+raises RuntimeError (the forward-mode rule runs with its forward and needs no stamp).  Instances whose adjoint status is not 1 (no solution, failed factorisation) get zero gradients; where
 an instance's active constraints are dependent the derivative does not exist and the regularised answer is returned
-(include/osqp_amd.h, osqp_amd_batch_adjoint).  The layer works on the whole batch: the `rows=` forms of
+(include/osqp_amd.h, osqp_amd_batch_adjoint); the same holds for the tangents (osqp_amd_batch_jvp).  The layer works on the whole batch: the `rows=` forms of
 `ResidentBatch.update` / `solve` are not offered here."""
 import torch
 
@@ -43,7 +47,22 @@ class BatchQPFunction(torch.autograd.Function):
         rb._qp_layer_stamp = getattr(rb, "_qp_layer_stamp", 0) + 1
         rb._qp_layer_info = info
         ctx.rb, ctx.stamp = rb, rb._qp_layer_stamp
+        ctx.given = tuple(k for k, t in given.items() if t is not None)  # for jvp: the inputs that have a tangent
         return x, y
+
+    @staticmethod
+    def jvp(ctx, t_rb, tq, tl, tu, tPx, tAx):
+        """Forward mode: the tangents of (x, y) along the tangents of the tensor inputs (an input without a tangent arrives
+        as zeros, a None input as None)."""
+        rb = ctx.rb
+        cols = dict(q=rb.n, l=rb.m, u=rb.m, Px=rb.nnzP, Ax=rb.nnzA)
+        tang = {k: t.contiguous() for k, t in zip(NAMES, (tq, tl, tu, tPx, tAx)) if k in ctx.given and t is not None and cols[k] > 0}
+        ref = next(iter(tang.values()))
+        tx = torch.empty((rb.count, rb.n), dtype=torch.float64, device=ref.device)
+        ty = torch.empty((rb.count, rb.m), dtype=torch.float64, device=ref.device)
+        _sync(ref)
+        rb.jvp(**tang, out=dict(x=tx, y=ty) if rb.m else dict(x=tx))
+        return tx, ty
 
     @staticmethod
     def backward(ctx, gx, gy):

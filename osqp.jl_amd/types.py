@@ -226,6 +226,8 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_adjoint": (c_int, [C.c_void_p] + [C.c_void_p] * 9 + [c_int]),
     "osqp_amd_batch_polish_launches": (c_int, []),
     "osqp_amd_batch_adjoint_launches": (c_int, []),
+    "osqp_amd_batch_jvp": (c_int, [C.c_void_p, c_int] + [C.c_void_p] * 9 + [c_int]),
+    "osqp_amd_batch_jvp_launches": (c_int, []),
     "osqp_amd_batch_update_setting": (c_int, [C.c_void_p, C.c_char_p, c_float]),
     "osqp_amd_batch_certificates": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_cert_launches": (c_int, []),

@@ -18,7 +18,12 @@ the resolve of the first, the resolve + polish launch of the second, then on the
 and with dq, dl, du only (device inputs and outputs).  One JSON line: the median over the timed periods of each, the mean
 iterations of the two resolves, and the polish launch estimated as the second resolve minus the first scaled by their
 iteration counts (the two handles warm-start from different points, so their ADMM launches are not the same work).
-usage: python tools/batch_closed_loop.py [--polish | --adjoint] [count] [K] [W]"""
+--jvp: the cost of the forward sensitivities next to the adjoint of the same job.  One leg-D handle (polish = 0, device
+pointers); per period, each call timed on its own: the resolve, `adjoint` with all five gradients and with dq, dl, du only,
+then `jvp` with all five tangents and with tq, tl, tu only, each at ndir = 1 and ndir = 8 (device inputs and outputs; one
+launch per call: one factorisation per instance, one solve per direction).  One JSON line with the medians and minima over the
+timed periods, also written to profiles/batch_jvp.json (--out=PATH: elsewhere).
+usage: python tools/batch_closed_loop.py [--polish | --adjoint | --jvp [--out=PATH]] [count] [K] [W]"""
 import json
 import os
 import sys
@@ -35,7 +40,9 @@ import batch_resident_ref as ref  # noqa: E402
 
 POLISH = "--polish" in sys.argv[1:]
 ADJOINT = "--adjoint" in sys.argv[1:]
-argv = [a for a in sys.argv[1:] if a not in ("--polish", "--adjoint")]
+JVP = "--jvp" in sys.argv[1:]
+JVP_OUT = ([a[6:] for a in sys.argv[1:] if a.startswith("--out=")] or [os.path.join(ROOT, "profiles", "batch_jvp.json")])[-1]
+argv = [a for a in sys.argv[1:] if a not in ("--polish", "--adjoint", "--jvp") and not a.startswith("--out=")]
 count = int(argv[0]) if len(argv) > 0 else 4096
 K = int(argv[1]) if len(argv) > 1 else 10
 W = int(argv[2]) if len(argv) > 2 else 2
@@ -88,8 +95,72 @@ def adjoint_legs():
     h0.close(); h1.close()
 
 
+class Directions:
+    """A [ndir x count x cols] device array for `ResidentBatch.jvp`: a DeviceArray of ndir * count rows, passed by address."""
+
+    def __init__(self, ndir, rows, cols, host=None):
+        self.arr, self.shape = batch.DeviceArray(lib, ndir * rows, cols), (ndir, rows, cols)
+        if host is not None:
+            self.arr.upload(host.reshape(ndir * rows, cols))
+
+    def data_ptr(self):
+        return self.arr.data_ptr()
+
+
+def jvp_legs():
+    h = batch.ResidentBatch(lib, *args, **dict(OPTS, polish=False))
+    out = h.alloc()
+    h.solve(out=out)
+    rng = np.random.default_rng(0)
+    gx, gy = dev(rng.standard_normal((count, h.n))), dev(rng.standard_normal((count, h.m)))
+    cols = dict(q=h.n, l=h.m, u=h.m, Px=h.nnzP, Ax=h.nnzA, act=h.m, status=1)
+    outs = {k: batch.DeviceArray(lib, count, c) for k, c in cols.items()}
+    dirs = (1, 8)
+    tang = {nd: {k: Directions(nd, count, cols[k], rng.standard_normal((nd, count, cols[k]))) for k in ("q", "l", "u", "Px", "Ax")} for nd in dirs}
+    touts = {nd: dict(x=Directions(nd, count, h.n), y=Directions(nd, count, h.m), status=outs["status"]) for nd in dirs}
+    names = ["resolve", "adjoint_all", "adjoint_qlu"] + [f"jvp_{w}_ndir{nd}" for w in ("all", "qlu") for nd in dirs]
+    t = {k: [] for k in names}
+    its, differentiated = [], 0
+    for k in range(1, W + K + 1):
+        dq, dl, du = (dev(a) for a in steps[k])
+        h.update(q=dq, l=dl, u=du)
+        t0 = time.perf_counter()
+        h.solve(out=out)
+        t["resolve"].append(1e3 * (time.perf_counter() - t0))
+        its.append(float(np.sum(out[2].numpy()[:, 0])))
+        for name, want in (("adjoint_all", ("q", "l", "u", "Px", "Ax")), ("adjoint_qlu", ("q", "l", "u"))):
+            t0 = time.perf_counter()
+            h.adjoint(dx=gx, dy=gy, want=want, out=outs)
+            t[name].append(1e3 * (time.perf_counter() - t0))
+        for w, keys in (("all", ("q", "l", "u", "Px", "Ax")), ("qlu", ("q", "l", "u"))):
+            for nd in dirs:
+                t0 = time.perf_counter()
+                h.jvp(**{key: tang[nd][key] for key in keys}, out=touts[nd])
+                t[f"jvp_{w}_ndir{nd}"].append(1e3 * (time.perf_counter() - t0))
+        if k > W:
+            differentiated += int(np.sum(outs["status"].numpy() == 1))
+        for a in (dq, dl, du):
+            a.free()
+    res = dict(what="forward sensitivities of the closed loop next to its adjoint, device pointers, one call timed at a time",
+               instances=count, periods=K, warmup=W, kernel=int(lib.osqp_amd_batch_last_kernel()), iterations_resolve=float(np.mean(its[W:])),
+               differentiated_fraction=differentiated / (count * K))
+    for name in names:
+        res[f"ms_{name}_median"] = float(np.median(t[name][W:]))
+        res[f"ms_{name}_min"] = float(np.min(t[name][W:]))
+    res["ms_per_further_direction_all"] = (res["ms_jvp_all_ndir8_median"] - res["ms_jvp_all_ndir1_median"]) / 7
+    res["ms_per_further_direction_qlu"] = (res["ms_jvp_qlu_ndir8_median"] - res["ms_jvp_qlu_ndir1_median"]) / 7
+    line = json.dumps(res)
+    print(line)
+    with open(JVP_OUT, "w") as f:
+        f.write(line + "\n")
+    h.close()
+
+
 if ADJOINT:
     adjoint_legs()
+    sys.exit(0)
+if JVP:
+    jvp_legs()
     sys.exit(0)
 handles = {"B": batch.ResidentBatch(lib, *args, **dict(OPTS, warm_start=False)), "C": batch.ResidentBatch(lib, *args, **OPTS),
            "D": batch.ResidentBatch(lib, *args, **OPTS)}
