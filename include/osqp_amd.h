@@ -550,10 +550,21 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             in its ADMM launch, in k_batch_cert and (polish = 1) in k_batch_polish; x_out [k x n], y_out [k x m],
  *             info_out [k x 6].  A bad selection -- k < 1, k > count, an entry out of range, a repeated entry (the message
  *             names it) -- returns 1 with a message and leaves the handle unchanged.
- *             polish_status(), certificates(), adjoint() and jvp() stay whole-batch calls: their row i is of instance i's OWN last
- *             resolve, whole or selected (polish status 0 when polish was off at that resolve).  adjoint() and jvp() need every
- *             instance current: a *_rows update or warm start makes its rows stale, resolve_rows makes them current, and
- *             the refusal names the first stale instance.
+ *             Row i of the whole-batch polish_status(), certificates(), adjoint() and jvp() is of instance i's OWN last
+ *             resolve, whole or selected (polish status 0 when polish was off at that resolve).  The whole-batch adjoint() and
+ *             jvp() need every instance current: a *_rows update or warm start makes its rows stale, resolve_rows makes them
+ *             current, and the refusal names the first stale instance.
+ *   adjoint_rows() / jvp_rows() / polish_status_rows() / certificates_rows(): the four reading calls for a SELECTION, with
+ *             rows and k as above.  Every array of the call is compact: dx, dy and the gradients [k x .], the tangents and
+ *             tx_out / ty_out [ndir x k x cols] (direction d is a contiguous [k x cols] block), act_out [k x m], status_out
+ *             [k], the certificates [k x m] / [k x n]; row j is of instance rows[j] and has the bits of row rows[j] of the
+ *             whole-batch call.  adjoint_rows and jvp_rows launch k workgroups and need only the SELECTED instances
+ *             current: the refusal names the first stale one in the order of rows, and nothing is launched.  Every other
+ *             rule is the whole-batch call's (NULL arguments, m = 0, status values, the LDS limit; polish_status_rows gives
+ *             zeros before the first resolve and after a whole resolve without polish; certificates_rows ignores the
+ *             first pointer with m = 0 and returns 1 when no certificate was asked for).  A bad selection returns 1
+ *             before anything else is looked at.  The calls only read the handle: a resolve after them is bit-identical
+ *             to one without them.
  * where: 0 = the array arguments are host pointers, 1 = device pointers on the handle's device (no host hop: a controller
  * whose state estimate lives in HBM).  A NULL array means "keep" (update_*) / "none" (warm_start).  Every call blocks until
  * done.  Single rank.  The handle is freed by osqp_amd_batch_destroy; it is not interchangeable with the handle of
@@ -578,22 +589,37 @@ c_int osqp_amd_batch_warm_start_rows(osqp_amd_batch *batch, const c_int *rows, c
 c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *x_out, c_float *y_out,
                                   c_float *info_out, c_int where);
 c_int osqp_amd_batch_polish_status(osqp_amd_batch *batch, c_float *status_out, c_int where);
+/* status_polish of the k selected instances: status_out [k] doubles, entry j of instance rows[j]. */
+c_int osqp_amd_batch_polish_status_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *status_out /* [k] */, c_int where);
 c_int osqp_amd_batch_update_polish(osqp_amd_batch *batch, c_int polish_new, c_int polish_refine_iter_new);
 c_int osqp_amd_batch_update_setting(osqp_amd_batch *batch, const char *name, c_float value);
 c_int osqp_amd_batch_certificates(osqp_amd_batch *batch, c_float *prim_inf_cert_out /* [count x m] */,
                                   c_float *dual_inf_cert_out /* [count x n] */, c_int where);
+/* The certificate rows of the k selected instances, gathered on the device: row j is row rows[j] of the whole call. */
+c_int osqp_amd_batch_certificates_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *prim_inf_cert_out /* [k x m] */,
+                                       c_float *dual_inf_cert_out /* [k x n] */, c_int where);
 c_int osqp_amd_batch_adjoint(osqp_amd_batch *batch, const c_float *dx, const c_float *dy,
                              c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
                              c_float *act_out, c_float *status_out, c_int where);
+/* adjoint() of the k selected instances in a launch of k workgroups; all arrays [k x .]; only they must be current. */
+c_int osqp_amd_batch_adjoint_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, const c_float *dx, const c_float *dy,
+                                  c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
+                                  c_float *act_out, c_float *status_out, c_int where);
 c_int osqp_amd_batch_jvp(osqp_amd_batch *batch, c_int ndir,
                          const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx, const c_float *tAx,
                          c_float *tx_out, c_float *ty_out, c_float *act_out, c_float *status_out, c_int where);
+/* jvp() of the k selected instances in a launch of k workgroups; direction-major arrays [ndir x k x cols]; only they must
+ * be current. */
+c_int osqp_amd_batch_jvp_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_int ndir,
+                              const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx, const c_float *tAx,
+                              c_float *tx_out, c_float *ty_out, c_float *act_out, c_float *status_out, c_int where);
 /* Diagnostic, like osqp_amd_batch_last_kernel: how many polish launches this process has made so far.  A resolve with
  * polish = 0 makes none -- its launch sequence is the one of a library without the polish kernel. */
 c_int osqp_amd_batch_polish_launches(void);
-/* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint that passed its checks, none otherwise. */
+/* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint / _adjoint_rows that passed its checks, none otherwise. */
 c_int osqp_amd_batch_adjoint_launches(void);
-/* The same for the sensitivity kernel: one launch per osqp_amd_batch_jvp that passed its checks, whatever ndir, none otherwise. */
+/* The same for the sensitivity kernel: one launch per osqp_amd_batch_jvp / _jvp_rows that passed its checks, whatever ndir, none
+ * otherwise. */
 c_int osqp_amd_batch_jvp_launches(void);
 /* The same for the certificate kernel: one launch per osqp_amd_batch_resolve / _resolve_rows, none by osqp_amd_batch_certificates or by the
  * one-shot entries. */

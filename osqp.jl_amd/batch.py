@@ -267,7 +267,7 @@ class ResidentBatch:
     `warm_start=False` in the settings: from zero).  P (upper triangle) and A are scipy matrices giving the pattern; the
     *_all arrays are [count x .] as for `solve_batch`.  Array arguments of `update` / `warm_start` and the `out` of `solve`
     may be numpy arrays (host form) or device arrays (`DeviceArray`, torch tensors: no host hop).
-    `update`, `warm_start` and `solve` take `rows=`: a selection of the instances (`selection` above: integers in any order,
+    `update`, `warm_start`, `solve`, `adjoint`, `jvp`, `certificates` and `polish_status` take `rows=`: a selection of the instances (`selection` above: integers in any order,
     or a boolean mask; always host data).  Their arrays are then compact, [k x .], row j for instance rows[j]; a selected
     instance gets the bits of the whole-batch call, every other instance is left exactly as it was -- data, record,
     certificates, polish status (include/osqp_amd.h, "*_rows")."""
@@ -388,18 +388,27 @@ class ResidentBatch:
         self._call("solve", resolve(ptrs[0], ptrs[1], ptrs[2], 1))
         return out
 
-    def polish_status(self, out=None):
+    def polish_status(self, out=None, rows=None):
         """status_polish of every instance from its own last `solve()` (whole or `rows=`): 1 accepted, -1 refused, 0 not polished (the instance was
         not Solved, or `polish` is off).  out=None: a numpy int array [count]; out = a device array [count x 1] of float64:
-        filled in place and returned."""
+        filled in place and returned.  rows: a selection (`selection`); the result is [k] ([k x 1]), entry j for instance
+        rows[j], gathered on the device."""
+        sel = None if rows is None else selection(rows, self.count)
+        k = self.count if sel is None else len(sel)
+
+        def status(ptr, where):
+            if sel is None:
+                return self.lib.osqp_amd_batch_polish_status(self.handle, ptr, where)
+            return self.lib.osqp_amd_batch_polish_status_rows(self.handle, _iptr(sel), k, ptr, where)
+
         if out is None:
-            st = np.empty(self.count)
-            self._call("polish status", self.lib.osqp_amd_batch_polish_status(self.handle, st.ctypes.data, 0))
+            st = np.empty(k)
+            self._call("polish status", status(st.ctypes.data, 0))
             return st.astype(np.int64)
         if not hasattr(out, "data_ptr"):
             raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
-        ptr = _batch_array("out", out, (self.count, 1))[1]
-        self._call("polish status", self.lib.osqp_amd_batch_polish_status(self.handle, ptr, 1))
+        ptr = _batch_array("out", out, (k, 1))[1]
+        self._call("polish status", status(ptr, 1))
         return out
 
     def update_polish(self, polish, polish_refine_iter=None):
@@ -436,30 +445,39 @@ class ResidentBatch:
             if key == "polish_refine_iter":
                 self.polish_refine_iter = int(value)
 
-    def certificates(self, out=None):
+    def certificates(self, out=None, rows=None):
         """(prim_inf_cert [count x m], dual_inf_cert [count x n]) of every instance's own last `solve()` (whole or `rows=`): row i of the first is the direction
         that proves instance i primal infeasible (status -3 or 3), of the second dual infeasible (-4 or 4), each with
         largest entry +-1 as a single model's results carry them; every other row is NaN, and all rows before the first
         solve.  out=None: numpy arrays; out=(p, d) of device arrays, either may be None: filled in place and returned.
-        With m = 0 the first element is None."""
+        With m = 0 the first element is None.  rows: a selection (`selection`); the arrays are [k x .], row j for instance
+        rows[j], gathered on the device."""
+        sel = None if rows is None else selection(rows, self.count)
+        k = self.count if sel is None else len(sel)
+
+        def certs(pp, dp, where):
+            if sel is None:
+                return self.lib.osqp_amd_batch_certificates(self.handle, pp, dp, where)
+            return self.lib.osqp_amd_batch_certificates_rows(self.handle, _iptr(sel), k, pp, dp, where)
+
         if out is None:
-            p = np.empty((self.count, self.m)) if self.m else None
-            d = np.empty((self.count, self.n))
-            self._call("certificates", self.lib.osqp_amd_batch_certificates(self.handle, None if p is None else p.ctypes.data, d.ctypes.data, 0))
+            p = np.empty((k, self.m)) if self.m else None
+            d = np.empty((k, self.n))
+            self._call("certificates", certs(None if p is None else p.ctypes.data, d.ctypes.data, 0))
             return p, d
         if len(out) != 2:
             raise ValueError("out: expected (prim_inf_cert, dual_inf_cert)")
         ptrs = []
-        for name, a, k in (("out[0]", out[0], self.m), ("out[1]", out[1], self.n)):
+        for name, a, cols in (("out[0]", out[0], self.m), ("out[1]", out[1], self.n)):
             if a is None:
                 ptrs.append(None)
                 continue
             if not hasattr(a, "data_ptr"):
                 raise ValueError(f"{name}: expected a device array (DeviceArray, torch tensor); omit `out` for numpy results")
-            ptrs.append(_batch_array(name, a, (self.count, k))[1])
+            ptrs.append(_batch_array(name, a, (k, cols))[1])
         if ptrs[1] is None and (ptrs[0] is None or self.m == 0):
             raise ValueError("out: no certificate was asked for")
-        self._call("certificates", self.lib.osqp_amd_batch_certificates(self.handle, ptrs[0], ptrs[1], 1))
+        self._call("certificates", certs(ptrs[0], ptrs[1], 1))
         return (None if self.m == 0 else out[0]), out[1]
 
     ADJOINT_WANT = ("q", "l", "u", "Px", "Ax")
@@ -467,7 +485,7 @@ class ResidentBatch:
     def _adjoint_cols(self):
         return dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA, act=self.m, status=1)
 
-    def adjoint(self, dx=None, dy=None, want=ADJOINT_WANT, out=None):
+    def adjoint(self, dx=None, dy=None, want=ADJOINT_WANT, out=None, rows=None):
         """Gradients of a scalar loss with respect to the data, through the solutions of the last `solve()`
         (osqp_amd_batch_adjoint): dx [count x n], dy [count x m] are the loss's gradients with respect to x and y (None: zero;
         not both).  Returns a dict with the entries of `want` -- "q" [count x n], "l", "u" [count x m], "Px" [count x nnz(P
@@ -478,7 +496,12 @@ class ResidentBatch:
         "act" and "status" ([count x 1]); they are filled in place and `out` is returned.  The handle must hold the solution
         of its current data, for EVERY instance: a `solve()` that served it since its last `update` / `warm_start` (`rows=` calls
         count per instance; the refusal names the first stale one).  Where the active constraints of an instance
-        are dependent the derivative does not exist and the regularised answer is returned (see include/osqp_amd.h)."""
+        are dependent the derivative does not exist and the regularised answer is returned (see include/osqp_amd.h).
+        rows: a selection (`selection`): a launch of k workgroups; dx, dy and every result are [k x .], row j for instance
+        rows[j] with the bits of row rows[j] of the whole call, and only the SELECTED instances must hold a current solution
+        (the refusal names the first stale one in the order of `rows`)."""
+        sel = None if rows is None else selection(rows, self.count)
+        cnt = self.count if sel is None else len(sel)
         cols = self._adjoint_cols()
         want = tuple(want)
         for w in want:
@@ -486,12 +509,12 @@ class ResidentBatch:
                 raise ValueError(f"want: unknown gradient {w!r}; expected a subset of {self.ADJOINT_WANT}")
         if dx is None and dy is None:
             raise ValueError("dx and dy: at least one incoming gradient is needed")
-        keep, ptrs, where = self._pair(("dx", "dy"), (dx, dy), (self.n, self.m))
+        keep, ptrs, where = self._pair(("dx", "dy"), (dx, dy), (self.n, self.m), cnt)
         names = [k for k in self.ADJOINT_WANT + ("act", "status") if cols[k] > 0]
         if not where:
             if out is not None:
                 raise ValueError("out: host gradients (numpy dx / dy) return numpy arrays; pass device arrays for dx / dy to fill `out`")
-            res = {k: np.empty((self.count, cols[k])) for k in names if k in want or k in ("act", "status")}
+            res = {k: np.empty((cnt, cols[k])) for k in names if k in want or k in ("act", "status")}
             addr = {k: v.ctypes.data for k, v in res.items()}
         else:
             if not isinstance(out, dict):
@@ -504,12 +527,15 @@ class ResidentBatch:
                 if k in out and (k in want or k in ("act", "status")):
                     if not hasattr(out[k], "data_ptr"):
                         raise ValueError(f"out[{k!r}]: expected a device array (DeviceArray, torch tensor)")
-                    addr[k] = _batch_array(f"out[{k!r}]", out[k], (self.count, cols[k]))[1]
+                    addr[k] = _batch_array(f"out[{k!r}]", out[k], (cnt, cols[k]))[1]
                 elif k in want:
                     raise ValueError(f"out: no array for the wanted gradient {k!r}")
             res = out
-        self._call("adjoint", self.lib.osqp_amd_batch_adjoint(self.handle, ptrs[0], ptrs[1], *[addr.get(k) for k in self.ADJOINT_WANT],
-                                                              addr.get("act"), addr.get("status"), where))
+        tail = [ptrs[0], ptrs[1]] + [addr.get(k) for k in self.ADJOINT_WANT] + [addr.get("act"), addr.get("status"), where]
+        if sel is None:
+            self._call("adjoint", self.lib.osqp_amd_batch_adjoint(self.handle, *tail))
+        else:
+            self._call("adjoint", self.lib.osqp_amd_batch_adjoint_rows(self.handle, _iptr(sel), cnt, *tail))
         if not where:
             if "act" in res:
                 res["act"] = res["act"].astype(np.int64)
@@ -518,7 +544,7 @@ class ResidentBatch:
 
     JVP_TANGENTS = ("q", "l", "u", "Px", "Ax")
 
-    def jvp(self, q=None, l=None, u=None, Px=None, Ax=None, out=None):
+    def jvp(self, q=None, l=None, u=None, Px=None, Ax=None, out=None, rows=None):
         """Forward sensitivities of the solutions of the last `solve()` along directions of the data (osqp_amd_batch_jvp): the
         tangents q [count x n], l, u [count x m], Px [count x nnz(P upper)], Ax [count x nnz(A)] (None: zero; not all), or
         each with a leading axis [ndir x count x .] for several directions at once -- one launch, one factorisation per
@@ -530,7 +556,11 @@ class ResidentBatch:
         effect.  Host form: numpy tangents, out=None, numpy results ("act" and "status" [count] as integers).  Device form:
         device arrays and `out` a dict of float64 device arrays -- "x" and (m > 0) "y", optionally "act" [count x m] and
         "status" [count x 1] -- filled in place and returned.  The handle must hold the solution of its current data for
-        EVERY instance, as for `adjoint`."""
+        EVERY instance, as for `adjoint`.  rows: a selection (`selection`): a launch of k workgroups; the tangents and the
+        results are [k x .] / [ndir x k x .], "act" [k x m], "status" [k], row j for instance rows[j] with the bits of row rows[j]
+        of the whole call, and only the SELECTED instances must hold a current solution."""
+        sel = None if rows is None else selection(rows, self.count)
+        cnt = self.count if sel is None else len(sel)
         cols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA)
         given = {k: v for k, v in zip(self.JVP_TANGENTS, (q, l, u, Px, Ax)) if v is not None}
         if not given:
@@ -543,14 +573,14 @@ class ResidentBatch:
         ndir = int((first.shape if hasattr(first, "data_ptr") else np.asarray(first).shape)[0]) if many else 1
         if ndir < 1:
             raise ValueError("tangents: ndir must be at least 1")
-        lead = (ndir, self.count) if many else (self.count,)
+        lead = (ndir, cnt) if many else (cnt,)
         got = {k: _batch_array(k, v, lead + (cols[k],)) for k, v in given.items()}
         forms = {g[2] for g in got.values()}
         if len(forms) > 1:
             raise ValueError("tangents: they must all be host arrays or all device arrays")
         where = forms.pop()
         ocols = dict(x=self.n, y=self.m, act=self.m, status=1)
-        oshape = dict(x=lead + (self.n,), y=lead + (self.m,), act=(self.count, self.m), status=(self.count, 1))
+        oshape = dict(x=lead + (self.n,), y=lead + (self.m,), act=(cnt, self.m), status=(cnt, 1))
         names = [k for k in ("x", "y", "act", "status") if ocols[k] > 0]
         if not where:
             if out is not None:
@@ -572,8 +602,12 @@ class ResidentBatch:
                 elif k in ("x", "y"):
                     raise ValueError(f"out: no array for {k!r}")
             res = out
-        self._call("jvp", self.lib.osqp_amd_batch_jvp(self.handle, ndir, *[got[k][1] if k in got else None for k in self.JVP_TANGENTS],
-                                                      addr.get("x"), addr.get("y"), addr.get("act"), addr.get("status"), where))
+        tail = [ndir] + [got[k][1] if k in got else None for k in self.JVP_TANGENTS]
+        tail += [addr.get("x"), addr.get("y"), addr.get("act"), addr.get("status"), where]
+        if sel is None:
+            self._call("jvp", self.lib.osqp_amd_batch_jvp(self.handle, *tail))
+        else:
+            self._call("jvp", self.lib.osqp_amd_batch_jvp_rows(self.handle, _iptr(sel), cnt, *tail))
         if not where:
             if "act" in res:
                 res["act"] = res["act"].astype(np.int64)

@@ -19,7 +19,7 @@
 //                     launch of its own on request (osqp_amd_batch_jvp): one factorisation per instance, one solve per direction;
 //   batch_cert.hpp    k_batch_cert -- the infeasibility certificates of the resident batch, a launch of its own after every
 //                     ADMM launch of osqp_amd_batch_resolve: normalises the directions that launch left in the records (RES_CERT);
-//   this file         the small kernels (warm start, rho fill, bound check, the row scatter of a selection, MPC generator), the
+//   this file         the small kernels (warm start, rho fill, bound check, the row scatter and gather of a selection, MPC generator), the
 //                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
 // Both kernels also run in RESIDENT mode (osqp_amd_batch_setup ... _resolve, "the state record" in batch_common.hpp):
@@ -100,6 +100,16 @@ __global__ __launch_bounds__(256) void k_batch_scatter_rows(const int *__restric
   if (pos >= k) return;
   const double *from = src + (size_t)pos * cols;
   double *to = dst + (size_t)sel[pos] * cols;
+  for (int c = threadIdx.x; c < cols; c += 256) to[c] = from[c];
+}
+// the other way: row sel[p] of src [count x cols] into row p of dst [k x cols] -- the polish status and the certificates of a
+// selection (osqp_amd_batch_polish_status_rows, _certificates_rows).  One workgroup per selected row.
+__global__ __launch_bounds__(256) void k_batch_gather_rows(const int *__restrict__ sel, int k, int cols, const double *__restrict__ src,
+                                                           double *__restrict__ dst) {
+  const int pos = blockIdx.x;
+  if (pos >= k) return;
+  const double *from = src + (size_t)sel[pos] * cols;
+  double *to = dst + (size_t)pos * cols;
   for (int c = threadIdx.x; c < cols; c += 256) to[c] = from[c];
 }
 // dst[sel[p]] = value (the polish status of instances re-solved without polish)
@@ -415,6 +425,24 @@ bool select_rows(BatchPlan &b, const c_int *rows, c_int k, hipStream_t s) {
 void scatter_rows(const BatchPlan &b, int k, int cols, const double *src, double *dst, hipStream_t s) {
   if (cols) OQ_LAUNCH(k_batch_scatter_rows, dim3(k), dim3(256), 0, s, b.sel.get(), k, cols, src, dst);
 }
+void gather_rows(const BatchPlan &b, int k, int cols, const double *src, double *dst, hipStream_t s) {
+  if (cols) OQ_LAUNCH(k_batch_gather_rows, dim3(k), dim3(256), 0, s, b.sel.get(), k, cols, src, dst);
+}
+// The rule of the derivative calls: every instance they serve holds the solution of its current data.  rows nullptr: all of
+// the batch (osqp_amd_batch_adjoint, _jvp); otherwise the selection (the *_rows forms), in its order.  false with the message
+// set, naming the first instance that does not.
+bool holds_current(const BatchPlan &b, const std::vector<int> *rows) {
+  const size_t len = rows ? rows->size() : b.current.size();
+  for (size_t j = 0; j < len; j++) {
+    const size_t i = rows ? (size_t)(*rows)[j] : j;
+    if (!b.current[i]) {
+      set_last_error("instance " + std::to_string(i) + " of the batch holds no current solution: call osqp_amd_batch_resolve (or _resolve_rows "
+                     "with this instance) after its last update or warm start");
+      return false;
+    }
+  }
+  return true;
+}
 // the LDS a polish launch of this pattern needs; a pattern it cannot serve is refused where polish is asked for (setup,
 // osqp_amd_batch_update_polish), never skipped
 void polish_check_fits(const Pattern &P) {
@@ -457,6 +485,115 @@ void set_polish(BatchPlan &b, c_int polish_new, c_int refine_new) {
 #define OQ_BATCH_CATCH                                                                          \
   catch (const Error &er) { set_last_error(er.what()); return er.code ? er.code : 6; }         \
   catch (const std::exception &ex) { set_last_error(ex.what()); return 6; }
+
+// osqp_amd_batch_adjoint (subset false: every instance, rows / k unused) and osqp_amd_batch_adjoint_rows (subset true: the
+// k instances of rows; every array of the call is compact, row j for instance rows[j]).  One launch of `cnt` workgroups.
+c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, const c_float *dx, const c_float *dy, c_float *dq,
+                    c_float *dl, c_float *du, c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
+  if (!subset && !holds_current(*b, nullptr)) return 1;
+  try {
+    const Pattern &P = b->dp.P;
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (subset) {  // only the selected instances must be current; nothing is launched when one is not
+      if (!select_rows(*b, rows, k, s)) return 1;
+      if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
+    }
+    polish_check_fits(P);
+    const int launch = subset ? (int)k : b->count;
+    const size_t cnt = (size_t)launch, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    if (!lm) { dy = nullptr; dl = du = act_out = nullptr; }
+    if (!la) dAx = nullptr;
+    if (!lp) dPx = nullptr;
+    // host pointers: the wanted outputs share one staging buffer, in this order
+    c_float *const host[7] = {dq, dl, du, dPx, dAx, act_out, status_out};
+    const size_t len[7] = {ln, lm, lm, lp, la, lm, cnt};
+    double *dev[7];
+    size_t total = 0;
+    for (int j = 0; j < 7; j++) if (host[j]) total += len[j];
+    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
+    size_t at = 0;
+    for (int j = 0; j < 7; j++) {
+      dev[j] = !host[j] ? nullptr : (where ? host[j] : b->adj_out.get() + at);
+      if (host[j] && !where) at += len[j];
+    }
+    polish::AdjointArgs a;
+    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
+    a.gx = dx ? device_ptr(dx, ln, where, b->in_a, s) : nullptr;
+    a.gy = dy ? device_ptr(dy, lm, where, b->in_b, s) : nullptr;
+    a.dq = dev[0]; a.dl = dev[1]; a.du = dev[2]; a.dPx = dev[3]; a.dAx = dev[4]; a.act = dev[5]; a.status = dev[6];
+    a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
+    a.sel = subset ? b->sel.get() : nullptr;
+    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
+    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+    g_batch_adjoint_launches++;
+    OQ_LAUNCH(polish::k_batch_adjoint, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
+    if (!where)
+      for (int j = 0; j < 7; j++) if (host[j]) HIP_CHECK(hipMemcpyAsync(host[j], dev[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+// osqp_amd_batch_jvp and osqp_amd_batch_jvp_rows, as batch_adjoint above; the direction-major arrays are [ndir x cnt x cols]
+c_int batch_jvp(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, c_int ndir, const c_float *tq, const c_float *tl,
+                const c_float *tu, const c_float *tPx, const c_float *tAx, c_float *tx_out, c_float *ty_out, c_float *act_out,
+                c_float *status_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (ndir < 1) { set_last_error("invalid batch data: the sensitivities need ndir >= 1"); return 1; }
+  if (!tq && !tl && !tu && !tPx && !tAx) { set_last_error("invalid batch data: the sensitivities need a tangent"); return 1; }
+  if (!tx_out && !ty_out) { set_last_error("invalid batch data: the sensitivities need tx_out or ty_out"); return 1; }
+  if (!subset && !holds_current(*b, nullptr)) return 1;
+  try {
+    const Pattern &P = b->dp.P;
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (subset) {
+      if (!select_rows(*b, rows, k, s)) return 1;
+      if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
+    }
+    polish_check_fits(P);
+    const int launch = subset ? (int)k : b->count;
+    const size_t cnt = (size_t)launch, nd = (size_t)ndir, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    if (!lm) { tl = tu = nullptr; ty_out = act_out = nullptr; }
+    if (!la) tAx = nullptr;
+    if (!lp) tPx = nullptr;
+    // host pointers: the wanted outputs share one staging buffer, in this order
+    c_float *const host[4] = {tx_out, ty_out, act_out, status_out};
+    const size_t len[4] = {nd * ln, nd * lm, lm, cnt};
+    double *dev[4];
+    size_t total = 0;
+    for (int j = 0; j < 4; j++) if (host[j]) total += len[j];
+    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
+    size_t at = 0;
+    for (int j = 0; j < 4; j++) {
+      dev[j] = !host[j] ? nullptr : (where ? host[j] : b->adj_out.get() + at);
+      if (host[j] && !where) at += len[j];
+    }
+    polish::JvpArgs a;
+    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
+    a.tq = tq ? device_ptr(tq, nd * ln, where, b->in_a, s) : nullptr;
+    a.tl = tl ? device_ptr(tl, nd * lm, where, b->in_b, s) : nullptr;
+    a.tu = tu ? device_ptr(tu, nd * lm, where, b->in_c, s) : nullptr;
+    a.tPx = tPx ? device_ptr(tPx, nd * lp, where, b->in_d, s) : nullptr;
+    a.tAx = tAx ? device_ptr(tAx, nd * la, where, b->in_e, s) : nullptr;
+    a.tx = dev[0]; a.ty = dev[1]; a.act = dev[2]; a.status = dev[3];
+    a.ndir = (int)ndir; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
+    a.sel = subset ? b->sel.get() : nullptr;
+    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
+    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_jvp, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+    g_batch_jvp_launches++;
+    OQ_LAUNCH(polish::k_batch_jvp, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
+    if (!where)
+      for (int j = 0; j < 4; j++) if (host[j]) HIP_CHECK(hipMemcpyAsync(host[j], dev[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
 
 }  // namespace
 }  // namespace oq
@@ -841,105 +978,21 @@ c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *handle, const c_int *rows, c_i
 
 c_int osqp_amd_batch_adjoint(osqp_amd_batch *handle, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
                              c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
-  for (size_t i = 0; i < b->current.size(); i++)
-    if (!b->current[i]) {
-      set_last_error("instance " + std::to_string(i) + " of the batch holds no current solution: call osqp_amd_batch_resolve (or _resolve_rows "
-                     "with this instance) after its last update or warm start");
-      return 1;
-    }
-  try {
-    const Pattern &P = b->dp.P;
-    polish_check_fits(P);
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    const size_t cnt = (size_t)b->count, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
-    if (!lm) { dy = nullptr; dl = du = act_out = nullptr; }
-    if (!la) dAx = nullptr;
-    if (!lp) dPx = nullptr;
-    // host pointers: the wanted outputs share one staging buffer, in this order
-    c_float *const host[7] = {dq, dl, du, dPx, dAx, act_out, status_out};
-    const size_t len[7] = {ln, lm, lm, lp, la, lm, cnt};
-    double *dev[7];
-    size_t total = 0;
-    for (int k = 0; k < 7; k++) if (host[k]) total += len[k];
-    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
-    size_t at = 0;
-    for (int k = 0; k < 7; k++) {
-      dev[k] = !host[k] ? nullptr : (where ? host[k] : b->adj_out.get() + at);
-      if (host[k] && !where) at += len[k];
-    }
-    polish::AdjointArgs a;
-    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
-    a.gx = dx ? device_ptr(dx, ln, where, b->in_a, s) : nullptr;
-    a.gy = dy ? device_ptr(dy, lm, where, b->in_b, s) : nullptr;
-    a.dq = dev[0]; a.dl = dev[1]; a.du = dev[2]; a.dPx = dev[3]; a.dAx = dev[4]; a.act = dev[5]; a.status = dev[6];
-    a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
-    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
-    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    g_batch_adjoint_launches++;
-    OQ_LAUNCH(polish::k_batch_adjoint, dim3(b->count), dim3(polish::PT), (size_t)L.total, s, P, b->count, L, a);
-    if (!where)
-      for (int k = 0; k < 7; k++) if (host[k]) HIP_CHECK(hipMemcpyAsync(host[k], dev[k], len[k] * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-  } OQ_BATCH_CATCH
+  return batch_adjoint(handle, false, nullptr, 0, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
+}
+c_int osqp_amd_batch_adjoint_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *dx, const c_float *dy, c_float *dq,
+                                  c_float *dl, c_float *du, c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
+  return batch_adjoint(handle, true, rows, k, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
 }
 
 c_int osqp_amd_batch_jvp(osqp_amd_batch *handle, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,
                          const c_float *tAx, c_float *tx_out, c_float *ty_out, c_float *act_out, c_float *status_out, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (ndir < 1) { set_last_error("invalid batch data: the sensitivities need ndir >= 1"); return 1; }
-  if (!tq && !tl && !tu && !tPx && !tAx) { set_last_error("invalid batch data: the sensitivities need a tangent"); return 1; }
-  if (!tx_out && !ty_out) { set_last_error("invalid batch data: the sensitivities need tx_out or ty_out"); return 1; }
-  for (size_t i = 0; i < b->current.size(); i++)
-    if (!b->current[i]) {
-      set_last_error("instance " + std::to_string(i) + " of the batch holds no current solution: call osqp_amd_batch_resolve (or _resolve_rows "
-                     "with this instance) after its last update or warm start");
-      return 1;
-    }
-  try {
-    const Pattern &P = b->dp.P;
-    polish_check_fits(P);
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    const size_t cnt = (size_t)b->count, nd = (size_t)ndir, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
-    if (!lm) { tl = tu = nullptr; ty_out = act_out = nullptr; }
-    if (!la) tAx = nullptr;
-    if (!lp) tPx = nullptr;
-    // host pointers: the wanted outputs share one staging buffer, in this order
-    c_float *const host[4] = {tx_out, ty_out, act_out, status_out};
-    const size_t len[4] = {nd * ln, nd * lm, lm, cnt};
-    double *dev[4];
-    size_t total = 0;
-    for (int k = 0; k < 4; k++) if (host[k]) total += len[k];
-    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
-    size_t at = 0;
-    for (int k = 0; k < 4; k++) {
-      dev[k] = !host[k] ? nullptr : (where ? host[k] : b->adj_out.get() + at);
-      if (host[k] && !where) at += len[k];
-    }
-    polish::JvpArgs a;
-    a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
-    a.tq = tq ? device_ptr(tq, nd * ln, where, b->in_a, s) : nullptr;
-    a.tl = tl ? device_ptr(tl, nd * lm, where, b->in_b, s) : nullptr;
-    a.tu = tu ? device_ptr(tu, nd * lm, where, b->in_c, s) : nullptr;
-    a.tPx = tPx ? device_ptr(tPx, nd * lp, where, b->in_d, s) : nullptr;
-    a.tAx = tAx ? device_ptr(tAx, nd * la, where, b->in_e, s) : nullptr;
-    a.tx = dev[0]; a.ty = dev[1]; a.act = dev[2]; a.status = dev[3];
-    a.ndir = (int)ndir; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
-    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
-    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_jvp, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    g_batch_jvp_launches++;
-    OQ_LAUNCH(polish::k_batch_jvp, dim3(b->count), dim3(polish::PT), (size_t)L.total, s, P, b->count, L, a);
-    if (!where)
-      for (int k = 0; k < 4; k++) if (host[k]) HIP_CHECK(hipMemcpyAsync(host[k], dev[k], len[k] * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-  } OQ_BATCH_CATCH
+  return batch_jvp(handle, false, nullptr, 0, ndir, tq, tl, tu, tPx, tAx, tx_out, ty_out, act_out, status_out, where);
+}
+c_int osqp_amd_batch_jvp_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_int ndir, const c_float *tq, const c_float *tl,
+                              const c_float *tu, const c_float *tPx, const c_float *tAx, c_float *tx_out, c_float *ty_out, c_float *act_out,
+                              c_float *status_out, c_int where) {
+  return batch_jvp(handle, true, rows, k, ndir, tq, tl, tu, tPx, tAx, tx_out, ty_out, act_out, status_out, where);
 }
 
 c_int osqp_amd_batch_polish_status(osqp_amd_batch *handle, c_float *status_out, c_int where) {
@@ -955,6 +1008,29 @@ c_int osqp_amd_batch_polish_status(osqp_amd_batch *handle, c_float *status_out, 
       else std::fill(status_out, status_out + len, 0.0);
     } else if (where) copy_d2d(status_out, b->pstat.get(), len, s);
     else b->pstat.download(status_out, len, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_polish_status_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *status_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!status_out) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (!select_rows(*b, rows, k, s)) return 1;
+    const size_t len = (size_t)k;
+    if (!b->pstat_live) {  // as osqp_amd_batch_polish_status: all 0
+      if (where) HIP_CHECK(hipMemsetAsync(status_out, 0, len * sizeof(double), s));
+      else std::fill(status_out, status_out + len, 0.0);
+    } else if (where) gather_rows(*b, (int)k, 1, b->pstat.get(), status_out, s);
+    else {  // host pointer: gathered into the staging of the derivative calls, then down
+      if (b->adj_out.n < len) b->adj_out.alloc(len);
+      gather_rows(*b, (int)k, 1, b->pstat.get(), b->adj_out.get(), s);
+      b->adj_out.download(status_out, len, s);
+    }
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
@@ -1016,6 +1092,36 @@ c_int osqp_amd_batch_certificates(osqp_amd_batch *handle, c_float *prim_inf_cert
     for (int k = 0; k < 2; k++) {
       if (!out[k]) continue;
       if (where) copy_d2d(out[k], src[k]->get(), len[k], s); else src[k]->download(out[k], len[k], s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_batch_certificates_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *prim_inf_cert_out,
+                                       c_float *dual_inf_cert_out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (b->m == 0) prim_inf_cert_out = nullptr;
+  if (!prim_inf_cert_out && !dual_inf_cert_out) { set_last_error("invalid batch data: no certificate was asked for"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (!select_rows(*b, rows, k, s)) return 1;
+    c_float *const out[2] = {prim_inf_cert_out, dual_inf_cert_out};
+    const double *const src[2] = {b->pcert.get(), b->dcert.get()};
+    const int cols[2] = {b->m, b->n};
+    // host pointers: the two share the staging of the derivative calls, in this order
+    size_t total = 0;
+    for (int j = 0; j < 2; j++) if (out[j]) total += (size_t)k * cols[j];
+    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
+    size_t at = 0;
+    for (int j = 0; j < 2; j++) {
+      if (!out[j]) continue;
+      const size_t len = (size_t)k * cols[j];
+      double *const dev = where ? out[j] : b->adj_out.get() + at;
+      gather_rows(*b, (int)k, cols[j], src[j], dev, s);
+      if (!where) { HIP_CHECK(hipMemcpyAsync(out[j], dev, len * sizeof(double), hipMemcpyDeviceToHost, s)); at += len; }
     }
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;

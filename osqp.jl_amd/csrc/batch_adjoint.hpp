@@ -27,31 +27,35 @@ namespace polish {
 
 struct AdjointArgs {
   const double *Px, *Ax, *l, *u, *info, *rec;  // of the handle: raw data, the info rows and the records of the last resolve
-  const double *gx, *gy;                        // incoming gradients [count x n], [count x m]; nullptr: zero
-  double *dq, *dl, *du, *dPx, *dAx, *act, *status;  // outputs; nullptr: not wanted
+  const double *gx, *gy;                        // of the call: incoming gradients [k x n], [k x m]; nullptr: zero
+  double *dq, *dl, *du, *dPx, *dAx, *act, *status;  // of the call: outputs, [k x .]; nullptr: not wanted
   int info_stride, rec_stride, refine;
   double delta;
+  // a selection (osqp_amd_batch_adjoint_rows): the workgroup at position p of the k launched serves instance sel[p]; what is
+  // "of the handle" above is addressed with the instance, what is "of the call" with the position.  nullptr: the identity
+  const int *sel = nullptr;
 };
 
-// the rows of an instance that is not differentiated: zeros
-__device__ __forceinline__ void adjoint_zero_rows(const Pattern &P, const AdjointArgs &a, int inst) {
+// the rows of the call (at position pos) of an instance that is not differentiated: zeros
+__device__ __forceinline__ void adjoint_zero_rows(const Pattern &P, const AdjointArgs &a, int pos) {
   const int tid = threadIdx.x, n = P.n, m = P.m;
-  for (int j = tid; j < n; j += PT) if (a.dq) a.dq[(size_t)inst * n + j] = 0.0;
+  for (int j = tid; j < n; j += PT) if (a.dq) a.dq[(size_t)pos * n + j] = 0.0;
   for (int i = tid; i < m; i += PT) {
-    if (a.dl) a.dl[(size_t)inst * m + i] = 0.0;
-    if (a.du) a.du[(size_t)inst * m + i] = 0.0;
-    if (a.act) a.act[(size_t)inst * m + i] = 0.0;
+    if (a.dl) a.dl[(size_t)pos * m + i] = 0.0;
+    if (a.du) a.du[(size_t)pos * m + i] = 0.0;
+    if (a.act) a.act[(size_t)pos * m + i] = 0.0;
   }
-  if (a.dPx) for (int k = tid; k < P.nnzP; k += PT) a.dPx[(size_t)inst * P.nnzP + k] = 0.0;
-  if (a.dAx) for (int k = tid; k < P.nnzA; k += PT) a.dAx[(size_t)inst * P.nnzA + k] = 0.0;
+  if (a.dPx) for (int k = tid; k < P.nnzP; k += PT) a.dPx[(size_t)pos * P.nnzP + k] = 0.0;
+  if (a.dAx) for (int k = tid; k < P.nnzA; k += PT) a.dAx[(size_t)pos * P.nnzA + k] = 0.0;
 }
 
 __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layout L, AdjointArgs a) {
-  const int inst = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
-  if (inst >= count) return;
+  const int pos = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
+  if (pos >= count) return;
+  const int inst = a.sel ? a.sel[pos] : pos;  // wave-uniform; `count` is the launch's: k workgroups
   if ((int)a.info[(size_t)inst * a.info_stride + 1] != OSQP_SOLVED) {  // no solution to differentiate
-    adjoint_zero_rows(P, a, inst);
-    if (tid == 0 && a.status) a.status[inst] = 0.0;
+    adjoint_zero_rows(P, a, pos);
+    if (tid == 0 && a.status) a.status[pos] = 0.0;
     return;
   }
   const Slots S = make_slots(L);
@@ -64,14 +68,14 @@ __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layo
   const double *const Axi = a.Ax + (size_t)inst * P.nnzA, *const Pxi = a.Px + (size_t)inst * P.nnzP;
   for (int j = tid; j < n; j += PT) {
     stage_matrices(P, S, j, Axi, Pxi, D, E, c);
-    q[j] = a.gx ? c * (a.gx[(size_t)inst * n + j] * D[j]) : 0.0;
+    q[j] = a.gx ? c * (a.gx[(size_t)pos * n + j] * D[j]) : 0.0;
   }
   for (int i = tid; i < m; i += PT) {
     const double e = E[i];
     const double li = fmax(a.l[(size_t)inst * m + i], -OSQP_INFTY) * e, ui = fmin(a.u[(size_t)inst * m + i], OSQP_INFTY) * e;
     const double yi = rec[rec_y(n, m) + i];
     const double on = li == ui ? -1.0 : classify(rec[rec_z(n, m) + i], yi, li, ui);  // an equality row is always active
-    const double g = (on != 0.0 && a.gy) ? a.gy[(size_t)inst * m + i] * e : 0.0;
+    const double g = (on != 0.0 && a.gy) ? a.gy[(size_t)pos * m + i] * e : 0.0;
     act[i] = on;
     l[i] = g; ry[i] = g;
     y[i] = 0.0;
@@ -79,8 +83,8 @@ __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layo
   }
   assemble_M(P, S, delta);
   if (!cholesky(n, S.M, S.rdg, S.col)) {
-    adjoint_zero_rows(P, a, inst);
-    if (tid == 0 && a.status) a.status[inst] = -1.0;
+    adjoint_zero_rows(P, a, pos);
+    if (tid == 0 && a.status) a.status[pos] = -1.0;
     return;
   }
   for (int it = 0; it <= a.refine; it++) kkt_step<false>(P, S, it, delta);
@@ -93,15 +97,15 @@ __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layo
   // ---- the gradients: a thread per row (dl, du, act), a thread per column (dq, its stored entries of P, its entries of A) ----
   for (int i = tid; i < m; i += PT) {
     const double on = act[i], r = ry[i];
-    if (a.dl) a.dl[(size_t)inst * m + i] = on < 0.0 ? r : 0.0;
-    if (a.du) a.du[(size_t)inst * m + i] = on > 0.0 ? r : 0.0;
-    if (a.act) a.act[(size_t)inst * m + i] = on;
+    if (a.dl) a.dl[(size_t)pos * m + i] = on < 0.0 ? r : 0.0;
+    if (a.du) a.du[(size_t)pos * m + i] = on > 0.0 ? r : 0.0;
+    if (a.act) a.act[(size_t)pos * m + i] = on;
   }
   for (int j = tid; j < n; j += PT) {
     const double rj = x[j], xj = t[j];
-    if (a.dq) a.dq[(size_t)inst * n + j] = -rj;
+    if (a.dq) a.dq[(size_t)pos * n + j] = -rj;
     if (a.dPx) {
-      double *const dP = a.dPx + (size_t)inst * P.nnzP;
+      double *const dP = a.dPx + (size_t)pos * P.nnzP;
       for (int f = P.Fp[j]; f < P.Fp[j + 1]; f++) {  // row j of the full P; its entries cc <= j are column j of the stored triangle
         const int cc = P.Fc[f];
         if (cc == j) dP[P.Fmap[f]] = -(rj * xj);
@@ -109,11 +113,11 @@ __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layo
       }
     }
     if (a.dAx) {
-      double *const dA = a.dAx + (size_t)inst * P.nnzA;
+      double *const dA = a.dAx + (size_t)pos * P.nnzA;
       for (int k = P.Ap[j]; k < P.Ap[j + 1]; k++) { const int i = P.Ai[k]; dA[k] = -(z[i] * rj + ry[i] * xj); }
     }
   }
-  if (tid == 0 && a.status) a.status[inst] = 1.0;
+  if (tid == 0 && a.status) a.status[pos] = 1.0;
 }
 
 }  // namespace polish

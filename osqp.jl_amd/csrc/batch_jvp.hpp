@@ -30,29 +30,35 @@ namespace polish {
 
 struct JvpArgs {
   const double *Px, *Ax, *l, *u, *info, *rec;  // of the handle: raw data, the info rows and the records of the last resolve
-  const double *tq, *tl, *tu, *tPx, *tAx;      // tangents, direction-major [ndir x count x cols]; nullptr: zero
-  double *tx, *ty, *act, *status;               // outputs: tx, ty direction-major, act [count x m], status [count]; nullptr: not wanted
+  const double *tq, *tl, *tu, *tPx, *tAx;      // of the call: tangents, direction-major [ndir x k x cols]; nullptr: zero
+  double *tx, *ty, *act, *status;               // of the call: tx, ty direction-major, act [k x m], status [k]; nullptr: not wanted
   int ndir, info_stride, rec_stride, refine;
   double delta;
+  // a selection (osqp_amd_batch_jvp_rows): the workgroup at position p of the k launched serves instance sel[p]; what is
+  // "of the handle" above is addressed with the instance, what is "of the call" with the position (row d * k + p of a
+  // direction-major array).  nullptr: the identity
+  const int *sel = nullptr;
 };
 
-// the rows of an instance that is not differentiated: zeros in every direction
-__device__ __forceinline__ void jvp_zero_rows(const Pattern &P, const JvpArgs &a, int count, int inst) {
+// the rows of the call (at position pos of the `count` launched) of an instance that is not differentiated: zeros in every
+// direction
+__device__ __forceinline__ void jvp_zero_rows(const Pattern &P, const JvpArgs &a, int count, int pos) {
   const int tid = threadIdx.x, n = P.n, m = P.m;
   for (int d = 0; d < a.ndir; d++) {
-    const size_t row = (size_t)d * count + inst;
+    const size_t row = (size_t)d * count + pos;
     if (a.tx) for (int j = tid; j < n; j += PT) a.tx[row * n + j] = 0.0;
     if (a.ty) for (int i = tid; i < m; i += PT) a.ty[row * m + i] = 0.0;
   }
-  if (a.act) for (int i = tid; i < m; i += PT) a.act[(size_t)inst * m + i] = 0.0;
+  if (a.act) for (int i = tid; i < m; i += PT) a.act[(size_t)pos * m + i] = 0.0;
 }
 
 __global__ __launch_bounds__(PT) void k_batch_jvp(Pattern P, int count, Layout L, JvpArgs a) {
-  const int inst = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
-  if (inst >= count) return;
+  const int pos = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
+  if (pos >= count) return;
+  const int inst = a.sel ? a.sel[pos] : pos;  // wave-uniform; `count` is the launch's: k workgroups
   if ((int)a.info[(size_t)inst * a.info_stride + 1] != OSQP_SOLVED) {  // no solution to differentiate
-    jvp_zero_rows(P, a, count, inst);
-    if (tid == 0 && a.status) a.status[inst] = 0.0;
+    jvp_zero_rows(P, a, count, pos);
+    if (tid == 0 && a.status) a.status[pos] = 0.0;
     return;
   }
   const Slots S = make_slots(L);
@@ -74,17 +80,17 @@ __global__ __launch_bounds__(PT) void k_batch_jvp(Pattern P, int count, Layout L
   }
   assemble_M(P, S, delta);
   if (!cholesky(n, S.M, S.rdg, S.col)) {
-    jvp_zero_rows(P, a, count, inst);
-    if (tid == 0 && a.status) a.status[inst] = -1.0;
+    jvp_zero_rows(P, a, count, pos);
+    if (tid == 0 && a.status) a.status[pos] = -1.0;
     return;
   }
   // ---- the factor is done with col: the caller-unit x = D x~ of the record goes there ----
   for (int j = tid; j < n; j += PT) xc[j] = D[j] * rec[rec_x(n, m) + j];
-  for (int i = tid; i < m; i += PT) if (a.act) a.act[(size_t)inst * m + i] = act[i];
+  for (int i = tid; i < m; i += PT) if (a.act) a.act[(size_t)pos * m + i] = act[i];
   __syncthreads();
 
   for (int d = 0; d < a.ndir; d++) {
-    const size_t row = (size_t)d * count + inst;
+    const size_t row = (size_t)d * count + pos;
     // ---- the right-hand side [c D rhs_x; (E rhs_a)_a] of this direction; xc and z are complete (the barrier above, or the one
     // that ends the last kkt_step), and the x, y, q, l, ry of the direction before are read by nobody any more ----
     const double *const tP = a.tPx ? a.tPx + row * P.nnzP : nullptr, *const tA = a.tAx ? a.tAx + row * P.nnzA : nullptr;
@@ -114,7 +120,7 @@ __global__ __launch_bounds__(PT) void k_batch_jvp(Pattern P, int count, Layout L
     // (no barrier: the next direction writes q, l, ry, which nobody reads here, and x, y only after kkt_step's own barriers)
     if (a.ty) for (int i = tid; i < m; i += PT) a.ty[row * m + i] = cinv * E[i] * y[i];
   }
-  if (tid == 0 && a.status) a.status[inst] = 1.0;
+  if (tid == 0 && a.status) a.status[pos] = 1.0;
 }
 
 }  // namespace polish

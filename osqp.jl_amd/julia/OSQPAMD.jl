@@ -410,6 +410,25 @@ function batch_polish_status(b::ResidentBatch, st::Ptr{Cdouble})
     return nothing
 end
 
+"status_polish of the instances `rows` only (osqp_amd_batch_polish_status_rows): entry j is of instance rows[j]."
+function batch_polish_status(b::ResidentBatch, rows::AbstractVector{<:Integer})
+    r = _batch_rows(rows)
+    st = Vector{Float64}(undef, length(r))
+    flag = ccall((:osqp_amd_batch_polish_status_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Cc_int),
+                 b.handle, r, length(r), st, 0)
+    flag == 0 || error("Error in batched polish status: $(last_error())")
+    return Int.(st)
+end
+
+"The same into a device array (a pointer to k doubles on the handle's device)."
+function batch_polish_status(b::ResidentBatch, rows::AbstractVector{<:Integer}, st::Ptr{Cdouble})
+    r = _batch_rows(rows)
+    flag = ccall((:osqp_amd_batch_polish_status_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Cc_int),
+                 b.handle, r, length(r), st, 1)
+    flag == 0 || error("Error in batched polish status: $(last_error())")
+    return nothing
+end
+
 "Polishing of the following solves on / off and its number of refinement steps: `OSQP.update_settings!(polish = ..., polish_refine_iter = ...)` for the batch."
 function batch_update_polish!(b::ResidentBatch, polish::Bool; polish_refine_iter::Integer = 3)
     flag = ccall((:osqp_amd_batch_update_polish, lib), Cc_int, (Ptr{Cvoid}, Cc_int, Cc_int), b.handle, polish ? 1 : 0, polish_refine_iter)
@@ -464,23 +483,61 @@ function batch_certificates(b::ResidentBatch, p::Ptr{Cdouble}, d::Ptr{Cdouble})
     return nothing
 end
 
+"The certificates of the instances `rows` only (osqp_amd_batch_certificates_rows) -> ([m x k], [n x k]); column j is of instance rows[j]."
+function batch_certificates(b::ResidentBatch, rows::AbstractVector{<:Integer})
+    r = _batch_rows(rows)
+    k = length(r)
+    p = b.m > 0 ? Matrix{Float64}(undef, b.m, k) : nothing
+    d = Matrix{Float64}(undef, b.n, k)
+    GC.@preserve p d begin
+        flag = ccall((:osqp_amd_batch_certificates_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, r, k, _batch_ptr(p), _batch_ptr(d), 0)
+    end
+    flag == 0 || error("Error in batched certificates: $(last_error())")
+    return p, d
+end
+
+"The same into device arrays (pointers to m * k and n * k doubles on the handle's device; `C_NULL`: not wanted)."
+function batch_certificates(b::ResidentBatch, rows::AbstractVector{<:Integer}, p::Ptr{Cdouble}, d::Ptr{Cdouble})
+    r = _batch_rows(rows)
+    flag = ccall((:osqp_amd_batch_certificates_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                 b.handle, r, length(r), p, d, 1)
+    flag == 0 || error("Error in batched certificates: $(last_error())")
+    return nothing
+end
+
 """
     batch_adjoint!(b; dx = nothing, dy = nothing, dq = nothing, dl = nothing, du = nothing, dPx = nothing, dAx = nothing,
-                   act = nothing, status = nothing)
+                   act = nothing, status = nothing, rows = nothing)
 
 Gradients of a scalar loss through the solutions of the last `batch_solve!` (osqp_amd_batch_adjoint in include/osqp_amd.h):
 `dx` [n x count] and `dy` [m x count] are the loss's gradients with respect to x and y (`nothing` = zero, not both); every
 output that is given is filled in place -- `dq` [n x count], `dl`, `du`, `act` [m x count], `dPx` [nnz(triu(P)) x count],
 `dAx` [nnz(A) x count], `status` [1 x count] -- and `nothing` means not wanted.  All arrays are host matrices or all are
 device pointers, as for `batch_update!`.  The handle must have been solved since its last update or warm start.
+`rows` (distinct 1-based instance numbers, any order): the instances `rows` only, in a launch of k workgroups
+(osqp_amd_batch_adjoint_rows); every array then has one column per selected instance, column j for instance rows[j], and
+only the selected instances must have been solved since their last update or warm start.
 """
 function batch_adjoint!(b::ResidentBatch; dx::BatchArg = nothing, dy::BatchArg = nothing, dq::BatchArg = nothing,
                         dl::BatchArg = nothing, du::BatchArg = nothing, dPx::BatchArg = nothing, dAx::BatchArg = nothing,
-                        act::BatchArg = nothing, status::BatchArg = nothing)
+                        act::BatchArg = nothing, status::BatchArg = nothing,
+                        rows::Union{Nothing,AbstractVector{<:Integer}} = nothing)
     all_args = (dx, dy, dq, dl, du, dPx, dAx, act, status)
     given = filter(a -> a !== nothing, collect(all_args))
     all(a -> a isa Ptr{Cdouble}, given) || all(a -> a isa Matrix{Float64}, given) ||
         error("batch_adjoint!: the arrays must all be host matrices or all device pointers")
+    if rows !== nothing
+        r = _batch_rows(rows)
+        GC.@preserve dx dy dq dl du dPx dAx act status begin
+            flag = ccall((:osqp_amd_batch_adjoint_rows, lib), Cc_int,
+                         (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                          Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                         b.handle, r, length(r), map(_batch_ptr, all_args)..., _batch_where(all_args...))
+        end
+        flag == 0 || error("Error in batched adjoint: $(last_error())")
+        return nothing
+    end
     GC.@preserve dx dy dq dl du dPx dAx act status begin
         flag = ccall((:osqp_amd_batch_adjoint, lib), Cc_int,
                      (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
@@ -496,7 +553,7 @@ _batch_ptr(a::Array{Float64,3}) = pointer(a)
 
 """
     batch_jvp!(b; tq = nothing, tl = nothing, tu = nothing, tPx = nothing, tAx = nothing, tx = nothing, ty = nothing,
-               act = nothing, status = nothing, ndir = nothing)
+               act = nothing, status = nothing, ndir = nothing, rows = nothing)
 
 Forward sensitivities of the solutions of the last `batch_solve!` along directions of the data (osqp_amd_batch_jvp in
 include/osqp_amd.h): the tangents `tq` [n x count], `tl`, `tu` [m x count], `tPx` [nnz(triu(P)) x count], `tAx`
@@ -505,12 +562,15 @@ launch (one factorisation per instance, one solve per direction).  `tx` [n x cou
 are filled in place (`nothing` = not wanted, not both), as are `act` [m x count] and `status` [1 x count], once per call.  All
 arrays are host arrays or all are device pointers, as for `batch_adjoint!`; with device pointers `ndir` gives the number of
 directions (default 1), with host arrays it is read from the third axis and all arrays must agree.  The handle must have
-been solved since its last update or warm start.  Julia is not installed in the build image: like the rest of this file
+been solved since its last update or warm start.  `rows` (distinct 1-based instance numbers, any order): the instances
+`rows` only, in a launch of k workgroups (osqp_amd_batch_jvp_rows); every array then has k columns, [. x k (x ndir)], column
+j for instance rows[j], and only the selected instances must be current.  Julia is not installed in the build image: like the rest of this file
 this function is not executed by the test suite; the Python mirror (`ResidentBatch.jvp`) is.
 """
 function batch_jvp!(b::ResidentBatch; tq::JvpArg = nothing, tl::JvpArg = nothing, tu::JvpArg = nothing, tPx::JvpArg = nothing,
                     tAx::JvpArg = nothing, tx::JvpArg = nothing, ty::JvpArg = nothing, act::BatchArg = nothing,
-                    status::BatchArg = nothing, ndir::Union{Nothing,Integer} = nothing)
+                    status::BatchArg = nothing, ndir::Union{Nothing,Integer} = nothing,
+                    rows::Union{Nothing,AbstractVector{<:Integer}} = nothing)
     dirs = (tq, tl, tu, tPx, tAx, tx, ty)
     all_args = (dirs..., act, status)
     given = filter(a -> a !== nothing, collect(all_args))
@@ -525,6 +585,17 @@ function batch_jvp!(b::ResidentBatch; tq::JvpArg = nothing, tl::JvpArg = nothing
         ndir = counts[1]
     end
     nd = ndir === nothing ? 1 : Int(ndir)
+    if rows !== nothing
+        r = _batch_rows(rows)
+        GC.@preserve tq tl tu tPx tAx tx ty act status begin
+            flag = ccall((:osqp_amd_batch_jvp_rows, lib), Cc_int,
+                         (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                          Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                         b.handle, r, length(r), nd, map(_batch_ptr, all_args)..., _batch_where(all_args...))
+        end
+        flag == 0 || error("Error in batched sensitivities: $(last_error())")
+        return nothing
+    end
     GC.@preserve tq tl tu tPx tAx tx ty act status begin
         flag = ccall((:osqp_amd_batch_jvp, lib), Cc_int,
                      (Ptr{Cvoid}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},

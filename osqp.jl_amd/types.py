@@ -231,6 +231,11 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_update_setting": (c_int, [C.c_void_p, C.c_char_p, c_float]),
     "osqp_amd_batch_certificates": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_cert_launches": (c_int, []),
+    # the reading calls for a selection: rows and k after the handle, every array compact ([k x .], [ndir x k x .])
+    "osqp_amd_batch_adjoint_rows": (c_int, [C.c_void_p, c_int_p, c_int] + [C.c_void_p] * 9 + [c_int]),
+    "osqp_amd_batch_jvp_rows": (c_int, [C.c_void_p, c_int_p, c_int, c_int] + [C.c_void_p] * 9 + [c_int]),
+    "osqp_amd_batch_polish_status_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, c_int]),
+    "osqp_amd_batch_certificates_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_device_alloc": (C.c_void_p, [c_int, c_int]),
     "osqp_amd_device_free": (c_int, [C.c_void_p, c_int]),
     "osqp_amd_device_copy": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int]),
