@@ -494,6 +494,14 @@ c_int osqp_amd_batch_destroy(osqp_amd_batch *batch);
  *             since (any update_* or warm_start; update_polish does not count), and a pattern whose working set exceeds
  *             the polish LDS limit.  The call changes nothing on the handle: a resolve after it is bit-identical to one
  *             without it.
+ *   adjoint_multi(): adjoint() for ncot >= 1 pairs (dx, dy) per instance in ONE launch.  Every array of the call but act_out
+ *             and status_out is cotangent-major: dx [ncot x count x n], dy [ncot x count x m], and dq, dl, du, dPx, dAx
+ *             [ncot x count x cols]; cotangent c of every array is a contiguous [count x cols] block.  act_out [count x m] and
+ *             status_out [count] are written once per instance.  The matrix is assembled and factorised ONCE per instance
+ *             and solved once per cotangent; nothing is carried from one cotangent to the next, so cotangent c of an ncot
+ *             call has the bits of adjoint() with that pair, and ncot = 1 is adjoint().  An instance with status 0 or -1 has
+ *             zeros in the rows of every cotangent.  ncot < 1 is refused with return 1 and a message; every other rule is
+ *             adjoint()'s.  adjoint_multi_rows() is to it what adjoint_rows() is to adjoint(): [ncot x k x cols] arrays.
  *   jvp():    forward sensitivities (Jacobian-vector products) of the solutions of the last resolve: the transpose of
  *             adjoint().  A direction of the data is (tq [n], tl, tu [m], tPx [nnz(P upper)], tAx [nnz(A)]) per instance, in
  *             the setup's pattern order; tP is the symmetric matrix of tPx (a stored off-diagonal entry stands for both
@@ -605,6 +613,14 @@ c_int osqp_amd_batch_adjoint(osqp_amd_batch *batch, const c_float *dx, const c_f
 c_int osqp_amd_batch_adjoint_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, const c_float *dx, const c_float *dy,
                                   c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
                                   c_float *act_out, c_float *status_out, c_int where);
+/* adjoint() / adjoint_rows() for ncot pairs (dx, dy) per instance in one launch: cotangent-major arrays [ncot x count x cols]
+ * ([ncot x k x cols]); act_out and status_out once per instance. */
+c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *batch, c_int ncot, const c_float *dx, const c_float *dy,
+                                   c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
+                                   c_float *act_out, c_float *status_out, c_int where);
+c_int osqp_amd_batch_adjoint_multi_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_int ncot, const c_float *dx, const c_float *dy,
+                                        c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx,
+                                        c_float *act_out, c_float *status_out, c_int where);
 c_int osqp_amd_batch_jvp(osqp_amd_batch *batch, c_int ndir,
                          const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx, const c_float *tAx,
                          c_float *tx_out, c_float *ty_out, c_float *act_out, c_float *status_out, c_int where);
@@ -616,7 +632,8 @@ c_int osqp_amd_batch_jvp_rows(osqp_amd_batch *batch, const c_int *rows, c_int k,
 /* Diagnostic, like osqp_amd_batch_last_kernel: how many polish launches this process has made so far.  A resolve with
  * polish = 0 makes none -- its launch sequence is the one of a library without the polish kernel. */
 c_int osqp_amd_batch_polish_launches(void);
-/* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint / _adjoint_rows that passed its checks, none otherwise. */
+/* The same for the adjoint kernel: one launch per osqp_amd_batch_adjoint / _adjoint_rows / _adjoint_multi /
+ * _adjoint_multi_rows that passed its checks, whatever ncot, none otherwise. */
 c_int osqp_amd_batch_adjoint_launches(void);
 /* The same for the sensitivity kernel: one launch per osqp_amd_batch_jvp / _jvp_rows that passed its checks, whatever ndir, none
  * otherwise. */

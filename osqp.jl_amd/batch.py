@@ -499,7 +499,11 @@ class ResidentBatch:
         are dependent the derivative does not exist and the regularised answer is returned (see include/osqp_amd.h).
         rows: a selection (`selection`): a launch of k workgroups; dx, dy and every result are [k x .], row j for instance
         rows[j] with the bits of row rows[j] of the whole call, and only the SELECTED instances must hold a current solution
-        (the refusal names the first stale one in the order of `rows`)."""
+        (the refusal names the first stale one in the order of `rows`).
+        Several cotangents at once: dx / dy with a leading axis, [ncot x count x .] ([ncot x k x .] with `rows`), both with the
+        same number of dimensions and the same ncot (osqp_amd_batch_adjoint_multi) -- one launch, one factorisation per
+        instance, one solve per cotangent, and cotangent c has the bits of a call with that pair alone.  The gradients are then
+        shaped like the cotangents, [ncot x count x .]; "act" [count x m] and "status" [count] stay per instance."""
         sel = None if rows is None else selection(rows, self.count)
         cnt = self.count if sel is None else len(sel)
         cols = self._adjoint_cols()
@@ -509,12 +513,29 @@ class ResidentBatch:
                 raise ValueError(f"want: unknown gradient {w!r}; expected a subset of {self.ADJOINT_WANT}")
         if dx is None and dy is None:
             raise ValueError("dx and dy: at least one incoming gradient is needed")
-        keep, ptrs, where = self._pair(("dx", "dy"), (dx, dy), (self.n, self.m), cnt)
+        dims = {k: len(tuple(v.shape)) if hasattr(v, "data_ptr") else np.asarray(v).ndim for k, v in (("dx", dx), ("dy", dy)) if v is not None}
+        if len(set(dims.values())) > 1 or next(iter(dims.values())) not in (2, 3):
+            raise ValueError(f"dx and dy: expected both [count x cols] or both [ncot x count x cols], got dimensions {dims}")
+        many = next(iter(dims.values())) == 3
+        if many:
+            ncots = {k: int((v.shape if hasattr(v, "data_ptr") else np.asarray(v).shape)[0]) for k, v in (("dx", dx), ("dy", dy)) if v is not None}
+            if len(set(ncots.values())) > 1:
+                raise ValueError(f"dx and dy: they must carry the same number of cotangents, got {ncots}")
+            ncot = next(iter(ncots.values()))
+            if ncot < 1:
+                raise ValueError("dx and dy: ncot must be at least 1")
+        lead = (ncot, cnt) if many else (cnt,)
+        got = [None if v is None else _batch_array(nm, v, lead + (k,)) for nm, v, k in (("dx", dx, self.n), ("dy", dy, self.m))]
+        forms = {g[2] for g in got if g is not None}
+        if len(forms) > 1:
+            raise ValueError("dx and dy must both be host arrays or both device arrays")
+        ptrs, where = [None if g is None else g[1] for g in got], forms.pop()
+        oshape = {k: ((cnt, cols[k]) if k in ("act", "status") else lead + (cols[k],)) for k in cols}
         names = [k for k in self.ADJOINT_WANT + ("act", "status") if cols[k] > 0]
         if not where:
             if out is not None:
                 raise ValueError("out: host gradients (numpy dx / dy) return numpy arrays; pass device arrays for dx / dy to fill `out`")
-            res = {k: np.empty((cnt, cols[k])) for k in names if k in want or k in ("act", "status")}
+            res = {k: np.empty(oshape[k]) for k in names if k in want or k in ("act", "status")}
             addr = {k: v.ctypes.data for k, v in res.items()}
         else:
             if not isinstance(out, dict):
@@ -527,12 +548,17 @@ class ResidentBatch:
                 if k in out and (k in want or k in ("act", "status")):
                     if not hasattr(out[k], "data_ptr"):
                         raise ValueError(f"out[{k!r}]: expected a device array (DeviceArray, torch tensor)")
-                    addr[k] = _batch_array(f"out[{k!r}]", out[k], (cnt, cols[k]))[1]
+                    addr[k] = _batch_array(f"out[{k!r}]", out[k], oshape[k])[1]
                 elif k in want:
                     raise ValueError(f"out: no array for the wanted gradient {k!r}")
             res = out
         tail = [ptrs[0], ptrs[1]] + [addr.get(k) for k in self.ADJOINT_WANT] + [addr.get("act"), addr.get("status"), where]
-        if sel is None:
+        if many:
+            if sel is None:
+                self._call("adjoint", self.lib.osqp_amd_batch_adjoint_multi(self.handle, ncot, *tail))
+            else:
+                self._call("adjoint", self.lib.osqp_amd_batch_adjoint_multi_rows(self.handle, _iptr(sel), cnt, ncot, *tail))
+        elif sel is None:
             self._call("adjoint", self.lib.osqp_amd_batch_adjoint(self.handle, *tail))
         else:
             self._call("adjoint", self.lib.osqp_amd_batch_adjoint_rows(self.handle, _iptr(sel), cnt, *tail))
@@ -613,6 +639,141 @@ class ResidentBatch:
                 res["act"] = res["act"].astype(np.int64)
             res["status"] = res["status"].ravel().astype(np.int64)
         return res
+
+    JACOBIAN_OF = ("x", "y")
+    JACOBIAN_BUDGET = 256 << 20  # bytes: the unit vectors and the largest output of one launch of `jacobian` (default chunk)
+
+    def jacobian(self, of=("x",), wrt=("q", "l", "u"), mode="auto", rows=None, out_rows=None, chunk=None, device=False):
+        """Jacobians of the solutions of the last `solve()` with respect to the data, instance by instance: a dict
+        {(o, w): [count x cols(o) x cols(w)]} for o in `of` (a subset of "x", "y") and w in `wrt` (a subset of "q", "l", "u",
+        "Px", "Ax"; the matrices in the setup's pattern order), entry [i, a, b] the derivative of component a of o with respect to
+        entry b of w of instance i, plus "act" and "status" as `adjoint` / `jvp` return them (an instance with status != 1 has
+        zeros).  out_rows: a dict {"x": indices, "y": indices} that restricts the outputs of `of` to these components (cols(o)
+        is then their number, in the order given) -- for an MPC instance the indices of the first input.
+        mode="reverse": unit cotangents through `adjoint` with a leading axis, one solve per requested output component;
+        mode="forward": unit directions through `jvp`, one solve per column of the `wrt` arrays; "auto": the one with fewer
+        solves (reverse on a tie).  Each is the plain derivative of the active-set solution: on a row with l == u the
+        derivative with respect to moving both bounds is in "l" and "u" is zero; an inactive bound has a zero column.
+        chunk: the most cotangents / directions per launch; the chunks of a call are independent launches whose results are
+        concatenated, so the result does not depend on it.  Default: as many as keep the unit vectors (every cotangent or
+        tangent array of the launch) and the largest output array of one launch under 256 MiB together, at least 1.
+        rows: a selection (`selection`): the arrays are [k x . x .], entry j for instance rows[j].  device=False: numpy
+        results; device=True: the unit vectors are made and the results returned as torch tensors on the handle's device
+        (no host hop).  Nothing is computed on the results: they are transposed and placed."""
+        sel = None if rows is None else selection(rows, self.count)
+        cnt = self.count if sel is None else len(sel)
+        of, wrt = tuple(of), tuple(wrt)
+        wcols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA)
+        ocols = dict(x=self.n, y=self.m)
+        if not of or len(set(of)) != len(of) or any(o not in self.JACOBIAN_OF for o in of):
+            raise ValueError(f"of: expected a non-empty subset of {self.JACOBIAN_OF} without repeats, got {of!r}")
+        if not wrt or len(set(wrt)) != len(wrt) or any(w not in self.ADJOINT_WANT for w in wrt):
+            raise ValueError(f"wrt: expected a non-empty subset of {self.ADJOINT_WANT} without repeats, got {wrt!r}")
+        if mode not in ("auto", "reverse", "forward"):
+            raise ValueError(f"mode: expected 'auto', 'reverse' or 'forward', got {mode!r}")
+        out_rows = {} if out_rows is None else dict(out_rows)
+        idx = {}
+        for o in out_rows:
+            if o not in of:
+                raise ValueError(f"out_rows: {o!r} is not in `of` {of!r}")
+        for o in of:
+            if o in out_rows:
+                a = np.asarray(out_rows[o])
+                if a.ndim != 1 or a.dtype.kind not in "iu":
+                    raise ValueError(f"out_rows[{o!r}]: expected a one-dimensional integer array, got shape {a.shape}, dtype {a.dtype}")
+                if a.size and (a.min() < 0 or a.max() >= ocols[o]):
+                    raise ValueError(f"out_rows[{o!r}]: components must be in [0, {ocols[o]})")
+                idx[o] = a.astype(np.int64)
+            else:
+                idx[o] = np.arange(ocols[o], dtype=np.int64)
+        if chunk is not None and (not isinstance(chunk, (int, np.integer)) or isinstance(chunk, bool) or chunk < 1):
+            raise ValueError(f"chunk: expected a positive integer, got {chunk!r}")
+        n_rev, n_fwd = sum(len(idx[o]) for o in of), sum(wcols[w] for w in wrt)
+        if n_rev == 0 or n_fwd == 0:
+            raise ValueError("jacobian: no output component or no data column is asked for")
+        if mode == "auto":
+            mode = "reverse" if n_rev <= n_fwd else "forward"
+        reverse = mode == "reverse"
+        total = n_rev if reverse else n_fwd
+        if chunk is None:
+            unit = sum(ocols[o] for o in of) if reverse else n_fwd
+            largest = max(wcols[w] for w in wrt) if reverse else max(ocols[o] for o in of)
+            chunk = max(1, self.JACOBIAN_BUDGET // (8 * cnt * (unit + largest)))
+        chunk = int(min(chunk, total))
+
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+
+            def zeros(*shape):
+                return torch.zeros(shape, dtype=torch.float64, device=dev)
+
+            def empty(*shape):
+                return torch.empty(shape, dtype=torch.float64, device=dev)
+
+            def index(a):
+                return torch.as_tensor(a, device=dev)
+
+            def moved(a, perm):
+                return a.permute(*perm)
+
+            def ready():
+                torch.cuda.current_stream(dev).synchronize()
+        else:
+            zeros, empty, index, ready = (lambda *shape: np.zeros(shape)), (lambda *shape: np.empty(shape)), (lambda a: a), (lambda: None)
+
+            def moved(a, perm):
+                return np.transpose(a, perm)
+
+        # the solves of the call in order: segment (name, first solve, number) -- the components of each o (reverse), the
+        # columns of each w (forward)
+        segs, at = [], 0
+        for name, width in ([(o, len(idx[o])) for o in of] if reverse else [(w, wcols[w]) for w in wrt]):
+            segs.append((name, at, width))
+            at += width
+        J = {(o, w): zeros(cnt, len(idx[o]), wcols[w]) for o in of for w in wrt}
+        res = {}
+        for c0 in range(0, total, chunk):
+            c1 = min(c0 + chunk, total)
+            nc = c1 - c0
+            # the part [a, b) of each segment that falls into this chunk, as positions of the chunk and of the segment
+            parts = [(name, max(s0, c0) - c0, min(s0 + w, c1) - c0, max(s0, c0) - s0) for name, s0, w in segs if max(s0, c0) < min(s0 + w, c1)]
+            if reverse:
+                cot = {o: zeros(nc, cnt, ocols[o]) for o in of if ocols[o] > 0}
+                for o, a, b, p0 in parts:
+                    cot[o][index(np.arange(a, b)), :, index(idx[o][p0:p0 + b - a])] = 1.0
+                want = tuple(w for w in wrt if wcols[w] > 0)
+                out = None
+                if device:
+                    out = {w: empty(nc, cnt, wcols[w]) for w in want}
+                    out.update(act=empty(cnt, self.m), status=empty(cnt, 1))
+                    if self.m == 0:
+                        del out["act"]
+                ready()
+                res = self.adjoint(dx=cot.get("x"), dy=cot.get("y"), want=want, out=out, rows=sel)
+                for o, a, b, p0 in parts:
+                    for w in want:
+                        J[(o, w)][:, p0:p0 + b - a, :] = moved(res[w][a:b], (1, 0, 2))
+            else:
+                tan = {w: zeros(nc, cnt, wcols[w]) for w in wrt if wcols[w] > 0}
+                for w, a, b, p0 in parts:
+                    tan[w][index(np.arange(a, b)), :, index(np.arange(p0, p0 + b - a))] = 1.0
+                out = None
+                if device:
+                    out = dict(x=empty(nc, cnt, self.n), y=empty(nc, cnt, self.m), act=empty(cnt, self.m), status=empty(cnt, 1))
+                    if self.m == 0:
+                        del out["y"], out["act"]
+                ready()
+                res = self.jvp(**tan, out=out, rows=sel)
+                for w, a, b, p0 in parts:
+                    for o in of:
+                        if ocols[o] > 0:
+                            J[(o, w)][:, :, p0:p0 + b - a] = moved(res[o][a:b][:, :, index(idx[o])], (1, 2, 0))
+        if "act" in res:
+            J["act"] = res["act"]
+        J["status"] = res["status"]
+        return J
 
     def alloc(self, k=None):
         """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints.  k: the number of

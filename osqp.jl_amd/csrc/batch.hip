@@ -14,7 +14,8 @@
 //   batch_polish.hpp  k_batch_polish -- solution polishing for the resident batch, a launch of its own after the ADMM launch
 //                     when the handle's settings.polish is 1; the solve kernels know nothing of it;
 //   batch_adjoint.hpp k_batch_adjoint -- adjoint derivatives of the solutions of the resident batch, a launch of its own on
-//                     request (osqp_amd_batch_adjoint); shares the factorisation and the solves of the polish kernel;
+//                     request (osqp_amd_batch_adjoint, _multi: ncot cotangents per launch); shares the factorisation and the
+//                     solves of the polish kernel;
 //   batch_jvp.hpp     k_batch_jvp -- forward sensitivities of the solutions of the resident batch along directions of the data, a
 //                     launch of its own on request (osqp_amd_batch_jvp): one factorisation per instance, one solve per direction;
 //   batch_cert.hpp    k_batch_cert -- the infeasibility certificates of the resident batch, a launch of its own after every
@@ -486,12 +487,15 @@ void set_polish(BatchPlan &b, c_int polish_new, c_int refine_new) {
   catch (const Error &er) { set_last_error(er.what()); return er.code ? er.code : 6; }         \
   catch (const std::exception &ex) { set_last_error(ex.what()); return 6; }
 
-// osqp_amd_batch_adjoint (subset false: every instance, rows / k unused) and osqp_amd_batch_adjoint_rows (subset true: the
-// k instances of rows; every array of the call is compact, row j for instance rows[j]).  One launch of `cnt` workgroups.
-c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, const c_float *dx, const c_float *dy, c_float *dq,
-                    c_float *dl, c_float *du, c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
+// osqp_amd_batch_adjoint, _multi (subset false: every instance, rows / k unused) and osqp_amd_batch_adjoint_rows, _multi_rows
+// (subset true: the k instances of rows; every array of the call is compact, row j for instance rows[j]).  ncot pairs
+// (dx, dy) per instance (1 for the two old entries): the cotangent-major arrays are [ncot x cnt x cols], act and status once
+// per instance.  One launch of `cnt` workgroups, whatever ncot is.
+c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, c_int ncot, const c_float *dx, const c_float *dy,
+                    c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
+  if (ncot < 1) { set_last_error("invalid batch data: the adjoint needs ncot >= 1"); return 1; }
   if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
   if (!subset && !holds_current(*b, nullptr)) return 1;
   try {
@@ -504,13 +508,13 @@ c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_in
     }
     polish_check_fits(P);
     const int launch = subset ? (int)k : b->count;
-    const size_t cnt = (size_t)launch, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    const size_t cnt = (size_t)launch, nc = (size_t)ncot, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
     if (!lm) { dy = nullptr; dl = du = act_out = nullptr; }
     if (!la) dAx = nullptr;
     if (!lp) dPx = nullptr;
     // host pointers: the wanted outputs share one staging buffer, in this order
     c_float *const host[7] = {dq, dl, du, dPx, dAx, act_out, status_out};
-    const size_t len[7] = {ln, lm, lm, lp, la, lm, cnt};
+    const size_t len[7] = {nc * ln, nc * lm, nc * lm, nc * lp, nc * la, lm, cnt};
     double *dev[7];
     size_t total = 0;
     for (int j = 0; j < 7; j++) if (host[j]) total += len[j];
@@ -522,10 +526,10 @@ c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_in
     }
     polish::AdjointArgs a;
     a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
-    a.gx = dx ? device_ptr(dx, ln, where, b->in_a, s) : nullptr;
-    a.gy = dy ? device_ptr(dy, lm, where, b->in_b, s) : nullptr;
+    a.gx = dx ? device_ptr(dx, nc * ln, where, b->in_a, s) : nullptr;
+    a.gy = dy ? device_ptr(dy, nc * lm, where, b->in_b, s) : nullptr;
     a.dq = dev[0]; a.dl = dev[1]; a.du = dev[2]; a.dPx = dev[3]; a.dAx = dev[4]; a.act = dev[5]; a.status = dev[6];
-    a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
+    a.ncot = (int)ncot; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
     a.sel = subset ? b->sel.get() : nullptr;
     const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
     HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
@@ -978,11 +982,20 @@ c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *handle, const c_int *rows, c_i
 
 c_int osqp_amd_batch_adjoint(osqp_amd_batch *handle, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
                              c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
-  return batch_adjoint(handle, false, nullptr, 0, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
+  return batch_adjoint(handle, false, nullptr, 0, 1, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
 }
 c_int osqp_amd_batch_adjoint_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *dx, const c_float *dy, c_float *dq,
                                   c_float *dl, c_float *du, c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
-  return batch_adjoint(handle, true, rows, k, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
+  return batch_adjoint(handle, true, rows, k, 1, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
+}
+c_int osqp_amd_batch_adjoint_multi(osqp_amd_batch *handle, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl,
+                                   c_float *du, c_float *dPx, c_float *dAx, c_float *act_out, c_float *status_out, c_int where) {
+  return batch_adjoint(handle, false, nullptr, 0, ncot, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
+}
+c_int osqp_amd_batch_adjoint_multi_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_int ncot, const c_float *dx, const c_float *dy,
+                                        c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx, c_float *act_out,
+                                        c_float *status_out, c_int where) {
+  return batch_adjoint(handle, true, rows, k, ncot, dx, dy, dq, dl, du, dPx, dAx, act_out, status_out, where);
 }
 
 c_int osqp_amd_batch_jvp(osqp_amd_batch *handle, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,

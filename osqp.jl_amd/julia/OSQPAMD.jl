@@ -506,9 +506,12 @@ function batch_certificates(b::ResidentBatch, rows::AbstractVector{<:Integer}, p
     return nothing
 end
 
+const AdjointArg = Union{Nothing,Matrix{Float64},Array{Float64,3},Ptr{Cdouble}}
+_batch_ptr(a::Array{Float64,3}) = pointer(a)
+
 """
     batch_adjoint!(b; dx = nothing, dy = nothing, dq = nothing, dl = nothing, du = nothing, dPx = nothing, dAx = nothing,
-                   act = nothing, status = nothing, rows = nothing)
+                   act = nothing, status = nothing, rows = nothing, ncot = nothing)
 
 Gradients of a scalar loss through the solutions of the last `batch_solve!` (osqp_amd_batch_adjoint in include/osqp_amd.h):
 `dx` [n x count] and `dy` [m x count] are the loss's gradients with respect to x and y (`nothing` = zero, not both); every
@@ -518,13 +521,41 @@ device pointers, as for `batch_update!`.  The handle must have been solved since
 `rows` (distinct 1-based instance numbers, any order): the instances `rows` only, in a launch of k workgroups
 (osqp_amd_batch_adjoint_rows); every array then has one column per selected instance, column j for instance rows[j], and
 only the selected instances must have been solved since their last update or warm start.
+`ncot` (>= 1): that many pairs (`dx`, `dy`) per instance in ONE launch (osqp_amd_batch_adjoint_multi, _multi_rows) -- one
+factorisation per instance, one solve per cotangent.  `dx`, `dy` and the five gradients then have a third axis,
+[. x count x ncot] ([. x k x ncot] with `rows`; host arrays `Array{Float64,3}`, whose third axis must be `ncot`), while `act` and
+`status` stay per instance.  `nothing`: the one-cotangent entries, as before.  Like the rest of this file the keyword is not
+executed by the test suite; the Python mirror (`ResidentBatch.adjoint` with a leading axis) is.
 """
-function batch_adjoint!(b::ResidentBatch; dx::BatchArg = nothing, dy::BatchArg = nothing, dq::BatchArg = nothing,
-                        dl::BatchArg = nothing, du::BatchArg = nothing, dPx::BatchArg = nothing, dAx::BatchArg = nothing,
+function batch_adjoint!(b::ResidentBatch; dx::AdjointArg = nothing, dy::AdjointArg = nothing, dq::AdjointArg = nothing,
+                        dl::AdjointArg = nothing, du::AdjointArg = nothing, dPx::AdjointArg = nothing, dAx::AdjointArg = nothing,
                         act::BatchArg = nothing, status::BatchArg = nothing,
-                        rows::Union{Nothing,AbstractVector{<:Integer}} = nothing)
+                        rows::Union{Nothing,AbstractVector{<:Integer}} = nothing, ncot::Union{Nothing,Integer} = nothing)
     all_args = (dx, dy, dq, dl, du, dPx, dAx, act, status)
     given = filter(a -> a !== nothing, collect(all_args))
+    if ncot !== nothing
+        ncot >= 1 || error("batch_adjoint!: ncot must be at least 1")
+        all(a -> a isa Ptr{Cdouble}, given) || all(a -> a isa Array{Float64}, given) ||
+            error("batch_adjoint!: the arrays must all be host arrays or all device pointers")
+        all(a -> !(a isa Array{Float64}) || (ndims(a) == 3 && size(a, 3) == ncot), all_args[1:7]) ||
+            error("batch_adjoint!: with ncot, dx, dy and the gradients are [. x count x ncot]")
+        GC.@preserve dx dy dq dl du dPx dAx act status begin
+            if rows !== nothing
+                r = _batch_rows(rows)
+                flag = ccall((:osqp_amd_batch_adjoint_multi_rows, lib), Cc_int,
+                             (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                              Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                             b.handle, r, length(r), ncot, map(_batch_ptr, all_args)..., _batch_where(all_args...))
+            else
+                flag = ccall((:osqp_amd_batch_adjoint_multi, lib), Cc_int,
+                             (Ptr{Cvoid}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                              Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                             b.handle, ncot, map(_batch_ptr, all_args)..., _batch_where(all_args...))
+            end
+        end
+        flag == 0 || error("Error in batched adjoint: $(last_error())")
+        return nothing
+    end
     all(a -> a isa Ptr{Cdouble}, given) || all(a -> a isa Matrix{Float64}, given) ||
         error("batch_adjoint!: the arrays must all be host matrices or all device pointers")
     if rows !== nothing
@@ -548,8 +579,7 @@ function batch_adjoint!(b::ResidentBatch; dx::BatchArg = nothing, dy::BatchArg =
     return nothing
 end
 
-const JvpArg = Union{Nothing,Matrix{Float64},Array{Float64,3},Ptr{Cdouble}}
-_batch_ptr(a::Array{Float64,3}) = pointer(a)
+const JvpArg = AdjointArg
 
 """
     batch_jvp!(b; tq = nothing, tl = nothing, tu = nothing, tPx = nothing, tAx = nothing, tx = nothing, ty = nothing,

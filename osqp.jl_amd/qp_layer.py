@@ -1,6 +1,6 @@
 """A resident batch as a differentiable torch layer: `BatchQPFunction` solves `count` QPs in its forward
 (`ResidentBatch.update` + `solve`, device pointers, no host hop) and differentiates their solutions in its backward
-(`ResidentBatch.adjoint`: one launch of k_batch_adjoint); under forward-mode differentiation (`torch.autograd.forward_ad`,
+(`ResidentBatch.adjoint`: one launch of k_batch_adjoint, also for a BATCH of cotangents -- below); under forward-mode differentiation (`torch.autograd.forward_ad`,
 `torch.func.jvp`) its `jvp` pushes the tangents of the inputs forward to the solutions (`ResidentBatch.jvp`: one launch of
 k_batch_jvp).  torch is plumbing only: tensors are passed to the library by address and nothing is computed in torch.
 
@@ -13,6 +13,18 @@ k_batch_jvp).  torch is plumbing only: tensors are passed to the library by addr
         tx = forward_ad.unpack_dual(x).tangent
 
     x, y = layer(q=q_t[sel], rows=sel)         # a selection (`batch.selection`): tensors [k x .], the others untouched
+
+    xs, vjp_fn = torch.func.vjp(lambda q: layer(q=q)[0], q_t)
+    (dq,) = torch.func.vmap(vjp_fn)(G)          # G [ncot x count x n]: ONE adjoint launch for all cotangents
+    J = torch.func.jacrev(lambda q: layer(q=q)[0])(q_t)   # [count x n x count x n], one launch as well
+    J = layer.jacobian(of=("x",), wrt=("q",))   # the per-instance blocks [count x n x n] (`ResidentBatch.jacobian`)
+
+Batched reverse mode: `BatchQPFunction` is a new-style Function (`forward` without ctx, `setup_context`) whose backward calls
+a second Function, `BatchQPAdjoint`; its `vmap` rule moves the batch axis of the cotangents to the front (a cotangent that
+arrives unbatched -- `jacrev` of x alone hands over gy as unbatched zeros -- is expanded) and calls `ResidentBatch.adjoint`
+with [ncot x k x .] arrays: one factorisation per instance, one solve per cotangent.  Out of scope: `torch.autograd.grad(...,
+is_grads_batched=True)`, which uses torch's legacy vmap -- that ignores the `vmap` rule and hands the backward batched
+tensors without addresses; and `torch.func.jacfwd`, that is `vmap` over the forward-mode rule.
 
 Three rules.  The library runs on its own stream and blocks, so torch's current stream is synchronised before every library
 call.  The handle holds ONE solution per instance: every forward stamps the instances it served (all of them without
@@ -48,16 +60,64 @@ def stamp_holds(rb, stamp, sel):
     return stamps is not None and bool(np.all(stamps[slice(None) if sel is None else sel] == stamp))
 
 
+def _check_inputs(given):
+    for name, t in given.items():
+        if t is not None and (not t.is_cuda or t.dtype != torch.float64):
+            raise ValueError(f"{name}: expected a float64 CUDA tensor")
+
+
+class BatchQPAdjoint(torch.autograd.Function):
+    """The pull-back of `BatchQPFunction` as a Function of its own, so that it can carry a `vmap` rule: (gx, gy) -> the
+    gradients `want` of the instances `sel` of `rb`, through `ResidentBatch.adjoint`.  Under `torch.func.vmap` the cotangents
+    arrive with a batch axis and go to the library as ONE launch with a leading axis [ncot x k x .]."""
+
+    @staticmethod
+    def forward(rb, sel, stamp, want, gx, gy):
+        return BatchQPAdjoint._pull(rb, sel, stamp, want, gx, gy, ())
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError("BatchQPAdjoint: the adjoint of the batch is not differentiable a second time")
+
+    @staticmethod
+    def vmap(info, in_dims, rb, sel, stamp, want, gx, gy):
+        ncot = info.batch_size
+
+        def front(g, dim):  # the batch axis to the front; a cotangent that arrives unbatched is the same for every one
+            if g is None:
+                return None
+            return g.unsqueeze(0).expand((ncot,) + tuple(g.shape)) if dim is None else g.movedim(dim, 0)
+
+        out = BatchQPAdjoint._pull(rb, sel, stamp, want, front(gx, in_dims[4]), front(gy, in_dims[5]), (ncot,))
+        return out, tuple(0 for _ in out)
+
+    @staticmethod
+    def _pull(rb, sel, stamp, want, gx, gy, lead):
+        if not stamp_holds(rb, stamp, sel):
+            raise RuntimeError("BatchQPFunction: the batch has been solved again since this forward; its handle holds one "
+                               "solution, so backward must run before the next forward")
+        k = rb.count if sel is None else len(sel)
+        cols = dict(q=rb.n, l=rb.m, u=rb.m, Px=rb.nnzP, Ax=rb.nnzA)
+        ref = gx if gx is not None else gy
+        out = {w: torch.empty(lead + (k, cols[w]), dtype=torch.float64, device=ref.device) for w in want}
+        _sync(ref)
+        rb.adjoint(dx=None if gx is None else gx.contiguous(), dy=None if gy is None or rb.m == 0 else gy.contiguous(), want=want, out=out,
+                   rows=sel)
+        return tuple(out[w] for w in want)
+
+
 class BatchQPFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rb, q, l, u, Px, Ax, rows=None):
+    def forward(rb, q, l, u, Px, Ax, rows=None):
         given = dict(zip(NAMES, (q, l, u, Px, Ax)))
         tensors = [t for t in given.values() if t is not None]
         if not tensors:
             raise ValueError("BatchQPFunction: at least one of q, l, u, Px, Ax must be a tensor")
-        for name, t in given.items():
-            if t is not None and (not t.is_cuda or t.dtype != torch.float64):
-                raise ValueError(f"{name}: expected a float64 CUDA tensor")
+        _check_inputs(given)
         sel = None if rows is None else selection(rows.cpu().numpy() if torch.is_tensor(rows) else rows, rb.count)
         k = rb.count if sel is None else len(sel)
         ref = tensors[0]
@@ -68,9 +128,15 @@ class BatchQPFunction(torch.autograd.Function):
         info = torch.empty((k, 6), dtype=torch.float64, device=ref.device)
         rb.solve(out=(x, y if rb.m else None, info), rows=sel)
         rb._qp_layer_info = info
-        ctx.rb, ctx.sel, ctx.k, ctx.stamp = rb, sel, k, stamp_forward(rb, sel)
-        ctx.given = tuple(name for name, t in given.items() if t is not None)  # for jvp: the inputs that have a tangent
+        rb._qp_layer_served = (sel, k, stamp_forward(rb, sel))  # for setup_context, which runs next
         return x, y
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        rb = inputs[0]
+        ctx.rb = rb
+        ctx.sel, ctx.k, ctx.stamp = rb._qp_layer_served
+        ctx.given = tuple(name for name, t in zip(NAMES, inputs[1:6]) if t is not None)  # for jvp: the inputs that have a tangent
 
     @staticmethod
     def jvp(ctx, t_rb, tq, tl, tu, tPx, tAx, *t_rows):
@@ -98,12 +164,10 @@ class BatchQPFunction(torch.autograd.Function):
         want = tuple(k for k in NAMES if need[k] and cols[k] > 0)
         if gx is None and gy is None:
             return (None,) * nargs
-        dev = gx.device if gx is not None else gy.device
-        out = {k: torch.empty((ctx.k, cols[k]), dtype=torch.float64, device=dev) for k in want}
-        _sync(gx if gx is not None else gy)
-        rb.adjoint(dx=None if gx is None else gx.contiguous(), dy=None if gy is None or rb.m == 0 else gy.contiguous(), want=want, out=out,
-                   rows=ctx.sel)
-        grads = {k: (out[k] if k in out else (torch.zeros((ctx.k, 0), dtype=torch.float64, device=dev) if need[k] else None)) for k in NAMES}
+        ref = gx if gx is not None else gy
+        out = dict(zip(want, BatchQPAdjoint.apply(rb, ctx.sel, ctx.stamp, want, gx, gy))) if want else {}
+        # a wanted gradient of width zero: zeros shaped like the others (`ref` carries the batch axis of a vmapped pull-back)
+        grads = {k: (out[k] if k in out else (ref.new_zeros((ctx.k, 0)) if need[k] else None)) for k in NAMES}
         return (None,) + tuple(grads[k] for k in NAMES) + (None,) * (nargs - 6)
 
 
@@ -121,5 +185,17 @@ class BatchQPLayer(torch.nn.Module):
             x, y = BatchQPFunction.apply(self.rb, q, l, u, Px, Ax)
         else:
             x, y = BatchQPFunction.apply(self.rb, q, l, u, Px, Ax, rows)
-        self.info = self.rb._qp_layer_info
+        self.info, self._served = self.rb._qp_layer_info, self.rb._qp_layer_served
         return x, y
+
+    def jacobian(self, of=("x",), wrt=("q", "l", "u"), mode="auto", out_rows=None, chunk=None):
+        """`ResidentBatch.jacobian` of the instances of the last forward, as tensors on the handle's device: a dict
+        {(o, w): [k x cols(o) x cols(w)]} plus "act" and "status".  Raises RuntimeError when one of these instances has been
+        served by a later forward on the same handle (the stamp rule)."""
+        served = getattr(self, "_served", None)
+        if served is None:
+            raise RuntimeError("BatchQPLayer.jacobian: no forward has run yet")
+        sel, _, stamp = served
+        if not stamp_holds(self.rb, stamp, sel):
+            raise RuntimeError("BatchQPLayer.jacobian: the batch has been solved again since the last forward of this layer")
+        return self.rb.jacobian(of=of, wrt=wrt, mode=mode, rows=sel, out_rows=out_rows, chunk=chunk, device=True)

@@ -234,6 +234,9 @@ EXT_SYMBOLS = {
     # the reading calls for a selection: rows and k after the handle, every array compact ([k x .], [ndir x k x .])
     "osqp_amd_batch_adjoint_rows": (c_int, [C.c_void_p, c_int_p, c_int] + [C.c_void_p] * 9 + [c_int]),
     "osqp_amd_batch_jvp_rows": (c_int, [C.c_void_p, c_int_p, c_int, c_int] + [C.c_void_p] * 9 + [c_int]),
+    # several cotangents per adjoint launch: ncot before the arrays, which are cotangent-major ([ncot x count x .], [ncot x k x .])
+    "osqp_amd_batch_adjoint_multi": (c_int, [C.c_void_p, c_int] + [C.c_void_p] * 9 + [c_int]),
+    "osqp_amd_batch_adjoint_multi_rows": (c_int, [C.c_void_p, c_int_p, c_int, c_int] + [C.c_void_p] * 9 + [c_int]),
     "osqp_amd_batch_polish_status_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, c_int]),
     "osqp_amd_batch_certificates_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_device_alloc": (C.c_void_p, [c_int, c_int]),
