@@ -390,6 +390,18 @@ c_int osqp_amd_get_iterate(OSQPWorkspace *work, c_float *x_out, c_float *y_out);
  *  op 3: y = K^{-1} x through the linear-system back-end (n+m -> n+m)        */
 c_int osqp_amd_apply(OSQPWorkspace *work, c_int op, const c_float *in, c_float *out);
 
+/* Which kernel and which layout the products of one matrix run on (tests only; read from what the host already
+ * holds, no device work).  which: 0 A, 1 A', 2 P (full symmetric).  Fills out[0..count):
+ *  0 kernel, as stats[12]: 0 CSR (k_spmv), 2 LDS-staged panels, 3 wide panels through L2
+ *  1 lanes per row G of the CSR kernel (what k_spmv<G> would be launched with)
+ *  2 panel shift (panels of 2^shift columns)   3 panels B   4 panels per group Gp   5 groups NG (the reduction depth)
+ *  6 tiles   7 slices   8 padded entries of the sliced copy   9 stored entries (nnz)
+ * 10 compact (the CSR column / value arrays of this matrix released) 0 / 1
+ * Entries 2-8 are 0 when the matrix runs on the CSR kernel.  Returns the number of entries written (at most
+ * OSQP_AMD_LAYOUT_COUNT), 0 on a bad argument. */
+#define OSQP_AMD_LAYOUT_COUNT 11
+c_int osqp_amd_spmv_layout(const OSQPWorkspace *work, c_int which, c_float *out, c_int count);
+
 /* Which kernel the last batched solve of this process ran (tests, benchmarks): -1 the 512-thread kernel (one QP per eight
  * wavefronts, the factorisation through an n x n scratch in global memory), k >= 0 entry k of the table of instantiations of
  * the four-wavefront kernel (csrc/batch_common.hpp OQ_QUAD_ENTRIES; 0 = the MPC family with its shape compiled in), -2 none yet. */

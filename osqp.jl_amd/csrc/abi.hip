@@ -762,6 +762,25 @@ c_int osqp_amd_apply(OSQPWorkspace *w, c_int op, const c_float *in, c_float *out
   });
 }
 
+c_int osqp_amd_spmv_layout(const OSQPWorkspace *w, c_int which, c_float *out, c_int count) {
+  if (!w || !out || which < 0 || which > 2) return 0;
+  const Engine &e = *E(w);
+  const DevCsr &M = which == 0 ? e.A : (which == 1 ? e.At : e.Pf);
+  const DevPanel &P = M.panel;
+  c_float v[OSQP_AMD_LAYOUT_COUNT] = {0};
+  v[0] = P.active ? (P.wide ? 3.0 : 2.0) : 0.0;
+  v[1] = (c_float)M.group;
+  if (P.active) {
+    v[2] = (c_float)P.shift; v[3] = (c_float)P.B; v[4] = (c_float)P.Gp; v[5] = (c_float)P.NG;
+    v[6] = (c_float)P.ntiles; v[7] = (c_float)P.slice_base.n; v[8] = (c_float)P.padded;
+  }
+  v[9] = (c_float)M.nnz;
+  v[10] = M.compact ? 1.0 : 0.0;
+  c_int k = 0;
+  for (; k < count && k < OSQP_AMD_LAYOUT_COUNT; k++) out[k] = v[k];
+  return k;
+}
+
 c_int osqp_amd_set_device(c_int device) {
   return guarded([&]() { HIP_CHECK(hipSetDevice((int)device)); return 0; });
 }

@@ -56,6 +56,7 @@ constexpr int kBatch = OQ_SELL_BATCH;  // entries of a slice per lane whose load
 constexpr int kWaves = kThreads / 64;
 constexpr int kTileRowsMax = 3968;  // row sums of a tile are staged in LDS (31 KB next to the 128 KB x panel)
 constexpr int kSortN = 4096;        // power of two >= kTileRowsMax: per-tile ordering of the rows in LDS
+constexpr int64_t kLenMax = 0x7FFFF;  // longest (row, panel) cell the 32-bit sort key of that ordering can hold (19 bits above the 12 of the row)
 
 // tunables (defaults from the sweep in profiles/r01_e_panel_sweep.md; overridable for experiments)
 int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
@@ -86,6 +87,12 @@ __global__ __launch_bounds__(kBlock) void k_panel_count(int rows, int B, int shi
     cnt[(size_t)b * rows + row] = hi - lo;
     cellsrc[(size_t)b * rows + row] = (uint32_t)lo;
   }
+}
+
+// *over = 1 when a (row, panel) cell holds more than `limit` entries (every writer stores the same value)
+__global__ __launch_bounds__(kBlock) void k_cell_over(int64_t cells, int64_t limit, const int64_t *__restrict__ cnt, int *__restrict__ over) {
+  const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c < cells && cnt[c] > limit) *over = 1;
 }
 
 // gcnt[g * rows + i] = entries of row i inside the panels of group g
@@ -148,7 +155,8 @@ __global__ __launch_bounds__(kBlock) void k_tile_ends(int rows, int ntiles, cons
 }
 
 // The rows of a tile ordered by length inside the panel, longest first, ties by row id: bitonic sort of
-// (maxlen - length) << 12 | local row in LDS (one 1024-thread workgroup; lengths <= W <= 2^15, rows < 2^12).
+// (kLenMax - length) << 12 | local row in LDS (one 1024-thread workgroup; rows < 2^12, lengths <= kLenMax = 2^19 - 1:
+// always so on LDS panels, W <= 2^15; panel_build refuses a wide layout with a longer cell before anything is sized).
 // On return key[i] & 4095 is the i-th local row and *nz_rows the number of rows with at least one entry.
 __device__ void order_tile_rows(uint32_t *key, const int64_t *__restrict__ po, int r0, int nrows, int *nz_rows) {
   if (threadIdx.x == 0) *nz_rows = 0;
@@ -158,7 +166,7 @@ __device__ void order_tile_rows(uint32_t *key, const int64_t *__restrict__ po, i
     uint32_t k = 0xFFFFFFFFu;
     if (i < nrows) {
       const uint32_t len = (uint32_t)(po[r0 + i + 1] - po[r0 + i]);
-      k = ((0x7FFFFu - len) << 12) | (uint32_t)i;
+      k = (((uint32_t)kLenMax - len) << 12) | (uint32_t)i;
       mine += len > 0;
     }
     key[i] = k;
@@ -177,7 +185,7 @@ __device__ void order_tile_rows(uint32_t *key, const int64_t *__restrict__ po, i
       __syncthreads();
     }
 }
-__device__ __forceinline__ uint32_t key_len(uint32_t key) { return 0x7FFFFu - (key >> 12); }
+__device__ __forceinline__ uint32_t key_len(uint32_t key) { return (uint32_t)kLenMax - (key >> 12); }
 
 // pass 1: number of slices and padded size of every tile
 __global__ __launch_bounds__(kThreads) void k_tile_measure(int rows, const int *__restrict__ tile_b, const int *__restrict__ tile_r0,
@@ -756,6 +764,19 @@ __global__ __launch_bounds__(kBlock) void k_sell_slot_of_pos(int rows, int shift
 
 size_t spmv_lds_bytes(int shift) { return (sizeof(double) << shift) + sizeof(double) * kTileRowsMax; }
 
+// The dynamic LDS a kernel may be launched with is an attribute of the function (per device), not of the launch, and a
+// process can hold workspaces of different panel widths at once: the attribute is raised when a width needs more than
+// was last allowed and never lowered -- the width of the first (or of the latest) layout says nothing about the next
+// launch.  seen: what this process has set so far, by device.
+void allow_dynamic_lds(const void *fn, size_t bytes, size_t (&seen)[64]) {
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  size_t &allowed = seen[dev & 63];
+  if (bytes <= allowed) return;
+  HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  allowed = bytes;
+}
+
 int64_t read_i64(const int64_t *dev, hipStream_t s) {
   int64_t v = 0;
   HIP_CHECK(hipMemcpyAsync(&v, dev, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -833,6 +854,18 @@ void panel_build(DevCsr &M, hipStream_t s, uint32_t *slot, bool will_compact, co
   DevBuf<uint32_t> cellsrc((size_t)cells);
   OQ_LAUNCH(k_panel_count, dim3(blocks_for((int64_t)M.rows * 64)), dim3(kBlock), 0, s, M.rows, P.B, P.shift, M.rowptr.get(),
             M.col.get(), cnt.get(), cellsrc.get());
+  // the per-tile ordering packs a row's length inside the panel into 19 bits of its sort key (order_tile_rows): an LDS
+  // panel is at most 2^15 columns wide, a wide one can be 2^19 or 2^20 -- a budget row over such a panel would wrap the key,
+  // and the slice tables are sized from it.  Such a matrix stays on the CSR kernel.
+  if ((int64_t)P.W > kLenMax) {
+    DevBuf<int> over(1);
+    over.zero(s);
+    OQ_LAUNCH(k_cell_over, dim3(blocks_for(cells)), dim3(kBlock), 0, s, cells, kLenMax, cnt.get(), over.get());
+    int h_over = 0;
+    over.download(&h_over, 1, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (h_over) throw PanelRefused(6, "panel layout: a row has more than 2^19 - 1 entries inside one wide panel");
+  }
   exclusive_scan(cnt.get(), off.get(), cells, s);
   P.Gp = panel_group_size(M, P.B);
   P.NG = (P.B + P.Gp - 1) / P.Gp;
@@ -924,9 +957,10 @@ void panel_build(DevCsr &M, hipStream_t s, uint32_t *slot, bool will_compact, co
     fill(3);
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  if (!P.wide)
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_spmv_sell<uint16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)spmv_lds_bytes(P.shift)));
+  if (!P.wide) {
+    static size_t allowed[64] = {0};
+    allow_dynamic_lds((const void *)k_spmv_sell<uint16_t, true>, spmv_lds_bytes(P.shift), allowed);
+  }
   P.active = true;
 }
 
@@ -966,11 +1000,8 @@ void spmv_pair(const DevCsr &Ma, const DevCsr &Mb, const double *x, double *ya, 
     return t;
   };
   const DevPanel &A = Ma.panel, &B = Mb.panel;
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_spmv_sell_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spmv_lds_bytes(A.shift)));
-    attr_set = true;
-  }
+  static size_t allowed[64] = {0};
+  allow_dynamic_lds((const void *)k_spmv_sell_pair, spmv_lds_bytes(A.shift), allowed);
   OQ_LAUNCH(k_spmv_sell_pair, dim3(A.ntiles + B.ntiles), dim3(kThreads), spmv_lds_bytes(A.shift), s, side(Ma), side(Mb), A.shift, x, g_skip);
   ReduceSide ra{Ma.rows, A.NG, reduce_grid(Ma.rows), A.partial.get(), ya, 0.0, nullptr, extra_a ? *extra_a : SpmvExtra()};
   ReduceSide rb{Mb.rows, B.NG, reduce_grid(Mb.rows), B.partial.get(), yb, gamma_b, vb, SpmvExtra()};

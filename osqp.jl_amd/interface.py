@@ -511,3 +511,16 @@ def stats(model, count=26):
     out = np.zeros(count)
     k = model.lib.osqp_amd_get_stats(model.workspace, _fptr(out), count)
     return out[:k]
+
+
+SPMV_LAYOUT_FIELDS = ("kernel", "G", "shift", "B", "Gp", "NG", "tiles", "slices", "padded", "nnz", "compact")
+
+
+def spmv_layout(model, which):
+    """Extension (tests): osqp_amd_spmv_layout as a dict of ints -- which kernel the products of A (0), A' (1) or P (2)
+    run on and the shape of its panel layout (include/osqp_amd.h)."""
+    out = np.zeros(len(SPMV_LAYOUT_FIELDS))
+    k = model.lib.osqp_amd_spmv_layout(model.workspace, which, _fptr(out), len(out))
+    if k != len(out):
+        raise OSQPError("osqp_amd_spmv_layout: bad argument")
+    return {name: int(v) for name, v in zip(SPMV_LAYOUT_FIELDS, out)}

@@ -184,6 +184,7 @@ EXT_SYMBOLS = {
     "osqp_amd_iterate": (c_int, [Workspace_p, c_int]),
     "osqp_amd_get_iterate": (c_int, [Workspace_p, c_float_p, c_float_p]),
     "osqp_amd_apply": (c_int, [Workspace_p, c_int, c_float_p, c_float_p]),
+    "osqp_amd_spmv_layout": (c_int, [Workspace_p, c_int, c_float_p, c_int]),
     "osqp_amd_batch_solve": (
         c_int,
         [c_int, c_int, c_int, c_int_p, c_int_p, c_float_p, c_int_p, c_int_p, c_float_p,

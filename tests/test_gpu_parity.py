@@ -170,6 +170,10 @@ def test_panel_spmv_matches_scipy(product_lib, oracle_lib, monkeypatch, mode, gr
     oracle_lib.oracle_data_free(d)
     m = oq.Model(product_lib)
     oq.setup_generated(m, 0, n, k, 21, scaling=0, verbose=False, linsys_solver="pcg")
+    for which in (0, 1, 2):  # A, A' and P really run the kernel the test names, with the panels per group it asks for
+        lay = oq.spmv_layout(m, which)
+        assert lay["kernel"] == int(mode) and lay["Gp"] == min(int(group), lay["B"]), (which, lay)
+        assert lay["B"] == (3 if mode == "2" else 1) and lay["compact"] == 0, (which, lay)
     rng = np.random.default_rng(5)
     xv, yv = rng.standard_normal(n), rng.standard_normal(n)
     Pfull = P + sp.triu(P, 1).T
@@ -193,6 +197,8 @@ def test_panel_spmv_matches_scipy(product_lib, oracle_lib, monkeypatch, mode, gr
     mp_ = oq.Model(product_lib); oq.setup_generated(mp_, 0, n, k, 21, **opts); rp = oq.solve(mp_)
     monkeypatch.setenv("OSQP_AMD_PANEL", "0")
     mc = oq.Model(product_lib); oq.setup_generated(mc, 0, n, k, 21, **opts); rc = oq.solve(mc)
+    for which in (0, 1, 2):
+        assert oq.spmv_layout(mp_, which)["kernel"] == int(mode) and oq.spmv_layout(mc, which)["kernel"] == 0
     assert rp.info.status == rc.info.status == "Solved" and rp.info.iter == rc.info.iter
     assert np.max(np.abs(rp.x - rc.x)) <= 1e-9 and np.max(np.abs(rp.y - rc.y)) <= 1e-9
 
@@ -223,6 +229,9 @@ def test_compact_mode(product_lib, oracle_lib, monkeypatch):
     m0 = oq.Model(product_lib)
     oq.setup_generated(m0, 0, n, k, 21, scaling=0, verbose=False, linsys_solver="pcg")
     assert oq.stats(m0)[18] == 1.0
+    for which in (0, 1, 2):  # all three on the LDS-staged panels, their CSR arrays released
+        lay = oq.spmv_layout(m0, which)
+        assert (lay["kernel"], lay["B"], lay["compact"]) == (2, 3, 1), (which, lay)
     bytes_compact = oq.stats(m0)[9]
     products(m0, Pu, A)
     # partial updates by index, then everything
@@ -244,6 +253,9 @@ def test_compact_mode(product_lib, oracle_lib, monkeypatch):
         monkeypatch.setenv("OSQP_AMD_COMPACT_NNZ", limit)
         m = oq.Model(product_lib); oq.setup_generated(m, 0, n, k, 21, **opts)
         assert oq.stats(m)[18] == (1.0 if mode == "compact" else 0.0)
+        for which in (0, 1, 2):
+            lay = oq.spmv_layout(m, which)
+            assert (lay["kernel"], lay["compact"]) == (2, int(mode == "compact")), (which, lay)
         if mode == "csr":
             assert oq.stats(m)[9] > bytes_compact + 12 * 2 * A.nnz  # what the three CSR copies weigh (roughly)
         r1 = oq.solve(m)
