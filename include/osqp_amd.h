@@ -672,6 +672,55 @@ c_int osqp_amd_device_copy(void *dst, const void *src, c_int bytes, c_int kind, 
  * returns infeasibility certificates (osqp_amd_batch_certificates) and takes settings updates after setup
  * (osqp_amd_batch_update_setting: the names of osqp_update_*; `time_limit` and `verbose` are stored and ignored as above). */
 
+/* ---- Adjoint derivatives of the solution of a single model (upstream OSQP 1.0:
+ * adjoint_derivative_compute / _get_mat / _get_vec) ----
+ *
+ * osqp_amd_adjoint differentiates a scalar loss through the solution the last osqp_solve left in `work`: from ncot
+ * pairs g_x = dloss/dx (dx, [ncot x n]) and g_y = dloss/dy (dy, [ncot x m]; either may be NULL = 0) it returns per pair
+ * dloss/dq (dq [ncot x n]), dloss/dl and dloss/du (dl, du [ncot x m]) and the gradients of the stored values of P and A
+ * (dPx [ncot x nnz(triu P)], dAx [ncot x nnz(A)]) indexed by the caller's nnz index -- the index space of osqp_update_P /
+ * _A, the setup-time order also where the columns of A came unsorted.  Any of the five may be NULL: not wanted, not
+ * computed.  act ([m], or NULL) receives the active set: -1 lower, 0 inactive, 1 upper.  All pointers are host pointers.
+ *
+ *   With L / U the rows active at the lower / upper bound, a = L u U and K = [P, Aa'; Aa, 0], one solve
+ *   K [r_x; r_a] = [g_x; (g_y)_a] per pair gives, with r_y = r_a scattered to length m (0 on inactive rows),
+ *     dq = -r_x;   dl_i = r_y,i on L, du_i = r_y,i on U, 0 elsewhere;
+ *     dPx(i, i) = -r_x,i x_i;   dPx(i, j) = -(r_x,i x_j + r_x,j x_i) for i < j (the stored entry stands for both halves);
+ *     dAx(i, j) = -(y_i r_x,j + r_y,i x_j).
+ *   Active rows: polish's rule on the workspace's scaled (z, y, l, u) -- z - l < -y lower, u - z < y upper -- and a row with
+ *   l == u is always active and counts as lower.  The solve runs on the scaled data through the factorisation of
+ *   [P + delta I, Aa'; Aa, -delta I], followed by `polish_refine_iter` refinement steps against the unregularised matrix
+ *   (0 steps: the regularised answer, made accurate by one step against the REGULARISED matrix -- the factorisation does not
+ *   pivot and its solve alone is good to ~1e-8).  A singular K is not detected: the refined regularised answer is returned.
+ *
+ *   The factor is KEPT: the first call after a solve classifies the rows, analyses and factorises (the work
+ *   of a polish; measured: DESIGN.md section 14); later calls on the same solution reuse it, ncot pairs in one call are ncot solve-and-refine passes on it, and
+ *   pair c of a call has the bits of a call with that pair alone.  osqp_solve, every osqp_update_* (settings included: delta
+ *   is inside the matrix), every osqp_warm_start*, osqp_amd_iterate, osqp_cleanup and osqp_amd_adjoint_release drop it; the
+ *   factor is as large as a polish's, so a caller who is done with a solution releases it.  The call changes nothing else:
+ *   not info, not the solution, not the iterate, rho or the ADMM factor -- solve, adjoint, solve gives the bits and the
+ *   iteration count of solve, solve.
+ *
+ *   Returns 0, or non-zero with the reason in osqp_amd_last_error and no output written: 7 NULL workspace; 1 ncot < 1, a
+ *   gradient wanted with dx and dy both NULL, nothing wanted at all, no current solution (no osqp_solve yet, or a data
+ *   update, warm start or osqp_amd_iterate after the last one: call osqp_solve), the last solve did not end with status
+ *   OSQP_SOLVED (solved inaccurate is refused too); 6 a compact or a row-sharded workspace (no CSR arrays, no reduced KKT
+ *   matrix; an iterative adjoint on the operator of the indirect back-end is not built), a reduced factor that is too
+ *   large; 4 a failed numeric factorisation. */
+c_int osqp_amd_adjoint(OSQPWorkspace *work, c_int ncot,
+                       const c_float *dx /* [ncot x n] or NULL = 0 */, const c_float *dy /* [ncot x m] or NULL = 0 */,
+                       c_float *dq /* [ncot x n] */, c_float *dl /* [ncot x m] */, c_float *du /* [ncot x m] */,
+                       c_float *dPx /* [ncot x nnz(triu P)] */, c_float *dAx /* [ncot x nnz(A)] */,
+                       c_float *act /* [m] or NULL */);
+/* Drop the kept factor now.  0, also when none is kept; 7 on a NULL workspace. */
+c_int osqp_amd_adjoint_release(OSQPWorkspace *work);
+/* Fills out[0..count): 0 factor builds so far, 1 KKT solves so far (1 + polish_refine_iter per pair; 2 at polish_refine_iter = 0), 2, 3 n_low and
+ * n_upp of the kept factor (0 if none), 4 1 if a factor is kept, 5 device bytes the kept factor holds with its index
+ * arrays and scratch.  Like osqp_amd_get_stats it returns the number of entries written (at most
+ * OSQP_AMD_ADJOINT_STATS_COUNT), 0 on a NULL argument. */
+#define OSQP_AMD_ADJOINT_STATS_COUNT 6
+c_int osqp_amd_adjoint_stats(const OSQPWorkspace *work, c_float *out, c_int count);
+
 /* Select the HIP device for workspaces created afterwards by this process
  * (one process per GPU: pass LOCAL_RANK). */
 c_int osqp_amd_set_device(c_int device);

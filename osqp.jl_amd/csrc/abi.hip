@@ -40,6 +40,14 @@ struct DeviceGuard {
 #define OQ_ON_DEVICE(w) DeviceGuard _dev_guard(E(w)->device)
 const Engine *E(const OSQPWorkspace *w) { return &((const Impl *)w->impl)->eng; }
 
+// The factor osqp_amd_adjoint keeps belongs to one solution under one set of settings (delta is inside its matrix): every entry
+// that changes the data, the iterate or a setting drops it; the first two also end the solution's being current.
+void adjoint_moved_on(OSQPWorkspace *w, bool solution_too) {
+  Engine &e = *E(w);
+  if (solution_too) e.solution_current = false;
+  model_adjoint_release(e);
+}
+
 }  // namespace
 
 namespace oq {
@@ -531,7 +539,12 @@ c_int osqp_amd_setup_generated_sharded(OSQPWorkspace **workp, c_int kind, c_int 
 c_int osqp_solve(OSQPWorkspace *w) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->solve(); });
+  return guarded([&]() {
+    adjoint_moved_on(w, true);
+    const int rc = E(w)->solve();
+    E(w)->solution_current = rc == 0;
+    return rc;
+  });
 }
 
 c_int osqp_cleanup(OSQPWorkspace *w) {
@@ -544,38 +557,38 @@ c_int osqp_cleanup(OSQPWorkspace *w) {
 c_int osqp_update_lin_cost(OSQPWorkspace *w, const c_float *q_new) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->update_lin_cost(q_new); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_lin_cost(q_new); });
 }
 c_int osqp_update_bounds(OSQPWorkspace *w, const c_float *l_new, const c_float *u_new) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->update_bounds(l_new, u_new); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_bounds(l_new, u_new); });
 }
 c_int osqp_update_lower_bound(OSQPWorkspace *w, const c_float *l_new) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->update_bounds(l_new, nullptr); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_bounds(l_new, nullptr); });
 }
 c_int osqp_update_upper_bound(OSQPWorkspace *w, const c_float *u_new) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->update_bounds(nullptr, u_new); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_bounds(nullptr, u_new); });
 }
 c_int osqp_update_P(OSQPWorkspace *w, const c_float *Px_new, const c_int *Px_new_idx, c_int P_new_n) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->update_PA(Px_new, Px_new_idx, P_new_n, nullptr, nullptr, 0, true, false); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_PA(Px_new, Px_new_idx, P_new_n, nullptr, nullptr, 0, true, false); });
 }
 c_int osqp_update_A(OSQPWorkspace *w, const c_float *Ax_new, const c_int *Ax_new_idx, c_int A_new_n) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->update_PA(nullptr, nullptr, 0, Ax_new, Ax_new_idx, A_new_n, false, true); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_PA(nullptr, nullptr, 0, Ax_new, Ax_new_idx, A_new_n, false, true); });
 }
 c_int osqp_update_P_A(OSQPWorkspace *w, const c_float *Px_new, const c_int *Px_new_idx, c_int P_new_n, const c_float *Ax_new,
                       const c_int *Ax_new_idx, c_int A_new_n) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->update_PA(Px_new, Px_new_idx, P_new_n, Ax_new, Ax_new_idx, A_new_n, true, true); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_PA(Px_new, Px_new_idx, P_new_n, Ax_new, Ax_new_idx, A_new_n, true, true); });
 }
 
 c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
@@ -584,6 +597,7 @@ c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
   if (!setting_ok_rho(rho_new)) return 1;
   return guarded([&]() {
     Engine &e = *E(w);
+    adjoint_moved_on(w, false);
     e.begin_update();
     int rc = e.update_rho(rho_new);
     w->settings->rho = e.st.rho;
@@ -599,6 +613,7 @@ c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
     if (!setting_ok_##field(v)) return 1;                 \
     OQ_ON_DEVICE(w);                                      \
     return guarded([&]() {                                \
+      adjoint_moved_on(w, false);                         \
       E(w)->st.field = v;                                 \
       E(w)->settings_changed();                           \
       w->settings->field = v;                             \
@@ -624,6 +639,7 @@ c_int osqp_update_polish(OSQPWorkspace *w, c_int v) {
   OQ_ON_DEVICE(w);
   if (!setting_ok_polish(v)) return 1;
   return guarded([&]() {
+    adjoint_moved_on(w, false);
     E(w)->st.polish = v;
     w->settings->polish = v;
     w->info->polish_time = 0.0;
@@ -634,17 +650,17 @@ c_int osqp_update_polish(OSQPWorkspace *w, c_int v) {
 c_int osqp_warm_start(OSQPWorkspace *w, const c_float *x, const c_float *y) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->warm_start(x, y); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->warm_start(x, y); });
 }
 c_int osqp_warm_start_x(OSQPWorkspace *w, const c_float *x) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->warm_start(x, nullptr); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->warm_start(x, nullptr); });
 }
 c_int osqp_warm_start_y(OSQPWorkspace *w, const c_float *y) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->warm_start(nullptr, y); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->warm_start(nullptr, y); });
 }
 
 // ---------------------------------------------------------------- extensions
@@ -691,6 +707,7 @@ c_float osqp_amd_time_kernel(OSQPWorkspace *w, c_int which, c_int reps) {
     Engine &e = *E(w);
     hipStream_t s = e.stream;
     if (which == 3) { result = e.lin->time_solve((int)reps); return 0; }
+    if (which == 5) adjoint_moved_on(w, true);  // advances the iterate, as osqp_amd_iterate does
     // sharded: the local block's product on whatever the gather buffers hold (exchange timed separately, id 7)
     const double *xin = e.comm ? e.gn.get() : e.x.get(), *yin = e.comm ? e.gm.get() : e.y.get();
     auto run = [&]() {
@@ -726,7 +743,7 @@ c_float osqp_amd_time_kernel(OSQPWorkspace *w, c_int which, c_int reps) {
 c_int osqp_amd_iterate(OSQPWorkspace *w, c_int iters) {
   if (!w) return 7;
   OQ_ON_DEVICE(w);
-  return guarded([&]() { return E(w)->iterate(iters); });
+  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->iterate(iters); });
 }
 
 c_int osqp_amd_get_iterate(OSQPWorkspace *w, c_float *x_out, c_float *y_out) {
@@ -778,6 +795,42 @@ c_int osqp_amd_spmv_layout(const OSQPWorkspace *w, c_int which, c_float *out, c_
   v[10] = M.compact ? 1.0 : 0.0;
   c_int k = 0;
   for (; k < count && k < OSQP_AMD_LAYOUT_COUNT; k++) out[k] = v[k];
+  return k;
+}
+
+// ---- adjoint derivatives of the solution of a single model (csrc/direct_adjoint.hpp) ----
+c_int osqp_amd_adjoint(OSQPWorkspace *w, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
+                       c_float *dPx, c_float *dAx, c_float *act) {
+  if (!w) { set_last_error("osqp_amd_adjoint: no workspace"); return 7; }
+  if (ncot < 1) { set_last_error("osqp_amd_adjoint: ncot must be at least 1"); return 1; }
+  if (ncot > 2147483647LL) { set_last_error("osqp_amd_adjoint: ncot out of range"); return 1; }
+  if ((dq || dl || du || dPx || dAx) && !dx && !dy) {
+    set_last_error("osqp_amd_adjoint: a gradient is wanted but dx and dy are both NULL");
+    return 1;
+  }
+  if (!dq && !dl && !du && !dPx && !dAx && !act) { set_last_error("osqp_amd_adjoint: no output is wanted"); return 1; }
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    if (!e.solution_current)
+      throw Error(1, "osqp_amd_adjoint: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
+    if (w->info->status_val != OSQP_SOLVED)
+      throw Error(1, std::string("osqp_amd_adjoint: the last osqp_solve did not end with status Solved (") + w->info->status +
+                         "): there is no solution to differentiate");
+    return model_adjoint_run(e, (int)ncot, dx, dy, dq, dl, du, dPx, dAx, act);
+  });
+}
+c_int osqp_amd_adjoint_release(OSQPWorkspace *w) {
+  if (!w) { set_last_error("osqp_amd_adjoint_release: no workspace"); return 7; }
+  OQ_ON_DEVICE(w);
+  return guarded([&]() { model_adjoint_release(*E(w)); return 0; });
+}
+c_int osqp_amd_adjoint_stats(const OSQPWorkspace *w, c_float *out, c_int count) {
+  if (!w || !out) return 0;
+  double v[OSQP_AMD_ADJOINT_STATS_COUNT];
+  model_adjoint_stats(*E(w), v);
+  c_int k = 0;
+  for (; k < count && k < OSQP_AMD_ADJOINT_STATS_COUNT; k++) out[k] = v[k];
   return k;
 }
 

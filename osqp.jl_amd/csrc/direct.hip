@@ -48,6 +48,8 @@ struct Step { int kind; int a, b, G; int U = 2, L = 64; };  // L: lanes per row 
 
 // ------------------------------------------------------------------ factor object
 int level_limit();
+int64_t factor_limit(const Engine &e, bool forced);
+double factor_flops_limit();
 struct LdlFactor {
   Engine &e;
   Symbolic S;
@@ -62,6 +64,15 @@ struct LdlFactor {
   int schur_ncols = 0;
   DevBuf<double> dsP1, dsP2;    // shares of the symmetric dense product, per tile (k_dense_apply_sym)
   double *Sinv = nullptr;       // which of S0a / S0b holds -S0^-1 after the last factorisation
+  // The explicit inverse is formed by Gauss-Jordan sweeps without pivoting: on a block that is badly conditioned (tiny sigma /
+  // delta pivots next to the 1 / sigma fill of variables without a cost term: tests/qp_zoo.py lasso_data) it can be useless where
+  // the triangular solves of the same pivots still serve.  So every factorisation PROBES it: r = v - S0 (S0^-1 v) for one fixed
+  // vector, from a copy of S0 taken before the sweeps; a residual above dense_probe_tol() makes refactor return 7 and the owner
+  // builds the factor again without the block (dense_top = false).  (The blocked inverse of 512 pivots and more is not probed.)
+  bool allow_dense_top = true;
+  DevBuf<double> S0chk, probe_v, probe_w, probe_r;
+  double dense_residual = 0.0;  // of the last factorisation
+  static double dense_probe_tol() { const char *v = getenv("OSQP_AMD_DENSE_PROBE_TOL"); return v ? atof(v) : 1e-6; }
   int ldD = 0;                  // leading dimension of the dense block's array (kD, or kD padded to 64 for the block sweeps)
   std::vector<char> long_rows;  // per level: phase 2 of the factorisation through dense work rows (k_ldl_entries_w)
   size_t w_half = 0;            // doubles in one half of W
@@ -133,8 +144,8 @@ struct LdlFactor {
   }
 
   LdlFactor(Engine &en, const std::vector<int> &row_map, int mr_, double sigma_, double cconst_, int64_t limit,
-            double flops_limit = 0.0)
-      : e(en), sigma(sigma_), cconst(cconst_) {
+            double flops_limit = 0.0, bool dense_top = true)
+      : e(en), sigma(sigma_), cconst(cconst_), allow_dense_top(dense_top) {
     e.fetch_host_pattern();
     e.setup_mark("  host pattern");
     // OSQP_AMD_FIRST_ORDERING=1: nested dissection at once (a caller who knows the problem is a long banded one saves the
@@ -254,7 +265,14 @@ struct LdlFactor {
         ldD = blocked ? (kD + 63) / 64 * 64 : kD;
         S0a.alloc((size_t)ldD * ldD);
         if (blocked) { gjT.alloc(2 * kGjK * kGjK); gjW.alloc((size_t)kGjK * ldD); gjC.alloc((size_t)kGjK * ldD); }
-        else S0b.alloc((size_t)kD * kD);
+        else {
+          S0b.alloc((size_t)kD * kD);
+          S0chk.alloc((size_t)kD * kD); probe_v.alloc(kD); probe_w.alloc(kD); probe_r.alloc(kD);
+          std::vector<double> pv(kD);
+          for (int i = 0; i < kD; i++) pv[i] = 1.0 + 0.25 * (double)(i % 7);
+          probe_v.upload(pv.data(), pv.size(), s);
+          e.sync();
+        }
         schur_ncols = 0;
         if (blocked && !S.Li.empty() && !(getenv("OSQP_AMD_SCHUR_DENSE") && atoi(getenv("OSQP_AMD_SCHUR_DENSE")) == 0)) {
           // the rank-64 form of the Schur complement when L21 is not very sparse: a rank-64 update costs (ld / 64)^2 / 2 tiles
@@ -1159,7 +1177,7 @@ struct LdlFactor {
     lD = nlev; cD = N; kD = 0;
     static const bool enabled = !(getenv("OSQP_AMD_DENSE_TOP") && atoi(getenv("OSQP_AMD_DENSE_TOP")) == 0);
     kD_dense = false;
-    if (enabled) choose_dense_top(S, kChainRows, dense_max(), kDenseSparseMax, kDenseMin, lD, cD, kD, &kD_dense);
+    if (enabled && allow_dense_top) choose_dense_top(S, kChainRows, dense_max(), kDenseSparseMax, kDenseMin, lD, cD, kD, &kD_dense);
   }
   // columns of the block whose work rows (N doubles each) are held at once: at most 256 MB
   int dense_batch() const { return (int)std::max<size_t>(1, std::min<size_t>((size_t)kD, ((size_t)256 << 20) / ((size_t)N * sizeof(double)))); }
@@ -1237,7 +1255,7 @@ struct LdlFactor {
     e.sync();
   }
 
-  // returns 0 ok, 4 zero pivot, 5 wrong inertia
+  // returns 0 ok, 4 zero pivot, 5 wrong inertia, 7 the explicit inverse of the dense top block failed its probe
   int refactor(const double *cdiag) {
     hipStream_t s = e.stream;
     Lx.zero(s);
@@ -1300,9 +1318,22 @@ struct LdlFactor {
     if (S.nnzL > 0 && !sn) OQ_LAUNCH(k_gather_csr, dim3(blocks_for(S.nnzL)), dim3(kBlock), 0, s, S.nnzL, Rmap.get(), Lx.get(), Rx.get());
     int st[2] = {0, 0};
     status.download(st, 2, s);
+    std::vector<double> pr;
+    if (probe_r.n) { pr.resize(probe_r.n); probe_r.download(pr.data(), pr.size(), s); }
     e.sync();
     factorizations++;
-    if (st[0]) return 4;
+    if (st[0]) return 4;  // (a zero pivot or a NaN: no rebuild would cure it)
+    if (!pr.empty()) {
+      double worst = 0.0;
+      bool finite = true;
+      for (size_t i = 0; i < pr.size(); i++) {
+        const double r = pr[i] + (1.0 + 0.25 * (double)(i % 7));
+        if (!(r == r)) finite = false;
+        worst = std::max(worst, std::fabs(r));
+      }
+      dense_residual = finite ? worst / 2.5 : INFINITY;  // relative to max |v|
+      if (!(dense_residual <= dense_probe_tol())) return 7;
+    }
     if (st[1] != n) return 5;
     return 0;
   }
@@ -1341,6 +1372,7 @@ struct LdlFactor {
       return;
     }
     double *cur = S0a.get(), *nxt = S0b.get();
+    HIP_CHECK(hipMemcpyAsync(S0chk.get(), S0a.get(), sizeof(double) * (size_t)kD * kD, hipMemcpyDeviceToDevice, s));
     const dim3 gs(blocks_for((int64_t)kD * kD));
     int p = 0;
     for (; p + 1 < kD; p += 2) {
@@ -1352,6 +1384,9 @@ struct LdlFactor {
       std::swap(cur, nxt);
     }
     Sinv = cur;
+    // the probe: w = S0^-1 v through the inverse, r = -(S0 w) through the copy (k_dense_apply negates); the host adds v
+    OQ_LAUNCH(k_dense_apply, dim3(blocks_for((int64_t)kD * 64)), dim3(kBlock), 0, s, kD, kD, (const double *)Sinv, (const double *)probe_v.get(), probe_w.get());
+    OQ_LAUNCH(k_dense_apply, dim3(blocks_for((int64_t)kD * 64)), dim3(kBlock), 0, s, kD, kD, (const double *)S0chk.get(), (const double *)probe_w.get(), probe_r.get());
   }
 
 #define OQ_CHAIN_CASE(UU, LL)                                                                                                      \
@@ -1659,8 +1694,38 @@ struct Direct : Linsys {
     e.drop_chunk_graph();
     return 6;
   }
-  int update_rho() override { return F->refactor(e.rho_inv.get()); }
-  int update_matrices() override { return F->refactor(e.rho_inv.get()); }
+  // numeric factorisation; where the dense top block fails its probe (LdlFactor: dense_probe_tol) the factor is built again
+  // without the block -- the same pivots by triangular solves -- and stays that way.  The new factor is held to the limits of
+  // make_direct.  At setup (`at_setup`) a factor that breaks them returns -1 and the problem goes to the indirect back-end where
+  // the setting allows it, as any other factor that is too large, too expensive or too deep; in the middle of a solve the
+  // back-end cannot change any more: a factor that does not fit is an error (6), one that is merely deep or expensive is kept.
+  int refactor(bool at_setup = false) {
+    int rc = F->refactor(e.rho_inv.get());
+    if (rc != 7) return rc;
+    const double residual = F->dense_residual;
+    const int block = F->kD;
+    const bool forced = e.st.linsys_solver == AMD_DIRECT_SOLVER;
+    std::vector<int> ident(e.m);
+    for (int i = 0; i < e.m; i++) ident[i] = i;
+    std::unique_ptr<LdlFactor> G(new LdlFactor(e, ident, e.m, e.st.sigma, 0.0, factor_limit(e, forced), forced ? 0.0 : factor_flops_limit(), false));
+    if (G->S.too_large) {
+      if (at_setup) return -1;
+      throw Error(6, "direct back-end: the dense top block of the factor failed its probe and the factor without the block does not fit");
+    }
+    if (at_setup && !forced && (G->flops_below_dense_block() > factor_flops_limit() || G->solve_levels() > level_limit())) return -1;
+    if (e.st.verbose && e.rank() == 0)
+      printf("[osqp-amd] the explicit inverse of the dense top block (%d pivots) failed its probe (residual %.1e): factor rebuilt without the block, %d levels\n",
+             block, residual, G->nlev);
+    e.sync();
+    F = std::move(G);
+    rhs_left = false;
+    e.drop_chunk_graph();
+    dense_rebuilds++;
+    return F->refactor(e.rho_inv.get());
+  }
+  long long dense_rebuilds = 0;
+  int update_rho() override { return refactor(); }
+  int update_matrices() override { return refactor(); }
   double nnzL() const override { return (double)F->S.nnzL; }
   double levels() const override { return (double)F->nlev; }
   double supernode_levels() const override { return F->sn ? (double)F->T.nlev : 0.0; }
@@ -1699,6 +1764,19 @@ int64_t factor_limit(const Engine &e, bool forced) {
   return forced ? (int64_t)2000000000LL : (int64_t)400000000LL;  // 4e8 entries = 9.6 GB of L (both copies)
 }
 
+// The factor of the delta-regularised reduced KKT matrix of an active set (polish, the adjoint), factorised; without the dense
+// top block where its explicit inverse fails the probe.  *rc: 0, -1 too large, else refactor's code.
+std::unique_ptr<LdlFactor> reduced_factor(Engine &e, const std::vector<int> &row_map, int mr, int *rc) {
+  std::unique_ptr<LdlFactor> F(new LdlFactor(e, row_map, mr, e.st.delta, -e.st.delta, 400000000LL));
+  if (F->S.too_large) { *rc = -1; return F; }
+  *rc = F->refactor(nullptr);
+  if (*rc != 7) return F;
+  F.reset(new LdlFactor(e, row_map, mr, e.st.delta, -e.st.delta, 400000000LL, 0.0, false));
+  if (F->S.too_large) { *rc = -1; return F; }
+  *rc = F->refactor(nullptr);
+  return F;
+}
+
 }  // namespace
 
 std::unique_ptr<Linsys> make_direct(Engine &e, int *err) {
@@ -1716,7 +1794,7 @@ std::unique_ptr<Linsys> make_direct(Engine &e, int *err) {
   // (round 4: a dense top block is priced by what inverting it costs now -- 31 ms for 6000 pivots -- not by its n^3 / 3 in the
   // sum: a dense P no longer sends a problem to PCG once its analysis has been paid for; equality_qp: 9 k it/s instead of 260)
   if (e.st.linsys_solver != AMD_DIRECT_SOLVER && (d->F->flops_below_dense_block() > factor_flops_limit() || d->F->solve_levels() > level_limit())) { *err = -1; return nullptr; }
-  int rc = d->F->refactor(e.rho_inv.get());
+  int rc = d->refactor(true);
   if (rc) { *err = rc; return nullptr; }
   return std::unique_ptr<Linsys>(d.release());
 }
@@ -1743,6 +1821,44 @@ __global__ __launch_bounds__(kBlock) void k_normal_cone(int m, double *__restric
   z[i] = zn; y[i] = s - zn;
 }
 
+// rhs -= (K_reg - K) sol = [delta sol_x ; -delta sol_a]: turns the residual against the unregularised matrix into the one
+// against the regularised matrix
+__global__ __launch_bounds__(kBlock) void k_sub_reg(int n, int nr, double delta, const double *__restrict__ sol, double *__restrict__ rhs) {
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  if (o < nr) rhs[o] -= (o < n ? delta : -delta) * sol[o];
+}
+
+// The solve-and-refine loop of polish and of the adjoint (direct_adjoint.hpp), one statement for both: sol <- F^-1 rhs_red, then
+// `steps` refinement steps against the unregularised reduced matrix [P, Aa'; Aa, 0] with the engine's own sparse products
+// (`against_regularised`: against F's own matrix, the +-delta terms added to the residual).  act_rows: the mr active rows in the
+// order of the reduced matrix.  Scratch: rhs [n + mr], yfull [m], Axv [m], px [n], ared_x [mr].  Returns the KKT solves made.
+struct RefineScratch { double *rhs, *yfull, *Axv, *px, *ared_x; };
+static int kkt_solve_refine(Engine &e, LdlFactor &F, const int *act_rows, int mr, const double *rhs_red, double *sol, const RefineScratch &w,
+                            int steps, bool against_regularised) {
+  hipStream_t s = e.stream;
+  const int n = e.n, m = e.m, nr = n + mr;
+  vec_copy(sol, rhs_red, nr, s);
+  F.solve(sol, nullptr);
+  for (int it = 0; it < steps; it++) {
+    vec_copy(w.rhs, rhs_red, nr, s);
+    spmv(e.Pf, sol, w.px, nullptr, 0.0, 0.0, nullptr, s);
+    vec_axpy(w.rhs, -1.0, w.px, n, s);
+    if (mr > 0) {
+      HIP_CHECK(hipMemsetAsync(w.yfull, 0, sizeof(double) * (size_t)(m ? m : 1), s));
+      OQ_LAUNCH(k_scatter_idx, dim3(blocks_for(mr)), dim3(kBlock), 0, s, mr, act_rows, (const double *)(sol + n), w.yfull);
+      spmv(e.At, w.yfull, w.px, nullptr, 0.0, 0.0, nullptr, s);
+      vec_axpy(w.rhs, -1.0, w.px, n, s);
+      spmv(e.A, sol, w.Axv, nullptr, 0.0, 0.0, nullptr, s);
+      OQ_LAUNCH(k_gather_idx, dim3(blocks_for(mr)), dim3(kBlock), 0, s, mr, act_rows, (const double *)w.Axv, w.ared_x);
+      vec_axpy(w.rhs + n, -1.0, w.ared_x, mr, s);
+    }
+    if (against_regularised) OQ_LAUNCH(k_sub_reg, dim3(blocks_for(nr)), dim3(kBlock), 0, s, n, nr, (double)e.st.delta, (const double *)sol, w.rhs);
+    F.solve(w.rhs, nullptr);
+    vec_axpy(sol, 1.0, w.rhs, nr, s);
+  }
+  return 1 + steps;
+}
+
 int polish_run(Engine &e) {
   // the reduced KKT system is assembled from the CSR arrays, which a compact workspace has released: iterative form (pcg.hip)
   // OSQP_AMD_POLISH_ITERATIVE=1 (tests): the iterative form wherever the indirect back-end runs, so that it can be compared
@@ -1767,9 +1883,11 @@ int polish_run(Engine &e) {
   for (int k = 0; k < n_low; k++) act[k] = ind_low[k];
   for (int k = 0; k < n_upp; k++) act[n_low + k] = ind_upp[k];
 
-  LdlFactor F(e, row_map, mr, e.st.delta, -e.st.delta, 400000000LL);
-  if (F.S.too_large) return e.lin && e.lin->kind() == 2 ? polish_run_pcg(e) : -1;  // no factor of the reduced system that fits: iterate instead
-  if (F.refactor(nullptr) != 0) return -1;
+  int frc = 0;
+  std::unique_ptr<LdlFactor> Fp = reduced_factor(e, row_map, mr, &frc);
+  LdlFactor &F = *Fp;
+  if (frc == -1) return e.lin && e.lin->kind() == 2 ? polish_run_pcg(e) : -1;  // no factor of the reduced system that fits: iterate instead
+  if (frc != 0) return -1;
   const int nr = n + mr;
   DevBuf<double> rhs_red(nr), sol(nr), rhs(nr), yfull(m), Axv(m), px(n), pz(m), py(m);
   DevBuf<int> dact(mr ? mr : 1);
@@ -1781,24 +1899,8 @@ int polish_run(Engine &e) {
   if (n_upp) OQ_LAUNCH(k_gather_idx, dim3(blocks_for(n_upp)), dim3(kBlock), 0, s, n_upp, dact.get() + n_low, e.u.get(), rhs_red.get() + n + n_low);
   // solve, then iterative refinement against the unregularised matrix: rhs = rhs_red - [P x + Ared' y ; Ared x]
   DevBuf<double> ared_x(mr ? mr : 1);
-  vec_copy(sol.get(), rhs_red.get(), nr, s);
-  F.solve(sol.get(), nullptr);
-  for (int it = 0; it < e.st.polish_refine_iter; it++) {
-    vec_copy(rhs.get(), rhs_red.get(), nr, s);
-    spmv(e.Pf, sol.get(), px.get(), nullptr, 0.0, 0.0, nullptr, s);
-    vec_axpy(rhs.get(), -1.0, px.get(), n, s);
-    if (mr > 0) {
-      yfull.zero(s);
-      OQ_LAUNCH(k_scatter_idx, dim3(blocks_for(mr)), dim3(kBlock), 0, s, mr, dact.get(), sol.get() + n, yfull.get());
-      spmv(e.At, yfull.get(), px.get(), nullptr, 0.0, 0.0, nullptr, s);
-      vec_axpy(rhs.get(), -1.0, px.get(), n, s);
-      spmv(e.A, sol.get(), Axv.get(), nullptr, 0.0, 0.0, nullptr, s);
-      OQ_LAUNCH(k_gather_idx, dim3(blocks_for(mr)), dim3(kBlock), 0, s, mr, dact.get(), Axv.get(), ared_x.get());
-      vec_axpy(rhs.get() + n, -1.0, ared_x.get(), mr, s);
-    }
-    F.solve(rhs.get(), nullptr);
-    vec_axpy(sol.get(), 1.0, rhs.get(), nr, s);
-  }
+  kkt_solve_refine(e, F, dact.get(), mr, rhs_red.get(), sol.get(), RefineScratch{rhs.get(), yfull.get(), Axv.get(), px.get(), ared_x.get()},
+                   (int)e.st.polish_refine_iter, false);
   // polished (x, z, y)
   vec_copy(px.get(), sol.get(), n, s);
   if (m > 0) spmv(e.A, px.get(), pz.get(), nullptr, 0.0, 0.0, nullptr, s);
@@ -1829,3 +1931,6 @@ int polish_run(Engine &e) {
 }
 
 }  // namespace oq
+
+// adjoint derivatives of the solution: the same factor object and the same solve-and-refine loop with another right-hand side
+#include "direct_adjoint.hpp"

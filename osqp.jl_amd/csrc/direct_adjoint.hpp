@@ -1,0 +1,253 @@
+// direct_adjoint.hpp -- adjoint derivatives of the solution of a single model (osqp_amd_adjoint)
+// Part of the direct KKT back-end and of its one translation unit: included by direct.hip after polish_run (like the
+// direct_*_kernels.hpp files it is a piece of that file, not a header for anybody else), whose factor object (LdlFactor,
+// reduced_factor) and whose solve-and-refine loop (kkt_solve_refine: one function for both) it uses with another right-hand side.  With a = L u U the active rows and K = [P, Aa'; Aa, 0], one solve
+// K [r_x; r_a] = [g_x; (g_y)_a] per cotangent gives dq = -r_x, dl / du = r_y on L / U, dPx(i, j) = -(r_x,i x_j + r_x,j x_i) (once
+// on the diagonal), dAx(i, j) = -(y_i r_x,j + r_y,i x_j).  The solve runs on the scaled data: [P~ + delta I, A~a'; A~a, -delta I]
+// factorised once per solution and KEPT, the right-hand side c D g_x and (E g_y)_a, r_x = D r~, r_y = E s / c.
+// Every kernel is one thread per output word, consecutive lanes on consecutive words, gathers through L2, no atomics: two calls
+// give the same bits.
+#pragma once
+#include "engine.hpp"
+
+namespace oq {
+namespace {
+
+// rhs = [c (D g_x) ; (E g_y) on the active rows, in the order of the reduced matrix]; a missing cotangent is zero
+__global__ __launch_bounds__(kBlock) void k_adj_rhs(int n, int mr, double c, const double *__restrict__ D, const double *__restrict__ E,
+                                                    const int *__restrict__ act_rows, const double *__restrict__ gx,
+                                                    const double *__restrict__ gy, double *__restrict__ rhs) {
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  if (o >= n + mr) return;
+  if (o < n) rhs[o] = gx ? c * (D[o] * gx[o]) : 0.0;
+  else {
+    const int i = act_rows[o - n];
+    rhs[o] = gy ? E[i] * gy[i] : 0.0;
+  }
+}
+
+// the caller-unit solution the matrix gradients multiply by: x = D x~, y = E y~ / c (once per kept factor)
+__global__ __launch_bounds__(kBlock) void k_adj_unscale(int n, int m, double c, const double *__restrict__ D, const double *__restrict__ E,
+                                                        const double *__restrict__ xs, const double *__restrict__ ys,
+                                                        double *__restrict__ x, double *__restrict__ y) {
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  if (o < n) x[o] = D[o] * xs[o];
+  else if (o < n + m) { const int i = o - n; y[i] = E[i] * ys[i] / c; }
+}
+
+// vectors: r_x = D r~ and dq = -r_x (threads [0, n)); r_y = E s / c on the active rows, 0 elsewhere, dl / du by the side of the
+// row (threads [n, n + m)).  Row i finds its multiplier through slot[i] (its position in the reduced matrix, -1: inactive):
+// a gather, so no thread writes another's word.  dq, dl, du may be null (not wanted); rx, ry feed the matrix kernels.
+__global__ __launch_bounds__(kBlock) void k_adj_vectors(int n, int m, double c, const double *__restrict__ D, const double *__restrict__ E,
+                                                        const int *__restrict__ slot, const double *__restrict__ side,
+                                                        const double *__restrict__ sol, double *__restrict__ rx, double *__restrict__ ry,
+                                                        double *__restrict__ dq, double *__restrict__ dl, double *__restrict__ du) {
+  const int o = blockIdx.x * kBlock + threadIdx.x;
+  if (o < n) {
+    const double r = D[o] * sol[o];
+    rx[o] = r;
+    if (dq) dq[o] = -r;
+  } else if (o < n + m) {
+    const int i = o - n, k = slot[i];
+    const double r = k >= 0 ? E[i] * sol[n + k] / c : 0.0, sd = side[i];
+    ry[i] = r;
+    if (dl) dl[i] = sd < 0.0 ? r : 0.0;
+    if (du) du[i] = sd > 0.0 ? r : 0.0;
+  }
+}
+
+// dPx: entry k of the caller's triu(P), row Pi[k], column Pcol[k] (expanded once per workspace)
+__global__ __launch_bounds__(kBlock) void k_adj_dP(int64_t nnz, const int *__restrict__ Pi, const int *__restrict__ Pcol,
+                                                   const double *__restrict__ rx, const double *__restrict__ x, double *__restrict__ dP) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nnz) return;
+  const int i = Pi[k], j = Pcol[k];
+  dP[k] = i == j ? -(rx[i] * x[i]) : -(rx[i] * x[j] + rx[j] * x[i]);
+}
+
+// dAx: entry k of the caller's A; to_sorted (may be null) translates a caller index into the sorted copy the workspace holds
+__global__ __launch_bounds__(kBlock) void k_adj_dA(int64_t nnz, const int64_t *__restrict__ to_sorted, const int *__restrict__ Ai,
+                                                   const int *__restrict__ Acol, const double *__restrict__ rx, const double *__restrict__ ry,
+                                                   const double *__restrict__ x, const double *__restrict__ y, double *__restrict__ dA) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nnz) return;
+  const int64_t ks = to_sorted ? to_sorted[k] : k;
+  const int i = Ai[ks], j = Acol[ks];
+  dA[k] = -(y[i] * rx[j] + ry[i] * x[j]);
+}
+
+// what one solution keeps: the factor, the active set in its three forms, the caller-unit solution, the scratch of the solves
+struct AdjointKept {
+  std::unique_ptr<LdlFactor> F;
+  int n_low = 0, n_upp = 0, mr = 0;
+  std::vector<double> h_side;                   // [m] -1 lower, 0 inactive, 1 upper (the `act` output)
+  DevBuf<int> act_rows, slot;                   // [mr] rows in the order of the reduced matrix; [m] row -> position, -1
+  DevBuf<double> side, xc, yc;                  // [m], [n], [m]
+  DevBuf<double> rhs_red, sol, rhs, yfull, Axv, px, ared_x, rx, ry;
+  size_t bytes = 0;                             // device bytes held (factor, index arrays, scratch)
+};
+
+}  // namespace
+
+struct ModelAdjoint {
+  std::unique_ptr<AdjointKept> kept;
+  DevBuf<int> Pcol, Acol;          // column of every entry of the caller's triu(P) / of A (sorted copy): once per workspace
+  DevBuf<int64_t> A_to_sorted;     // the engine's map on the device (empty: the caller's columns were sorted)
+  bool patterns = false;
+  long long builds = 0, solves = 0;
+};
+void model_adjoint_destroy(ModelAdjoint *a) { delete a; }
+
+void model_adjoint_release(Engine &e) {
+  if (e.adj && e.adj->kept) { e.sync(); e.adj->kept.reset(); }
+}
+
+void model_adjoint_stats(const Engine &e, double out[6]) {
+  const ModelAdjoint *a = e.adj.get();
+  const AdjointKept *k = a ? a->kept.get() : nullptr;
+  out[0] = a ? (double)a->builds : 0.0;
+  out[1] = a ? (double)a->solves : 0.0;
+  out[2] = k ? (double)k->n_low : 0.0;
+  out[3] = k ? (double)k->n_upp : 0.0;
+  out[4] = k ? 1.0 : 0.0;
+  out[5] = k ? (double)k->bytes : 0.0;
+}
+
+namespace {
+
+// classify the rows on the scaled (z, y, l, u) of the solution -- polish's rule, and a row with l == u is always active and
+// counts as lower --, analyse and factorise the reduced matrix, set up what every later call on this solution reuses
+void adjoint_build(Engine &e, ModelAdjoint &A) {
+  hipStream_t s = e.stream;
+  const int n = e.n, m = e.m;
+  const size_t bytes0 = g_device_bytes;
+  std::unique_ptr<AdjointKept> K(new AdjointKept());
+  std::vector<double> hz(m), hy(m), hl(m), hu(m);
+  e.z.download(hz.data(), m, s); e.y.download(hy.data(), m, s); e.l.download(hl.data(), m, s); e.u.download(hu.data(), m, s);
+  e.sync();
+  K->h_side.assign(m, 0.0);
+  std::vector<int> row_map(m, -1), rows;
+  for (int i = 0; i < m; i++) {
+    const bool low = (hz[i] - hl[i] < -hy[i]) || hl[i] == hu[i];
+    const bool upp = !low && (hu[i] - hz[i] < hy[i]);
+    K->h_side[i] = low ? -1.0 : (upp ? 1.0 : 0.0);
+    if (low) K->n_low++;
+    if (upp) K->n_upp++;
+  }
+  const int mr = K->mr = K->n_low + K->n_upp;
+  rows.resize(mr);
+  for (int i = 0, kl = 0, ku = K->n_low; i < m; i++) {  // lower rows first, as polish orders its reduced matrix
+    if (K->h_side[i] < 0.0) { row_map[i] = kl; rows[kl++] = i; }
+    else if (K->h_side[i] > 0.0) { row_map[i] = ku; rows[ku++] = i; }
+  }
+  int frc = 0;
+  K->F = reduced_factor(e, row_map, mr, &frc);
+  if (frc == -1)
+    throw Error(6, "osqp_amd_adjoint: the factor of the reduced KKT matrix of the active set is too large for the device (an iterative adjoint is not built)");
+  if (frc != 0)
+    throw Error(4, "osqp_amd_adjoint: the numeric factorisation of the regularised KKT matrix of the active set failed");
+  const int nr = n + mr;
+  K->act_rows.alloc(mr ? mr : 1); K->act_rows.upload(rows.data(), mr, s);
+  K->slot.alloc(m ? m : 1); K->slot.upload(row_map.data(), m, s);
+  K->side.alloc(m ? m : 1); K->side.upload(K->h_side.data(), m, s);
+  K->xc.alloc(n); K->yc.alloc(m ? m : 1);
+  K->rhs_red.alloc(nr); K->sol.alloc(nr); K->rhs.alloc(nr); K->yfull.alloc(m ? m : 1); K->Axv.alloc(m ? m : 1); K->px.alloc(n);
+  K->ared_x.alloc(mr ? mr : 1); K->rx.alloc(n); K->ry.alloc(m ? m : 1);
+  OQ_LAUNCH(k_adj_unscale, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), e.x.get(), e.y.get(),
+            K->xc.get(), K->yc.get());
+  e.sync();  // (the uploads above read host vectors of this scope)
+  K->bytes = g_device_bytes > bytes0 ? g_device_bytes - bytes0 : 0;
+  A.kept = std::move(K);
+  A.builds++;
+}
+
+// one cotangent: right-hand side, the regularised solve, polish_refine_iter steps against the unregularised matrix (the loop
+// of polish_run on scratch of its own: the engine's Ax / Px / Aty keep what the last residual evaluation left).
+// polish_refine_iter = 0 asks for the regularised answer itself.  The factorisation does not pivot and eliminates rows of
+// -delta before their variables wherever the fill-reducing order says so: multipliers of 1 / delta, a solve accurate to
+// ~1e-8 where the matrix has a condition of 1e3 (control(): 1.0e-8 against a dense solve; the steps against the
+// unregularised matrix remove that as well, which is why polish never sees it).  So with 0 steps ONE step runs against
+// the REGULARISED matrix: the answer is the regularised one, to working accuracy.
+void adjoint_pass(Engine &e, ModelAdjoint &A, const double *gx, const double *gy) {
+  AdjointKept &K = *A.kept;
+  LdlFactor &F = *K.F;
+  hipStream_t s = e.stream;
+  const int n = e.n, mr = K.mr, nr = n + mr;
+  OQ_LAUNCH(k_adj_rhs, dim3(blocks_for(nr)), dim3(kBlock), 0, s, n, mr, e.c, e.D.get(), e.E.get(), K.act_rows.get(), gx, gy, K.rhs_red.get());
+  const bool regularised = e.st.polish_refine_iter == 0;
+  A.solves += kkt_solve_refine(e, F, K.act_rows.get(), mr, K.rhs_red.get(), K.sol.get(),
+                               RefineScratch{K.rhs.get(), K.yfull.get(), K.Axv.get(), K.px.get(), K.ared_x.get()},
+                               regularised ? 1 : (int)e.st.polish_refine_iter, regularised);
+}
+
+}  // namespace
+
+int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
+                      double *dAx, double *act) {
+  // no CSR arrays and no reduced KKT matrix: what polish_run hands to its iterative form
+  if (e.comm) throw Error(6, "osqp_amd_adjoint: not available on a row-sharded workspace (a row block has no reduced KKT matrix; an iterative adjoint is not built)");
+  if (e.compact || e.A.compact || e.At.compact || e.Pf.compact || (e.nnzPtriu > 0 && e.Pi_keep.n == 0))
+    throw Error(6, "osqp_amd_adjoint: not available on a compact workspace (its CSR arrays are released, there is no reduced KKT matrix to factorise; "
+                   "an iterative adjoint is not built; OSQP_AMD_COMPACT_NNZ=-1 at setup keeps the arrays)");
+  hipStream_t s = e.stream;
+  const int n = e.n, m = e.m;
+  if (!e.adj) e.adj.reset(new ModelAdjoint());
+  ModelAdjoint &A = *e.adj;
+  const bool grads = dq || dl || du || dPx || dAx;
+  if (!A.kept) adjoint_build(e, A);
+  AdjointKept &K = *A.kept;
+  if ((dPx || dAx) && !A.patterns) {
+    A.Pcol.alloc(std::max<int64_t>(1, e.nnzPtriu)); A.Acol.alloc(std::max<int64_t>(1, e.nnzA));
+    expand_colptr(n, e.Pp_keep.get(), e.nnzPtriu, A.Pcol.get(), s);
+    expand_colptr(n, e.At.rowptr.get(), e.nnzA, A.Acol.get(), s);
+    if (!e.A_to_sorted.empty()) { A.A_to_sorted.alloc(e.A_to_sorted.size()); A.A_to_sorted.upload(e.A_to_sorted.data(), e.A_to_sorted.size(), s); }
+    e.sync();
+    A.patterns = true;
+  }
+  if (grads) {
+    const size_t nc = (size_t)ncot;
+    DevBuf<double> gx, gy, oq_, ol, ou, oP, oA;
+    if (dx) { gx.alloc(nc * n); gx.upload(dx, nc * n, s); }
+    if (dy && m > 0) { gy.alloc(nc * m); gy.upload(dy, nc * m, s); }
+    if (dq) oq_.alloc(nc * n);
+    if (dl) ol.alloc(nc * m);
+    if (du) ou.alloc(nc * m);
+    if (dPx) oP.alloc(nc * (size_t)e.nnzPtriu);
+    if (dAx) oA.alloc(nc * (size_t)e.nnzA);
+    const long long solves0 = A.solves;
+    auto passes = [&]() {
+      for (size_t c = 0; c < nc; c++) {
+        adjoint_pass(e, A, gx.p ? gx.get() + c * n : nullptr, gy.p ? gy.get() + c * m : nullptr);
+        OQ_LAUNCH(k_adj_vectors, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), K.slot.get(), K.side.get(),
+                  K.sol.get(), K.rx.get(), K.ry.get(), dq ? oq_.get() + c * n : nullptr, dl ? ol.get() + c * m : nullptr,
+                  du ? ou.get() + c * m : nullptr);
+        if (dPx && e.nnzPtriu > 0)
+          OQ_LAUNCH(k_adj_dP, dim3(blocks_for(e.nnzPtriu)), dim3(kBlock), 0, s, e.nnzPtriu, e.Pi_keep.get(), A.Pcol.get(), K.rx.get(), K.xc.get(),
+                    oP.get() + c * (size_t)e.nnzPtriu);
+        if (dAx && e.nnzA > 0)
+          OQ_LAUNCH(k_adj_dA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, A.A_to_sorted.n ? A.A_to_sorted.get() : (const int64_t *)nullptr,
+                    e.At.col.get(), A.Acol.get(), K.rx.get(), K.ry.get(), K.xc.get(), K.yc.get(), oA.get() + c * (size_t)e.nnzA);
+      }
+      e.sync();
+    };
+    passes();
+    if (K.F->faulted()) {  // a wait inside the one-launch supernodal solve timed out: one launch per level, and once more
+      *K.F->sn_fault_host = 0;
+      K.F->sn_tree = false;
+      A.solves = solves0;
+      passes();
+      if (K.F->faulted()) throw TreeFault();
+    }
+    // outputs last: a call that fails has written nothing
+    if (dq) oq_.download(dq, nc * n, s);
+    if (dl) ol.download(dl, nc * m, s);
+    if (du) ou.download(du, nc * m, s);
+    if (dPx) oP.download(dPx, nc * (size_t)e.nnzPtriu, s);
+    if (dAx) oA.download(dAx, nc * (size_t)e.nnzA, s);
+    e.sync();
+  }
+  if (act) std::copy(K.h_side.begin(), K.h_side.end(), act);
+  return 0;
+}
+
+}  // namespace oq

@@ -58,6 +58,7 @@ static double limit_scaling(double v) {
 
 Engine::Engine() {}
 Engine::~Engine() {
+  adj.reset();
   lin.reset();
   if (chunk_exec) (void)hipGraphExecDestroy(chunk_exec);
   if (h_slots) (void)hipHostFree(h_slots);

@@ -20,6 +20,12 @@ namespace oq {
 
 struct Engine;
 
+// Adjoint derivatives of the solution of a single model (direct_adjoint.hpp): the factor of the
+// delta-regularised KKT matrix of the active set, kept from the first osqp_amd_adjoint after a solve until the model moves on.
+struct ModelAdjoint;
+void model_adjoint_destroy(ModelAdjoint *a);
+struct ModelAdjointDeleter { void operator()(ModelAdjoint *a) const { model_adjoint_destroy(a); } };
+
 // KKT back-end interface (the reference's `linsys_solver` plug-in point,
 // [REF src/constants.jl:1-2, src/interface.jl:749-773]).
 struct Linsys {
@@ -120,6 +126,11 @@ struct Engine {
   std::vector<double> h_l, h_u;  // unscaled bounds on the host (validation of bound updates)
 
   std::unique_ptr<Linsys> lin;
+
+  // osqp_amd_adjoint: (x, z, y) are the solution of the last osqp_solve (set by it, cleared by whatever changes the data, the
+  // settings or the iterate); the kept factor and its counters (created by the first call, direct_adjoint.hpp)
+  bool solution_current = false;
+  std::unique_ptr<ModelAdjoint, ModelAdjointDeleter> adj;
 
   // PCG tolerance rule state
   double sc_pri = 0, sc_dua = 0, lambda0 = 0.015, lambda = 0.015, g_ref = 0;
@@ -239,6 +250,11 @@ std::unique_ptr<Linsys> make_direct(Engine &e, int *err);
 int polish_run(Engine &e);
 // the same without a factorisation, on the operator of the indirect back-end (pcg.hip): compact workspaces, factors that do not fit
 int polish_run_pcg(Engine &e);
+// osqp_amd_adjoint / _release / _stats on a workspace that passed the checks of the C boundary (direct_adjoint.hpp); host pointers
+int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
+                      double *dAx, double *act);
+void model_adjoint_release(Engine &e);  // drops the kept factor (the counters stay)
+void model_adjoint_stats(const Engine &e, double out[6]);
 const char *last_error_cstr();
 
 // device generators (gen.hip)

@@ -524,3 +524,80 @@ def spmv_layout(model, which):
     if k != len(out):
         raise OSQPError("osqp_amd_spmv_layout: bad argument")
     return {name: int(v) for name, v in zip(SPMV_LAYOUT_FIELDS, out)}
+
+
+ADJOINT_GRADS = ("q", "l", "u", "Px", "Ax")
+ADJOINT_STATS_FIELDS = ("builds", "solves", "n_low", "n_upp", "kept", "bytes")
+
+
+def _adjoint_symbol(model, name):
+    """The entry point, or OSQPError when the library does not have it (the CPU oracle has no adjoint)."""
+    fn = getattr(model.lib, name, None)
+    if fn is None or fn.argtypes is None:
+        raise OSQPError(f"this library does not export {name}: adjoint derivatives are an extension of libosqp_amd.so")
+    return fn
+
+
+def _cotangent(name, a, cols):
+    """A cotangent argument of `adjoint` as (float64 C-contiguous array [ncot x cols], had a leading axis?).  Shape and
+    element type are checked here, before the library sees the pointer."""
+    arr = np.asarray(a)
+    if arr.dtype.kind not in "fiu":
+        raise ValueError(f"{name}: expected a real numeric array, got dtype {arr.dtype}")
+    if arr.ndim not in (1, 2) or arr.shape[-1] != cols or (arr.ndim == 2 and arr.shape[0] < 1):
+        raise ValueError(f"{name}: expected shape ({cols},) or (ncot, {cols}) with ncot >= 1, got {arr.shape}")
+    return _as_f64(arr).reshape(-1, cols), arr.ndim == 2
+
+
+def adjoint(model, dx=None, dy=None, want=ADJOINT_GRADS):
+    """Extension: osqp_amd_adjoint (include/osqp_amd.h).  From dx = dloss/dx and dy = dloss/dy at the solution of the last
+    `solve` (either may be None = 0) the gradients named in `want` -- "q", "l", "u", "Px" (upper triangle of P), "Ax", both
+    in the nnz order `update` takes -- as a dict of numpy arrays, plus "act" [m] (-1 lower, 0 inactive, 1 upper).  Inputs
+    [n] / [m] give outputs without a leading axis, inputs [ncot x n] / [ncot x m] outputs with one.  `want=()` with no
+    cotangent returns "act" alone.  The first call after a solve factorises and keeps the factor (`adjoint_release`)."""
+    fn = _adjoint_symbol(model, "osqp_amd_adjoint")
+    want = tuple(want)
+    for k in want:
+        if k not in ADJOINT_GRADS:
+            raise ValueError(f"want: unknown gradient {k!r} (known: {', '.join(ADJOINT_GRADS)})")
+    if len(set(want)) != len(want):
+        raise ValueError("want: a gradient is named twice")
+    n, m = dimensions(model)
+    given = [(nm, v, k) for nm, v, k in (("dx", dx, n), ("dy", dy, m)) if v is not None]
+    got = {nm: _cotangent(nm, v, k) for nm, v, k in given}
+    if want and not got:
+        raise ValueError("adjoint: a gradient is wanted but dx and dy are both None")
+    if len({lead for _, lead in got.values()}) > 1:
+        raise ValueError("dx and dy must both have a leading cotangent axis or both have none")
+    ncots = {arr.shape[0] for arr, _ in got.values()}
+    if len(ncots) > 1:
+        raise ValueError(f"dx and dy differ in the number of cotangents: {sorted(ncots)}")
+    ncot = ncots.pop() if ncots else 1
+    many = any(lead for _, lead in got.values())
+    st = stats(model, 4)
+    cols = dict(q=n, l=m, u=m, Px=int(st[3]), Ax=int(st[1]))
+    out = {k: np.full((ncot, cols[k]), np.nan) for k in want}
+    act = np.zeros(m)
+    ptr = lambda a: None if a is None else _fptr(a)
+    gx, gy = (got[k][0] if k in got else None for k in ("dx", "dy"))
+    if fn(model.workspace, ncot, ptr(gx), ptr(gy), *(ptr(out.get(k)) for k in ADJOINT_GRADS), _fptr(act)) != 0:
+        raise OSQPError("Error in adjoint: " + model.lib.osqp_amd_last_error().decode())
+    res = {k: (v if many else v[0]) for k, v in out.items()}
+    res["act"] = act.astype(int)
+    return res
+
+
+def adjoint_release(model):
+    """Extension: drop the factor `adjoint` keeps (it is as large as a polish's)."""
+    if _adjoint_symbol(model, "osqp_amd_adjoint_release")(model.workspace) != 0:
+        raise OSQPError("Error in adjoint_release: " + model.lib.osqp_amd_last_error().decode())
+
+
+def adjoint_stats(model):
+    """Extension: osqp_amd_adjoint_stats as a dict of ints -- factor builds and KKT solves so far, n_low / n_upp of the kept
+    factor, whether one is kept, and the device bytes it holds."""
+    fn = _adjoint_symbol(model, "osqp_amd_adjoint_stats")
+    out = np.zeros(len(ADJOINT_STATS_FIELDS))
+    if fn(model.workspace, _fptr(out), len(out)) != len(out):
+        raise OSQPError("osqp_amd_adjoint_stats: bad argument")
+    return {name: int(v) for name, v in zip(ADJOINT_STATS_FIELDS, out)}

@@ -81,6 +81,58 @@ function iterate!(model::OSQP.Model, iters::Integer)
 end
 
 """
+    adjoint(model; dx = nothing, dy = nothing, want = (:q, :l, :u, :Px, :Ax)) -> NamedTuple
+
+Gradients of a scalar loss through the solution of the last `OSQP.solve!` (osqp_amd_adjoint in include/osqp_amd.h): from
+`dx` = dloss/dx and `dy` = dloss/dy (either may be `nothing` = 0) the gradients named in `want` -- `q`, `l`, `u`, `Px` (upper
+triangle of P), `Ax`, both in the nnz order `OSQP.update!` takes -- plus `act` (-1 lower, 0 inactive, 1 upper).  Vectors give
+vectors; matrices with one column per cotangent (`n x ncot`, `m x ncot`: column-major here is cotangent-major on the C side)
+give matrices with one column per cotangent.  The first call after a solve factorises and keeps the factor
+(`adjoint_release!`); every update, warm start and solve drops it.
+"""
+function adjoint(model::OSQP.Model; dx::Union{Nothing,VecOrMat{Float64}} = nothing, dy::Union{Nothing,VecOrMat{Float64}} = nothing,
+                 want = (:q, :l, :u, :Px, :Ax))
+    (n, m) = OSQP.dimensions(model)
+    all(k -> k in (:q, :l, :u, :Px, :Ax), want) || error("want: unknown gradient")
+    isempty(want) || dx !== nothing || dy !== nothing || error("a gradient is wanted but dx and dy are both nothing")
+    dx === nothing || size(dx, 1) == n || error("dx must have n = $n rows")
+    dy === nothing || size(dy, 1) == m || error("dy must have m = $m rows")
+    ncot = dx !== nothing ? size(dx, 2) : (dy !== nothing ? size(dy, 2) : 1)
+    dx === nothing || dy === nothing || (size(dy, 2) == ncot && ndims(dx) == ndims(dy)) || error("dx and dy differ in the number of cotangents")
+    many = (dx !== nothing && dx isa Matrix) || (dy !== nothing && dy isa Matrix)
+    st = stats(model)
+    rows = (q = n, l = m, u = m, Px = Int(st[4]), Ax = Int(st[2]))
+    out = Dict(k => fill(NaN, rows[k], ncot) for k in want)
+    act = zeros(Float64, m)
+    ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve dx dy out act begin
+        flag = ccall((:osqp_amd_adjoint, lib), Cc_int,
+                     (Ptr{OSQP.Workspace}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                      Ptr{Cdouble}, Ptr{Cdouble}),
+                     model.workspace, ncot, ptr(dx), ptr(dy), ptr(get(out, :q, nothing)), ptr(get(out, :l, nothing)),
+                     ptr(get(out, :u, nothing)), ptr(get(out, :Px, nothing)), ptr(get(out, :Ax, nothing)), act)
+    end
+    flag == 0 || error("Error in adjoint: $(last_error())")
+    grads = [k => (many ? out[k] : vec(out[k])) for k in want]
+    return (; grads..., act = Int.(act))
+end
+
+"Drop the factor `adjoint` keeps (osqp_amd_adjoint_release); it is as large as a polish's."
+function adjoint_release!(model::OSQP.Model)
+    flag = ccall((:osqp_amd_adjoint_release, lib), Cc_int, (Ptr{OSQP.Workspace},), model.workspace)
+    flag == 0 || error("Error in adjoint_release!: $(last_error())")
+    return nothing
+end
+
+"(builds, solves, n_low, n_upp, kept, bytes) of the adjoint's kept factor (osqp_amd_adjoint_stats)."
+function adjoint_stats(model::OSQP.Model)
+    out = zeros(Float64, 6)  # OSQP_AMD_ADJOINT_STATS_COUNT (include/osqp_amd.h)
+    k = ccall((:osqp_amd_adjoint_stats, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Cc_int), model.workspace, out, length(out))
+    k == length(out) || error("osqp_amd_adjoint_stats: bad argument")
+    return (builds = Int(out[1]), solves = Int(out[2]), n_low = Int(out[3]), n_upp = Int(out[4]), kept = out[5] == 1.0, bytes = Int(out[6]))
+end
+
+"""
     batch_solve(P, A, Px, Ax, q, l, u; device = 0, settings...) -> (x, y, infos)
 
 `count` independent QPs that share the sparsity pattern of `P` (upper triangle) and `A`; the value arrays

@@ -31,10 +31,19 @@ call.  The handle holds ONE solution per instance: every forward stamps the inst
 `rows`), and a backward raises RuntimeError when one of ITS instances has been served by a later forward -- two forwards on
 disjoint selections can both run their backward (the forward-mode rule runs with its forward and needs no stamp).  Instances whose adjoint status is not 1 (no solution, failed factorisation) get zero gradients; where
 an instance's active constraints are dependent the derivative does not exist and the regularised answer is returned
-(include/osqp_amd.h, osqp_amd_batch_adjoint); the same holds for the tangents (osqp_amd_batch_jvp)."""
+(include/osqp_amd.h, osqp_amd_batch_adjoint); the same holds for the tangents (osqp_amd_batch_jvp).
+
+A single model (`interface.Model`: one large sparse QP, any n) as a layer: `QPFunction` / `QPLayer(model)`, at the end of this
+file.  Its arrays are host arrays (include/osqp_amd.h: every single-model entry takes host pointers), so tensors on any
+device go through the host; the forward is `update` + `solve`, the backward one `interface.adjoint` call on the kept factor.
+
+    layer = QPLayer(model)
+    x, y = layer(q=q_t, l=l_t, u=u_t)           # float64 tensors [n] / [m]; None keeps the model's data
+    loss(x, y).backward()                        # q_t.grad, l_t.grad, u_t.grad through osqp_amd_adjoint"""
 import numpy as np
 import torch
 
+from . import interface as _iface
 from .batch import selection
 
 NAMES = ("q", "l", "u", "Px", "Ax")
@@ -199,3 +208,66 @@ class BatchQPLayer(torch.nn.Module):
         if not stamp_holds(self.rb, stamp, sel):
             raise RuntimeError("BatchQPLayer.jacobian: the batch has been solved again since the last forward of this layer")
         return self.rb.jacobian(of=of, wrt=wrt, mode=mode, rows=sel, out_rows=out_rows, chunk=chunk, device=True)
+
+
+def stamp_model_forward(model):
+    """A forward has solved `model`: it carries that forward's stamp, which is returned (the single-model form of
+    `stamp_forward`: a model holds ONE solution)."""
+    model._qp_layer_stamp = getattr(model, "_qp_layer_stamp", 0) + 1
+    return model._qp_layer_stamp
+
+
+class QPFunction(torch.autograd.Function):
+    """(x, y) of a single model as a function of the data given: each tensor goes through `interface.update`, then `solve`,
+    which must end Solved.  backward: ONE `interface.adjoint` call that asks only for the gradients of the inputs that
+    require grad; it raises when a later forward has solved the model again (the stamp), and the library itself refuses a
+    model that was updated or warm-started by hand since (OSQPError: no current solution)."""
+
+    @staticmethod
+    def forward(ctx, model, q, l, u, Px, Ax):
+        given = dict(zip(NAMES, (q, l, u, Px, Ax)))
+        for name, t in given.items():
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != 1):
+                raise ValueError(f"{name}: expected a one-dimensional float64 tensor")
+        host = {name: t.detach().cpu().contiguous().numpy() for name, t in given.items() if t is not None}
+        if host:
+            _iface.update(model, **host)
+        res = _iface.solve(model)
+        ctx.model, ctx.stamp = model, stamp_model_forward(model)
+        model._qp_layer_info = res.info
+        if res.info.status != "Solved":
+            raise RuntimeError(f"QPFunction: the solve ended with status {res.info.status}; there is no solution to differentiate")
+        ref = next((t for t in given.values() if t is not None), None)
+        dev = ref.device if ref is not None else torch.device("cpu")
+        return torch.from_numpy(res.x.copy()).to(dev), torch.from_numpy(res.y.copy()).to(dev)
+
+    @staticmethod
+    def backward(ctx, gx, gy):
+        model = ctx.model
+        if getattr(model, "_qp_layer_stamp", None) != ctx.stamp:
+            raise RuntimeError("QPFunction: the model has been solved again since this forward; it holds one solution, so "
+                               "backward must run before the next forward")
+        need = dict(zip(NAMES, ctx.needs_input_grad[1:6]))
+        want = tuple(k for k in NAMES if need[k])
+        if not want or (gx is None and gy is None):
+            return (None,) * 6
+        ref = gx if gx is not None else gy
+        n, m = _iface.dimensions(model)
+        out = _iface.adjoint(model, dx=None if gx is None else gx.detach().cpu().numpy(),
+                             dy=None if gy is None or m == 0 else gy.detach().cpu().numpy(), want=want)
+        return (None,) + tuple(torch.from_numpy(out[k]).to(ref.device) if need[k] else None for k in NAMES)
+
+
+class QPLayer(torch.nn.Module):
+    """`layer(q=None, l=None, u=None, Px=None, Ax=None) -> (x, y)` on the single model `model` (set up, direct back-end, not
+    compact); `layer.info` is the `Info` of the last forward.  Px / Ax: full value arrays in the nnz order of `update`."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model, self.info = model, None
+
+    def forward(self, q=None, l=None, u=None, Px=None, Ax=None):
+        try:
+            return QPFunction.apply(self.model, q, l, u, Px, Ax)
+        finally:
+            self.info = getattr(self.model, "_qp_layer_info", None)

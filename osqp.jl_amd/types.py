@@ -185,6 +185,10 @@ EXT_SYMBOLS = {
     "osqp_amd_get_iterate": (c_int, [Workspace_p, c_float_p, c_float_p]),
     "osqp_amd_apply": (c_int, [Workspace_p, c_int, c_float_p, c_float_p]),
     "osqp_amd_spmv_layout": (c_int, [Workspace_p, c_int, c_float_p, c_int]),
+    # adjoint derivatives of a single model's solution: host arrays dx, dy in; dq, dl, du, dPx, dAx, act out (None = NULL)
+    "osqp_amd_adjoint": (c_int, [Workspace_p, c_int] + [c_float_p] * 8),
+    "osqp_amd_adjoint_release": (c_int, [Workspace_p]),
+    "osqp_amd_adjoint_stats": (c_int, [Workspace_p, c_float_p, c_int]),
     "osqp_amd_batch_solve": (
         c_int,
         [c_int, c_int, c_int, c_int_p, c_int_p, c_float_p, c_int_p, c_int_p, c_float_p,

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""What the adjoint of a single model costs (osqp_amd_adjoint): on the two large workloads of bench.py that the direct
+back-end serves -- control-1e6 and grid2d-5e5, built as bench.py builds them, bench.py's settings with polish = 1 -- one solve,
+then: the first adjoint call (classification, analysis, factorisation, one cotangent), K further calls at ncot = 1 and at
+ncot = 8 on the kept factor (all five gradients, host arrays in and out, so the copies are inside), the same with dq, dl, du
+only, `info.polish_time` of that solve (the same analysis and factorisation), the per-iteration solve time, and the bytes the
+kept factor holds.  A host clock around the blocking calls.  One JSON object per workload into the output file.  A report,
+not a gate.
+usage: python tools/model_adjoint.py [--out FILE] [--scale F] [K]      (--scale 0.01: the same structures 100 times smaller)"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import osqp_jl_amd as oq  # noqa: E402
+import bench  # noqa: E402
+import qp_zoo  # noqa: E402
+
+argv = sys.argv[1:]
+out_path, scale = os.path.join(ROOT, "profiles", "model_adjoint.json"), 1.0
+for flag in ("--out", "--scale"):
+    if flag in argv:
+        at = argv.index(flag)
+        if flag == "--out":
+            out_path = argv[at + 1]
+        else:
+            scale = float(argv[at + 1])
+        del argv[at:at + 2]
+K = int(argv[0]) if argv else 5
+lib = oq.load_library()
+SETTINGS = dict(bench.SETTINGS, polish=True)
+
+
+def build(workload):
+    kind, size, _, linsys = bench.WORKLOADS[workload]
+    if kind == "control":
+        prob = bench.control_problem(max(4, int(size * scale)))
+    else:
+        prob = qp_zoo.grid2d(max(8, int(size * scale ** 0.5)))
+    model = oq.Model(lib)
+    t0 = time.time()
+    oq.setup(model, linsys_solver=linsys, **prob, **SETTINGS)
+    return model, time.time() - t0
+
+
+def timed(fn, reps):
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return dict(min_ms=min(ts), median_ms=float(np.median(ts)), max_ms=max(ts))
+
+
+report = dict(scale=scale, K=K, settings={k: v for k, v in SETTINGS.items()}, workloads={})
+for workload in ("control-1e6", "grid2d-5e5"):
+    model, setup_s = build(workload)
+    n, m = oq.dimensions(model)
+    r = oq.solve(model)
+    st = oq.stats(model)
+    rec = dict(n=n, m=m, nnzA=int(st[1]), nnzP_triu=int(st[3]), setup_s=setup_s, status=r.info.status, iters=r.info.iter,
+               status_polish=r.info.status_polish, polish_time_ms=r.info.polish_time * 1e3, solve_time_ms=r.info.solve_time * 1e3,
+               per_iteration_ms=r.info.solve_time * 1e3 / max(1, r.info.iter), admm_kkt_solve_ms=float(lib.osqp_amd_time_kernel(model.workspace, 3, 20)),
+               refine=int(SETTINGS.get("polish_refine_iter", 3)))
+    if r.info.status == "Solved":
+        rng = np.random.default_rng(1)
+        gx, gy = rng.standard_normal((8, n)), rng.standard_normal((8, m))
+        t0 = time.perf_counter()
+        first = oq.adjoint(model, dx=gx[0], dy=gy[0])
+        rec["first_call_ms"] = (time.perf_counter() - t0) * 1e3
+        s = oq.adjoint_stats(model)
+        rec.update(n_low=s["n_low"], n_upp=s["n_upp"], factor_bytes=s["bytes"])
+        rec["later_ncot1"] = timed(lambda: oq.adjoint(model, dx=gx[0], dy=gy[0]), K)
+        rec["later_ncot8"] = timed(lambda: oq.adjoint(model, dx=gx, dy=gy), K)
+        rec["later_ncot1_vectors_only"] = timed(lambda: oq.adjoint(model, dx=gx[0], dy=gy[0], want=("q", "l", "u")), K)
+        rec["later_ncot8_vectors_only"] = timed(lambda: oq.adjoint(model, dx=gx, dy=gy, want=("q", "l", "u")), K)
+        rec["per_further_cotangent_ms"] = (rec["later_ncot8"]["median_ms"] - rec["later_ncot1"]["median_ms"]) / 7.0
+        rec["per_further_cotangent_vectors_only_ms"] = (rec["later_ncot8_vectors_only"]["median_ms"] - rec["later_ncot1_vectors_only"]["median_ms"]) / 7.0
+        again = oq.adjoint(model, dx=gx[0], dy=gy[0])
+        rec["repeat_is_bit_identical"] = all(np.array_equal(first[k], again[k]) for k in first)
+        s2 = oq.adjoint_stats(model)
+        rec.update(builds=s2["builds"], kkt_solves=s2["solves"])
+        oq.adjoint_release(model)
+    oq.clean(model)
+    report["workloads"][workload] = rec
+    print(workload, json.dumps(rec), flush=True)
+
+os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+with open(out_path, "w") as f:
+    json.dump(report, f, indent=1, sort_keys=True)
+    f.write("\n")
+print("wrote", out_path)
