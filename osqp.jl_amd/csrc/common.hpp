@@ -146,7 +146,7 @@ struct DevPanel {
   DevBuf<int> unit_s0, unit_ns;              // unit u owns slices [unit_s0[u], unit_s0[u] + unit_ns[u])
   DevBuf<uint32_t> slice_base;               // offset of the slice inside sval / scol
   DevBuf<int> slice_len;                     // padded row length of the slice
-  DevBuf<int> slice_rows;                    // [64 per slice] row id of every lane (-1: empty lane)
+  DevBuf<uint16_t> slice_rows;               // [64 per slice] lane's row inside its tile (0xFFFF: empty lane)
   DevBuf<uint32_t> cellbase;                 // [B * rows] slot of the first entry of (panel, row): value refresh
   DevBuf<double> sval;
   DevBuf<uint16_t> scol;

@@ -39,6 +39,7 @@
 // Algorithmic bytes keep the CSR accounting of SURVEY.md 8d (12 nnz + ...); the panel copy
 // actually moves 10 B per stored entry + 16 B per (row, panel) of partial sums.
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.hpp"
 #include <functional>
@@ -62,6 +63,28 @@ constexpr int64_t kLenMax = 0x7FFFF;  // longest (row, panel) cell the 32-bit so
 int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 int panel_shift() { return env_int("OSQP_AMD_PANEL_SHIFT", 14); }           // W = 16384 columns = 128 KB of fp64 in LDS
 int panel_tile_nnz() { return env_int("OSQP_AMD_PANEL_TILE_NNZ", 65536); }  // non-zeros per workgroup tile
+
+// An entry of slice_rows (one per lane of a slice): the lane's row inside its tile (< kTileRowsMax, so 16 bits hold it and
+// 0xFFFF is no row), or kLaneEmpty when the slice has fewer than 64 rows.  2 bytes per lane: the table is read once per
+// product next to the entries (128 B per slice of ~17 positions x 640 B).
+constexpr uint16_t kLaneEmpty = 0xFFFF;
+
+// OSQP_AMD_SELL_NT (default on; read once per process): the LDS-staged product reads what it reads exactly once -- values,
+// column ids, slice descriptors -- with non-temporal loads; 0: default-policy loads.  The same bits either way.
+bool sell_nt() {
+  static const bool v = env_int("OSQP_AMD_SELL_NT", 1) != 0;
+  return v;
+}
+template <typename F>
+void with_sell_nt(F &&f) {
+  if (sell_nt()) f(std::true_type());
+  else f(std::false_type());
+}
+template <bool kNT, typename T>
+__device__ __forceinline__ T ld_once(const T *p) {
+  if constexpr (kNT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
 
 // first position in [s, e) with col >= target (cols ascending inside a row)
 __device__ __forceinline__ int64_t lower_bound_col(const int *__restrict__ col, int64_t s, int64_t e, int target) {
@@ -211,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void k_tile_layout(int rows, const int *_
                                                           const int64_t *__restrict__ slice0, const int64_t *__restrict__ padded0,
                                                           int *__restrict__ tile_s0, int *__restrict__ tile_ns,
                                                           uint32_t *__restrict__ slice_base, int *__restrict__ slice_len,
-                                                          int *__restrict__ slice_rows, uint32_t *__restrict__ cellbase) {
+                                                          uint16_t *__restrict__ slice_rows, uint32_t *__restrict__ cellbase) {
   __shared__ uint32_t key[kSortN];
   __shared__ uint32_t sbase[kSortN / 64 + 1];
   __shared__ int nz;
@@ -229,12 +252,12 @@ __global__ __launch_bounds__(kThreads) void k_tile_layout(int rows, const int *_
   const int64_t s0 = slice0[t];
   for (int i = threadIdx.x; i < ns * 64; i += kThreads) {
     const int sl = i >> 6, lane = i & 63;
-    int row = -1;
+    uint16_t e = kLaneEmpty;
     if (i < nz) {
-      row = r0 + (int)(key[i] & 4095u);
-      cellbase[(size_t)b * rows + row] = sbase[sl] + (uint32_t)lane;
+      e = (uint16_t)(key[i] & 4095u);
+      cellbase[(size_t)b * rows + r0 + (int)e] = sbase[sl] + (uint32_t)lane;
     }
-    slice_rows[(size_t)(s0 + sl) * 64 + lane] = row;
+    slice_rows[(size_t)(s0 + sl) * 64 + lane] = e;
     if (lane == 0) { slice_base[s0 + sl] = sbase[sl]; slice_len[s0 + sl] = (int)key_len(key[sl * 64]); }
   }
 }
@@ -289,9 +312,10 @@ constexpr int kFillK = 16;            // positions per pass
 constexpr int kFillStride = 65;       // LDS row stride (64 rows + 1: the transposed writes spread over the banks)
 constexpr int kFillWaves = 4;
 template <typename ColT>
-__global__ __launch_bounds__(kFillWaves * 64) void k_sell_fill_lds(int rows, int shift, const int *__restrict__ ub, const int *__restrict__ unit_s0,
+__global__ __launch_bounds__(kFillWaves * 64) void k_sell_fill_lds(int rows, int shift, const int *__restrict__ ub, const int *__restrict__ unit_r0,
+                                                                 const int *__restrict__ unit_s0,
                                                                  const int *__restrict__ unit_ns, const uint32_t *__restrict__ slice_base,
-                                                                 const int *__restrict__ slice_len, const int *__restrict__ slice_rows,
+                                                                 const int *__restrict__ slice_len, const uint16_t *__restrict__ slice_rows,
                                                                  const uint32_t *__restrict__ cellsrc, const int64_t *__restrict__ off,
                                                                  const int *__restrict__ col, const double *__restrict__ val,
                                                                  ColT *__restrict__ scol, double *__restrict__ sval, uint32_t *__restrict__ slot,
@@ -300,7 +324,7 @@ __global__ __launch_bounds__(kFillWaves * 64) void k_sell_fill_lds(int rows, int
   __shared__ double tv[kFillWaves][kFillK * kFillStride];
   __shared__ uint32_t tc[kFillWaves][kFillK * kFillStride];
   __shared__ int start[kFillWaves][65];
-  const int u = blockIdx.x, b = ub[u];
+  const int u = blockIdx.x, b = ub[u], r0 = unit_r0[u];
   const int s0 = unit_s0[u], ns = unit_ns[u];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int mask = (1 << shift) - 1;
@@ -310,11 +334,11 @@ __global__ __launch_bounds__(kFillWaves * 64) void k_sell_fill_lds(int rows, int
   for (int sl = s0 + wave; sl < s0 + ns; sl += kFillWaves) {
     const uint32_t base = slice_base[sl];
     const int L = slice_len[sl];
-    const int row = slice_rows[(size_t)sl * 64 + lane];
+    const uint16_t ent = slice_rows[(size_t)sl * 64 + lane];
     uint32_t src = 0;
     int len = 0;
-    if (row >= 0) {
-      const size_t c = (size_t)b * rows + row;
+    if (ent != kLaneEmpty) {
+      const size_t c = (size_t)b * rows + r0 + (int)ent;
       src = cellsrc[c];
       len = (int)(off[c + 1] - off[c]);
     }
@@ -370,12 +394,13 @@ __global__ __launch_bounds__(kFillWaves * 64) void k_sell_fill_lds(int rows, int
 // the product
 // ---------------------------------------------------------------------------------------------
 // kSquare: y = (M .* M) x -- the Jacobi diagonal of A' diag(rho) A is this product of A' with rho (compact mode)
-template <typename ColT, bool kStageX, bool kSquare>
+// kNT: non-temporal loads for the matrix stream and the slice descriptors (sell_nt()); x, LDS and the row sums as ever
+template <typename ColT, bool kStageX, bool kSquare, bool kNT>
 __device__ __forceinline__ void sell_tile(int t, int rows, int cols, int shift, int B, int Gp, const int *__restrict__ tile_g,
                                           const int *__restrict__ tile_r0, const int *__restrict__ tile_r1,
                                           const int *__restrict__ unit_s0, const int *__restrict__ unit_ns,
                                           const uint32_t *__restrict__ slice_base, const int *__restrict__ slice_len,
-                                          const int *__restrict__ slice_rows, const ColT *__restrict__ scol,
+                                          const uint16_t *__restrict__ slice_rows, const ColT *__restrict__ scol,
                                           const double *__restrict__ sval, const double *__restrict__ x, double *__restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int g = tile_g[t];
@@ -422,13 +447,18 @@ __device__ __forceinline__ void sell_tile(int t, int rows, int cols, int shift, 
     // the tail of a slice is a guarded batch (the guards are wave-uniform), not one load at a time.
     int sl = s0 + wave;
     size_t nbase = 0;
-    int nL = 0, nrow = -1;
-    if (sl < s0 + ns) { nbase = (size_t)slice_base[sl]; nL = slice_len[sl]; nrow = slice_rows[(size_t)sl * 64 + lane]; }
+    int nL = 0;
+    uint16_t nrow = kLaneEmpty;
+    if (sl < s0 + ns) {
+      nbase = (size_t)ld_once<kNT>(slice_base + sl); nL = ld_once<kNT>(slice_len + sl); nrow = ld_once<kNT>(slice_rows + (size_t)sl * 64 + lane);
+    }
     for (; sl < s0 + ns; sl += kWaves) {
       const size_t base = nbase + lane;
-      const int L = nL, row = nrow;
+      const int L = nL;
+      const uint16_t row = nrow;
       if (sl + kWaves < s0 + ns) {
-        nbase = (size_t)slice_base[sl + kWaves]; nL = slice_len[sl + kWaves]; nrow = slice_rows[(size_t)(sl + kWaves) * 64 + lane];
+        nbase = (size_t)ld_once<kNT>(slice_base + sl + kWaves); nL = ld_once<kNT>(slice_len + sl + kWaves);
+        nrow = ld_once<kNT>(slice_rows + (size_t)(sl + kWaves) * 64 + lane);
       }
       const double *v = sval + base;
       const ColT *c = scol + base;
@@ -438,55 +468,58 @@ __device__ __forceinline__ void sell_tile(int t, int rows, int cols, int shift, 
         ColT cc[kBatch];
         if (k + kBatch <= L) {
 #pragma unroll
-          for (int u = 0; u < kBatch; u++) { cv[u] = v[(size_t)(k + u) * 64]; cc[u] = c[(size_t)(k + u) * 64]; }
+          for (int u = 0; u < kBatch; u++) { cv[u] = ld_once<kNT>(v + (size_t)(k + u) * 64); cc[u] = ld_once<kNT>(c + (size_t)(k + u) * 64); }
         } else {
 #pragma unroll
           for (int u = 0; u < kBatch; u++) {
             const bool in = k + u < L;
-            cv[u] = in ? v[(size_t)(k + u) * 64] : 0.0;
-            cc[u] = in ? c[(size_t)(k + u) * 64] : (ColT)0;
+            cv[u] = in ? ld_once<kNT>(v + (size_t)(k + u) * 64) : 0.0;
+            cc[u] = in ? ld_once<kNT>(c + (size_t)(k + u) * 64) : (ColT)0;
           }
         }
 #pragma unroll
         for (int u = 0; u < kBatch; u++) a0 += (kSquare ? cv[u] * cv[u] : cv[u]) * xs[cc[u]];
       }
-      if (row >= 0) ys[row - r0] += a0;  // a row appears once per panel; panels are separated by barriers
+      if (row != kLaneEmpty) ys[row] += a0;  // a row appears once per panel; panels are separated by barriers
     }
   }
   __syncthreads();
   double *out = partial + (size_t)g * rows + r0;
   for (int i = threadIdx.x; i < nrows; i += kThreads) out[i] = ys[i];
 }
-template <typename ColT, bool kStageX, bool kSquare = false>
+template <typename ColT, bool kStageX, bool kSquare, bool kNT>
 __global__ __launch_bounds__(kThreads) void k_spmv_sell(int rows, int cols, int shift, int B, int Gp, const int *__restrict__ tile_g,
                                                         const int *__restrict__ tile_r0, const int *__restrict__ tile_r1,
                                                         const int *__restrict__ unit_s0, const int *__restrict__ unit_ns,
                                                         const uint32_t *__restrict__ slice_base, const int *__restrict__ slice_len,
-                                                        const int *__restrict__ slice_rows, const ColT *__restrict__ scol,
+                                                        const uint16_t *__restrict__ slice_rows, const ColT *__restrict__ scol,
                                                         const double *__restrict__ sval, const double *__restrict__ x,
                                                         double *__restrict__ partial, const int *__restrict__ skip) {
   if (skip && *skip) return;
-  sell_tile<ColT, kStageX, kSquare>(blockIdx.x, rows, cols, shift, B, Gp, tile_g, tile_r0, tile_r1, unit_s0, unit_ns, slice_base, slice_len,
-                                    slice_rows, scol, sval, x, partial);
+  sell_tile<ColT, kStageX, kSquare, kNT>(blockIdx.x, rows, cols, shift, B, Gp, tile_g, tile_r0, tile_r1, unit_s0, unit_ns, slice_base,
+                                          slice_len, slice_rows, scol, sval, x, partial);
 }
 // Two matrices against the same vector in one launch (A p and P p of a CG iteration): at mid size neither fills the
 // device on its own -- 1e7 non-zeros are 153 tiles on 256 CUs -- and the two products do not depend on each other.  Same
 // tiles, same arithmetic: the results are those of the two single launches, bit for bit.
 struct SellSide {
   int rows, cols, B, Gp, ntiles;
-  const int *tile_g, *tile_r0, *tile_r1, *unit_s0, *unit_ns, *slice_len, *slice_rows;
+  const int *tile_g, *tile_r0, *tile_r1, *unit_s0, *unit_ns, *slice_len;
+  const uint16_t *slice_rows;
   const uint32_t *slice_base;
   const uint16_t *scol;
   const double *sval;
   double *partial;
 };
+template <bool kNT>
 __global__ __launch_bounds__(kThreads) void k_spmv_sell_pair(SellSide a, SellSide b, int shift, const double *__restrict__ x,
                                                              const int *__restrict__ skip) {
   if (skip && *skip) return;
   const bool first = (int)blockIdx.x < a.ntiles;
   const SellSide &m = first ? a : b;
-  sell_tile<uint16_t, true, false>(first ? (int)blockIdx.x : (int)blockIdx.x - a.ntiles, m.rows, m.cols, shift, m.B, m.Gp, m.tile_g, m.tile_r0,
-                                   m.tile_r1, m.unit_s0, m.unit_ns, m.slice_base, m.slice_len, m.slice_rows, m.scol, m.sval, x, m.partial);
+  sell_tile<uint16_t, true, false, kNT>(first ? (int)blockIdx.x : (int)blockIdx.x - a.ntiles, m.rows, m.cols, shift, m.B, m.Gp, m.tile_g,
+                                         m.tile_r0, m.tile_r1, m.unit_s0, m.unit_ns, m.slice_base, m.slice_len, m.slice_rows, m.scol, m.sval, x,
+                                         m.partial);
 }
 
 // y[i] = (rscale ? rscale[i] : 1) * sum_g partial[g][i] + beta * y[i] + gamma * v[i]   (group order is fixed)
@@ -582,7 +615,7 @@ __global__ __launch_bounds__(kThreads) void k_sell_visit(int rows, int shift, in
                                                          const int *__restrict__ tile_r0, const int *__restrict__ tile_r1,
                                                          const int *__restrict__ unit_s0, const int *__restrict__ unit_ns,
                                                          const uint32_t *__restrict__ slice_base, const int *__restrict__ slice_len,
-                                                         const int *__restrict__ slice_rows, const ColT *__restrict__ scol,
+                                                         const uint16_t *__restrict__ slice_rows, const ColT *__restrict__ scol,
                                                          double *__restrict__ sval, const double *__restrict__ r, const double *__restrict__ c,
                                                          int order, double scalar, int row0, double *__restrict__ out) {
   __shared__ double ys[kOp == 1 ? kTileRowsMax : 1];
@@ -599,8 +632,9 @@ __global__ __launch_bounds__(kThreads) void k_sell_visit(int rows, int shift, in
     for (int sl = s0 + wave; sl < s0 + ns; sl += kWaves) {
       const size_t base = (size_t)slice_base[sl] + lane;
       const int L = slice_len[sl];
-      const int row = slice_rows[(size_t)sl * 64 + lane];
-      if (row < 0) continue;
+      const uint16_t ent = slice_rows[(size_t)sl * 64 + lane];
+      if (ent == kLaneEmpty) continue;
+      const int row = r0 + (int)ent;
       double mx = 0.0;
       for (int k = 0; k < L; k++) {
         const size_t at = base + (size_t)k * 64;
@@ -643,7 +677,7 @@ __global__ __launch_bounds__(kThreads) void k_sell_scale_norm(int rows, int cols
                                                               const int *__restrict__ tile_r0, const int *__restrict__ tile_r1,
                                                               const int *__restrict__ unit_s0, const int *__restrict__ unit_ns,
                                                               const uint32_t *__restrict__ slice_base, const int *__restrict__ slice_len,
-                                                              const int *__restrict__ slice_rows, const ColT *__restrict__ scol,
+                                                              const uint16_t *__restrict__ slice_rows, const ColT *__restrict__ scol,
                                                               double *__restrict__ sval, const double *__restrict__ r,
                                                               const double *__restrict__ c, int order, double pre, int row0,
                                                               double *__restrict__ partial) {
@@ -681,8 +715,12 @@ __global__ __launch_bounds__(kThreads) void k_sell_scale_norm(int rows, int cols
     size_t nbase = 0;
     int nL = 0, nrow = -1;
     double nrs = 1.0;
+    auto lane_global_row = [&](size_t slice) {  // -1: empty lane
+      const uint16_t ent = slice_rows[slice * 64 + lane];
+      return ent == kLaneEmpty ? -1 : r0 + (int)ent;
+    };
     if (sl < s0 + ns) {
-      nbase = (size_t)slice_base[sl]; nL = slice_len[sl]; nrow = slice_rows[(size_t)sl * 64 + lane];
+      nbase = (size_t)slice_base[sl]; nL = slice_len[sl]; nrow = lane_global_row((size_t)sl);
       nrs = nrow >= 0 ? rv[nrow] : 1.0;
     }
     for (; sl < s0 + ns; sl += kWaves) {
@@ -690,7 +728,7 @@ __global__ __launch_bounds__(kThreads) void k_sell_scale_norm(int rows, int cols
       const int L = nL, row = nrow;
       const double rs = nrs;
       if (sl + kWaves < s0 + ns) {
-        nbase = (size_t)slice_base[sl + kWaves]; nL = slice_len[sl + kWaves]; nrow = slice_rows[(size_t)(sl + kWaves) * 64 + lane];
+        nbase = (size_t)slice_base[sl + kWaves]; nL = slice_len[sl + kWaves]; nrow = lane_global_row((size_t)(sl + kWaves));
         nrs = nrow >= 0 ? rv[nrow] : 1.0;
       }
       double *v = sval + base;
@@ -926,11 +964,11 @@ void panel_build(DevCsr &M, hipStream_t s, uint32_t *slot, bool will_compact, co
   static const bool lds_fill = !(getenv("OSQP_AMD_SELL_FILL") && atoi(getenv("OSQP_AMD_SELL_FILL")) == 0);
   auto fill = [&](int what) {
     if (P.wide)
-      OQ_LAUNCH(k_sell_fill_lds<uint32_t>, dim3((unsigned)nunits), dim3(kFillWaves * 64), 0, s, M.rows, P.shift, ub.get(), P.unit_s0.get(),
+      OQ_LAUNCH(k_sell_fill_lds<uint32_t>, dim3((unsigned)nunits), dim3(kFillWaves * 64), 0, s, M.rows, P.shift, ub.get(), u0.get(), P.unit_s0.get(),
                 P.unit_ns.get(), P.slice_base.get(), P.slice_len.get(), P.slice_rows.get(), cellsrc.get(), off.get(), M.col.get(), M.val.get(),
                 P.scol32.get(), P.sval.get(), slot, what);
     else
-      OQ_LAUNCH(k_sell_fill_lds<uint16_t>, dim3((unsigned)nunits), dim3(kFillWaves * 64), 0, s, M.rows, P.shift, ub.get(), P.unit_s0.get(),
+      OQ_LAUNCH(k_sell_fill_lds<uint16_t>, dim3((unsigned)nunits), dim3(kFillWaves * 64), 0, s, M.rows, P.shift, ub.get(), u0.get(), P.unit_s0.get(),
                 P.unit_ns.get(), P.slice_base.get(), P.slice_len.get(), P.slice_rows.get(), cellsrc.get(), off.get(), M.col.get(), M.val.get(),
                 P.scol.get(), P.sval.get(), slot, what);
   };
@@ -957,10 +995,6 @@ void panel_build(DevCsr &M, hipStream_t s, uint32_t *slot, bool will_compact, co
     fill(3);
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  if (!P.wide) {
-    static size_t allowed[64] = {0};
-    allow_dynamic_lds((const void *)k_spmv_sell<uint16_t, true>, spmv_lds_bytes(P.shift), allowed);
-  }
   P.active = true;
 }
 
@@ -970,14 +1004,20 @@ void spmv_panel(const DevCsr &M, const double *x, double *y, const double *rscal
                 hipStream_t s, const SpmvExtra *extra) {
   const DevPanel &P = M.panel;
   const SpmvExtra ex = extra ? *extra : SpmvExtra();
-  if (P.wide)
-    OQ_LAUNCH((k_spmv_sell<uint32_t, false>), dim3(P.ntiles), dim3(kThreads), sizeof(double) * kTileRowsMax, s, M.rows, M.cols, P.shift, P.B,
-              P.Gp, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(),
+  if (P.wide) {  // default-policy loads: its x is served by the L2 the matrix stream passes through
+    OQ_LAUNCH((k_spmv_sell<uint32_t, false, false, false>), dim3(P.ntiles), dim3(kThreads), sizeof(double) * kTileRowsMax, s, M.rows, M.cols,
+              P.shift, P.B, P.Gp, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(),
               P.slice_len.get(), P.slice_rows.get(), P.scol32.get(), P.sval.get(), x, P.partial.get(), g_skip);
-  else
-    OQ_LAUNCH((k_spmv_sell<uint16_t, true>), dim3(P.ntiles), dim3(kThreads), spmv_lds_bytes(P.shift), s, M.rows, M.cols, P.shift, P.B,
-              P.Gp, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(),
-              P.slice_len.get(), P.slice_rows.get(), P.scol.get(), P.sval.get(), x, P.partial.get(), g_skip);
+  } else {
+    with_sell_nt([&](auto nt) {
+      constexpr bool kNT = decltype(nt)::value;
+      static size_t allowed[64] = {0};
+      allow_dynamic_lds((const void *)k_spmv_sell<uint16_t, true, false, kNT>, spmv_lds_bytes(P.shift), allowed);
+      OQ_LAUNCH((k_spmv_sell<uint16_t, true, false, kNT>), dim3(P.ntiles), dim3(kThreads), spmv_lds_bytes(P.shift), s, M.rows, M.cols, P.shift,
+                P.B, P.Gp, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(),
+                P.slice_len.get(), P.slice_rows.get(), P.scol.get(), P.sval.get(), x, P.partial.get(), g_skip);
+    });
+  }
   OQ_LAUNCH(k_panel_reduce, dim3(reduce_grid(M.rows)), dim3(kBlock), 0, s, M.rows, P.NG, P.partial.get(), y, rscale, beta, gamma, v, ex, g_skip);
 }
 
@@ -1000,9 +1040,12 @@ void spmv_pair(const DevCsr &Ma, const DevCsr &Mb, const double *x, double *ya, 
     return t;
   };
   const DevPanel &A = Ma.panel, &B = Mb.panel;
-  static size_t allowed[64] = {0};
-  allow_dynamic_lds((const void *)k_spmv_sell_pair, spmv_lds_bytes(A.shift), allowed);
-  OQ_LAUNCH(k_spmv_sell_pair, dim3(A.ntiles + B.ntiles), dim3(kThreads), spmv_lds_bytes(A.shift), s, side(Ma), side(Mb), A.shift, x, g_skip);
+  with_sell_nt([&](auto nt) {
+    constexpr bool kNT = decltype(nt)::value;
+    static size_t allowed[64] = {0};
+    allow_dynamic_lds((const void *)k_spmv_sell_pair<kNT>, spmv_lds_bytes(A.shift), allowed);
+    OQ_LAUNCH(k_spmv_sell_pair<kNT>, dim3(A.ntiles + B.ntiles), dim3(kThreads), spmv_lds_bytes(A.shift), s, side(Ma), side(Mb), A.shift, x, g_skip);
+  });
   ReduceSide ra{Ma.rows, A.NG, reduce_grid(Ma.rows), A.partial.get(), ya, 0.0, nullptr, extra_a ? *extra_a : SpmvExtra()};
   ReduceSide rb{Mb.rows, B.NG, reduce_grid(Mb.rows), B.partial.get(), yb, gamma_b, vb, SpmvExtra()};
   OQ_LAUNCH(k_panel_reduce_pair, dim3(ra.grid + rb.grid), dim3(kBlock), 0, s, ra, rb, g_skip);
@@ -1048,11 +1091,14 @@ void panel_diag(const DevCsr &M, double *diag, int row0, hipStream_t s) {
 // y = (M .* M) x + gamma v  (LDS-staged panels only; the wide mode keeps its CSR arrays)
 void spmv_panel_squared(const DevCsr &M, const double *x, double *y, double gamma, const double *v, hipStream_t s) {
   const DevPanel &P = M.panel;
-  HIP_CHECK(hipFuncSetAttribute((const void *)k_spmv_sell<uint16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)spmv_lds_bytes(P.shift)));
-  OQ_LAUNCH((k_spmv_sell<uint16_t, true, true>), dim3(P.ntiles), dim3(kThreads), spmv_lds_bytes(P.shift), s, M.rows, M.cols, P.shift, P.B,
-            P.Gp, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(),
-            P.slice_len.get(), P.slice_rows.get(), P.scol.get(), P.sval.get(), x, P.partial.get(), (const int *)nullptr);
+  with_sell_nt([&](auto nt) {
+    constexpr bool kNT = decltype(nt)::value;
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_spmv_sell<uint16_t, true, true, kNT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)spmv_lds_bytes(P.shift)));
+    OQ_LAUNCH((k_spmv_sell<uint16_t, true, true, kNT>), dim3(P.ntiles), dim3(kThreads), spmv_lds_bytes(P.shift), s, M.rows, M.cols, P.shift,
+              P.B, P.Gp, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(),
+              P.slice_len.get(), P.slice_rows.get(), P.scol.get(), P.sval.get(), x, P.partial.get(), (const int *)nullptr);
+  });
   OQ_LAUNCH(k_panel_reduce, dim3(reduce_grid(M.rows)), dim3(kBlock), 0, s, M.rows, P.NG, P.partial.get(), y, (const double *)nullptr, 0.0, gamma, v,
             SpmvExtra(), (const int *)nullptr);
 }
