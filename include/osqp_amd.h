@@ -712,9 +712,38 @@ c_int osqp_amd_adjoint(OSQPWorkspace *work, c_int ncot,
                        c_float *dq /* [ncot x n] */, c_float *dl /* [ncot x m] */, c_float *du /* [ncot x m] */,
                        c_float *dPx /* [ncot x nnz(triu P)] */, c_float *dAx /* [ncot x nnz(A)] */,
                        c_float *act /* [m] or NULL */);
+/* ---- Forward sensitivities of the solution of a single model ----
+ *
+ * osqp_amd_jvp pushes ndir directions of the data forward to the solution the last osqp_solve left in `work`: a direction is
+ * (tq [n], tl, tu [m], tPx [nnz(triu P)], tAx [nnz(A)]), the matrix tangents as value arrays in the caller's nnz order (the
+ * index space of osqp_update_P / _A, also where the columns of A came unsorted); the arrays are direction-major
+ * ([ndir x cols]) and any of the five may be NULL = zero.  tx [ndir x n] and ty [ndir x m] receive dx/dtheta . t and
+ * dy/dtheta . t; either may be NULL (not wanted); act as for osqp_amd_adjoint.  All pointers are host pointers.
+ *
+ *   With a = L u U and K = [P, Aa'; Aa, 0] of osqp_amd_adjoint, one solve per direction
+ *     K [tx; ty_a] = [-(tq + tP x + tA' y); (tb - tA x)_a],   tb_i = tl_i on L, tu_i on U,   ty = 0 off a,
+ *   tP the symmetric matrix of the stored upper triangle (a diagonal entry counts once), x and y the solution.  On a row with
+ *   l == u (always active, counts as lower) only tl is read.  The solve is osqp_amd_adjoint's: the same kept factor, the same
+ *   refinement (and the same rule at polish_refine_iter = 0).  Direction d of a call has the bits of a call with that
+ *   direction alone, and a NULL tangent those of a tangent of zeros.
+ *
+ *   The kept state is osqp_amd_adjoint's, created by whichever of the two is called first after a solve and used by both: a
+ *   jvp after an adjoint on the same solution (or the other way round) builds nothing; what drops the factor is unchanged,
+ *   and so is "the call changes nothing else".  The first call with tPx or tAx adds two maps of 4 bytes per stored entry of
+ *   the full P and of A to the workspace (until osqp_cleanup).
+ *
+ *   Returns 0, or non-zero with the reason in osqp_amd_last_error and no output written, with osqp_amd_adjoint's codes: 7
+ *   NULL workspace; 1 ndir < 1, tx or ty wanted with all five tangents NULL, nothing wanted at all, no current solution, a
+ *   status other than OSQP_SOLVED; 6 a compact or a row-sharded workspace, a reduced factor that is too large; 4 a failed
+ *   numeric factorisation. */
+c_int osqp_amd_jvp(OSQPWorkspace *work, c_int ndir,
+                   const c_float *tq /* [ndir x n] or NULL = 0 */, const c_float *tl /* [ndir x m] */, const c_float *tu /* [ndir x m] */,
+                   const c_float *tPx /* [ndir x nnz(triu P)] */, const c_float *tAx /* [ndir x nnz(A)] */,
+                   c_float *tx /* [ndir x n] or NULL */, c_float *ty /* [ndir x m] or NULL */, c_float *act /* [m] or NULL */);
 /* Drop the kept factor now.  0, also when none is kept; 7 on a NULL workspace. */
 c_int osqp_amd_adjoint_release(OSQPWorkspace *work);
-/* Fills out[0..count): 0 factor builds so far, 1 KKT solves so far (1 + polish_refine_iter per pair; 2 at polish_refine_iter = 0), 2, 3 n_low and
+/* Entries 0 and 1 count the builds and the KKT solves of osqp_amd_adjoint and of osqp_amd_jvp together (one factor serves both).
+ * Fills out[0..count): 0 factor builds so far, 1 KKT solves so far (1 + polish_refine_iter per pair or direction; 2 at polish_refine_iter = 0), 2, 3 n_low and
  * n_upp of the kept factor (0 if none), 4 1 if a factor is kept, 5 device bytes the kept factor holds with its index
  * arrays and scratch.  Like osqp_amd_get_stats it returns the number of entries written (at most
  * OSQP_AMD_ADJOINT_STATS_COUNT), 0 on a NULL argument. */

@@ -820,6 +820,28 @@ c_int osqp_amd_adjoint(OSQPWorkspace *w, c_int ncot, const c_float *dx, const c_
     return model_adjoint_run(e, (int)ncot, dx, dy, dq, dl, du, dPx, dAx, act);
   });
 }
+// ---- forward sensitivities on the same kept factor (csrc/direct_jvp.hpp) ----
+c_int osqp_amd_jvp(OSQPWorkspace *w, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,
+                   const c_float *tAx, c_float *tx, c_float *ty, c_float *act) {
+  if (!w) { set_last_error("osqp_amd_jvp: no workspace"); return 7; }
+  if (ndir < 1) { set_last_error("osqp_amd_jvp: ndir must be at least 1"); return 1; }
+  if (ndir > 2147483647LL) { set_last_error("osqp_amd_jvp: ndir out of range"); return 1; }
+  if ((tx || ty) && !tq && !tl && !tu && !tPx && !tAx) {
+    set_last_error("osqp_amd_jvp: a sensitivity is wanted but tq, tl, tu, tPx and tAx are all NULL");
+    return 1;
+  }
+  if (!tx && !ty && !act) { set_last_error("osqp_amd_jvp: no output is wanted"); return 1; }
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    if (!e.solution_current)
+      throw Error(1, "osqp_amd_jvp: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
+    if (w->info->status_val != OSQP_SOLVED)
+      throw Error(1, std::string("osqp_amd_jvp: the last osqp_solve did not end with status Solved (") + w->info->status +
+                         "): there is no solution to differentiate");
+    return model_jvp_run(e, (int)ndir, tq, tl, tu, tPx, tAx, tx, ty, act);
+  });
+}
 c_int osqp_amd_adjoint_release(OSQPWorkspace *w) {
   if (!w) { set_last_error("osqp_amd_adjoint_release: no workspace"); return 7; }
   OQ_ON_DEVICE(w);

@@ -1934,3 +1934,5 @@ int polish_run(Engine &e) {
 
 // adjoint derivatives of the solution: the same factor object and the same solve-and-refine loop with another right-hand side
 #include "direct_adjoint.hpp"
+// forward sensitivities on the same kept factor: the right-hand side of a direction of the data
+#include "direct_jvp.hpp"

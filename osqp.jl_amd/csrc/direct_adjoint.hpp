@@ -94,6 +94,10 @@ struct ModelAdjoint {
   DevBuf<int> Pcol, Acol;          // column of every entry of the caller's triu(P) / of A (sorted copy): once per workspace
   DevBuf<int64_t> A_to_sorted;     // the engine's map on the device (empty: the caller's columns were sorted)
   bool patterns = false;
+  // osqp_amd_jvp (direct_jvp.hpp): for every position of Pf the entry of the caller's triu(P) it mirrors, for every position
+  // of A (CSR) the entry of the sorted CSC copy -- P_k2lo / P_k2up / A_k2pos inverted, at the first call with tPx or tAx
+  DevBuf<int> Ppos2k, Apos2k;
+  bool jvp_maps = false;
   long long builds = 0, solves = 0;
 };
 void model_adjoint_destroy(ModelAdjoint *a) { delete a; }
@@ -117,7 +121,7 @@ namespace {
 
 // classify the rows on the scaled (z, y, l, u) of the solution -- polish's rule, and a row with l == u is always active and
 // counts as lower --, analyse and factorise the reduced matrix, set up what every later call on this solution reuses
-void adjoint_build(Engine &e, ModelAdjoint &A) {
+void adjoint_build(Engine &e, ModelAdjoint &A, const char *who = "osqp_amd_adjoint", const char *form = "adjoint") {
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
   const size_t bytes0 = g_device_bytes;
@@ -143,9 +147,9 @@ void adjoint_build(Engine &e, ModelAdjoint &A) {
   int frc = 0;
   K->F = reduced_factor(e, row_map, mr, &frc);
   if (frc == -1)
-    throw Error(6, "osqp_amd_adjoint: the factor of the reduced KKT matrix of the active set is too large for the device (an iterative adjoint is not built)");
+    throw Error(6, std::string(who) + ": the factor of the reduced KKT matrix of the active set is too large for the device (an iterative " + form + " is not built)");
   if (frc != 0)
-    throw Error(4, "osqp_amd_adjoint: the numeric factorisation of the regularised KKT matrix of the active set failed");
+    throw Error(4, std::string(who) + ": the numeric factorisation of the regularised KKT matrix of the active set failed");
   const int nr = n + mr;
   K->act_rows.alloc(mr ? mr : 1); K->act_rows.upload(rows.data(), mr, s);
   K->slot.alloc(m ? m : 1); K->slot.upload(row_map.data(), m, s);
@@ -180,15 +184,20 @@ void adjoint_pass(Engine &e, ModelAdjoint &A, const double *gx, const double *gy
                                regularised ? 1 : (int)e.st.polish_refine_iter, regularised);
 }
 
+// no CSR arrays and no reduced KKT matrix: what polish_run hands to its iterative form
+void adjoint_needs_csr(const Engine &e, const char *who, const char *form) {
+  if (e.comm)
+    throw Error(6, std::string(who) + ": not available on a row-sharded workspace (a row block has no reduced KKT matrix; an iterative " + form + " is not built)");
+  if (e.compact || e.A.compact || e.At.compact || e.Pf.compact || (e.nnzPtriu > 0 && e.Pi_keep.n == 0))
+    throw Error(6, std::string(who) + ": not available on a compact workspace (its CSR arrays are released, there is no reduced KKT matrix to factorise; "
+                   "an iterative " + form + " is not built; OSQP_AMD_COMPACT_NNZ=-1 at setup keeps the arrays)");
+}
+
 }  // namespace
 
 int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
                       double *dAx, double *act) {
-  // no CSR arrays and no reduced KKT matrix: what polish_run hands to its iterative form
-  if (e.comm) throw Error(6, "osqp_amd_adjoint: not available on a row-sharded workspace (a row block has no reduced KKT matrix; an iterative adjoint is not built)");
-  if (e.compact || e.A.compact || e.At.compact || e.Pf.compact || (e.nnzPtriu > 0 && e.Pi_keep.n == 0))
-    throw Error(6, "osqp_amd_adjoint: not available on a compact workspace (its CSR arrays are released, there is no reduced KKT matrix to factorise; "
-                   "an iterative adjoint is not built; OSQP_AMD_COMPACT_NNZ=-1 at setup keeps the arrays)");
+  adjoint_needs_csr(e, "osqp_amd_adjoint", "adjoint");
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
   if (!e.adj) e.adj.reset(new ModelAdjoint());

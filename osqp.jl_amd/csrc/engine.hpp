@@ -253,6 +253,9 @@ int polish_run_pcg(Engine &e);
 // osqp_amd_adjoint / _release / _stats on a workspace that passed the checks of the C boundary (direct_adjoint.hpp); host pointers
 int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
                       double *dAx, double *act);
+// osqp_amd_jvp on the same kept state (direct_jvp.hpp): ndir directions (tq, tl, tu, tPx, tAx; null = zero) to (tx, ty); host pointers
+int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const double *tu, const double *tPx, const double *tAx,
+                  double *tx, double *ty, double *act);
 void model_adjoint_release(Engine &e);  // drops the kept factor (the counters stay)
 void model_adjoint_stats(const Engine &e, double out[6]);
 const char *last_error_cstr();

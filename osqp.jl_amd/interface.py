@@ -546,7 +546,7 @@ def _cotangent(name, a, cols):
         raise ValueError(f"{name}: expected a real numeric array, got dtype {arr.dtype}")
     if arr.ndim not in (1, 2) or arr.shape[-1] != cols or (arr.ndim == 2 and arr.shape[0] < 1):
         raise ValueError(f"{name}: expected shape ({cols},) or (ncot, {cols}) with ncot >= 1, got {arr.shape}")
-    return _as_f64(arr).reshape(-1, cols), arr.ndim == 2
+    return _as_f64(arr).reshape(arr.shape[0] if arr.ndim == 2 else 1, cols), arr.ndim == 2  # (cols may be 0: m = 0)
 
 
 def adjoint(model, dx=None, dy=None, want=ADJOINT_GRADS):
@@ -585,6 +585,132 @@ def adjoint(model, dx=None, dy=None, want=ADJOINT_GRADS):
     res = {k: (v if many else v[0]) for k, v in out.items()}
     res["act"] = act.astype(int)
     return res
+
+
+def _data_cols(model):
+    """Widths of the five data arrays: q [n], l, u [m], Px [nnz(triu P)], Ax [nnz(A)]."""
+    n, m = dimensions(model)
+    st = stats(model, 4)
+    return dict(q=n, l=m, u=m, Px=int(st[3]), Ax=int(st[1]))
+
+
+def jvp(model, q=None, l=None, u=None, Px=None, Ax=None):
+    """Extension: osqp_amd_jvp (include/osqp_amd.h).  The forward sensitivities of the solution of the last `solve` along a
+    direction of the data: tangents q [n], l, u [m], Px [nnz(P upper)], Ax [nnz(A)] in the nnz order `update` takes (None =
+    zero; not all).  Returns a dict "x" (tangent of x), "y" (of the multipliers; zero on inactive rows) and "act" [m].
+    Inputs [cols] give outputs without a leading axis, inputs [ndir x cols] outputs with one; all tangents agree on this
+    and on ndir.  On a row with l == u only `l` is read.  The factor is `adjoint`'s: whichever is called first after a
+    solve builds it, the other reuses it (`adjoint_release`, `adjoint_stats`)."""
+    fn = _adjoint_symbol(model, "osqp_amd_jvp")
+    n, m = dimensions(model)
+    given = [(nm, v) for nm, v in zip(ADJOINT_GRADS, (q, l, u, Px, Ax)) if v is not None]
+    if not given:
+        raise ValueError("jvp: q, l, u, Px and Ax are all None: at least one tangent is needed")
+    cols = dict(q=n, l=m, u=m)
+    if Px is not None or Ax is not None:
+        cols = _data_cols(model)
+    got = {nm: _cotangent(nm, v, cols[nm]) for nm, v in given}
+    if len({lead for _, lead in got.values()}) > 1:
+        raise ValueError("the tangents must all have a leading direction axis or all have none")
+    ndirs = {arr.shape[0] for arr, _ in got.values()}
+    if len(ndirs) > 1:
+        raise ValueError(f"the tangents differ in the number of directions: {sorted(ndirs)}")
+    ndir = ndirs.pop()
+    many = any(lead for _, lead in got.values())
+    tx, ty, act = np.full((ndir, n), np.nan), np.full((ndir, m), np.nan), np.zeros(m)
+    ptr = lambda a: None if a is None else _fptr(a)
+    if fn(model.workspace, ndir, *(ptr(got[k][0]) if k in got else None for k in ADJOINT_GRADS), _fptr(tx), _fptr(ty), _fptr(act)) != 0:
+        raise OSQPError("Error in jvp: " + model.lib.osqp_amd_last_error().decode())
+    return dict(x=tx if many else tx[0], y=ty if many else ty[0], act=act.astype(int))
+
+
+JACOBIAN_OF = ("x", "y")
+JACOBIAN_BUDGET = 256 << 20  # bytes: the unit vectors and the largest output of one call of `jacobian` (default chunk)
+
+
+def jacobian(model, of=("x",), wrt=("q", "l", "u"), mode="auto", out_rows=None, chunk=None):
+    """Jacobians of the solution of the last `solve` with respect to the data (`ResidentBatch.jacobian` for a single model):
+    a dict {(o, w): [cols(o) x cols(w)]} for o in `of` (a subset of "x", "y") and w in `wrt` (a subset of "q", "l", "u",
+    "Px", "Ax"), entry [a, b] the derivative of component a of o with respect to entry b of w, plus "act".  out_rows: a dict
+    {"x": indices, "y": indices} that restricts the outputs to these components, in the order given.
+    mode="reverse": unit cotangents through `adjoint`, one solve per requested output component; mode="forward": unit
+    directions through `jvp`, one solve per column of the `wrt` arrays; "auto": the one with fewer solves (reverse on a tie).
+    On a row with l == u the derivative with respect to moving both bounds is in "l" and "u" is zero; an inactive bound has
+    a zero column.  chunk: the most unit vectors per call; the chunks are independent calls on the kept factor whose
+    results are placed side by side, so the result does not depend on it.  Default: as many as keep the unit vectors and
+    the largest output array of one call under 256 MiB together, at least 1.  Nothing is computed on the results."""
+    for name in ("osqp_amd_adjoint", "osqp_amd_jvp"):
+        _adjoint_symbol(model, name)
+    of, wrt = tuple(of), tuple(wrt)
+    if not of or len(set(of)) != len(of) or any(o not in JACOBIAN_OF for o in of):
+        raise ValueError(f"of: expected a non-empty subset of {JACOBIAN_OF} without repeats, got {of!r}")
+    if not wrt or len(set(wrt)) != len(wrt) or any(w not in ADJOINT_GRADS for w in wrt):
+        raise ValueError(f"wrt: expected a non-empty subset of {ADJOINT_GRADS} without repeats, got {wrt!r}")
+    if mode not in ("auto", "reverse", "forward"):
+        raise ValueError(f"mode: expected 'auto', 'reverse' or 'forward', got {mode!r}")
+    if chunk is not None and (not isinstance(chunk, (int, np.integer)) or isinstance(chunk, bool) or chunk < 1):
+        raise ValueError(f"chunk: expected a positive integer, got {chunk!r}")
+    wcols = _data_cols(model)
+    ocols = dict(x=wcols["q"], y=wcols["l"])
+    out_rows = {} if out_rows is None else dict(out_rows)
+    idx = {}
+    for o in out_rows:
+        if o not in of:
+            raise ValueError(f"out_rows: {o!r} is not in `of` {of!r}")
+    for o in of:
+        if o in out_rows:
+            a = np.asarray(out_rows[o])
+            if a.ndim != 1 or a.dtype.kind not in "iu":
+                raise ValueError(f"out_rows[{o!r}]: expected a one-dimensional integer array, got shape {a.shape}, dtype {a.dtype}")
+            if a.size and (a.min() < 0 or a.max() >= ocols[o]):
+                raise ValueError(f"out_rows[{o!r}]: components must be in [0, {ocols[o]})")
+            idx[o] = a.astype(np.int64)
+        else:
+            idx[o] = np.arange(ocols[o], dtype=np.int64)
+    n_rev, n_fwd = sum(len(idx[o]) for o in of), sum(wcols[w] for w in wrt)
+    if n_rev == 0 or n_fwd == 0:
+        raise ValueError("jacobian: no output component or no data column is asked for")
+    if mode == "auto":
+        mode = "reverse" if n_rev <= n_fwd else "forward"
+    reverse = mode == "reverse"
+    total = n_rev if reverse else n_fwd
+    if chunk is None:
+        unit = sum(ocols[o] for o in of) if reverse else n_fwd
+        largest = max(wcols[w] for w in wrt) if reverse else max(ocols[o] for o in of)
+        chunk = max(1, JACOBIAN_BUDGET // (8 * (unit + largest)))
+    chunk = int(min(chunk, total))
+    # the solves of the call in order: segment (name, first solve, number) -- the components of each o (reverse), the columns
+    # of each w (forward)
+    segs, at = [], 0
+    for name, width in ([(o, len(idx[o])) for o in of] if reverse else [(w, wcols[w]) for w in wrt]):
+        segs.append((name, at, width))
+        at += width
+    J = {(o, w): np.zeros((len(idx[o]), wcols[w])) for o in of for w in wrt}
+    res = {}
+    for c0 in range(0, total, chunk):
+        c1 = min(c0 + chunk, total)
+        nc = c1 - c0
+        parts = [(name, max(s0, c0) - c0, min(s0 + w, c1) - c0, max(s0, c0) - s0) for name, s0, w in segs if max(s0, c0) < min(s0 + w, c1)]
+        if reverse:
+            cot = {o: np.zeros((nc, ocols[o])) for o in of if ocols[o] > 0}
+            for o, a, b, p0 in parts:
+                cot[o][np.arange(a, b), idx[o][p0:p0 + b - a]] = 1.0
+            want = tuple(w for w in wrt if wcols[w] > 0)
+            res = adjoint(model, dx=cot.get("x"), dy=cot.get("y"), want=want)
+            for o, a, b, p0 in parts:
+                for w in want:
+                    J[(o, w)][p0:p0 + b - a, :] = res[w][a:b]
+        else:
+            tan = {w: np.zeros((nc, wcols[w])) for w in wrt if wcols[w] > 0}
+            for w, a, b, p0 in parts:
+                tan[w][np.arange(a, b), np.arange(p0, p0 + b - a)] = 1.0
+            res = jvp(model, **tan)
+            for w, a, b, p0 in parts:
+                for o in of:
+                    if ocols[o] > 0:
+                        J[(o, w)][:, p0:p0 + b - a] = res[o][a:b][:, idx[o]].T
+    J["act"] = res["act"]
+    return J
 
 
 def adjoint_release(model):

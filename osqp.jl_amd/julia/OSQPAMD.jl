@@ -117,6 +117,44 @@ function adjoint(model::OSQP.Model; dx::Union{Nothing,VecOrMat{Float64}} = nothi
     return (; grads..., act = Int.(act))
 end
 
+"""
+    jvp(model; q = nothing, l = nothing, u = nothing, Px = nothing, Ax = nothing) -> (x, y, act)
+
+Forward sensitivities of the solution of the last `OSQP.solve!` along a direction of the data (osqp_amd_jvp in
+include/osqp_amd.h): tangents `q` [n], `l`, `u` [m], `Px` (upper triangle of P), `Ax`, both in the nnz order `OSQP.update!` takes
+(`nothing` = 0; not all).  Vectors give vectors; matrices with one column per direction (column-major here is direction-major
+on the C side) give matrices with one column per direction.  On a row with `l == u` only `l` is read.  The factor is
+`adjoint`'s: whichever is called first after a solve builds it, the other reuses it.  Not executed by the test suite; the
+Python mirror (`interface.jvp`) is.
+"""
+function jvp(model::OSQP.Model; q::Union{Nothing,VecOrMat{Float64}} = nothing, l::Union{Nothing,VecOrMat{Float64}} = nothing,
+             u::Union{Nothing,VecOrMat{Float64}} = nothing, Px::Union{Nothing,VecOrMat{Float64}} = nothing,
+             Ax::Union{Nothing,VecOrMat{Float64}} = nothing)
+    (n, m) = OSQP.dimensions(model)
+    st = stats(model)
+    rows = (q = n, l = m, u = m, Px = Int(st[4]), Ax = Int(st[2]))
+    given = [(k, v) for (k, v) in pairs((q = q, l = l, u = u, Px = Px, Ax = Ax)) if v !== nothing]
+    isempty(given) && error("jvp: q, l, u, Px and Ax are all nothing: at least one tangent is needed")
+    for (k, v) in given
+        size(v, 1) == rows[k] || error("$k must have $(rows[k]) rows")
+    end
+    length(unique(ndims(v) for (_, v) in given)) == 1 || error("the tangents must all be vectors or all be matrices")
+    ndir = size(given[1][2], 2)
+    all(size(v, 2) == ndir for (_, v) in given) || error("the tangents differ in the number of directions")
+    ndir >= 1 || error("jvp: ndir must be at least 1")
+    many = given[1][2] isa Matrix
+    tx, ty, act = fill(NaN, n, ndir), fill(NaN, m, ndir), zeros(Float64, m)
+    ptr(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve q l u Px Ax tx ty act begin
+        flag = ccall((:osqp_amd_jvp, lib), Cc_int,
+                     (Ptr{OSQP.Workspace}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                      Ptr{Cdouble}, Ptr{Cdouble}),
+                     model.workspace, ndir, ptr(q), ptr(l), ptr(u), ptr(Px), ptr(Ax), tx, ty, act)
+    end
+    flag == 0 || error("Error in jvp: $(last_error())")
+    return (x = many ? tx : vec(tx), y = many ? ty : vec(ty), act = Int.(act))
+end
+
 "Drop the factor `adjoint` keeps (osqp_amd_adjoint_release); it is as large as a polish's."
 function adjoint_release!(model::OSQP.Model)
     flag = ccall((:osqp_amd_adjoint_release, lib), Cc_int, (Ptr{OSQP.Workspace},), model.workspace)

@@ -35,7 +35,8 @@ an instance's active constraints are dependent the derivative does not exist and
 
 A single model (`interface.Model`: one large sparse QP, any n) as a layer: `QPFunction` / `QPLayer(model)`, at the end of this
 file.  Its arrays are host arrays (include/osqp_amd.h: every single-model entry takes host pointers), so tensors on any
-device go through the host; the forward is `update` + `solve`, the backward one `interface.adjoint` call on the kept factor.
+device go through the host; the forward is `update` + `solve`, the backward one `interface.adjoint` call on the kept factor,
+and under `torch.autograd.forward_ad` the tangents of (x, y) come from one `interface.jvp` call on the same factor.
 
     layer = QPLayer(model)
     x, y = layer(q=q_t, l=l_t, u=u_t)           # float64 tensors [n] / [m]; None keeps the model's data
@@ -234,12 +235,28 @@ class QPFunction(torch.autograd.Function):
             _iface.update(model, **host)
         res = _iface.solve(model)
         ctx.model, ctx.stamp = model, stamp_model_forward(model)
+        ctx.given = tuple(name for name, t in given.items() if t is not None)  # for jvp: the inputs that can carry a tangent
         model._qp_layer_info = res.info
         if res.info.status != "Solved":
             raise RuntimeError(f"QPFunction: the solve ended with status {res.info.status}; there is no solution to differentiate")
         ref = next((t for t in given.values() if t is not None), None)
         dev = ref.device if ref is not None else torch.device("cpu")
         return torch.from_numpy(res.x.copy()).to(dev), torch.from_numpy(res.y.copy()).to(dev)
+
+    @staticmethod
+    def jvp(ctx, t_model, tq, tl, tu, tPx, tAx):
+        """Forward mode (`torch.autograd.forward_ad`): ONE `interface.jvp` call with the tangents of the inputs that carry
+        one, on the factor `backward` uses; the same stamp rule."""
+        model = ctx.model
+        if getattr(model, "_qp_layer_stamp", None) != ctx.stamp:
+            raise RuntimeError("QPFunction: the model has been solved again since this forward; it holds one solution, so "
+                               "jvp must run before the next forward")
+        tang = {k: t for k, t in zip(NAMES, (tq, tl, tu, tPx, tAx)) if k in ctx.given and t is not None and t.numel() > 0}
+        if not tang:
+            return None, None
+        ref = next(iter(tang.values()))
+        out = _iface.jvp(model, **{k: t.detach().cpu().contiguous().numpy() for k, t in tang.items()})
+        return torch.from_numpy(out["x"]).to(ref.device), torch.from_numpy(out["y"]).to(ref.device)
 
     @staticmethod
     def backward(ctx, gx, gy):

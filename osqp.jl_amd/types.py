@@ -187,6 +187,8 @@ EXT_SYMBOLS = {
     "osqp_amd_spmv_layout": (c_int, [Workspace_p, c_int, c_float_p, c_int]),
     # adjoint derivatives of a single model's solution: host arrays dx, dy in; dq, dl, du, dPx, dAx, act out (None = NULL)
     "osqp_amd_adjoint": (c_int, [Workspace_p, c_int] + [c_float_p] * 8),
+    # forward sensitivities on the same kept factor: host arrays tq, tl, tu, tPx, tAx in; tx, ty, act out (None = NULL)
+    "osqp_amd_jvp": (c_int, [Workspace_p, c_int] + [c_float_p] * 8),
     "osqp_amd_adjoint_release": (c_int, [Workspace_p]),
     "osqp_amd_adjoint_stats": (c_int, [Workspace_p, c_float_p, c_int]),
     "osqp_amd_batch_solve": (
