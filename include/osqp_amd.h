@@ -750,6 +750,72 @@ c_int osqp_amd_adjoint_release(OSQPWorkspace *work);
 #define OSQP_AMD_ADJOINT_STATS_COUNT 6
 c_int osqp_amd_adjoint_stats(const OSQPWorkspace *work, c_float *out, c_int count);
 
+/* ---- Device-pointer forms of a single model's life cycle ----
+ *
+ * The calls above take host arrays.  Each call below is the twin of one of them with every array argument a DEVICE pointer
+ * on the workspace's device (fp64, contiguous): update and warm start from HBM, read the solution into HBM, differentiate
+ * HBM to HBM.  Nothing passes through the host but return codes and, for a bounds update, one flag word.
+ *
+ *   Bit contract.  A device-form call leaves the workspace in exactly the state its host twin leaves it in for the same
+ *   numbers -- data, iterate, info reset, rho vector, the dropped kept factor -- and writes the numbers the twin would have
+ *   returned, bit for bit: it runs the twin's kernels in the twin's order on the same operands, and only the upload is
+ *   replaced by a device-to-device copy (or the array is read where it lies).  The forms mix freely on one workspace.
+ *
+ *   Stream rule (as for `where = 1` of the resident batch).  The library runs on its own stream and blocks until it is done:
+ *   the caller must have finished producing the inputs before the call (synchronise the producing stream), and may read the
+ *   outputs as soon as the call returns.
+ *
+ *   Every call returns 7 on a NULL workspace and 6, with a message, on a row-sharded workspace (a rank holds a row block).
+ *   A compact workspace is served by the four life-cycle calls as by their host twins; osqp_amd_adjoint_dev / _jvp_dev
+ *   refuse it with the host twins' code 6 and a message that says "compact".
+ *
+ * osqp_amd_update_vectors_dev: osqp_update_lin_cost (q) followed by osqp_update_bounds / _lower_bound / _upper_bound (l, u;
+ *   NULL = keep).  The rule on the bounds is theirs -- any l_i > u_i, a new l against the STORED u where only l is given and
+ *   the reverse: return 1, nothing changed, q included -- and it is decided on the device, by a kernel that reduces the
+ *   comparison to one word.  The workspace's host copy of the raw bounds stays truthful across the two forms: a host-form
+ *   one-sided update after a device-form update validates against the device-given bound, and the reverse.  A lower bound below
+ *   -OSQP_INFTY and an upper bound above OSQP_INFTY are stored as -OSQP_INFTY / OSQP_INFTY (what the wrappers of the host
+ *   forms do on the host before the call is part of this call, as in the resident batch); within that range the numbers are
+ *   taken as given.
+ * osqp_amd_update_values_dev: osqp_update_P / _A / _P_A with full value arrays in the caller's nnz order (NULL = keep; a
+ *   call that gives indices stays with the host forms).  Where the columns of A came unsorted at setup the values are
+ *   permuted on the device.  Returns what the host form returns on a failed refactorisation or an indefinite P.
+ * osqp_amd_warm_start_dev: osqp_warm_start (both given), osqp_warm_start_x (y NULL: the stored y is zeroed) or
+ *   osqp_warm_start_y (x NULL).
+ *   These three end the solution's being current and drop the factor osqp_amd_adjoint keeps, as their twins do; all NULL is
+ *   a call that does nothing and returns 0.
+ * osqp_amd_solution_dev: x = D x~ [n] and y = E y~ / c [m] of the solution of the last osqp_solve with the operations that
+ *   fill solution->x / ->y (either may be NULL); NaN where that solve ended without a solution (infeasible, non-convex), as
+ *   the host mirrors are filled.  Returns 1 before any osqp_solve has run, and when an update or a warm start since the
+ *   last one has ended the solution's being current (the iterate is then no longer that solution).  Changes nothing.
+ * osqp_amd_adjoint_dev / osqp_amd_jvp_dev: the arguments, the mathematics, the kept factor, the counters and the refusals of
+ *   osqp_amd_adjoint / osqp_amd_jvp; cotangents and tangents are read in place, the output kernels write the caller's arrays
+ *   (no staging array, no download) and act [m] is a copy of the kept array of doubles.  A device-form call after a
+ *   host-form call on one solution builds nothing, and the reverse; osqp_amd_adjoint_stats counts both forms together.
+ *   Every refusal (7, 1, 6 compact or too large, 4) is decided before the first kernel that writes to a caller's array: a
+ *   refused call has written nothing.  The one exception is an internal error: when a wait inside the one-launch
+ *   supernodal solve times out the passes run again by levels and overwrite the outputs; a second fault (code 6) may leave
+ *   partial output behind.
+ * osqp_amd_device_form_calls: out[0..count) (a HOST array) = the device-form calls that returned 0 on this workspace so
+ *   far: 0 updates of vectors, 1 updates of values, 2 warm starts, 3 solution reads, 4 adjoints, 5 jvps.  Returns the number
+ *   of entries written (at most OSQP_AMD_DEVICE_FORM_COUNT), 0 on a NULL argument. */
+c_int osqp_amd_update_vectors_dev(OSQPWorkspace *work, const c_float *q /* [n] or NULL */, const c_float *l /* [m] or NULL */,
+                                  const c_float *u /* [m] or NULL */);
+c_int osqp_amd_update_values_dev(OSQPWorkspace *work, const c_float *Px /* [nnz(triu P)] or NULL */, const c_float *Ax /* [nnz(A)] or NULL */);
+c_int osqp_amd_warm_start_dev(OSQPWorkspace *work, const c_float *x /* [n] or NULL */, const c_float *y /* [m] or NULL */);
+c_int osqp_amd_solution_dev(OSQPWorkspace *work, c_float *x_out /* [n] or NULL */, c_float *y_out /* [m] or NULL */);
+c_int osqp_amd_adjoint_dev(OSQPWorkspace *work, c_int ncot,
+                           const c_float *dx /* [ncot x n] or NULL = 0 */, const c_float *dy /* [ncot x m] or NULL = 0 */,
+                           c_float *dq /* [ncot x n] */, c_float *dl /* [ncot x m] */, c_float *du /* [ncot x m] */,
+                           c_float *dPx /* [ncot x nnz(triu P)] */, c_float *dAx /* [ncot x nnz(A)] */,
+                           c_float *act /* [m] or NULL */);
+c_int osqp_amd_jvp_dev(OSQPWorkspace *work, c_int ndir,
+                       const c_float *tq /* [ndir x n] or NULL = 0 */, const c_float *tl /* [ndir x m] */, const c_float *tu /* [ndir x m] */,
+                       const c_float *tPx /* [ndir x nnz(triu P)] */, const c_float *tAx /* [ndir x nnz(A)] */,
+                       c_float *tx /* [ndir x n] or NULL */, c_float *ty /* [ndir x m] or NULL */, c_float *act /* [m] or NULL */);
+#define OSQP_AMD_DEVICE_FORM_COUNT 6
+c_int osqp_amd_device_form_calls(const OSQPWorkspace *work, c_float *out, c_int count);
+
 /* Select the HIP device for workspaces created afterwards by this process
  * (one process per GPU: pass LOCAL_RANK). */
 c_int osqp_amd_set_device(c_int device);

@@ -16,6 +16,6 @@ from .interface import (  # noqa: F401
     Model, Results, Info, OSQPError, setup, setup_generated, solve, update, update_settings, warm_start,
     warm_start_x, warm_start_y, warm_start_x_y, update_q, update_l, update_u, update_bounds, update_P, update_A,
     update_P_A, clean, version, dimensions, default_settings, make_settings, stats, ManagedCcsc, ccsc_to_scipy,
-    spmv_layout, adjoint, adjoint_release, adjoint_stats, jvp, jacobian,
+    spmv_layout, adjoint, adjoint_release, adjoint_stats, jvp, jacobian, solution, device_form_calls,
 )
 from .types import load_library, PRODUCT_LIB_PATH, ORACLE_LIB_PATH  # noqa: F401

@@ -542,6 +542,7 @@ c_int osqp_solve(OSQPWorkspace *w) {
   return guarded([&]() {
     adjoint_moved_on(w, true);
     const int rc = E(w)->solve();
+    E(w)->solves_run++;
     E(w)->solution_current = rc == 0;
     return rc;
   });
@@ -841,6 +842,121 @@ c_int osqp_amd_jvp(OSQPWorkspace *w, c_int ndir, const c_float *tq, const c_floa
                          "): there is no solution to differentiate");
     return model_jvp_run(e, (int)ndir, tq, tl, tu, tPx, tAx, tx, ty, act);
   });
+}
+// ---- device-pointer forms of a single model's life cycle (Engine::update_vectors_dev ...) ----
+static bool dev_form_refused(OSQPWorkspace *w, const char *who) {
+  if (!w) { set_last_error(std::string(who) + ": no workspace"); return true; }
+  return false;
+}
+static void dev_form_needs_whole_model(const Engine &e, const char *who) {
+  if (e.comm)
+    throw Error(6, std::string(who) + ": not available on a row-sharded workspace (a rank holds a row block; the device forms take whole arrays on one device)");
+}
+c_int osqp_amd_update_vectors_dev(OSQPWorkspace *w, const c_float *q, const c_float *l, const c_float *u) {
+  if (dev_form_refused(w, "osqp_amd_update_vectors_dev")) return 7;
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    dev_form_needs_whole_model(e, "osqp_amd_update_vectors_dev");
+    if (!q && !l && !u) return 0;
+    adjoint_moved_on(w, true);
+    const int rc = e.update_vectors_dev(q, l, u);
+    if (rc == 0) e.dev_calls[0]++;
+    else if (rc == 1) set_last_error("osqp_amd_update_vectors_dev: a lower bound is greater than its upper bound; nothing was changed");
+    return rc;
+  });
+}
+c_int osqp_amd_update_values_dev(OSQPWorkspace *w, const c_float *Px, const c_float *Ax) {
+  if (dev_form_refused(w, "osqp_amd_update_values_dev")) return 7;
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    dev_form_needs_whole_model(e, "osqp_amd_update_values_dev");
+    if (!Px && !Ax) return 0;
+    adjoint_moved_on(w, true);
+    const int rc = e.update_values_dev(Px, Ax);
+    if (rc == 0) e.dev_calls[1]++;
+    return rc;
+  });
+}
+c_int osqp_amd_warm_start_dev(OSQPWorkspace *w, const c_float *x, const c_float *y) {
+  if (dev_form_refused(w, "osqp_amd_warm_start_dev")) return 7;
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    dev_form_needs_whole_model(e, "osqp_amd_warm_start_dev");
+    if (!x && !y) return 0;
+    adjoint_moved_on(w, true);
+    const int rc = e.warm_start(x, y, true);
+    if (rc == 0) e.dev_calls[2]++;
+    return rc;
+  });
+}
+c_int osqp_amd_solution_dev(OSQPWorkspace *w, c_float *x_out, c_float *y_out) {
+  if (dev_form_refused(w, "osqp_amd_solution_dev")) return 7;
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    dev_form_needs_whole_model(e, "osqp_amd_solution_dev");
+    if (e.solves_run == 0) throw Error(1, "osqp_amd_solution_dev: no osqp_solve has run on this workspace yet");
+    if (!e.solution_current)
+      throw Error(1, "osqp_amd_solution_dev: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
+    const int rc = e.solution_dev(x_out, y_out);
+    if (rc == 0) e.dev_calls[3]++;
+    return rc;
+  });
+}
+c_int osqp_amd_adjoint_dev(OSQPWorkspace *w, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
+                           c_float *dPx, c_float *dAx, c_float *act) {
+  if (dev_form_refused(w, "osqp_amd_adjoint_dev")) return 7;
+  if (ncot < 1) { set_last_error("osqp_amd_adjoint_dev: ncot must be at least 1"); return 1; }
+  if (ncot > 2147483647LL) { set_last_error("osqp_amd_adjoint_dev: ncot out of range"); return 1; }
+  if ((dq || dl || du || dPx || dAx) && !dx && !dy) {
+    set_last_error("osqp_amd_adjoint_dev: a gradient is wanted but dx and dy are both NULL");
+    return 1;
+  }
+  if (!dq && !dl && !du && !dPx && !dAx && !act) { set_last_error("osqp_amd_adjoint_dev: no output is wanted"); return 1; }
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    if (!e.solution_current)
+      throw Error(1, "osqp_amd_adjoint_dev: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
+    if (w->info->status_val != OSQP_SOLVED)
+      throw Error(1, std::string("osqp_amd_adjoint_dev: the last osqp_solve did not end with status Solved (") + w->info->status +
+                         "): there is no solution to differentiate");
+    const int rc = model_adjoint_run(e, (int)ncot, dx, dy, dq, dl, du, dPx, dAx, act, true);
+    if (rc == 0) e.dev_calls[4]++;
+    return rc;
+  });
+}
+c_int osqp_amd_jvp_dev(OSQPWorkspace *w, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,
+                       const c_float *tAx, c_float *tx, c_float *ty, c_float *act) {
+  if (dev_form_refused(w, "osqp_amd_jvp_dev")) return 7;
+  if (ndir < 1) { set_last_error("osqp_amd_jvp_dev: ndir must be at least 1"); return 1; }
+  if (ndir > 2147483647LL) { set_last_error("osqp_amd_jvp_dev: ndir out of range"); return 1; }
+  if ((tx || ty) && !tq && !tl && !tu && !tPx && !tAx) {
+    set_last_error("osqp_amd_jvp_dev: a sensitivity is wanted but tq, tl, tu, tPx and tAx are all NULL");
+    return 1;
+  }
+  if (!tx && !ty && !act) { set_last_error("osqp_amd_jvp_dev: no output is wanted"); return 1; }
+  OQ_ON_DEVICE(w);
+  return guarded([&]() {
+    Engine &e = *E(w);
+    if (!e.solution_current)
+      throw Error(1, "osqp_amd_jvp_dev: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
+    if (w->info->status_val != OSQP_SOLVED)
+      throw Error(1, std::string("osqp_amd_jvp_dev: the last osqp_solve did not end with status Solved (") + w->info->status +
+                         "): there is no solution to differentiate");
+    const int rc = model_jvp_run(e, (int)ndir, tq, tl, tu, tPx, tAx, tx, ty, act, true);
+    if (rc == 0) e.dev_calls[5]++;
+    return rc;
+  });
+}
+c_int osqp_amd_device_form_calls(const OSQPWorkspace *w, c_float *out, c_int count) {
+  if (!w || !out) return 0;
+  c_int k = 0;
+  for (; k < count && k < OSQP_AMD_DEVICE_FORM_COUNT; k++) out[k] = (c_float)E(w)->dev_calls[k];
+  return k;
 }
 c_int osqp_amd_adjoint_release(OSQPWorkspace *w) {
   if (!w) { set_last_error("osqp_amd_adjoint_release: no workspace"); return 7; }

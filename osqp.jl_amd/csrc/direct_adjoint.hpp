@@ -92,7 +92,6 @@ struct AdjointKept {
 struct ModelAdjoint {
   std::unique_ptr<AdjointKept> kept;
   DevBuf<int> Pcol, Acol;          // column of every entry of the caller's triu(P) / of A (sorted copy): once per workspace
-  DevBuf<int64_t> A_to_sorted;     // the engine's map on the device (empty: the caller's columns were sorted)
   bool patterns = false;
   // osqp_amd_jvp (direct_jvp.hpp): for every position of Pf the entry of the caller's triu(P) it mirrors, for every position
   // of A (CSR) the entry of the sorted CSC copy -- P_k2lo / P_k2up / A_k2pos inverted, at the first call with tPx or tAx
@@ -196,7 +195,7 @@ void adjoint_needs_csr(const Engine &e, const char *who, const char *form) {
 }  // namespace
 
 int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
-                      double *dAx, double *act) {
+                      double *dAx, double *act, bool dev) {
   adjoint_needs_csr(e, "osqp_amd_adjoint", "adjoint");
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
@@ -209,33 +208,43 @@ int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, d
     A.Pcol.alloc(std::max<int64_t>(1, e.nnzPtriu)); A.Acol.alloc(std::max<int64_t>(1, e.nnzA));
     expand_colptr(n, e.Pp_keep.get(), e.nnzPtriu, A.Pcol.get(), s);
     expand_colptr(n, e.At.rowptr.get(), e.nnzA, A.Acol.get(), s);
-    if (!e.A_to_sorted.empty()) { A.A_to_sorted.alloc(e.A_to_sorted.size()); A.A_to_sorted.upload(e.A_to_sorted.data(), e.A_to_sorted.size(), s); }
+    e.device_A_to_sorted();
     e.sync();
     A.patterns = true;
   }
   if (grads) {
     const size_t nc = (size_t)ncot;
+    // host form: staged copies of the cotangents and of the outputs; device form: the caller's arrays themselves (every
+    // refusal -- the checks of the C boundary, adjoint_needs_csr, adjoint_build -- lies before the first kernel below)
     DevBuf<double> gx, gy, oq_, ol, ou, oP, oA;
-    if (dx) { gx.alloc(nc * n); gx.upload(dx, nc * n, s); }
-    if (dy && m > 0) { gy.alloc(nc * m); gy.upload(dy, nc * m, s); }
-    if (dq) oq_.alloc(nc * n);
-    if (dl) ol.alloc(nc * m);
-    if (du) ou.alloc(nc * m);
-    if (dPx) oP.alloc(nc * (size_t)e.nnzPtriu);
-    if (dAx) oA.alloc(nc * (size_t)e.nnzA);
+    const double *pgx = nullptr, *pgy = nullptr;
+    double *pq = dq, *pl = dl, *pu = du, *pP = dPx, *pA = dAx;
+    if (dev) {
+      pgx = dx;
+      pgy = m > 0 ? dy : nullptr;
+    } else {
+      if (dx) { gx.alloc(nc * n); gx.upload(dx, nc * n, s); pgx = gx.get(); }
+      if (dy && m > 0) { gy.alloc(nc * m); gy.upload(dy, nc * m, s); pgy = gy.get(); }
+      if (dq) { oq_.alloc(nc * n); pq = oq_.get(); }
+      if (dl) { ol.alloc(nc * m); pl = ol.get(); }
+      if (du) { ou.alloc(nc * m); pu = ou.get(); }
+      if (dPx) { oP.alloc(nc * (size_t)e.nnzPtriu); pP = oP.get(); }
+      if (dAx) { oA.alloc(nc * (size_t)e.nnzA); pA = oA.get(); }
+    }
+    const int64_t *to_sorted = dAx ? e.device_A_to_sorted() : nullptr;
     const long long solves0 = A.solves;
     auto passes = [&]() {
       for (size_t c = 0; c < nc; c++) {
-        adjoint_pass(e, A, gx.p ? gx.get() + c * n : nullptr, gy.p ? gy.get() + c * m : nullptr);
+        adjoint_pass(e, A, pgx ? pgx + c * n : nullptr, pgy ? pgy + c * m : nullptr);
         OQ_LAUNCH(k_adj_vectors, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), K.slot.get(), K.side.get(),
-                  K.sol.get(), K.rx.get(), K.ry.get(), dq ? oq_.get() + c * n : nullptr, dl ? ol.get() + c * m : nullptr,
-                  du ? ou.get() + c * m : nullptr);
+                  K.sol.get(), K.rx.get(), K.ry.get(), dq ? pq + c * n : nullptr, dl ? pl + c * m : nullptr,
+                  du ? pu + c * m : nullptr);
         if (dPx && e.nnzPtriu > 0)
           OQ_LAUNCH(k_adj_dP, dim3(blocks_for(e.nnzPtriu)), dim3(kBlock), 0, s, e.nnzPtriu, e.Pi_keep.get(), A.Pcol.get(), K.rx.get(), K.xc.get(),
-                    oP.get() + c * (size_t)e.nnzPtriu);
+                    pP + c * (size_t)e.nnzPtriu);
         if (dAx && e.nnzA > 0)
-          OQ_LAUNCH(k_adj_dA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, A.A_to_sorted.n ? A.A_to_sorted.get() : (const int64_t *)nullptr,
-                    e.At.col.get(), A.Acol.get(), K.rx.get(), K.ry.get(), K.xc.get(), K.yc.get(), oA.get() + c * (size_t)e.nnzA);
+          OQ_LAUNCH(k_adj_dA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, to_sorted,
+                    e.At.col.get(), A.Acol.get(), K.rx.get(), K.ry.get(), K.xc.get(), K.yc.get(), pA + c * (size_t)e.nnzA);
       }
       e.sync();
     };
@@ -247,15 +256,21 @@ int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, d
       passes();
       if (K.F->faulted()) throw TreeFault();
     }
-    // outputs last: a call that fails has written nothing
-    if (dq) oq_.download(dq, nc * n, s);
-    if (dl) ol.download(dl, nc * m, s);
-    if (du) ou.download(du, nc * m, s);
-    if (dPx) oP.download(dPx, nc * (size_t)e.nnzPtriu, s);
-    if (dAx) oA.download(dAx, nc * (size_t)e.nnzA, s);
-    e.sync();
+    // outputs last: a call that fails has written nothing (device form: the re-run above overwrites what the faulted pass
+    // wrote; only a second tree fault, an internal error, leaves partial output behind)
+    if (!dev) {
+      if (dq) oq_.download(dq, nc * n, s);
+      if (dl) ol.download(dl, nc * m, s);
+      if (du) ou.download(du, nc * m, s);
+      if (dPx) oP.download(dPx, nc * (size_t)e.nnzPtriu, s);
+      if (dAx) oA.download(dAx, nc * (size_t)e.nnzA, s);
+      e.sync();
+    }
   }
-  if (act) std::copy(K.h_side.begin(), K.h_side.end(), act);
+  if (act) {
+    if (dev) { e.copy_dev(act, K.side.get(), (size_t)m); e.sync(); }
+    else std::copy(K.h_side.begin(), K.h_side.end(), act);
+  }
   return 0;
 }
 

@@ -145,7 +145,7 @@ void jvp_rhs(Engine &e, ModelAdjoint &A, const double *tq, const double *tl, con
 }  // namespace
 
 int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const double *tu, const double *tPx, const double *tAx,
-                  double *tx, double *ty, double *act) {
+                  double *tx, double *ty, double *act, bool dev) {
   adjoint_needs_csr(e, "osqp_amd_jvp", "form");
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
@@ -163,38 +163,45 @@ int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const
     invert_map(e.nnzPtriu, e.P_k2lo.get(), 0, e.Pf.nnz, A.Ppos2k.get(), s);
     invert_map(e.nnzPtriu, e.P_k2up.get(), 0, e.Pf.nnz, A.Ppos2k.get(), s);  // -1 on the diagonal: outside [0, nnz), it counts once
     invert_map(e.nnzA, e.A_k2pos.get(), 0, e.nnzA, A.Apos2k.get(), s);
-    if (!e.A_to_sorted.empty() && !A.A_to_sorted.n) { A.A_to_sorted.alloc(e.A_to_sorted.size()); A.A_to_sorted.upload(e.A_to_sorted.data(), e.A_to_sorted.size(), s); }
+    e.device_A_to_sorted();
     e.sync();
     A.jvp_maps = true;
   }
   if (tx || ty) {
     const size_t nd = (size_t)ndir, nzP = (size_t)e.nnzPtriu, nzA = (size_t)e.nnzA;
+    // host form: staged copies of the tangents and of the outputs; device form: the caller's arrays themselves (every
+    // refusal lies before the first kernel below)
     DevBuf<double> dq, dl, du, dP, dA, dAs, ox, oy;
-    if (tq) { dq.alloc(nd * n); dq.upload(tq, nd * n, s); }
-    if (tl) { dl.alloc(nd * m); dl.upload(tl, nd * m, s); }
-    if (tu) { du.alloc(nd * m); du.upload(tu, nd * m, s); }
-    if (tPx) { dP.alloc(nd * nzP); dP.upload(tPx, nd * nzP, s); }
-    if (tAx) { dA.alloc(nd * nzA); dA.upload(tAx, nd * nzA, s); }
-    const bool unsorted = tAx && A.A_to_sorted.n;
+    const double *pq = tq, *pl = tl, *pu = tu, *pP = tPx, *pA = tAx;
+    double *px = tx, *py = ty && m > 0 ? ty : nullptr;
+    if (!dev) {
+      if (tq) { dq.alloc(nd * n); dq.upload(tq, nd * n, s); pq = dq.get(); }
+      if (tl) { dl.alloc(nd * m); dl.upload(tl, nd * m, s); pl = dl.get(); }
+      if (tu) { du.alloc(nd * m); du.upload(tu, nd * m, s); pu = du.get(); }
+      if (tPx) { dP.alloc(nd * nzP); dP.upload(tPx, nd * nzP, s); pP = dP.get(); }
+      if (tAx) { dA.alloc(nd * nzA); dA.upload(tAx, nd * nzA, s); pA = dA.get(); }
+      if (tx) { ox.alloc(nd * n); px = ox.get(); }
+      if (py) { oy.alloc(nd * m); py = oy.get(); }
+    }
+    const int64_t *to_sorted = tAx ? e.device_A_to_sorted() : nullptr;
+    const bool unsorted = to_sorted != nullptr;
     if (unsorted) dAs.alloc(nzA);  // one direction's tAx in sorted order
-    if (tx) ox.alloc(nd * n);
-    if (ty && m > 0) oy.alloc(nd * m);
     const long long solves0 = A.solves;
     const bool regularised = e.st.polish_refine_iter == 0;
     auto passes = [&]() {
       for (size_t d = 0; d < nd; d++) {
-        const double *tA_d = tAx ? dA.get() + d * nzA : nullptr;
+        const double *tA_d = tAx ? pA + d * nzA : nullptr;
         if (unsorted) {
-          OQ_LAUNCH(k_jvp_sort_tA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, (const int64_t *)A.A_to_sorted.get(), tA_d, dAs.get());
+          OQ_LAUNCH(k_jvp_sort_tA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, to_sorted, tA_d, dAs.get());
           tA_d = dAs.get();
         }
-        jvp_rhs(e, A, tq ? dq.get() + d * n : nullptr, tl ? dl.get() + d * m : nullptr, tu ? du.get() + d * m : nullptr,
-                tPx ? dP.get() + d * nzP : nullptr, tA_d);
+        jvp_rhs(e, A, tq ? pq + d * n : nullptr, tl ? pl + d * m : nullptr, tu ? pu + d * m : nullptr,
+                tPx ? pP + d * nzP : nullptr, tA_d);
         A.solves += kkt_solve_refine(e, *K.F, K.act_rows.get(), K.mr, K.rhs_red.get(), K.sol.get(),
                                      RefineScratch{K.rhs.get(), K.yfull.get(), K.Axv.get(), K.px.get(), K.ared_x.get()},
                                      regularised ? 1 : (int)e.st.polish_refine_iter, regularised);
         OQ_LAUNCH(k_jvp_out, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), K.slot.get(), K.sol.get(),
-                  tx ? ox.get() + d * n : nullptr, oy.p ? oy.get() + d * m : nullptr);
+                  tx ? px + d * n : nullptr, py ? py + d * m : nullptr);
       }
       e.sync();
     };
@@ -206,12 +213,17 @@ int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const
       passes();
       if (K.F->faulted()) throw TreeFault();
     }
-    // outputs last: a call that fails has written nothing
-    if (tx) ox.download(tx, nd * n, s);
-    if (oy.p) oy.download(ty, nd * m, s);
-    e.sync();
+    // outputs last: a call that fails has written nothing (device form: as in model_adjoint_run)
+    if (!dev) {
+      if (tx) ox.download(tx, nd * n, s);
+      if (oy.p) oy.download(ty, nd * m, s);
+      e.sync();
+    }
   }
-  if (act) std::copy(K.h_side.begin(), K.h_side.end(), act);
+  if (act) {
+    if (dev) { e.copy_dev(act, K.side.get(), (size_t)m); e.sync(); }
+    else std::copy(K.h_side.begin(), K.h_side.end(), act);
+  }
   return 0;
 }
 

@@ -1383,9 +1383,9 @@ void Engine::begin_update() {
 }
 void Engine::end_update() { sync(); ws->info->update_time += toc(); }
 
-int Engine::update_lin_cost(const double *q_new) {
+int Engine::update_lin_cost(const double *q_new, bool dev) {
   begin_update();
-  q.upload(q_new + n0, n, stream);
+  load(q.get(), q_new + n0, n, dev);
   sync();
   if (st.scaling) vec_scale_by_vec_scalar(q.get(), D.get(), c, n, stream);
   reset_info(ws->info);
@@ -1395,6 +1395,7 @@ int Engine::update_lin_cost(const double *q_new) {
 
 int Engine::update_bounds(const double *l_new, const double *u_new) {
   begin_update();
+  refresh_bounds_mirror();  // (a device-form update since the last host-form one: update_vectors_dev)
   std::vector<double> nl(h_l), nu(h_u);
   if (l_new) nl.assign(l_new + m0, l_new + m0 + m);
   if (u_new) nu.assign(u_new + m0, u_new + m0 + m);
@@ -1405,6 +1406,11 @@ int Engine::update_bounds(const double *l_new, const double *u_new) {
   h_l.swap(nl); h_u.swap(nu);
   if (l_new) { l.upload(h_l.data(), m, stream); sync(); if (st.scaling) vec_ew_prod(l.get(), l.get(), E.get(), m, stream); }
   if (u_new) { u.upload(h_u.data(), m, stream); sync(); if (st.scaling) vec_ew_prod(u.get(), u.get(), E.get(), m, stream); }
+  if (l_raw.n) {  // the raw device copies exist (a device-form update has run): they follow
+    if (l_new) l_raw.upload(h_l.data(), m, stream);
+    if (u_new) u_raw.upload(h_u.data(), m, stream);
+    sync();
+  }
   reset_info(ws->info);
   int e = update_rho_vec_from_bounds();
   end_update();
@@ -1443,7 +1449,7 @@ __global__ __launch_bounds__(kBlock) void k_pick_new_vals(int64_t n, const int *
 }
 
 int Engine::update_PA(const double *Px_new, const c_int *Pidx, c_int Pn, const double *Ax_new, const c_int *Aidx, c_int An,
-                      bool doP, bool doA) {
+                      bool doP, bool doA, bool dev) {
   begin_update();
   if (doP) { if (Pidx) { if (Pn > nnzPtriu) return 1; } else if (Pn != nnzPtriu && Pn != 0) return 1; }
   if (doA) { if (Aidx) { if (An > nnzA) return 2; } else if (An != nnzA && An != 0) return 2; }
@@ -1452,7 +1458,7 @@ int Engine::update_PA(const double *Px_new, const c_int *Pidx, c_int Pn, const d
   // a workspace built from a sorted copy of the caller's A (unsorted columns at setup): the caller's nnz indices -> ours
   std::vector<c_int> Aidx_sorted;
   std::vector<double> Ax_sorted;
-  if (doA && !A_to_sorted.empty() && Ax_new) {
+  if (doA && !A_to_sorted.empty() && Ax_new && !dev) {  // (device form: update_values_dev has permuted on the device)
     if (Aidx) {
       Aidx_sorted.resize((size_t)An);
       for (c_int i = 0; i < An; i++) Aidx_sorted[(size_t)i] = (c_int)A_to_sorted[(size_t)Aidx[i]];
@@ -1473,22 +1479,24 @@ int Engine::update_PA(const double *Px_new, const c_int *Pidx, c_int Pn, const d
   if (st.scaling) unscale_data();
   auto scatter = [&](const double *vals, const c_int *idx, c_int k, double *t1, const int *map1, double *t2, const int *map2) {
     if (k <= 0) return;
-    DevBuf<double> dv((size_t)k);
+    DevBuf<double> dv;
     DevBuf<long long> di;
-    dv.upload(vals, (size_t)k, stream);
+    const double *src = vals;  // device form: the values are read where they lie
+    if (!dev) { dv.alloc((size_t)k); dv.upload(vals, (size_t)k, stream); src = dv.get(); }
     if (idx) { di.alloc((size_t)k); di.upload((const long long *)idx, (size_t)k, stream); }
     OQ_LAUNCH(k_scatter_vals, dim3(blocks_for(k)), dim3(kBlock), 0, stream, (int64_t)k, idx ? di.get() : (const long long *)nullptr,
-                       dv.get(), t1, map1, t2, map2);
+                       src, t1, map1, t2, map2);
     sync();
   };
   auto scatter_slots = [&](const double *vals, const c_int *idx, c_int k, double *t1, const uint32_t *map1, double *t2, const uint32_t *map2) {
     if (k <= 0) return;
-    DevBuf<double> dv((size_t)k);
+    DevBuf<double> dv;
     DevBuf<long long> di;
-    dv.upload(vals, (size_t)k, stream);
+    const double *src = vals;
+    if (!dev) { dv.alloc((size_t)k); dv.upload(vals, (size_t)k, stream); src = dv.get(); }
     if (idx) { di.alloc((size_t)k); di.upload((const long long *)idx, (size_t)k, stream); }
     OQ_LAUNCH(k_scatter_vals_slot, dim3(blocks_for(k)), dim3(kBlock), 0, stream, (int64_t)k, idx ? di.get() : (const long long *)nullptr,
-              dv.get(), t1, map1, t2, map2);
+              src, t1, map1, t2, map2);
     sync();
   };
   // every copy through its own map: slots of the sliced-ELL copy where the CSR arrays are gone, CSR positions otherwise
@@ -1544,11 +1552,11 @@ int Engine::update_PA(const double *Px_new, const c_int *Pidx, c_int Pn, const d
   return e;
 }
 
-int Engine::warm_start(const double *xw, const double *yw) {
+int Engine::warm_start(const double *xw, const double *yw, bool dev) {
   st.warm_start = 1;
   ws->settings->warm_start = 1;
   if (xw) {
-    x.upload(xw + n0, n, stream); sync();
+    load(x.get(), xw + n0, n, dev); sync();
     if (st.scaling) vec_ew_prod(x.get(), x.get(), Dinv.get(), n, stream);
     if (m > 0) spmv(A, full_n(x.get()), z.get(), nullptr, 0.0, 0.0, nullptr, stream);
   } else {
@@ -1558,10 +1566,125 @@ int Engine::warm_start(const double *xw, const double *yw) {
     x.zero(stream); z.zero(stream);
   }
   if (yw) {
-    y.upload(yw + m0, m, stream); sync();
+    load(y.get(), yw + m0, m, dev); sync();
     if (st.scaling) vec_scale_by_vec_scalar(y.get(), Einv.get(), c, m, stream);
   } else {
     y.zero(stream);
+  }
+  sync();
+  return 0;
+}
+
+// --------------------------------------------------------------------------
+// device forms of the updates (osqp_amd_*_dev): every array is a device array on this engine's
+// device.  Each is its host twin with the upload replaced by a device-to-device copy on `stream`: the same kernels in the
+// same order on the same operands, so the workspace ends in the same state bit for bit.  update_lin_cost, warm_start and
+// update_PA are the twins themselves with dev = true; the bounds and the solution read are below.
+// --------------------------------------------------------------------------
+// flag = 1 where some l[i] > u[i] (the rule of update_bounds; a NaN compares false there as here), on the bounds as they will
+// be stored: clamped to +-OSQP_INFTY.  Every thread that finds one stores the same word: no atomics needed.
+__global__ __launch_bounds__(kBlock) void k_bounds_crossed(int m, const double *__restrict__ l, const double *__restrict__ u, int *__restrict__ flag) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < m && fmax(l[i], -OSQP_INFTY) > fmin(u[i], OSQP_INFTY)) *flag = 1;
+}
+
+// a full value array in the caller's nnz order into the order of the sorted copy the workspace holds: every entry has one
+// target (to_sorted is a permutation), no atomics
+__global__ __launch_bounds__(kBlock) void k_permute_vals(int64_t nnz, const int64_t *__restrict__ to_sorted, const double *__restrict__ in,
+                                                         double *__restrict__ out) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k < nnz) out[to_sorted[k]] = in[k];
+}
+
+const int64_t *Engine::device_A_to_sorted() {
+  if (A_to_sorted.empty()) return nullptr;
+  if (!A_to_sorted_dev.n) {
+    A_to_sorted_dev.alloc(A_to_sorted.size());
+    A_to_sorted_dev.upload(A_to_sorted.data(), A_to_sorted.size(), stream);
+    sync();
+  }
+  return A_to_sorted_dev.get();
+}
+
+// the host mirror of the raw bounds, brought up to date after device-form updates (called by the host forms before they
+// validate against it)
+void Engine::refresh_bounds_mirror() {
+  if (h_l_stale) l_raw.download(h_l.data(), m, stream);
+  if (h_u_stale) u_raw.download(h_u.data(), m, stream);
+  if (h_l_stale || h_u_stale) sync();
+  h_l_stale = h_u_stale = false;
+}
+
+int Engine::update_vectors_dev(const double *q_new, const double *l_new, const double *u_new) {
+  if (m == 0) l_new = u_new = nullptr;  // nothing to say
+  const bool bounds = l_new || u_new;
+  if (bounds) {
+    // the rule of update_bounds, decided on the device before anything is touched: the new l against the new u, or against
+    // the one in force where only one side is given; the host reads one word
+    begin_update();
+    if (!l_raw.n) {
+      refresh_bounds_mirror();
+      l_raw.alloc(m); u_raw.alloc(m);
+      l_raw.upload(h_l.data(), m, stream); u_raw.upload(h_u.data(), m, stream);
+      sync();
+    }
+    flag.zero(stream);
+    OQ_LAUNCH(k_bounds_crossed, dim3(blocks_for(m)), dim3(kBlock), 0, stream, m, l_new ? l_new : (const double *)l_raw.get(),
+              u_new ? u_new : (const double *)u_raw.get(), flag.get());
+    int crossed = 0;
+    flag.download(&crossed, 1, stream);
+    sync();
+    if (crossed) return 1;
+    end_update();
+  }
+  if (q_new) update_lin_cost(q_new, true);
+  if (!bounds) return 0;
+  begin_update();  // update_bounds
+  if (l_new) {
+    // (the wrappers of the host forms clamp to +-OSQP_INFTY on the host before the call; here it is part of the call)
+    copy_dev(l_raw.get(), l_new, m); vec_clamp(l_raw.get(), -OSQP_INFTY, HUGE_VAL, m, stream); h_l_stale = true;
+    copy_dev(l.get(), l_raw.get(), m); sync();
+    if (st.scaling) vec_ew_prod(l.get(), l.get(), E.get(), m, stream);
+  }
+  if (u_new) {
+    copy_dev(u_raw.get(), u_new, m); vec_clamp(u_raw.get(), -HUGE_VAL, OSQP_INFTY, m, stream); h_u_stale = true;
+    copy_dev(u.get(), u_raw.get(), m); sync();
+    if (st.scaling) vec_ew_prod(u.get(), u.get(), E.get(), m, stream);
+  }
+  reset_info(ws->info);
+  int e = update_rho_vec_from_bounds();
+  end_update();
+  return e;
+}
+
+int Engine::update_values_dev(const double *Px_new, const double *Ax_new) {
+  const double *Ax_use = Ax_new;
+  DevBuf<double> Ax_sorted;
+  if (Ax_new && nnzA > 0) {
+    if (const int64_t *map = device_A_to_sorted()) {  // the host form permutes on the host (update_PA)
+      Ax_sorted.alloc((size_t)nnzA);
+      OQ_LAUNCH(k_permute_vals, dim3(blocks_for(nnzA)), dim3(kBlock), 0, stream, nnzA, map, Ax_new, Ax_sorted.get());
+      Ax_use = Ax_sorted.get();
+    }
+  }
+  return update_PA(Px_new, nullptr, (c_int)nnzPtriu, Ax_use, nullptr, (c_int)nnzA, Px_new != nullptr, Ax_new != nullptr, true);
+}
+
+// x = D x~ and y = (E y~) / c with the operations of store_solution, into the caller's device arrays; NaN where the last
+// solve left no solution, as the host mirrors are filled
+int Engine::solution_dev(double *x_out, double *y_out) {
+  if (m == 0) y_out = nullptr;
+  if (has_solution(ws->info)) {
+    if (st.scaling) {
+      if (x_out) vec_ew_prod(x_out, x.get(), D.get(), n, stream);
+      if (y_out) { vec_ew_prod(y_out, y.get(), E.get(), m, stream); vec_scale(y_out, cinv, m, stream); }
+    } else {
+      if (x_out) copy_dev(x_out, x.get(), n);
+      if (y_out) copy_dev(y_out, y.get(), m);
+    }
+  } else {
+    if (x_out) vec_set(x_out, NAN, n, stream);
+    if (y_out) vec_set(y_out, NAN, m, stream);
   }
   sync();
   return 0;

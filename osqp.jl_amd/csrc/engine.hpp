@@ -124,6 +124,14 @@ struct Engine {
   double res[16] = {0};       // norms of the last residual evaluation (Slot order)
   double c = 1.0, cinv = 1.0;
   std::vector<double> h_l, h_u;  // unscaled bounds on the host (validation of bound updates)
+  // device forms: the unscaled bounds as device arrays, allocated by the first device-form update of
+  // a bound and kept equal to the bounds in force from then on by both forms.  A device-form update leaves its side of the
+  // host mirror stale; the next host-form update refreshes it before it validates (refresh_bounds_mirror).
+  DevBuf<double> l_raw, u_raw;
+  bool h_l_stale = false, h_u_stale = false;
+  DevBuf<int64_t> A_to_sorted_dev;  // A_to_sorted on the device (uploaded by whoever needs it first: device_A_to_sorted)
+  long long solves_run = 0;         // osqp_solve calls so far (osqp_amd_solution_dev refuses before the first)
+  long long dev_calls[6] = {0, 0, 0, 0, 0, 0};  // osqp_amd_device_form_calls: vectors, values, warm starts, solution reads, adjoints, jvps
 
   std::unique_ptr<Linsys> lin;
 
@@ -214,10 +222,25 @@ struct Engine {
   double obj_from_slots() const;
 
   // ---- updates ----
-  int update_lin_cost(const double *q_new);
+  // dev: the arrays are device arrays on this engine's device -- copied on `stream` (or read where they lie) instead of uploaded;
+  // everything after the copy is the same code.  Not on a row-sharded workspace (refused at the C boundary).
+  int update_lin_cost(const double *q_new, bool dev = false);
   int update_bounds(const double *l_new, const double *u_new);
-  int update_PA(const double *Px, const c_int *Pidx, c_int Pn, const double *Ax, const c_int *Aidx, c_int An, bool doP, bool doA);
-  int warm_start(const double *x, const double *y);
+  // dev: full replacement only, no indices
+  int update_PA(const double *Px, const c_int *Pidx, c_int Pn, const double *Ax, const c_int *Aidx, c_int An, bool doP, bool doA,
+                bool dev = false);
+  int warm_start(const double *x, const double *y, bool dev = false);
+  // ---- osqp_amd_*_dev ----
+  int update_vectors_dev(const double *q_new, const double *l_new, const double *u_new);  // update_lin_cost, then the bounds
+  int update_values_dev(const double *Px_new, const double *Ax_new);                      // update_PA behind the permutation
+  int solution_dev(double *x_out, double *y_out);
+  void refresh_bounds_mirror();
+  const int64_t *device_A_to_sorted();  // null: the caller's columns were sorted
+  // a host array (uploaded) or a device array (copied) into a device vector, on `stream`
+  void load(double *dst, const double *src, size_t count, bool dev) {
+    if (count) HIP_CHECK(hipMemcpyAsync(dst, src, count * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+  }
+  void copy_dev(double *dst, const double *src, size_t count) { load(dst, src, count, true); }
 
   // ---- helpers ----
   void tic() { t0 = std::chrono::steady_clock::now(); }
@@ -250,12 +273,15 @@ std::unique_ptr<Linsys> make_direct(Engine &e, int *err);
 int polish_run(Engine &e);
 // the same without a factorisation, on the operator of the indirect back-end (pcg.hip): compact workspaces, factors that do not fit
 int polish_run_pcg(Engine &e);
-// osqp_amd_adjoint / _release / _stats on a workspace that passed the checks of the C boundary (direct_adjoint.hpp); host pointers
+// osqp_amd_adjoint / _release / _stats on a workspace that passed the checks of the C boundary (direct_adjoint.hpp); host
+// pointers, or with dev = true (osqp_amd_adjoint_dev) device pointers: cotangents read in place, the output kernels write the
+// caller's arrays, act is a copy of the kept side array -- the same kernels on the same operands, no staging, no download
 int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
-                      double *dAx, double *act);
-// osqp_amd_jvp on the same kept state (direct_jvp.hpp): ndir directions (tq, tl, tu, tPx, tAx; null = zero) to (tx, ty); host pointers
+                      double *dAx, double *act, bool dev = false);
+// osqp_amd_jvp on the same kept state (direct_jvp.hpp): ndir directions (tq, tl, tu, tPx, tAx; null = zero) to (tx, ty); host
+// pointers, or device pointers with dev = true (osqp_amd_jvp_dev)
 int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const double *tu, const double *tPx, const double *tAx,
-                  double *tx, double *ty, double *act);
+                  double *tx, double *ty, double *act, bool dev = false);
 void model_adjoint_release(Engine &e);  // drops the kept factor (the counters stay)
 void model_adjoint_stats(const Engine &e, double out[6]);
 const char *last_error_cstr();

@@ -422,8 +422,75 @@ def update_P_A(model, Px, Px_idx, Ax, Ax_idx):
         raise OSQPError("Error updating P and A")
 
 
+def _is_device(a):
+    """The rule of `batch._batch_array`: a device array is an object with `data_ptr()` and `shape` -- `batch.DeviceArray`, a
+    torch CUDA tensor.  (A torch tensor that says it lives on the host is host data, converted like anything else.)"""
+    return hasattr(a, "data_ptr") and hasattr(a, "shape") and getattr(a, "is_cuda", True) is not False
+
+
+def _device_form(who, given):
+    """Do the arrays of one call (name -> array, None left out) come in the device form?  One form per call: a mixture
+    raises ValueError, before any library call."""
+    dev = [k for k, v in given.items() if _is_device(v)]
+    if dev and len(dev) != len(given):
+        host = [k for k in given if k not in dev]
+        raise ValueError(f"{who}: one form per call -- {', '.join(dev)} are device arrays, {', '.join(host)} are not")
+    return bool(dev)
+
+
+def _device_checked(name, a):
+    """Element type and layout of a device array, before its shape is known."""
+    dt = getattr(a, "dtype", None)
+    if dt is not None and "float64" not in str(dt):
+        raise ValueError(f"{name}: device arrays must be float64, got {dt}")
+    if hasattr(a, "is_contiguous") and not a.is_contiguous():
+        raise ValueError(f"{name}: device arrays must be contiguous")
+    return tuple(int(k) for k in a.shape)
+
+
+def _device_vector(name, a, cols):
+    """Address of a device array of shape (cols,) -- or (1, cols), what `batch.DeviceArray` calls a vector --, or None when it
+    has no entries (the library takes NULL: nothing to say)."""
+    shape = _device_checked(name, a)
+    if shape not in ((cols,), (1, cols)):
+        raise ValueError(f"{name}: expected shape ({cols},), got {shape}")
+    return a.data_ptr() if cols > 0 else None
+
+
+def _device_symbol(model, name):
+    fn = getattr(model.lib, name, None)
+    if fn is None or fn.argtypes is None:
+        raise OSQPError(f"this library does not export {name}: the device-pointer forms are an extension of libosqp_amd.so")
+    return fn
+
+
+def _update_device(model, given):
+    """`update` with device arrays: osqp_amd_update_vectors_dev (q, l, u in one call), then osqp_amd_update_values_dev."""
+    for name, a in given.items():
+        _device_checked(name, a)
+    n, m = dimensions(model)
+    cols = _data_cols(model) if ("Px" in given or "Ax" in given) else dict(q=n, l=m, u=m)
+    ptr = {name: _device_vector(name, a, cols[name]) for name, a in given.items()}
+    if any(ptr.get(k) is not None for k in ("q", "l", "u")):
+        if _device_symbol(model, "osqp_amd_update_vectors_dev")(model.workspace, ptr.get("q"), ptr.get("l"), ptr.get("u")) != 0:
+            raise OSQPError("Error updating q, l, u from device arrays: " + model.lib.osqp_amd_last_error().decode())
+    if ptr.get("Px") is not None or ptr.get("Ax") is not None:
+        if _device_symbol(model, "osqp_amd_update_values_dev")(model.workspace, ptr.get("Px"), ptr.get("Ax")) != 0:
+            raise OSQPError("Error updating P and A from device arrays: " + model.lib.osqp_amd_last_error().decode())
+    elif "Px" in given or "Ax" in given:
+        # value arrays without entries only: no data to move, the host form's round (unscale, scale, refactorise) as it is
+        update(model, **{k: np.zeros(0) for k in ("Px", "Ax") if k in given})
+
+
 def update(model, q=None, l=None, u=None, Px=None, Px_idx=None, Ax=None, Ax_idx=None):
-    """[REF src/interface.jl:408-440]"""
+    """[REF src/interface.jl:408-440].  Extension: device arrays (`_is_device`: torch CUDA tensors, `batch.DeviceArray`) take
+    the device-pointer forms of the library -- no host hop; one form per call, full value arrays only (no Px_idx / Ax_idx).
+    The caller has finished producing them (the library runs on its own stream and blocks)."""
+    given = {k: v for k, v in (("q", q), ("l", l), ("u", u), ("Px", Px), ("Ax", Ax)) if v is not None}
+    if _device_form("update", given):
+        if Px_idx is not None or Ax_idx is not None:
+            raise ValueError("update: Px_idx / Ax_idx go with host values; the device form replaces the full value arrays")
+        return _update_device(model, given)
     if q is not None:
         update_q(model, q)
     if l is not None and u is not None:
@@ -497,7 +564,17 @@ def warm_start_x_y(model, x, y):
 
 
 def warm_start(model, x=None, y=None):
-    """[REF src/interface.jl:720-732]"""
+    """[REF src/interface.jl:720-732].  Extension: device arrays take osqp_amd_warm_start_dev (the rule of `update`); x alone
+    zeroes the stored y and y alone the stored x, as the host forms do."""
+    given = {k: v for k, v in (("x", x), ("y", y)) if v is not None}
+    if _device_form("warm_start", given):
+        for name, a in given.items():
+            _device_checked(name, a)
+        n, m = dimensions(model)
+        ptr = {name: _device_vector(name, a, n if name == "x" else m) for name, a in given.items()}
+        if _device_symbol(model, "osqp_amd_warm_start_dev")(model.workspace, ptr.get("x"), ptr.get("y")) != 0:
+            raise OSQPError("Error in warm starting from device arrays: " + model.lib.osqp_amd_last_error().decode())
+        return
     if x is not None and y is not None:
         warm_start_x_y(model, x, y)
     elif x is not None:
@@ -549,19 +626,90 @@ def _cotangent(name, a, cols):
     return _as_f64(arr).reshape(arr.shape[0] if arr.ndim == 2 else 1, cols), arr.ndim == 2  # (cols may be 0: m = 0)
 
 
-def adjoint(model, dx=None, dy=None, want=ADJOINT_GRADS):
+def _device_empty(model, like, shape):
+    """An uninitialised fp64 device array of `shape` beside `like`: a torch tensor when `like` is one, else a
+    `batch.DeviceArray` ([1 x cols] for a vector)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.is_tensor(like):
+        return torch.empty(shape, dtype=torch.float64, device=like.device)
+    from .batch import DeviceArray
+
+    return DeviceArray(model.lib, shape[0] if len(shape) == 2 else 1, shape[-1], getattr(like, "device", 0))
+
+
+def _device_leading(who, what, given, width):
+    """Shapes of the device inputs of `adjoint` / `jvp` (name -> array, all checked for type): (count, had a leading axis?)."""
+    shapes = {nm: _device_checked(nm, a) for nm, a in given.items()}
+    for nm, shp in shapes.items():
+        if len(shp) not in (1, 2) or shp[-1] != width[nm] or (len(shp) == 2 and shp[0] < 1):
+            raise ValueError(f"{nm}: expected shape ({width[nm]},) or ({what}, {width[nm]}) with {what} >= 1, got {shp}")
+    if len({len(shp) for shp in shapes.values()}) > 1:
+        raise ValueError(f"{who}: the arrays must all have a leading axis or all have none")
+    many = len(next(iter(shapes.values()))) == 2
+    counts = {shp[0] if many else 1 for shp in shapes.values()}
+    if len(counts) > 1:
+        raise ValueError(f"{who}: the arrays differ in their leading axis: {sorted(counts)}")
+    return counts.pop(), many
+
+
+def _device_outputs(model, like, names, shape_of, out):
+    """The device arrays a call writes: those of `out` (checked), fresh ones beside `like` for the rest."""
+    res = {}
+    for k in names:
+        shape = shape_of(k)
+        a = None if out is None else out.get(k)
+        if a is None:
+            a = _device_empty(model, like, shape)
+        else:
+            if not _is_device(a):
+                raise ValueError(f"out[{k!r}]: expected a device array")
+            got = _device_checked(f"out[{k!r}]", a)
+            if got != shape and got != (1,) + shape:
+                raise ValueError(f"out[{k!r}]: expected shape {shape}, got {got}")
+        res[k] = a
+    return res
+
+
+def _adjoint_device(model, given, want, out):
+    for nm, a in given.items():
+        _device_checked(nm, a)
+    fn = _device_symbol(model, "osqp_amd_adjoint_dev")
+    n, m = dimensions(model)
+    ncot, many = _device_leading("adjoint", "ncot", given, dict(dx=n, dy=m))
+    cols = _data_cols(model) if ("Px" in want or "Ax" in want) else dict(q=n, l=m, u=m)
+    like = next(iter(given.values()))
+    res = _device_outputs(model, like, want + ("act",), lambda k: (m,) if k == "act" else ((ncot, cols[k]) if many else (cols[k],)), out)
+    addr = lambda a, width: a.data_ptr() if a is not None and width > 0 else None
+    args = [addr(given.get("dx"), n), addr(given.get("dy"), m)] + [addr(res.get(k), cols.get(k, 0)) for k in ADJOINT_GRADS] + [addr(res["act"], m)]
+    if any(p is not None for p in args[2:]):  # (m = 0 and only "l" / "u" wanted: nothing to compute)
+        if fn(model.workspace, ncot, *args) != 0:
+            raise OSQPError("Error in adjoint: " + model.lib.osqp_amd_last_error().decode())
+    return res
+
+
+def adjoint(model, dx=None, dy=None, want=ADJOINT_GRADS, out=None):
     """Extension: osqp_amd_adjoint (include/osqp_amd.h).  From dx = dloss/dx and dy = dloss/dy at the solution of the last
     `solve` (either may be None = 0) the gradients named in `want` -- "q", "l", "u", "Px" (upper triangle of P), "Ax", both
     in the nnz order `update` takes -- as a dict of numpy arrays, plus "act" [m] (-1 lower, 0 inactive, 1 upper).  Inputs
     [n] / [m] give outputs without a leading axis, inputs [ncot x n] / [ncot x m] outputs with one.  `want=()` with no
-    cotangent returns "act" alone.  The first call after a solve factorises and keeps the factor (`adjoint_release`)."""
-    fn = _adjoint_symbol(model, "osqp_amd_adjoint")
+    cotangent returns "act" alone.  The first call after a solve factorises and keeps the factor (`adjoint_release`).
+    Device arrays (the rule of `update`; one form per call) take osqp_amd_adjoint_dev: the gradients and "act" ([m], -1.0 /
+    0.0 / 1.0 as the library keeps it) come back as device arrays -- torch tensors beside the inputs when those are tensors,
+    `batch.DeviceArray` otherwise -- or are written into the arrays of the dict `out` (name -> device array; the others are
+    allocated), as `ResidentBatch.adjoint` has it."""
     want = tuple(want)
     for k in want:
         if k not in ADJOINT_GRADS:
             raise ValueError(f"want: unknown gradient {k!r} (known: {', '.join(ADJOINT_GRADS)})")
     if len(set(want)) != len(want):
         raise ValueError("want: a gradient is named twice")
+    if _device_form("adjoint", {nm: v for nm, v in (("dx", dx), ("dy", dy)) if v is not None}):
+        return _adjoint_device(model, {nm: v for nm, v in (("dx", dx), ("dy", dy)) if v is not None}, want, out)
+    if out is not None:
+        raise ValueError("adjoint: out= goes with device arrays; host inputs return numpy arrays")
+    fn = _adjoint_symbol(model, "osqp_amd_adjoint")
     n, m = dimensions(model)
     given = [(nm, v, k) for nm, v, k in (("dx", dx, n), ("dy", dy, m)) if v is not None]
     got = {nm: _cotangent(nm, v, k) for nm, v, k in given}
@@ -594,16 +742,40 @@ def _data_cols(model):
     return dict(q=n, l=m, u=m, Px=int(st[3]), Ax=int(st[1]))
 
 
-def jvp(model, q=None, l=None, u=None, Px=None, Ax=None):
+def _jvp_device(model, given, out):
+    for nm, a in given.items():
+        _device_checked(nm, a)
+    fn = _device_symbol(model, "osqp_amd_jvp_dev")
+    n, m = dimensions(model)
+    cols = _data_cols(model) if ("Px" in given or "Ax" in given) else dict(q=n, l=m, u=m)
+    ndir, many = _device_leading("jvp", "ndir", given, cols)
+    like = next(iter(given.values()))
+    width = dict(x=n, y=m, act=m)
+    res = _device_outputs(model, like, ("x", "y", "act"), lambda k: (ndir, width[k]) if many and k != "act" else (width[k],), out)
+    addr = lambda a, w: a.data_ptr() if a is not None and w > 0 else None
+    tang = [addr(given.get(k), cols.get(k, 0)) for k in ADJOINT_GRADS]
+    if all(p is None for p in tang):
+        raise ValueError("jvp: every tangent given is an array without entries")
+    if fn(model.workspace, ndir, *tang, addr(res["x"], n), addr(res["y"], m), addr(res["act"], m)) != 0:
+        raise OSQPError("Error in jvp: " + model.lib.osqp_amd_last_error().decode())
+    return res
+
+
+def jvp(model, q=None, l=None, u=None, Px=None, Ax=None, out=None):
     """Extension: osqp_amd_jvp (include/osqp_amd.h).  The forward sensitivities of the solution of the last `solve` along a
     direction of the data: tangents q [n], l, u [m], Px [nnz(P upper)], Ax [nnz(A)] in the nnz order `update` takes (None =
     zero; not all).  Returns a dict "x" (tangent of x), "y" (of the multipliers; zero on inactive rows) and "act" [m].
     Inputs [cols] give outputs without a leading axis, inputs [ndir x cols] outputs with one; all tangents agree on this
     and on ndir.  On a row with l == u only `l` is read.  The factor is `adjoint`'s: whichever is called first after a
-    solve builds it, the other reuses it (`adjoint_release`, `adjoint_stats`)."""
+    solve builds it, the other reuses it (`adjoint_release`, `adjoint_stats`).  Device arrays (the rule of `update`; one form
+    per call) take osqp_amd_jvp_dev and give device arrays, `out` as in `adjoint`."""
+    given = [(nm, v) for nm, v in zip(ADJOINT_GRADS, (q, l, u, Px, Ax)) if v is not None]
+    if _device_form("jvp", dict(given)):
+        return _jvp_device(model, dict(given), out)
+    if out is not None:
+        raise ValueError("jvp: out= goes with device arrays; host inputs return numpy arrays")
     fn = _adjoint_symbol(model, "osqp_amd_jvp")
     n, m = dimensions(model)
-    given = [(nm, v) for nm, v in zip(ADJOINT_GRADS, (q, l, u, Px, Ax)) if v is not None]
     if not given:
         raise ValueError("jvp: q, l, u, Px and Ax are all None: at least one tangent is needed")
     cols = dict(q=n, l=m, u=m)
@@ -711,6 +883,41 @@ def jacobian(model, of=("x",), wrt=("q", "l", "u"), mode="auto", out_rows=None, 
                         J[(o, w)][:, p0:p0 + b - a] = res[o][a:b][:, idx[o]].T
     J["act"] = res["act"]
     return J
+
+
+DEVICE_FORM_FIELDS = ("update_vectors", "update_values", "warm_start", "solution", "adjoint", "jvp")
+
+
+def solution(model, x=None, y=None, device=0):
+    """Extension: osqp_amd_solution_dev -- the solution of the last `solve` read into device arrays: x [n] and y [m] are
+    filled where given (device arrays, the rule of `update`), allocated where not (`batch.DeviceArray` [1 x n] / [1 x m] on
+    `device`, or torch tensors beside the one that was given).  Returns (x, y); NaN where the solve ended without a solution."""
+    given = {k: v for k, v in (("x", x), ("y", y)) if v is not None}
+    for name, a in given.items():
+        if not _is_device(a):
+            raise ValueError(f"solution: {name} must be a device array (a torch CUDA tensor or a batch.DeviceArray)")
+        _device_checked(name, a)
+    fn = _device_symbol(model, "osqp_amd_solution_dev")
+    n, m = dimensions(model)
+    like = next(iter(given.values()), None)
+    if like is None:
+        from .batch import DeviceArray
+
+        like = DeviceArray(model.lib, 1, n, device)
+        given["x"] = like
+    res = _device_outputs(model, like, ("x", "y"), lambda k: (n,) if k == "x" else (m,), given)
+    if fn(model.workspace, res["x"].data_ptr(), res["y"].data_ptr() if m > 0 else None) != 0:
+        raise OSQPError("Error in solution: " + model.lib.osqp_amd_last_error().decode())
+    return res["x"], res["y"]
+
+
+def device_form_calls(model):
+    """Extension: osqp_amd_device_form_calls as a dict of ints -- the device-form calls this model has served so far."""
+    fn = _device_symbol(model, "osqp_amd_device_form_calls")
+    out = np.zeros(len(DEVICE_FORM_FIELDS))
+    if fn(model.workspace, _fptr(out), len(out)) != len(out):
+        raise OSQPError("osqp_amd_device_form_calls: bad argument")
+    return {name: int(v) for name, v in zip(DEVICE_FORM_FIELDS, out)}
 
 
 def adjoint_release(model):

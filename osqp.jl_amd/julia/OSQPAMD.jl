@@ -170,6 +170,87 @@ function adjoint_stats(model::OSQP.Model)
     return (builds = Int(out[1]), solves = Int(out[2]), n_low = Int(out[3]), n_upp = Int(out[4]), kept = out[5] == 1.0, bytes = Int(out[6]))
 end
 
+# ---- device-pointer forms of a single model's life cycle (include/osqp_amd.h, DESIGN.md section 16) ----
+# Every array is a DEVICE address on the model's device, as a `Ptr{Cdouble}` (`C_NULL`: not given / not wanted) -- for an
+# AMDGPU.jl array `Ptr{Cdouble}(UInt(pointer(a)))`; the package itself does not depend on a GPU array type.  The library runs
+# on its own stream and blocks: the caller has finished producing the inputs before the call.  Each call leaves the model in
+# the state its host twin leaves it in, bit for bit.  Not executed by the test suite; the Python mirror (`interface.update`,
+# `warm_start`, `solution`, `adjoint`, `jvp` with device arrays) is.
+const DevicePtr = Ptr{Cdouble}
+const DEV_NULL = Ptr{Cdouble}(C_NULL)
+
+"`OSQP.update!(model; q, l, u)` from device arrays (osqp_amd_update_vectors_dev); a crossed pair of bounds changes nothing."
+function update_vectors_dev!(model::OSQP.Model; q::DevicePtr = DEV_NULL, l::DevicePtr = DEV_NULL, u::DevicePtr = DEV_NULL)
+    flag = ccall((:osqp_amd_update_vectors_dev, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                 model.workspace, q, l, u)
+    flag == 0 || error("Error updating q, l, u from device arrays: $(last_error())")
+    return nothing
+end
+
+"`OSQP.update!(model; Px, Ax)` with full value arrays on the device, in the caller's nnz order (osqp_amd_update_values_dev)."
+function update_values_dev!(model::OSQP.Model; Px::DevicePtr = DEV_NULL, Ax::DevicePtr = DEV_NULL)
+    flag = ccall((:osqp_amd_update_values_dev, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Ptr{Cdouble}), model.workspace, Px, Ax)
+    flag == 0 || error("Error updating P and A from device arrays: $(last_error())")
+    return nothing
+end
+
+"`OSQP.warm_start!(model; x, y)` from device arrays (osqp_amd_warm_start_dev); one of them alone zeroes the other block."
+function warm_start_dev!(model::OSQP.Model; x::DevicePtr = DEV_NULL, y::DevicePtr = DEV_NULL)
+    flag = ccall((:osqp_amd_warm_start_dev, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Ptr{Cdouble}), model.workspace, x, y)
+    flag == 0 || error("Error in warm starting from device arrays: $(last_error())")
+    return nothing
+end
+
+"The solution of the last `OSQP.solve!` into the device arrays `x` [n] and `y` [m] (osqp_amd_solution_dev)."
+function solution_dev!(model::OSQP.Model; x::DevicePtr = DEV_NULL, y::DevicePtr = DEV_NULL)
+    flag = ccall((:osqp_amd_solution_dev, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Ptr{Cdouble}), model.workspace, x, y)
+    flag == 0 || error("Error in solution_dev!: $(last_error())")
+    return nothing
+end
+
+"""
+    adjoint_dev!(model, ncot; dx, dy, dq, dl, du, dPx, dAx, act)
+
+`adjoint` from device arrays into device arrays (osqp_amd_adjoint_dev): cotangents `[ncot x n]` / `[ncot x m]` cotangent-major,
+the outputs that are given are written, `act` is `[m]` doubles.  The kept factor is `adjoint`'s.
+"""
+function adjoint_dev!(model::OSQP.Model, ncot::Integer = 1; dx::DevicePtr = DEV_NULL, dy::DevicePtr = DEV_NULL, dq::DevicePtr = DEV_NULL,
+                      dl::DevicePtr = DEV_NULL, du::DevicePtr = DEV_NULL, dPx::DevicePtr = DEV_NULL, dAx::DevicePtr = DEV_NULL,
+                      act::DevicePtr = DEV_NULL)
+    flag = ccall((:osqp_amd_adjoint_dev, lib), Cc_int,
+                 (Ptr{OSQP.Workspace}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                  Ptr{Cdouble}, Ptr{Cdouble}),
+                 model.workspace, ncot, dx, dy, dq, dl, du, dPx, dAx, act)
+    flag == 0 || error("Error in adjoint_dev!: $(last_error())")
+    return nothing
+end
+
+"""
+    jvp_dev!(model, ndir; q, l, u, Px, Ax, tx, ty, act)
+
+`jvp` from device arrays into device arrays (osqp_amd_jvp_dev): tangents `[ndir x cols]` direction-major, `tx` / `ty` written
+where given.
+"""
+function jvp_dev!(model::OSQP.Model, ndir::Integer = 1; q::DevicePtr = DEV_NULL, l::DevicePtr = DEV_NULL, u::DevicePtr = DEV_NULL,
+                  Px::DevicePtr = DEV_NULL, Ax::DevicePtr = DEV_NULL, tx::DevicePtr = DEV_NULL, ty::DevicePtr = DEV_NULL,
+                  act::DevicePtr = DEV_NULL)
+    flag = ccall((:osqp_amd_jvp_dev, lib), Cc_int,
+                 (Ptr{OSQP.Workspace}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                  Ptr{Cdouble}, Ptr{Cdouble}),
+                 model.workspace, ndir, q, l, u, Px, Ax, tx, ty, act)
+    flag == 0 || error("Error in jvp_dev!: $(last_error())")
+    return nothing
+end
+
+"The device-form calls this model has served (osqp_amd_device_form_calls)."
+function device_form_calls(model::OSQP.Model)
+    out = zeros(Float64, 6)  # OSQP_AMD_DEVICE_FORM_COUNT (include/osqp_amd.h)
+    k = ccall((:osqp_amd_device_form_calls, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Cc_int), model.workspace, out, length(out))
+    k == length(out) || error("osqp_amd_device_form_calls: bad argument")
+    return (update_vectors = Int(out[1]), update_values = Int(out[2]), warm_start = Int(out[3]), solution = Int(out[4]),
+            adjoint = Int(out[5]), jvp = Int(out[6]))
+end
+
 """
     batch_solve(P, A, Px, Ax, q, l, u; device = 0, settings...) -> (x, y, infos)
 

@@ -34,9 +34,13 @@ an instance's active constraints are dependent the derivative does not exist and
 (include/osqp_amd.h, osqp_amd_batch_adjoint); the same holds for the tangents (osqp_amd_batch_jvp).
 
 A single model (`interface.Model`: one large sparse QP, any n) as a layer: `QPFunction` / `QPLayer(model)`, at the end of this
-file.  Its arrays are host arrays (include/osqp_amd.h: every single-model entry takes host pointers), so tensors on any
-device go through the host; the forward is `update` + `solve`, the backward one `interface.adjoint` call on the kept factor,
-and under `torch.autograd.forward_ad` the tangents of (x, y) come from one `interface.jvp` call on the same factor.
+file.  The forward is `update` + `solve`, the backward one `interface.adjoint` call on the kept factor, and under
+`torch.autograd.forward_ad` the tangents of (x, y) come from one `interface.jvp` call on the same factor.  Two routes, by
+where the tensors live.  CUDA tensors (all of them, on the model's device) take the device-pointer forms of the library
+(include/osqp_amd.h: osqp_amd_update_vectors_dev ... osqp_amd_jvp_dev): the data are read from HBM, x, y and the gradients
+are torch-allocated CUDA tensors the library writes into, nothing goes through the host; torch's current stream is
+synchronised before every library call, as for the batch.  CPU tensors take the host forms.  The two routes give the same
+bits (the device forms are the host forms with the copy removed); a mixture of CPU and CUDA tensors raises ValueError.
 
     layer = QPLayer(model)
     x, y = layer(q=q_t, l=l_t, u=u_t)           # float64 tensors [n] / [m]; None keeps the model's data
@@ -218,11 +222,21 @@ def stamp_model_forward(model):
     return model._qp_layer_stamp
 
 
+def _route(who, tensors):
+    """True: the device route (every tensor a CUDA tensor), False: the host route (every tensor a CPU tensor, or none given);
+    a mixture raises ValueError."""
+    cuda = [t.is_cuda for t in tensors]
+    if any(cuda) and not all(cuda):
+        raise ValueError(f"{who}: CPU and CUDA tensors are mixed; give all of them on one side")
+    return bool(cuda) and all(cuda)
+
+
 class QPFunction(torch.autograd.Function):
     """(x, y) of a single model as a function of the data given: each tensor goes through `interface.update`, then `solve`,
     which must end Solved.  backward: ONE `interface.adjoint` call that asks only for the gradients of the inputs that
     require grad; it raises when a later forward has solved the model again (the stamp), and the library itself refuses a
-    model that was updated or warm-started by hand since (OSQPError: no current solution)."""
+    model that was updated or warm-started by hand since (OSQPError: no current solution).  CUDA tensors: the device forms
+    throughout (x, y and the gradients are CUDA tensors the library writes into); CPU tensors: the host forms."""
 
     @staticmethod
     def forward(ctx, model, q, l, u, Px, Ax):
@@ -230,18 +244,29 @@ class QPFunction(torch.autograd.Function):
         for name, t in given.items():
             if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != 1):
                 raise ValueError(f"{name}: expected a one-dimensional float64 tensor")
-        host = {name: t.detach().cpu().contiguous().numpy() for name, t in given.items() if t is not None}
-        if host:
-            _iface.update(model, **host)
+        tensors = {name: t for name, t in given.items() if t is not None}
+        on_device = _route("QPFunction", tensors.values())
+        if on_device:
+            ref = next(iter(tensors.values()))
+            data = {name: t.detach().contiguous() for name, t in tensors.items()}
+            _sync(ref)  # (after the copies `contiguous` may have queued)
+            _iface.update(model, **data)
+        elif tensors:
+            _iface.update(model, **{name: t.detach().cpu().contiguous().numpy() for name, t in tensors.items()})
         res = _iface.solve(model)
         ctx.model, ctx.stamp = model, stamp_model_forward(model)
-        ctx.given = tuple(name for name, t in given.items() if t is not None)  # for jvp: the inputs that can carry a tangent
+        ctx.given = tuple(tensors)  # for jvp: the inputs that can carry a tangent
         model._qp_layer_info = res.info
         if res.info.status != "Solved":
             raise RuntimeError(f"QPFunction: the solve ended with status {res.info.status}; there is no solution to differentiate")
-        ref = next((t for t in given.values() if t is not None), None)
-        dev = ref.device if ref is not None else torch.device("cpu")
-        return torch.from_numpy(res.x.copy()).to(dev), torch.from_numpy(res.y.copy()).to(dev)
+        if on_device:
+            n, m = _iface.dimensions(model)
+            x = torch.empty(n, dtype=torch.float64, device=ref.device)
+            y = torch.empty(m, dtype=torch.float64, device=ref.device)
+            _sync(ref)
+            _iface.solution(model, x=x, y=y)
+            return x, y
+        return torch.from_numpy(res.x.copy()), torch.from_numpy(res.y.copy())
 
     @staticmethod
     def jvp(ctx, t_model, tq, tl, tu, tPx, tAx):
@@ -255,8 +280,16 @@ class QPFunction(torch.autograd.Function):
         if not tang:
             return None, None
         ref = next(iter(tang.values()))
+        if _route("QPFunction.jvp", tang.values()):
+            n, m = _iface.dimensions(model)
+            tx = torch.empty(n, dtype=torch.float64, device=ref.device)
+            ty = torch.empty(m, dtype=torch.float64, device=ref.device)
+            data = {k: t.detach().contiguous() for k, t in tang.items()}
+            _sync(ref)
+            _iface.jvp(model, **data, out=dict(x=tx, y=ty))
+            return tx, ty
         out = _iface.jvp(model, **{k: t.detach().cpu().contiguous().numpy() for k, t in tang.items()})
-        return torch.from_numpy(out["x"]).to(ref.device), torch.from_numpy(out["y"]).to(ref.device)
+        return torch.from_numpy(out["x"]), torch.from_numpy(out["y"])
 
     @staticmethod
     def backward(ctx, gx, gy):
@@ -270,14 +303,24 @@ class QPFunction(torch.autograd.Function):
             return (None,) * 6
         ref = gx if gx is not None else gy
         n, m = _iface.dimensions(model)
-        out = _iface.adjoint(model, dx=None if gx is None else gx.detach().cpu().numpy(),
-                             dy=None if gy is None or m == 0 else gy.detach().cpu().numpy(), want=want)
-        return (None,) + tuple(torch.from_numpy(out[k]).to(ref.device) if need[k] else None for k in NAMES)
+        if m == 0:
+            gy = None
+        if gx is None and gy is None:  # (m = 0 and only gy came: nothing reaches the data)
+            return (None,) * 6
+        if _route("QPFunction.backward", [g for g in (gx, gy) if g is not None]):
+            gx, gy = (None if g is None else g.detach().contiguous() for g in (gx, gy))
+            _sync(ref)
+            out = _iface.adjoint(model, dx=gx, dy=gy, want=want)
+            return (None,) + tuple(out[k] if need[k] else None for k in NAMES)
+        out = _iface.adjoint(model, dx=None if gx is None else gx.detach().numpy(), dy=None if gy is None else gy.detach().numpy(), want=want)
+        return (None,) + tuple(torch.from_numpy(out[k]) if need[k] else None for k in NAMES)
 
 
 class QPLayer(torch.nn.Module):
     """`layer(q=None, l=None, u=None, Px=None, Ax=None) -> (x, y)` on the single model `model` (set up, direct back-end, not
-    compact); `layer.info` is the `Info` of the last forward.  Px / Ax: full value arrays in the nnz order of `update`."""
+    compact); `layer.info` is the `Info` of the last forward.  Px / Ax: full value arrays in the nnz order of `update`.
+    Tensors on the model's device stay there (device-pointer forms, no host hop; x, y and the gradients come back as CUDA
+    tensors); CPU tensors go the host way and give CPU tensors; both at once is a ValueError."""
 
     def __init__(self, model):
         super().__init__()

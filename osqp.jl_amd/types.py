@@ -189,6 +189,14 @@ EXT_SYMBOLS = {
     "osqp_amd_adjoint": (c_int, [Workspace_p, c_int] + [c_float_p] * 8),
     # forward sensitivities on the same kept factor: host arrays tq, tl, tu, tPx, tAx in; tx, ty, act out (None = NULL)
     "osqp_amd_jvp": (c_int, [Workspace_p, c_int] + [c_float_p] * 8),
+    # the device-pointer forms of a single model's life cycle: every array argument is a device address (None = NULL)
+    "osqp_amd_update_vectors_dev": (c_int, [Workspace_p] + [C.c_void_p] * 3),
+    "osqp_amd_update_values_dev": (c_int, [Workspace_p] + [C.c_void_p] * 2),
+    "osqp_amd_warm_start_dev": (c_int, [Workspace_p] + [C.c_void_p] * 2),
+    "osqp_amd_solution_dev": (c_int, [Workspace_p] + [C.c_void_p] * 2),
+    "osqp_amd_adjoint_dev": (c_int, [Workspace_p, c_int] + [C.c_void_p] * 8),
+    "osqp_amd_jvp_dev": (c_int, [Workspace_p, c_int] + [C.c_void_p] * 8),
+    "osqp_amd_device_form_calls": (c_int, [Workspace_p, c_float_p, c_int]),
     "osqp_amd_adjoint_release": (c_int, [Workspace_p]),
     "osqp_amd_adjoint_stats": (c_int, [Workspace_p, c_float_p, c_int]),
     "osqp_amd_batch_solve": (
