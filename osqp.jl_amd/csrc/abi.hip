@@ -151,6 +151,67 @@ void require_device() {
     throw Error(6, "libosqp_amd: no HIP device available (this library has no CPU fallback)");
 }
 
+// f(engine) on the workspace's device, behind `guarded`; no workspace: 7 (with a message where the symbol `who` gives its name)
+template <typename F>
+c_int on_workspace(OSQPWorkspace *w, const char *who, F &&f) {
+  if (!w) {
+    if (who) set_last_error(std::string(who) + ": no workspace");
+    return 7;
+  }
+  OQ_ON_DEVICE(w);
+  return guarded([&]() { return f(*E(w)); });
+}
+
+// a call that moves the model on (new data, a new iterate): the solution stops being current, the kept factor goes, then the body
+template <typename F>
+c_int moving_on(OSQPWorkspace *w, F &&body) {
+  return on_workspace(w, nullptr, [&](Engine &e) { adjoint_moved_on(w, true); return body(e); });
+}
+
+// ---- device-pointer forms of a single model's life cycle (Engine::update_vectors_dev ..., DESIGN.md section 16) ----
+void dev_form_needs_whole_model(const Engine &e, const char *who) {
+  if (e.comm)
+    throw Error(6, std::string(who) + ": not available on a row-sharded workspace (a rank holds a row block; the device forms take whole arrays on one device)");
+}
+// the device form of a call that moves the model on; nothing_given (every array NULL): 0 and the model stays where it is.
+// call: its place in Engine::dev_calls, counted when the body returns 0
+template <typename F>
+c_int dev_moving_on(OSQPWorkspace *w, const char *who, int call, bool nothing_given, F &&body) {
+  return on_workspace(w, who, [&](Engine &e) {
+    dev_form_needs_whole_model(e, who);
+    if (nothing_given) return 0;
+    adjoint_moved_on(w, true);
+    const int rc = body(e);
+    if (rc == 0) e.dev_calls[call]++;
+    return rc;
+  });
+}
+
+void needs_current_solution(const Engine &e, const char *who) {
+  if (!e.solution_current)
+    throw Error(1, std::string(who) + ": the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
+}
+
+// osqp_amd_adjoint, _jvp and their _dev forms: the checks of the arguments (given: an input array is there, wanted: a
+// derivative is asked for, act: the active set is) and of the state of the workspace, then run(engine)
+template <typename F>
+c_int derivative_call(OSQPWorkspace *w, const char *who, bool dev, bool jvp, c_int count, bool given, bool wanted, bool act, F &&run) {
+  return on_workspace(w, who, [&](Engine &e) {
+    const std::string name = std::string(who) + ": ", cnt = jvp ? "ndir" : "ncot";
+    if (count < 1) throw Error(1, name + cnt + " must be at least 1");
+    if (count > 2147483647LL) throw Error(1, name + cnt + " out of range");
+    if (wanted && !given)
+      throw Error(1, name + (jvp ? "a sensitivity is wanted but tq, tl, tu, tPx and tAx are all NULL" : "a gradient is wanted but dx and dy are both NULL"));
+    if (!wanted && !act) throw Error(1, name + "no output is wanted");
+    needs_current_solution(e, who);
+    if (w->info->status_val != OSQP_SOLVED)
+      throw Error(1, name + "the last osqp_solve did not end with status Solved (" + w->info->status + "): there is no solution to differentiate");
+    const int rc = run(e);
+    if (dev && rc == 0) e.dev_calls[jvp ? 5 : 4]++;
+    return rc;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -537,13 +598,10 @@ c_int osqp_amd_setup_generated_sharded(OSQPWorkspace **workp, c_int kind, c_int 
 }
 
 c_int osqp_solve(OSQPWorkspace *w) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    adjoint_moved_on(w, true);
-    const int rc = E(w)->solve();
-    E(w)->solves_run++;
-    E(w)->solution_current = rc == 0;
+  return moving_on(w, [&](Engine &e) {
+    const int rc = e.solve();
+    e.solves_run++;
+    e.solution_current = rc == 0;
     return rc;
   });
 }
@@ -556,40 +614,26 @@ c_int osqp_cleanup(OSQPWorkspace *w) {
 }
 
 c_int osqp_update_lin_cost(OSQPWorkspace *w, const c_float *q_new) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_lin_cost(q_new); });
+  return moving_on(w, [&](Engine &e) { return e.update_lin_cost(q_new); });
 }
 c_int osqp_update_bounds(OSQPWorkspace *w, const c_float *l_new, const c_float *u_new) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_bounds(l_new, u_new); });
+  return moving_on(w, [&](Engine &e) { return e.update_bounds(l_new, u_new); });
 }
 c_int osqp_update_lower_bound(OSQPWorkspace *w, const c_float *l_new) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_bounds(l_new, nullptr); });
+  return moving_on(w, [&](Engine &e) { return e.update_bounds(l_new, nullptr); });
 }
 c_int osqp_update_upper_bound(OSQPWorkspace *w, const c_float *u_new) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_bounds(nullptr, u_new); });
+  return moving_on(w, [&](Engine &e) { return e.update_bounds(nullptr, u_new); });
 }
 c_int osqp_update_P(OSQPWorkspace *w, const c_float *Px_new, const c_int *Px_new_idx, c_int P_new_n) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_PA(Px_new, Px_new_idx, P_new_n, nullptr, nullptr, 0, true, false); });
+  return moving_on(w, [&](Engine &e) { return e.update_PA(Px_new, Px_new_idx, P_new_n, nullptr, nullptr, 0, true, false); });
 }
 c_int osqp_update_A(OSQPWorkspace *w, const c_float *Ax_new, const c_int *Ax_new_idx, c_int A_new_n) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_PA(nullptr, nullptr, 0, Ax_new, Ax_new_idx, A_new_n, false, true); });
+  return moving_on(w, [&](Engine &e) { return e.update_PA(nullptr, nullptr, 0, Ax_new, Ax_new_idx, A_new_n, false, true); });
 }
 c_int osqp_update_P_A(OSQPWorkspace *w, const c_float *Px_new, const c_int *Px_new_idx, c_int P_new_n, const c_float *Ax_new,
                       const c_int *Ax_new_idx, c_int A_new_n) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->update_PA(Px_new, Px_new_idx, P_new_n, Ax_new, Ax_new_idx, A_new_n, true, true); });
+  return moving_on(w, [&](Engine &e) { return e.update_PA(Px_new, Px_new_idx, P_new_n, Ax_new, Ax_new_idx, A_new_n, true, true); });
 }
 
 c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
@@ -649,19 +693,13 @@ c_int osqp_update_polish(OSQPWorkspace *w, c_int v) {
 }
 
 c_int osqp_warm_start(OSQPWorkspace *w, const c_float *x, const c_float *y) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->warm_start(x, y); });
+  return moving_on(w, [&](Engine &e) { return e.warm_start(x, y); });
 }
 c_int osqp_warm_start_x(OSQPWorkspace *w, const c_float *x) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->warm_start(x, nullptr); });
+  return moving_on(w, [&](Engine &e) { return e.warm_start(x, nullptr); });
 }
 c_int osqp_warm_start_y(OSQPWorkspace *w, const c_float *y) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->warm_start(nullptr, y); });
+  return moving_on(w, [&](Engine &e) { return e.warm_start(nullptr, y); });
 }
 
 // ---------------------------------------------------------------- extensions
@@ -742,15 +780,11 @@ c_float osqp_amd_time_kernel(OSQPWorkspace *w, c_int which, c_int reps) {
 }
 
 c_int osqp_amd_iterate(OSQPWorkspace *w, c_int iters) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { adjoint_moved_on(w, true); return E(w)->iterate(iters); });
+  return moving_on(w, [&](Engine &e) { return e.iterate(iters); });
 }
 
 c_int osqp_amd_get_iterate(OSQPWorkspace *w, c_float *x_out, c_float *y_out) {
-  if (!w) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { E(w)->get_iterate(x_out, y_out); return 0; });
+  return on_workspace(w, nullptr, [&](Engine &e) { e.get_iterate(x_out, y_out); return 0; });
 }
 
 c_int osqp_amd_apply(OSQPWorkspace *w, c_int op, const c_float *in, c_float *out) {
@@ -799,156 +833,56 @@ c_int osqp_amd_spmv_layout(const OSQPWorkspace *w, c_int which, c_float *out, c_
   return k;
 }
 
-// ---- adjoint derivatives of the solution of a single model (csrc/direct_adjoint.hpp) ----
+// ---- adjoint derivatives of the solution of a single model (csrc/direct_adjoint.hpp) and forward sensitivities on the same
+// kept factor (csrc/direct_jvp.hpp); the _dev forms take device pointers ----
+static c_int adjoint_call(OSQPWorkspace *w, const char *who, bool dev, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq,
+                          c_float *dl, c_float *du, c_float *dPx, c_float *dAx, c_float *act) {
+  return derivative_call(w, who, dev, false, ncot, dx || dy, dq || dl || du || dPx || dAx, act != nullptr,
+                         [&](Engine &e) { return model_adjoint_run(e, who, dev, (int)ncot, dx, dy, dq, dl, du, dPx, dAx, act); });
+}
+static c_int jvp_call(OSQPWorkspace *w, const char *who, bool dev, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu,
+                      const c_float *tPx, const c_float *tAx, c_float *tx, c_float *ty, c_float *act) {
+  return derivative_call(w, who, dev, true, ndir, tq || tl || tu || tPx || tAx, tx || ty, act != nullptr,
+                         [&](Engine &e) { return model_jvp_run(e, who, dev, (int)ndir, tq, tl, tu, tPx, tAx, tx, ty, act); });
+}
 c_int osqp_amd_adjoint(OSQPWorkspace *w, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
                        c_float *dPx, c_float *dAx, c_float *act) {
-  if (!w) { set_last_error("osqp_amd_adjoint: no workspace"); return 7; }
-  if (ncot < 1) { set_last_error("osqp_amd_adjoint: ncot must be at least 1"); return 1; }
-  if (ncot > 2147483647LL) { set_last_error("osqp_amd_adjoint: ncot out of range"); return 1; }
-  if ((dq || dl || du || dPx || dAx) && !dx && !dy) {
-    set_last_error("osqp_amd_adjoint: a gradient is wanted but dx and dy are both NULL");
-    return 1;
-  }
-  if (!dq && !dl && !du && !dPx && !dAx && !act) { set_last_error("osqp_amd_adjoint: no output is wanted"); return 1; }
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    if (!e.solution_current)
-      throw Error(1, "osqp_amd_adjoint: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
-    if (w->info->status_val != OSQP_SOLVED)
-      throw Error(1, std::string("osqp_amd_adjoint: the last osqp_solve did not end with status Solved (") + w->info->status +
-                         "): there is no solution to differentiate");
-    return model_adjoint_run(e, (int)ncot, dx, dy, dq, dl, du, dPx, dAx, act);
-  });
+  return adjoint_call(w, "osqp_amd_adjoint", false, ncot, dx, dy, dq, dl, du, dPx, dAx, act);
 }
-// ---- forward sensitivities on the same kept factor (csrc/direct_jvp.hpp) ----
+c_int osqp_amd_adjoint_dev(OSQPWorkspace *w, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
+                           c_float *dPx, c_float *dAx, c_float *act) {
+  return adjoint_call(w, "osqp_amd_adjoint_dev", true, ncot, dx, dy, dq, dl, du, dPx, dAx, act);
+}
 c_int osqp_amd_jvp(OSQPWorkspace *w, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,
                    const c_float *tAx, c_float *tx, c_float *ty, c_float *act) {
-  if (!w) { set_last_error("osqp_amd_jvp: no workspace"); return 7; }
-  if (ndir < 1) { set_last_error("osqp_amd_jvp: ndir must be at least 1"); return 1; }
-  if (ndir > 2147483647LL) { set_last_error("osqp_amd_jvp: ndir out of range"); return 1; }
-  if ((tx || ty) && !tq && !tl && !tu && !tPx && !tAx) {
-    set_last_error("osqp_amd_jvp: a sensitivity is wanted but tq, tl, tu, tPx and tAx are all NULL");
-    return 1;
-  }
-  if (!tx && !ty && !act) { set_last_error("osqp_amd_jvp: no output is wanted"); return 1; }
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    if (!e.solution_current)
-      throw Error(1, "osqp_amd_jvp: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
-    if (w->info->status_val != OSQP_SOLVED)
-      throw Error(1, std::string("osqp_amd_jvp: the last osqp_solve did not end with status Solved (") + w->info->status +
-                         "): there is no solution to differentiate");
-    return model_jvp_run(e, (int)ndir, tq, tl, tu, tPx, tAx, tx, ty, act);
-  });
+  return jvp_call(w, "osqp_amd_jvp", false, ndir, tq, tl, tu, tPx, tAx, tx, ty, act);
 }
-// ---- device-pointer forms of a single model's life cycle (Engine::update_vectors_dev ..., DESIGN.md section 16) ----
-static bool dev_form_refused(OSQPWorkspace *w, const char *who) {
-  if (!w) { set_last_error(std::string(who) + ": no workspace"); return true; }
-  return false;
-}
-static void dev_form_needs_whole_model(const Engine &e, const char *who) {
-  if (e.comm)
-    throw Error(6, std::string(who) + ": not available on a row-sharded workspace (a rank holds a row block; the device forms take whole arrays on one device)");
+c_int osqp_amd_jvp_dev(OSQPWorkspace *w, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,
+                       const c_float *tAx, c_float *tx, c_float *ty, c_float *act) {
+  return jvp_call(w, "osqp_amd_jvp_dev", true, ndir, tq, tl, tu, tPx, tAx, tx, ty, act);
 }
 c_int osqp_amd_update_vectors_dev(OSQPWorkspace *w, const c_float *q, const c_float *l, const c_float *u) {
-  if (dev_form_refused(w, "osqp_amd_update_vectors_dev")) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    dev_form_needs_whole_model(e, "osqp_amd_update_vectors_dev");
-    if (!q && !l && !u) return 0;
-    adjoint_moved_on(w, true);
+  const char *who = "osqp_amd_update_vectors_dev";
+  return dev_moving_on(w, who, 0, !q && !l && !u, [&](Engine &e) {
     const int rc = e.update_vectors_dev(q, l, u);
-    if (rc == 0) e.dev_calls[0]++;
-    else if (rc == 1) set_last_error("osqp_amd_update_vectors_dev: a lower bound is greater than its upper bound; nothing was changed");
+    if (rc == 1) set_last_error(std::string(who) + ": a lower bound is greater than its upper bound; nothing was changed");
     return rc;
   });
 }
 c_int osqp_amd_update_values_dev(OSQPWorkspace *w, const c_float *Px, const c_float *Ax) {
-  if (dev_form_refused(w, "osqp_amd_update_values_dev")) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    dev_form_needs_whole_model(e, "osqp_amd_update_values_dev");
-    if (!Px && !Ax) return 0;
-    adjoint_moved_on(w, true);
-    const int rc = e.update_values_dev(Px, Ax);
-    if (rc == 0) e.dev_calls[1]++;
-    return rc;
-  });
+  return dev_moving_on(w, "osqp_amd_update_values_dev", 1, !Px && !Ax, [&](Engine &e) { return e.update_values_dev(Px, Ax); });
 }
 c_int osqp_amd_warm_start_dev(OSQPWorkspace *w, const c_float *x, const c_float *y) {
-  if (dev_form_refused(w, "osqp_amd_warm_start_dev")) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    dev_form_needs_whole_model(e, "osqp_amd_warm_start_dev");
-    if (!x && !y) return 0;
-    adjoint_moved_on(w, true);
-    const int rc = e.warm_start(x, y, true);
-    if (rc == 0) e.dev_calls[2]++;
-    return rc;
-  });
+  return dev_moving_on(w, "osqp_amd_warm_start_dev", 2, !x && !y, [&](Engine &e) { return e.warm_start(x, y, true); });
 }
 c_int osqp_amd_solution_dev(OSQPWorkspace *w, c_float *x_out, c_float *y_out) {
-  if (dev_form_refused(w, "osqp_amd_solution_dev")) return 7;
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    dev_form_needs_whole_model(e, "osqp_amd_solution_dev");
-    if (e.solves_run == 0) throw Error(1, "osqp_amd_solution_dev: no osqp_solve has run on this workspace yet");
-    if (!e.solution_current)
-      throw Error(1, "osqp_amd_solution_dev: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
+  const char *who = "osqp_amd_solution_dev";
+  return on_workspace(w, who, [&](Engine &e) {
+    dev_form_needs_whole_model(e, who);
+    if (e.solves_run == 0) throw Error(1, std::string(who) + ": no osqp_solve has run on this workspace yet");
+    needs_current_solution(e, who);
     const int rc = e.solution_dev(x_out, y_out);
     if (rc == 0) e.dev_calls[3]++;
-    return rc;
-  });
-}
-c_int osqp_amd_adjoint_dev(OSQPWorkspace *w, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
-                           c_float *dPx, c_float *dAx, c_float *act) {
-  if (dev_form_refused(w, "osqp_amd_adjoint_dev")) return 7;
-  if (ncot < 1) { set_last_error("osqp_amd_adjoint_dev: ncot must be at least 1"); return 1; }
-  if (ncot > 2147483647LL) { set_last_error("osqp_amd_adjoint_dev: ncot out of range"); return 1; }
-  if ((dq || dl || du || dPx || dAx) && !dx && !dy) {
-    set_last_error("osqp_amd_adjoint_dev: a gradient is wanted but dx and dy are both NULL");
-    return 1;
-  }
-  if (!dq && !dl && !du && !dPx && !dAx && !act) { set_last_error("osqp_amd_adjoint_dev: no output is wanted"); return 1; }
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    if (!e.solution_current)
-      throw Error(1, "osqp_amd_adjoint_dev: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
-    if (w->info->status_val != OSQP_SOLVED)
-      throw Error(1, std::string("osqp_amd_adjoint_dev: the last osqp_solve did not end with status Solved (") + w->info->status +
-                         "): there is no solution to differentiate");
-    const int rc = model_adjoint_run(e, (int)ncot, dx, dy, dq, dl, du, dPx, dAx, act, true);
-    if (rc == 0) e.dev_calls[4]++;
-    return rc;
-  });
-}
-c_int osqp_amd_jvp_dev(OSQPWorkspace *w, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu, const c_float *tPx,
-                       const c_float *tAx, c_float *tx, c_float *ty, c_float *act) {
-  if (dev_form_refused(w, "osqp_amd_jvp_dev")) return 7;
-  if (ndir < 1) { set_last_error("osqp_amd_jvp_dev: ndir must be at least 1"); return 1; }
-  if (ndir > 2147483647LL) { set_last_error("osqp_amd_jvp_dev: ndir out of range"); return 1; }
-  if ((tx || ty) && !tq && !tl && !tu && !tPx && !tAx) {
-    set_last_error("osqp_amd_jvp_dev: a sensitivity is wanted but tq, tl, tu, tPx and tAx are all NULL");
-    return 1;
-  }
-  if (!tx && !ty && !act) { set_last_error("osqp_amd_jvp_dev: no output is wanted"); return 1; }
-  OQ_ON_DEVICE(w);
-  return guarded([&]() {
-    Engine &e = *E(w);
-    if (!e.solution_current)
-      throw Error(1, "osqp_amd_jvp_dev: the workspace holds no current solution: call osqp_solve first (after the last osqp_update_* / osqp_warm_start*)");
-    if (w->info->status_val != OSQP_SOLVED)
-      throw Error(1, std::string("osqp_amd_jvp_dev: the last osqp_solve did not end with status Solved (") + w->info->status +
-                         "): there is no solution to differentiate");
-    const int rc = model_jvp_run(e, (int)ndir, tq, tl, tu, tPx, tAx, tx, ty, act, true);
-    if (rc == 0) e.dev_calls[5]++;
     return rc;
   });
 }
@@ -959,9 +893,7 @@ c_int osqp_amd_device_form_calls(const OSQPWorkspace *w, c_float *out, c_int cou
   return k;
 }
 c_int osqp_amd_adjoint_release(OSQPWorkspace *w) {
-  if (!w) { set_last_error("osqp_amd_adjoint_release: no workspace"); return 7; }
-  OQ_ON_DEVICE(w);
-  return guarded([&]() { model_adjoint_release(*E(w)); return 0; });
+  return on_workspace(w, "osqp_amd_adjoint_release", [&](Engine &e) { model_adjoint_release(e); return 0; });
 }
 c_int osqp_amd_adjoint_stats(const OSQPWorkspace *w, c_float *out, c_int count) {
   if (!w || !out) return 0;

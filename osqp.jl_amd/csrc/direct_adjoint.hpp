@@ -120,7 +120,7 @@ namespace {
 
 // classify the rows on the scaled (z, y, l, u) of the solution -- polish's rule, and a row with l == u is always active and
 // counts as lower --, analyse and factorise the reduced matrix, set up what every later call on this solution reuses
-void adjoint_build(Engine &e, ModelAdjoint &A, const char *who = "osqp_amd_adjoint", const char *form = "adjoint") {
+void adjoint_build(Engine &e, ModelAdjoint &A, const char *who, const char *form) {
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
   const size_t bytes0 = g_device_bytes;
@@ -164,23 +164,27 @@ void adjoint_build(Engine &e, ModelAdjoint &A, const char *who = "osqp_amd_adjoi
   A.builds++;
 }
 
-// one cotangent: right-hand side, the regularised solve, polish_refine_iter steps against the unregularised matrix (the loop
-// of polish_run on scratch of its own: the engine's Ax / Px / Aty keep what the last residual evaluation left).
-// polish_refine_iter = 0 asks for the regularised answer itself.  The factorisation does not pivot and eliminates rows of
-// -delta before their variables wherever the fill-reducing order says so: multipliers of 1 / delta, a solve accurate to
-// ~1e-8 where the matrix has a condition of 1e3 (control(): 1.0e-8 against a dense solve; the steps against the
+// the solve on the kept factor from K.rhs_red to K.sol: the regularised solve, polish_refine_iter steps against the
+// unregularised matrix (the loop of polish_run on scratch of its own: the engine's Ax / Px / Aty keep what the last residual
+// evaluation left).  polish_refine_iter = 0 asks for the regularised answer itself.  The factorisation does not pivot and
+// eliminates rows of -delta before their variables wherever the fill-reducing order says so: multipliers of 1 / delta, a solve
+// accurate to ~1e-8 where the matrix has a condition of 1e3 (control(): 1.0e-8 against a dense solve; the steps against the
 // unregularised matrix remove that as well, which is why polish never sees it).  So with 0 steps ONE step runs against
 // the REGULARISED matrix: the answer is the regularised one, to working accuracy.
-void adjoint_pass(Engine &e, ModelAdjoint &A, const double *gx, const double *gy) {
+void kept_solve(Engine &e, ModelAdjoint &A) {
   AdjointKept &K = *A.kept;
-  LdlFactor &F = *K.F;
-  hipStream_t s = e.stream;
-  const int n = e.n, mr = K.mr, nr = n + mr;
-  OQ_LAUNCH(k_adj_rhs, dim3(blocks_for(nr)), dim3(kBlock), 0, s, n, mr, e.c, e.D.get(), e.E.get(), K.act_rows.get(), gx, gy, K.rhs_red.get());
   const bool regularised = e.st.polish_refine_iter == 0;
-  A.solves += kkt_solve_refine(e, F, K.act_rows.get(), mr, K.rhs_red.get(), K.sol.get(),
+  A.solves += kkt_solve_refine(e, *K.F, K.act_rows.get(), K.mr, K.rhs_red.get(), K.sol.get(),
                                RefineScratch{K.rhs.get(), K.yfull.get(), K.Axv.get(), K.px.get(), K.ared_x.get()},
                                regularised ? 1 : (int)e.st.polish_refine_iter, regularised);
+}
+
+// one cotangent: right-hand side and solve
+void adjoint_pass(Engine &e, ModelAdjoint &A, const double *gx, const double *gy) {
+  AdjointKept &K = *A.kept;
+  const int n = e.n, mr = K.mr;
+  OQ_LAUNCH(k_adj_rhs, dim3(blocks_for(n + mr)), dim3(kBlock), 0, e.stream, n, mr, e.c, e.D.get(), e.E.get(), K.act_rows.get(), gx, gy, K.rhs_red.get());
+  kept_solve(e, A);
 }
 
 // no CSR arrays and no reduced KKT matrix: what polish_run hands to its iterative form
@@ -192,18 +196,80 @@ void adjoint_needs_csr(const Engine &e, const char *who, const char *form) {
                    "an iterative " + form + " is not built; OSQP_AMD_COMPACT_NNZ=-1 at setup keeps the arrays)");
 }
 
+// ---- the driver model_adjoint_run and model_jvp_run (direct_jvp.hpp) share ----
+// the workspace's derivative state with what the current solution keeps present (built by the first call after a solve);
+// who: the exported symbol that was called, form: what its refusals say is not built
+ModelAdjoint &kept_state(Engine &e, const char *who, const char *form) {
+  adjoint_needs_csr(e, who, form);
+  if (!e.adj) e.adj.reset(new ModelAdjoint());
+  if (!e.adj->kept) adjoint_build(e, *e.adj, who, form);
+  return *e.adj;
+}
+
+// The operands of one call as device arrays.  Device form: the caller's arrays themselves.  Host form: in() gives an uploaded
+// copy, out() a fresh device array that deliver() downloads into the caller's; a null operand stays null and allocates nothing.
+// Every refusal (the checks of the C boundary, kept_state) lies before the first kernel, and deliver() comes after the passes:
+// a call that fails has written nothing (device form: the re-run of with_tree_retry overwrites what a faulted pass wrote; only a
+// second tree fault, an internal error, leaves partial output behind).
+struct Staged {
+  Engine &e;
+  bool dev;
+  struct Out { double *host; size_t at, count; };
+  std::vector<DevBuf<double>> held;
+  std::vector<Out> outs;
+  Staged(Engine &e_, bool dev_) : e(e_), dev(dev_) {}
+  ~Staged() { while (!held.empty()) held.pop_back(); }  // released last-allocated first, as a function's local buffers are
+  const double *in(const double *p, size_t count) {
+    if (dev || !p) return p;
+    held.emplace_back(count);
+    held.back().upload(p, count, e.stream);
+    return held.back().get();
+  }
+  double *out(double *p, size_t count) {
+    if (dev || !p) return p;
+    held.emplace_back(count);
+    outs.push_back({p, held.size() - 1, count});
+    return held.back().get();
+  }
+  void deliver() {
+    if (dev) return;
+    for (const Out &o : outs) held[o.at].download(o.host, o.count, e.stream);
+    e.sync();
+  }
+};
+
+// passes() with the one re-run a supernodal tree fault is answered with
+template <typename F>
+void with_tree_retry(Engine &e, ModelAdjoint &A, F &&passes) {
+  AdjointKept &K = *A.kept;
+  const long long solves0 = A.solves;
+  passes();
+  e.sync();
+  if (K.F->faulted()) {  // a wait inside the one-launch supernodal solve timed out: one launch per level, and once more
+    *K.F->sn_fault_host = 0;
+    K.F->sn_tree = false;
+    A.solves = solves0;
+    passes();
+    e.sync();
+    if (K.F->faulted()) throw TreeFault();
+  }
+}
+
+// the `act` output: [m] -1 lower, 0 inactive, 1 upper
+void write_act(Engine &e, const AdjointKept &K, double *act, bool dev) {
+  if (!act) return;
+  if (dev) { e.copy_dev(act, K.side.get(), (size_t)e.m); e.sync(); }
+  else std::copy(K.h_side.begin(), K.h_side.end(), act);
+}
+
 }  // namespace
 
-int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
-                      double *dAx, double *act, bool dev) {
-  adjoint_needs_csr(e, "osqp_amd_adjoint", "adjoint");
+int model_adjoint_run(Engine &e, const char *who, bool dev, int ncot, const double *dx, const double *dy, double *dq, double *dl,
+                      double *du, double *dPx, double *dAx, double *act) {
+  ModelAdjoint &A = kept_state(e, who, "adjoint");
+  AdjointKept &K = *A.kept;
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
-  if (!e.adj) e.adj.reset(new ModelAdjoint());
-  ModelAdjoint &A = *e.adj;
-  const bool grads = dq || dl || du || dPx || dAx;
-  if (!A.kept) adjoint_build(e, A);
-  AdjointKept &K = *A.kept;
   if ((dPx || dAx) && !A.patterns) {
     A.Pcol.alloc(std::max<int64_t>(1, e.nnzPtriu)); A.Acol.alloc(std::max<int64_t>(1, e.nnzA));
     expand_colptr(n, e.Pp_keep.get(), e.nnzPtriu, A.Pcol.get(), s);
@@ -212,65 +278,28 @@ int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, d
     e.sync();
     A.patterns = true;
   }
-  if (grads) {
-    const size_t nc = (size_t)ncot;
-    // host form: staged copies of the cotangents and of the outputs; device form: the caller's arrays themselves (every
-    // refusal -- the checks of the C boundary, adjoint_needs_csr, adjoint_build -- lies before the first kernel below)
-    DevBuf<double> gx, gy, oq_, ol, ou, oP, oA;
-    const double *pgx = nullptr, *pgy = nullptr;
-    double *pq = dq, *pl = dl, *pu = du, *pP = dPx, *pA = dAx;
-    if (dev) {
-      pgx = dx;
-      pgy = m > 0 ? dy : nullptr;
-    } else {
-      if (dx) { gx.alloc(nc * n); gx.upload(dx, nc * n, s); pgx = gx.get(); }
-      if (dy && m > 0) { gy.alloc(nc * m); gy.upload(dy, nc * m, s); pgy = gy.get(); }
-      if (dq) { oq_.alloc(nc * n); pq = oq_.get(); }
-      if (dl) { ol.alloc(nc * m); pl = ol.get(); }
-      if (du) { ou.alloc(nc * m); pu = ou.get(); }
-      if (dPx) { oP.alloc(nc * (size_t)e.nnzPtriu); pP = oP.get(); }
-      if (dAx) { oA.alloc(nc * (size_t)e.nnzA); pA = oA.get(); }
-    }
+  if (dq || dl || du || dPx || dAx) {
+    const size_t nc = (size_t)ncot, nzP = (size_t)e.nnzPtriu, nzA = (size_t)e.nnzA;
+    Staged st(e, dev);
+    const double *gx = st.in(dx, nc * n), *gy = st.in(m > 0 ? dy : nullptr, nc * m);
+    double *oq_ = st.out(dq, nc * n), *ol = st.out(dl, nc * m), *ou = st.out(du, nc * m), *oP = st.out(dPx, nc * nzP), *oA = st.out(dAx, nc * nzA);
     const int64_t *to_sorted = dAx ? e.device_A_to_sorted() : nullptr;
-    const long long solves0 = A.solves;
-    auto passes = [&]() {
+    with_tree_retry(e, A, [&]() {
       for (size_t c = 0; c < nc; c++) {
-        adjoint_pass(e, A, pgx ? pgx + c * n : nullptr, pgy ? pgy + c * m : nullptr);
+        adjoint_pass(e, A, gx ? gx + c * n : nullptr, gy ? gy + c * m : nullptr);
         OQ_LAUNCH(k_adj_vectors, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), K.slot.get(), K.side.get(),
-                  K.sol.get(), K.rx.get(), K.ry.get(), dq ? pq + c * n : nullptr, dl ? pl + c * m : nullptr,
-                  du ? pu + c * m : nullptr);
+                  K.sol.get(), K.rx.get(), K.ry.get(), oq_ ? oq_ + c * n : nullptr, ol ? ol + c * m : nullptr, ou ? ou + c * m : nullptr);
         if (dPx && e.nnzPtriu > 0)
           OQ_LAUNCH(k_adj_dP, dim3(blocks_for(e.nnzPtriu)), dim3(kBlock), 0, s, e.nnzPtriu, e.Pi_keep.get(), A.Pcol.get(), K.rx.get(), K.xc.get(),
-                    pP + c * (size_t)e.nnzPtriu);
+                    oP + c * nzP);
         if (dAx && e.nnzA > 0)
           OQ_LAUNCH(k_adj_dA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, to_sorted,
-                    e.At.col.get(), A.Acol.get(), K.rx.get(), K.ry.get(), K.xc.get(), K.yc.get(), pA + c * (size_t)e.nnzA);
+                    e.At.col.get(), A.Acol.get(), K.rx.get(), K.ry.get(), K.xc.get(), K.yc.get(), oA + c * nzA);
       }
-      e.sync();
-    };
-    passes();
-    if (K.F->faulted()) {  // a wait inside the one-launch supernodal solve timed out: one launch per level, and once more
-      *K.F->sn_fault_host = 0;
-      K.F->sn_tree = false;
-      A.solves = solves0;
-      passes();
-      if (K.F->faulted()) throw TreeFault();
-    }
-    // outputs last: a call that fails has written nothing (device form: the re-run above overwrites what the faulted pass
-    // wrote; only a second tree fault, an internal error, leaves partial output behind)
-    if (!dev) {
-      if (dq) oq_.download(dq, nc * n, s);
-      if (dl) ol.download(dl, nc * m, s);
-      if (du) ou.download(du, nc * m, s);
-      if (dPx) oP.download(dPx, nc * (size_t)e.nnzPtriu, s);
-      if (dAx) oA.download(dAx, nc * (size_t)e.nnzA, s);
-      e.sync();
-    }
+    });
+    st.deliver();
   }
-  if (act) {
-    if (dev) { e.copy_dev(act, K.side.get(), (size_t)m); e.sync(); }
-    else std::copy(K.h_side.begin(), K.h_side.end(), act);
-  }
+  write_act(e, K, act, dev);
   return 0;
 }
 

@@ -80,13 +80,6 @@ __global__ __launch_bounds__(kBlock) void k_jvp_rhs_a(int n, int mr, const doubl
   }
 }
 
-// tAx of a caller whose columns came unsorted, into the order of the sorted copy: every entry has one target, no atomics
-__global__ __launch_bounds__(kBlock) void k_jvp_sort_tA(int64_t nnz, const int64_t *__restrict__ to_sorted, const double *__restrict__ in,
-                                                        double *__restrict__ out) {
-  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (k < nnz) out[to_sorted[k]] = in[k];
-}
-
 // tx = D r~ (threads [0, n)); ty_i = E[i] s[slot[i]] / c on the active rows, 0 elsewhere (threads [n, n + m)): a gather through
 // slot, one thread per output word.  tx, ty may be null (not wanted).
 __global__ __launch_bounds__(kBlock) void k_jvp_out(int n, int m, double c, const double *__restrict__ D, const double *__restrict__ E,
@@ -144,15 +137,12 @@ void jvp_rhs(Engine &e, ModelAdjoint &A, const double *tq, const double *tl, con
 
 }  // namespace
 
-int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const double *tu, const double *tPx, const double *tAx,
-                  double *tx, double *ty, double *act, bool dev) {
-  adjoint_needs_csr(e, "osqp_amd_jvp", "form");
+int model_jvp_run(Engine &e, const char *who, bool dev, int ndir, const double *tq, const double *tl, const double *tu,
+                  const double *tPx, const double *tAx, double *tx, double *ty, double *act) {
+  ModelAdjoint &A = kept_state(e, who, "form");
+  AdjointKept &K = *A.kept;
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
-  if (!e.adj) e.adj.reset(new ModelAdjoint());
-  ModelAdjoint &A = *e.adj;
-  if (!A.kept) adjoint_build(e, A, "osqp_amd_jvp", "form");
-  AdjointKept &K = *A.kept;
   // a tangent of an array without entries has nothing to say
   if (m == 0) { tl = tu = nullptr; }
   if (e.nnzPtriu == 0) tPx = nullptr;
@@ -169,61 +159,28 @@ int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const
   }
   if (tx || ty) {
     const size_t nd = (size_t)ndir, nzP = (size_t)e.nnzPtriu, nzA = (size_t)e.nnzA;
-    // host form: staged copies of the tangents and of the outputs; device form: the caller's arrays themselves (every
-    // refusal lies before the first kernel below)
-    DevBuf<double> dq, dl, du, dP, dA, dAs, ox, oy;
-    const double *pq = tq, *pl = tl, *pu = tu, *pP = tPx, *pA = tAx;
-    double *px = tx, *py = ty && m > 0 ? ty : nullptr;
-    if (!dev) {
-      if (tq) { dq.alloc(nd * n); dq.upload(tq, nd * n, s); pq = dq.get(); }
-      if (tl) { dl.alloc(nd * m); dl.upload(tl, nd * m, s); pl = dl.get(); }
-      if (tu) { du.alloc(nd * m); du.upload(tu, nd * m, s); pu = du.get(); }
-      if (tPx) { dP.alloc(nd * nzP); dP.upload(tPx, nd * nzP, s); pP = dP.get(); }
-      if (tAx) { dA.alloc(nd * nzA); dA.upload(tAx, nd * nzA, s); pA = dA.get(); }
-      if (tx) { ox.alloc(nd * n); px = ox.get(); }
-      if (py) { oy.alloc(nd * m); py = oy.get(); }
-    }
+    Staged st(e, dev);
+    const double *pq = st.in(tq, nd * n), *pl = st.in(tl, nd * m), *pu = st.in(tu, nd * m), *pP = st.in(tPx, nd * nzP), *pA = st.in(tAx, nd * nzA);
+    double *px = st.out(tx, nd * n), *py = st.out(m > 0 ? ty : nullptr, nd * m);
     const int64_t *to_sorted = tAx ? e.device_A_to_sorted() : nullptr;
-    const bool unsorted = to_sorted != nullptr;
-    if (unsorted) dAs.alloc(nzA);  // one direction's tAx in sorted order
-    const long long solves0 = A.solves;
-    const bool regularised = e.st.polish_refine_iter == 0;
-    auto passes = [&]() {
+    DevBuf<double> dAs;  // one direction's tAx in sorted order, for a caller whose columns came unsorted
+    if (to_sorted) dAs.alloc(nzA);
+    with_tree_retry(e, A, [&]() {
       for (size_t d = 0; d < nd; d++) {
-        const double *tA_d = tAx ? pA + d * nzA : nullptr;
-        if (unsorted) {
-          OQ_LAUNCH(k_jvp_sort_tA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, to_sorted, tA_d, dAs.get());
+        const double *tA_d = pA ? pA + d * nzA : nullptr;
+        if (to_sorted) {
+          permute_vals(e.nnzA, to_sorted, tA_d, dAs.get(), s);
           tA_d = dAs.get();
         }
-        jvp_rhs(e, A, tq ? pq + d * n : nullptr, tl ? pl + d * m : nullptr, tu ? pu + d * m : nullptr,
-                tPx ? pP + d * nzP : nullptr, tA_d);
-        A.solves += kkt_solve_refine(e, *K.F, K.act_rows.get(), K.mr, K.rhs_red.get(), K.sol.get(),
-                                     RefineScratch{K.rhs.get(), K.yfull.get(), K.Axv.get(), K.px.get(), K.ared_x.get()},
-                                     regularised ? 1 : (int)e.st.polish_refine_iter, regularised);
+        jvp_rhs(e, A, pq ? pq + d * n : nullptr, pl ? pl + d * m : nullptr, pu ? pu + d * m : nullptr, pP ? pP + d * nzP : nullptr, tA_d);
+        kept_solve(e, A);
         OQ_LAUNCH(k_jvp_out, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), K.slot.get(), K.sol.get(),
-                  tx ? px + d * n : nullptr, py ? py + d * m : nullptr);
+                  px ? px + d * n : nullptr, py ? py + d * m : nullptr);
       }
-      e.sync();
-    };
-    passes();
-    if (K.F->faulted()) {  // a wait inside the one-launch supernodal solve timed out: one launch per level, and once more
-      *K.F->sn_fault_host = 0;
-      K.F->sn_tree = false;
-      A.solves = solves0;
-      passes();
-      if (K.F->faulted()) throw TreeFault();
-    }
-    // outputs last: a call that fails has written nothing (device form: as in model_adjoint_run)
-    if (!dev) {
-      if (tx) ox.download(tx, nd * n, s);
-      if (oy.p) oy.download(ty, nd * m, s);
-      e.sync();
-    }
+    });
+    st.deliver();
   }
-  if (act) {
-    if (dev) { e.copy_dev(act, K.side.get(), (size_t)m); e.sync(); }
-    else std::copy(K.h_side.begin(), K.h_side.end(), act);
-  }
+  write_act(e, K, act, dev);
   return 0;
 }
 

@@ -1404,11 +1404,25 @@ int Engine::update_bounds(const double *l_new, const double *u_new) {
   if (comm) bad = agree_max(bad ? 1.0 : 0.0) > 0.0;
   if (bad) return 1;
   h_l.swap(nl); h_u.swap(nu);
-  if (l_new) { l.upload(h_l.data(), m, stream); sync(); if (st.scaling) vec_ew_prod(l.get(), l.get(), E.get(), m, stream); }
-  if (u_new) { u.upload(h_u.data(), m, stream); sync(); if (st.scaling) vec_ew_prod(u.get(), u.get(), E.get(), m, stream); }
-  if (l_raw.n) {  // the raw device copies exist (a device-form update has run): they follow
-    if (l_new) l_raw.upload(h_l.data(), m, stream);
-    if (u_new) u_raw.upload(h_u.data(), m, stream);
+  return store_bounds(l_new ? l_new + m0 : nullptr, u_new ? u_new + m0 : nullptr, false);
+}
+
+// the accepted bounds (this rank's rows) into l / u, scaled by E, inside an update that has begun; ends it.  Host form: the
+// host mirror holds them already; the raw device copies follow where they exist (a device-form update has run).  Device form:
+// the caller's arrays into the raw copies, clamped to +-OSQP_INFTY there (the wrappers of the host forms clamp on the host
+// before the call, a C caller's values are stored as they come), l / u from those, and the mirror is stale.
+int Engine::store_bounds(const double *l_src, const double *u_src, bool dev) {
+  auto side = [&](const double *src, DevBuf<double> &raw, DevBuf<double> &cur, double lo, double hi, bool &stale) {
+    if (!src) return;
+    if (dev) { copy_dev(raw.get(), src, m); vec_clamp(raw.get(), lo, hi, m, stream); stale = true; src = raw.get(); }
+    load(cur.get(), src, m, dev); sync();
+    if (st.scaling) vec_ew_prod(cur.get(), cur.get(), E.get(), m, stream);
+  };
+  side(l_src, l_raw, l, -OSQP_INFTY, HUGE_VAL, h_l_stale);
+  side(u_src, u_raw, u, -HUGE_VAL, OSQP_INFTY, h_u_stale);
+  if (!dev && l_raw.n) {
+    if (l_src) l_raw.upload(l_src, m, stream);
+    if (u_src) u_raw.upload(u_src, m, stream);
     sync();
   }
   reset_info(ws->info);
@@ -1477,26 +1491,19 @@ int Engine::update_PA(const double *Px_new, const c_int *Pidx, c_int Pn, const d
       throw Error(6, "osqp_update_P / osqp_update_A: this row-sharded workspace keeps no nnz-index maps (not set up by column ranges, OSQP_AMD_SHARD_UPDATES=0, or nnz >= 2^31)");
   }
   if (st.scaling) unscale_data();
-  auto scatter = [&](const double *vals, const c_int *idx, c_int k, double *t1, const int *map1, double *t2, const int *map2) {
+  // int maps: CSR positions (null: the identity, -1: no such copy); uint32_t maps: slots of the sliced-ELL copy (all ones: none)
+  auto scatter = [&]<typename M>(const double *vals, const c_int *idx, c_int k, double *t1, const M *map1, double *t2, decltype(map1) map2) {
     if (k <= 0) return;
     DevBuf<double> dv;
     DevBuf<long long> di;
     const double *src = vals;  // device form: the values are read where they lie
     if (!dev) { dv.alloc((size_t)k); dv.upload(vals, (size_t)k, stream); src = dv.get(); }
     if (idx) { di.alloc((size_t)k); di.upload((const long long *)idx, (size_t)k, stream); }
-    OQ_LAUNCH(k_scatter_vals, dim3(blocks_for(k)), dim3(kBlock), 0, stream, (int64_t)k, idx ? di.get() : (const long long *)nullptr,
-                       src, t1, map1, t2, map2);
-    sync();
-  };
-  auto scatter_slots = [&](const double *vals, const c_int *idx, c_int k, double *t1, const uint32_t *map1, double *t2, const uint32_t *map2) {
-    if (k <= 0) return;
-    DevBuf<double> dv;
-    DevBuf<long long> di;
-    const double *src = vals;
-    if (!dev) { dv.alloc((size_t)k); dv.upload(vals, (size_t)k, stream); src = dv.get(); }
-    if (idx) { di.alloc((size_t)k); di.upload((const long long *)idx, (size_t)k, stream); }
-    OQ_LAUNCH(k_scatter_vals_slot, dim3(blocks_for(k)), dim3(kBlock), 0, stream, (int64_t)k, idx ? di.get() : (const long long *)nullptr,
-              src, t1, map1, t2, map2);
+    const long long *didx = idx ? di.get() : nullptr;
+    if constexpr (std::is_same_v<M, uint32_t>)
+      OQ_LAUNCH(k_scatter_vals_slot, dim3(blocks_for(k)), dim3(kBlock), 0, stream, (int64_t)k, didx, src, t1, map1, t2, map2);
+    else
+      OQ_LAUNCH(k_scatter_vals, dim3(blocks_for(k)), dim3(kBlock), 0, stream, (int64_t)k, didx, src, t1, map1, t2, map2);
     sync();
   };
   // every copy through its own map: slots of the sliced-ELL copy where the CSR arrays are gone, CSR positions otherwise
@@ -1529,16 +1536,16 @@ int Engine::update_PA(const double *Px_new, const c_int *Pidx, c_int Pn, const d
     if (doA) replace(Ax_new, Aidx, kA, nnzA, {{&At, &At_org}, {&A, &A_org}});
   } else {
   if (doP) {
-    if (Pf.compact) scatter_slots(Px_new, Pidx, kP, Pf.panel.sval.get(), (const uint32_t *)P_k2lo.get(), Pf.panel.sval.get(), (const uint32_t *)P_k2up.get());
+    if (Pf.compact) scatter(Px_new, Pidx, kP, Pf.panel.sval.get(), (const uint32_t *)P_k2lo.get(), Pf.panel.sval.get(), (const uint32_t *)P_k2up.get());
     else scatter(Px_new, Pidx, kP, Pf.val.get(), P_k2lo.get(), Pf.val.get(), P_k2up.get());
   }
   if (doA) {
-    if (At.compact && A.compact) scatter_slots(Ax_new, Aidx, kA, At.panel.sval.get(), At_k2slot.get(), A.panel.sval.get(), (const uint32_t *)A_k2pos.get());
-    else if (!At.compact && !A.compact) scatter(Ax_new, Aidx, kA, At.val.get(), nullptr, A.val.get(), A_k2pos.get());
+    if (At.compact && A.compact) scatter(Ax_new, Aidx, kA, At.panel.sval.get(), At_k2slot.get(), A.panel.sval.get(), (const uint32_t *)A_k2pos.get());
+    else if (!At.compact && !A.compact) scatter(Ax_new, Aidx, kA, At.val.get(), (const int *)nullptr, A.val.get(), A_k2pos.get());
     else {
-      if (At.compact) scatter_slots(Ax_new, Aidx, kA, At.panel.sval.get(), At_k2slot.get(), At.panel.sval.get(), At_k2slot.get());
-      else scatter(Ax_new, Aidx, kA, At.val.get(), nullptr, nullptr, nullptr);
-      if (A.compact) scatter_slots(Ax_new, Aidx, kA, A.panel.sval.get(), (const uint32_t *)A_k2pos.get(), A.panel.sval.get(), (const uint32_t *)A_k2pos.get());
+      if (At.compact) scatter(Ax_new, Aidx, kA, At.panel.sval.get(), At_k2slot.get(), At.panel.sval.get(), At_k2slot.get());
+      else scatter(Ax_new, Aidx, kA, At.val.get(), (const int *)nullptr, nullptr, nullptr);
+      if (A.compact) scatter(Ax_new, Aidx, kA, A.panel.sval.get(), (const uint32_t *)A_k2pos.get(), A.panel.sval.get(), (const uint32_t *)A_k2pos.get());
       else scatter(Ax_new, Aidx, kA, A.val.get(), A_k2pos.get(), nullptr, nullptr);
     }
   }
@@ -1588,14 +1595,6 @@ __global__ __launch_bounds__(kBlock) void k_bounds_crossed(int m, const double *
   if (i < m && fmax(l[i], -OSQP_INFTY) > fmin(u[i], OSQP_INFTY)) *flag = 1;
 }
 
-// a full value array in the caller's nnz order into the order of the sorted copy the workspace holds: every entry has one
-// target (to_sorted is a permutation), no atomics
-__global__ __launch_bounds__(kBlock) void k_permute_vals(int64_t nnz, const int64_t *__restrict__ to_sorted, const double *__restrict__ in,
-                                                         double *__restrict__ out) {
-  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (k < nnz) out[to_sorted[k]] = in[k];
-}
-
 const int64_t *Engine::device_A_to_sorted() {
   if (A_to_sorted.empty()) return nullptr;
   if (!A_to_sorted_dev.n) {
@@ -1640,21 +1639,7 @@ int Engine::update_vectors_dev(const double *q_new, const double *l_new, const d
   if (q_new) update_lin_cost(q_new, true);
   if (!bounds) return 0;
   begin_update();  // update_bounds
-  if (l_new) {
-    // (the wrappers of the host forms clamp to +-OSQP_INFTY on the host before the call; here it is part of the call)
-    copy_dev(l_raw.get(), l_new, m); vec_clamp(l_raw.get(), -OSQP_INFTY, HUGE_VAL, m, stream); h_l_stale = true;
-    copy_dev(l.get(), l_raw.get(), m); sync();
-    if (st.scaling) vec_ew_prod(l.get(), l.get(), E.get(), m, stream);
-  }
-  if (u_new) {
-    copy_dev(u_raw.get(), u_new, m); vec_clamp(u_raw.get(), -HUGE_VAL, OSQP_INFTY, m, stream); h_u_stale = true;
-    copy_dev(u.get(), u_raw.get(), m); sync();
-    if (st.scaling) vec_ew_prod(u.get(), u.get(), E.get(), m, stream);
-  }
-  reset_info(ws->info);
-  int e = update_rho_vec_from_bounds();
-  end_update();
-  return e;
+  return store_bounds(l_new, u_new, true);
 }
 
 int Engine::update_values_dev(const double *Px_new, const double *Ax_new) {
@@ -1663,7 +1648,7 @@ int Engine::update_values_dev(const double *Px_new, const double *Ax_new) {
   if (Ax_new && nnzA > 0) {
     if (const int64_t *map = device_A_to_sorted()) {  // the host form permutes on the host (update_PA)
       Ax_sorted.alloc((size_t)nnzA);
-      OQ_LAUNCH(k_permute_vals, dim3(blocks_for(nnzA)), dim3(kBlock), 0, stream, nnzA, map, Ax_new, Ax_sorted.get());
+      permute_vals(nnzA, map, Ax_new, Ax_sorted.get(), stream);
       Ax_use = Ax_sorted.get();
     }
   }

@@ -226,6 +226,7 @@ struct Engine {
   // everything after the copy is the same code.  Not on a row-sharded workspace (refused at the C boundary).
   int update_lin_cost(const double *q_new, bool dev = false);
   int update_bounds(const double *l_new, const double *u_new);
+  int store_bounds(const double *l_src, const double *u_src, bool dev);  // what both forms do once the new bounds are accepted
   // dev: full replacement only, no indices
   int update_PA(const double *Px, const c_int *Pidx, c_int Pn, const double *Ax, const c_int *Aidx, c_int An, bool doP, bool doA,
                 bool dev = false);
@@ -275,13 +276,14 @@ int polish_run(Engine &e);
 int polish_run_pcg(Engine &e);
 // osqp_amd_adjoint / _release / _stats on a workspace that passed the checks of the C boundary (direct_adjoint.hpp); host
 // pointers, or with dev = true (osqp_amd_adjoint_dev) device pointers: cotangents read in place, the output kernels write the
-// caller's arrays, act is a copy of the kept side array -- the same kernels on the same operands, no staging, no download
-int model_adjoint_run(Engine &e, int ncot, const double *dx, const double *dy, double *dq, double *dl, double *du, double *dPx,
-                      double *dAx, double *act, bool dev = false);
+// caller's arrays, act is a copy of the kept side array -- the same kernels on the same operands, no staging, no download.
+// who: the exported symbol that was called (the refusals name it)
+int model_adjoint_run(Engine &e, const char *who, bool dev, int ncot, const double *dx, const double *dy, double *dq, double *dl,
+                      double *du, double *dPx, double *dAx, double *act);
 // osqp_amd_jvp on the same kept state (direct_jvp.hpp): ndir directions (tq, tl, tu, tPx, tAx; null = zero) to (tx, ty); host
 // pointers, or device pointers with dev = true (osqp_amd_jvp_dev)
-int model_jvp_run(Engine &e, int ndir, const double *tq, const double *tl, const double *tu, const double *tPx, const double *tAx,
-                  double *tx, double *ty, double *act, bool dev = false);
+int model_jvp_run(Engine &e, const char *who, bool dev, int ndir, const double *tq, const double *tl, const double *tu,
+                  const double *tPx, const double *tAx, double *tx, double *ty, double *act);
 void model_adjoint_release(Engine &e);  // drops the kept factor (the counters stay)
 void model_adjoint_stats(const Engine &e, double out[6]);
 const char *last_error_cstr();

@@ -423,6 +423,16 @@ void invert_map(int64_t nnz, const int *src, int64_t lo, int64_t hi, int *k2pos,
   if (nnz == 0) return;
   OQ_LAUNCH(k_invert_map, dim3(blocks_for(nnz)), dim3(kBlock), 0, s, nnz, src, lo, hi, k2pos);
 }
+// a full value array in the caller's nnz order into the order of the sorted copy the workspace holds: every entry has one
+// target (to_sorted is a permutation), no atomics
+__global__ __launch_bounds__(kBlock) void k_permute_vals(int64_t nnz, const int64_t *__restrict__ to_sorted, const double *__restrict__ in,
+                                                         double *__restrict__ out) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k < nnz) out[to_sorted[k]] = in[k];
+}
+void permute_vals(int64_t nnz, const int64_t *to_sorted, const double *in, double *out, hipStream_t s) {
+  OQ_LAUNCH(k_permute_vals, dim3(blocks_for(nnz)), dim3(kBlock), 0, s, nnz, to_sorted, in, out);
+}
 __global__ __launch_bounds__(kBlock) void k_convert_i64_i32(int64_t n, const int64_t *__restrict__ in, int *__restrict__ out) {
   int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (k < n) out[k] = (int)in[k];

@@ -30,6 +30,8 @@ void csr_from_coo(int rows, int cols, int64_t E, const int *erow, const int *eco
                   DevBuf<int> &src, hipStream_t s);
 void gather_values(int64_t nnz, const int *src, const double *in, double *out, int64_t modulo, hipStream_t s);
 void invert_map(int64_t nnz, const int *src, int64_t lo, int64_t hi, int *k2pos, hipStream_t s);
+// values in the caller's nnz order into the order of the sorted copy of A: entry k goes to to_sorted[k] (nnz > 0)
+void permute_vals(int64_t nnz, const int64_t *to_sorted, const double *in, double *out, hipStream_t s);
 void convert_i64_i32(int64_t n, const int64_t *in, int *out, hipStream_t s);
 // choose lanes-per-row for the SpMV kernel from the mean row length
 int pick_group(int rows, int64_t nnz);

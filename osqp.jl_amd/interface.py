@@ -457,25 +457,39 @@ def _device_vector(name, a, cols):
     return a.data_ptr() if cols > 0 else None
 
 
-def _device_symbol(model, name):
+_DERIVATIVES, _DEVICE_FORMS = "adjoint derivatives are", "the device-pointer forms are"
+
+
+def _symbol(model, name, what):
+    """The entry point, or OSQPError when the library does not have it (the CPU oracle has none of the extensions)."""
     fn = getattr(model.lib, name, None)
     if fn is None or fn.argtypes is None:
-        raise OSQPError(f"this library does not export {name}: the device-pointer forms are an extension of libosqp_amd.so")
+        raise OSQPError(f"this library does not export {name}: {what} an extension of libosqp_amd.so")
     return fn
+
+
+def _data_cols(model, matrices=True):
+    """Widths of the five data arrays: q [n], l, u [m], Px [nnz(triu P)], Ax [nnz(A)] -- the last two, a read of the library's
+    counters, only with `matrices`."""
+    n, m = dimensions(model)
+    cols = dict(q=n, l=m, u=m)
+    if matrices:
+        st = stats(model, 4)
+        cols.update(Px=int(st[3]), Ax=int(st[1]))
+    return cols
 
 
 def _update_device(model, given):
     """`update` with device arrays: osqp_amd_update_vectors_dev (q, l, u in one call), then osqp_amd_update_values_dev."""
     for name, a in given.items():
         _device_checked(name, a)
-    n, m = dimensions(model)
-    cols = _data_cols(model) if ("Px" in given or "Ax" in given) else dict(q=n, l=m, u=m)
+    cols = _data_cols(model, "Px" in given or "Ax" in given)
     ptr = {name: _device_vector(name, a, cols[name]) for name, a in given.items()}
     if any(ptr.get(k) is not None for k in ("q", "l", "u")):
-        if _device_symbol(model, "osqp_amd_update_vectors_dev")(model.workspace, ptr.get("q"), ptr.get("l"), ptr.get("u")) != 0:
+        if _symbol(model, "osqp_amd_update_vectors_dev", _DEVICE_FORMS)(model.workspace, ptr.get("q"), ptr.get("l"), ptr.get("u")) != 0:
             raise OSQPError("Error updating q, l, u from device arrays: " + model.lib.osqp_amd_last_error().decode())
     if ptr.get("Px") is not None or ptr.get("Ax") is not None:
-        if _device_symbol(model, "osqp_amd_update_values_dev")(model.workspace, ptr.get("Px"), ptr.get("Ax")) != 0:
+        if _symbol(model, "osqp_amd_update_values_dev", _DEVICE_FORMS)(model.workspace, ptr.get("Px"), ptr.get("Ax")) != 0:
             raise OSQPError("Error updating P and A from device arrays: " + model.lib.osqp_amd_last_error().decode())
     elif "Px" in given or "Ax" in given:
         # value arrays without entries only: no data to move, the host form's round (unscale, scale, refactorise) as it is
@@ -572,7 +586,7 @@ def warm_start(model, x=None, y=None):
             _device_checked(name, a)
         n, m = dimensions(model)
         ptr = {name: _device_vector(name, a, n if name == "x" else m) for name, a in given.items()}
-        if _device_symbol(model, "osqp_amd_warm_start_dev")(model.workspace, ptr.get("x"), ptr.get("y")) != 0:
+        if _symbol(model, "osqp_amd_warm_start_dev", _DEVICE_FORMS)(model.workspace, ptr.get("x"), ptr.get("y")) != 0:
             raise OSQPError("Error in warm starting from device arrays: " + model.lib.osqp_amd_last_error().decode())
         return
     if x is not None and y is not None:
@@ -607,23 +621,33 @@ ADJOINT_GRADS = ("q", "l", "u", "Px", "Ax")
 ADJOINT_STATS_FIELDS = ("builds", "solves", "n_low", "n_upp", "kept", "bytes")
 
 
-def _adjoint_symbol(model, name):
-    """The entry point, or OSQPError when the library does not have it (the CPU oracle has no adjoint)."""
-    fn = getattr(model.lib, name, None)
-    if fn is None or fn.argtypes is None:
-        raise OSQPError(f"this library does not export {name}: adjoint derivatives are an extension of libosqp_amd.so")
-    return fn
+_LEADING = dict(ncot="cotangents", ndir="directions")
 
 
-def _cotangent(name, a, cols):
-    """A cotangent argument of `adjoint` as (float64 C-contiguous array [ncot x cols], had a leading axis?).  Shape and
-    element type are checked here, before the library sees the pointer."""
-    arr = np.asarray(a)
-    if arr.dtype.kind not in "fiu":
-        raise ValueError(f"{name}: expected a real numeric array, got dtype {arr.dtype}")
-    if arr.ndim not in (1, 2) or arr.shape[-1] != cols or (arr.ndim == 2 and arr.shape[0] < 1):
-        raise ValueError(f"{name}: expected shape ({cols},) or (ncot, {cols}) with ncot >= 1, got {arr.shape}")
-    return _as_f64(arr).reshape(arr.shape[0] if arr.ndim == 2 else 1, cols), arr.ndim == 2  # (cols may be 0: m = 0)
+def _leading(who, what, shapes, width):
+    """The leading axis the input arrays of one `adjoint` (what = "ncot") or `jvp` ("ndir") call agree on, host or device form,
+    from their shapes (name -> tuple; width: name -> columns): (count, had a leading axis?).  No array: (1, False)."""
+    for nm, shp in shapes.items():
+        if len(shp) not in (1, 2) or shp[-1] != width[nm] or (len(shp) == 2 and shp[0] < 1):
+            raise ValueError(f"{nm}: expected shape ({width[nm]},) or ({what}, {width[nm]}) with {what} >= 1, got {shp}")
+    if len({len(shp) for shp in shapes.values()}) > 1:
+        raise ValueError(f"{who}: {' and '.join(shapes)} must all have a leading axis or all have none")
+    many = any(len(shp) == 2 for shp in shapes.values())
+    counts = {shp[0] if many else 1 for shp in shapes.values()}
+    if len(counts) > 1:
+        raise ValueError(f"{who}: {' and '.join(shapes)} differ in their leading axis, the number of {_LEADING[what]}: {sorted(counts)}")
+    return (counts.pop() if counts else 1), many
+
+
+def _host_inputs(who, what, given, width):
+    """The host inputs of `adjoint` / `jvp` (name -> array-like) as float64 C-contiguous arrays [count x cols] (cols may be 0:
+    m = 0), with (count, had a leading axis?).  Element types and shapes are checked here, before the library sees a pointer."""
+    arrs = {nm: np.asarray(a) for nm, a in given.items()}
+    for nm, arr in arrs.items():
+        if arr.dtype.kind not in "fiu":
+            raise ValueError(f"{nm}: expected a real numeric array, got dtype {arr.dtype}")
+    count, many = _leading(who, what, {nm: arr.shape for nm, arr in arrs.items()}, width)
+    return {nm: _as_f64(arr).reshape(count, width[nm]) for nm, arr in arrs.items()}, count, many
 
 
 def _device_empty(model, like, shape):
@@ -637,21 +661,6 @@ def _device_empty(model, like, shape):
     from .batch import DeviceArray
 
     return DeviceArray(model.lib, shape[0] if len(shape) == 2 else 1, shape[-1], getattr(like, "device", 0))
-
-
-def _device_leading(who, what, given, width):
-    """Shapes of the device inputs of `adjoint` / `jvp` (name -> array, all checked for type): (count, had a leading axis?)."""
-    shapes = {nm: _device_checked(nm, a) for nm, a in given.items()}
-    for nm, shp in shapes.items():
-        if len(shp) not in (1, 2) or shp[-1] != width[nm] or (len(shp) == 2 and shp[0] < 1):
-            raise ValueError(f"{nm}: expected shape ({width[nm]},) or ({what}, {width[nm]}) with {what} >= 1, got {shp}")
-    if len({len(shp) for shp in shapes.values()}) > 1:
-        raise ValueError(f"{who}: the arrays must all have a leading axis or all have none")
-    many = len(next(iter(shapes.values()))) == 2
-    counts = {shp[0] if many else 1 for shp in shapes.values()}
-    if len(counts) > 1:
-        raise ValueError(f"{who}: the arrays differ in their leading axis: {sorted(counts)}")
-    return counts.pop(), many
 
 
 def _device_outputs(model, like, names, shape_of, out):
@@ -673,12 +682,11 @@ def _device_outputs(model, like, names, shape_of, out):
 
 
 def _adjoint_device(model, given, want, out):
-    for nm, a in given.items():
-        _device_checked(nm, a)
-    fn = _device_symbol(model, "osqp_amd_adjoint_dev")
+    shapes = {nm: _device_checked(nm, a) for nm, a in given.items()}
+    fn = _symbol(model, "osqp_amd_adjoint_dev", _DEVICE_FORMS)
     n, m = dimensions(model)
-    ncot, many = _device_leading("adjoint", "ncot", given, dict(dx=n, dy=m))
-    cols = _data_cols(model) if ("Px" in want or "Ax" in want) else dict(q=n, l=m, u=m)
+    ncot, many = _leading("adjoint", "ncot", shapes, dict(dx=n, dy=m))
+    cols = _data_cols(model, "Px" in want or "Ax" in want)
     like = next(iter(given.values()))
     res = _device_outputs(model, like, want + ("act",), lambda k: (m,) if k == "act" else ((ncot, cols[k]) if many else (cols[k],)), out)
     addr = lambda a, width: a.data_ptr() if a is not None and width > 0 else None
@@ -709,46 +717,28 @@ def adjoint(model, dx=None, dy=None, want=ADJOINT_GRADS, out=None):
         return _adjoint_device(model, {nm: v for nm, v in (("dx", dx), ("dy", dy)) if v is not None}, want, out)
     if out is not None:
         raise ValueError("adjoint: out= goes with device arrays; host inputs return numpy arrays")
-    fn = _adjoint_symbol(model, "osqp_amd_adjoint")
+    fn = _symbol(model, "osqp_amd_adjoint", _DERIVATIVES)
     n, m = dimensions(model)
-    given = [(nm, v, k) for nm, v, k in (("dx", dx, n), ("dy", dy, m)) if v is not None]
-    got = {nm: _cotangent(nm, v, k) for nm, v, k in given}
+    got, ncot, many = _host_inputs("adjoint", "ncot", {nm: v for nm, v in (("dx", dx), ("dy", dy)) if v is not None}, dict(dx=n, dy=m))
     if want and not got:
         raise ValueError("adjoint: a gradient is wanted but dx and dy are both None")
-    if len({lead for _, lead in got.values()}) > 1:
-        raise ValueError("dx and dy must both have a leading cotangent axis or both have none")
-    ncots = {arr.shape[0] for arr, _ in got.values()}
-    if len(ncots) > 1:
-        raise ValueError(f"dx and dy differ in the number of cotangents: {sorted(ncots)}")
-    ncot = ncots.pop() if ncots else 1
-    many = any(lead for _, lead in got.values())
-    st = stats(model, 4)
-    cols = dict(q=n, l=m, u=m, Px=int(st[3]), Ax=int(st[1]))
+    cols = _data_cols(model)
     out = {k: np.full((ncot, cols[k]), np.nan) for k in want}
     act = np.zeros(m)
     ptr = lambda a: None if a is None else _fptr(a)
-    gx, gy = (got[k][0] if k in got else None for k in ("dx", "dy"))
-    if fn(model.workspace, ncot, ptr(gx), ptr(gy), *(ptr(out.get(k)) for k in ADJOINT_GRADS), _fptr(act)) != 0:
+    if fn(model.workspace, ncot, ptr(got.get("dx")), ptr(got.get("dy")), *(ptr(out.get(k)) for k in ADJOINT_GRADS), _fptr(act)) != 0:
         raise OSQPError("Error in adjoint: " + model.lib.osqp_amd_last_error().decode())
     res = {k: (v if many else v[0]) for k, v in out.items()}
     res["act"] = act.astype(int)
     return res
 
 
-def _data_cols(model):
-    """Widths of the five data arrays: q [n], l, u [m], Px [nnz(triu P)], Ax [nnz(A)]."""
-    n, m = dimensions(model)
-    st = stats(model, 4)
-    return dict(q=n, l=m, u=m, Px=int(st[3]), Ax=int(st[1]))
-
-
 def _jvp_device(model, given, out):
-    for nm, a in given.items():
-        _device_checked(nm, a)
-    fn = _device_symbol(model, "osqp_amd_jvp_dev")
-    n, m = dimensions(model)
-    cols = _data_cols(model) if ("Px" in given or "Ax" in given) else dict(q=n, l=m, u=m)
-    ndir, many = _device_leading("jvp", "ndir", given, cols)
+    shapes = {nm: _device_checked(nm, a) for nm, a in given.items()}
+    fn = _symbol(model, "osqp_amd_jvp_dev", _DEVICE_FORMS)
+    cols = _data_cols(model, "Px" in given or "Ax" in given)
+    n, m = cols["q"], cols["l"]
+    ndir, many = _leading("jvp", "ndir", shapes, cols)
     like = next(iter(given.values()))
     width = dict(x=n, y=m, act=m)
     res = _device_outputs(model, like, ("x", "y", "act"), lambda k: (ndir, width[k]) if many and k != "act" else (width[k],), out)
@@ -774,24 +764,15 @@ def jvp(model, q=None, l=None, u=None, Px=None, Ax=None, out=None):
         return _jvp_device(model, dict(given), out)
     if out is not None:
         raise ValueError("jvp: out= goes with device arrays; host inputs return numpy arrays")
-    fn = _adjoint_symbol(model, "osqp_amd_jvp")
-    n, m = dimensions(model)
+    fn = _symbol(model, "osqp_amd_jvp", _DERIVATIVES)
     if not given:
         raise ValueError("jvp: q, l, u, Px and Ax are all None: at least one tangent is needed")
-    cols = dict(q=n, l=m, u=m)
-    if Px is not None or Ax is not None:
-        cols = _data_cols(model)
-    got = {nm: _cotangent(nm, v, cols[nm]) for nm, v in given}
-    if len({lead for _, lead in got.values()}) > 1:
-        raise ValueError("the tangents must all have a leading direction axis or all have none")
-    ndirs = {arr.shape[0] for arr, _ in got.values()}
-    if len(ndirs) > 1:
-        raise ValueError(f"the tangents differ in the number of directions: {sorted(ndirs)}")
-    ndir = ndirs.pop()
-    many = any(lead for _, lead in got.values())
+    cols = _data_cols(model, Px is not None or Ax is not None)
+    n, m = cols["q"], cols["l"]
+    got, ndir, many = _host_inputs("jvp", "ndir", dict(given), cols)
     tx, ty, act = np.full((ndir, n), np.nan), np.full((ndir, m), np.nan), np.zeros(m)
     ptr = lambda a: None if a is None else _fptr(a)
-    if fn(model.workspace, ndir, *(ptr(got[k][0]) if k in got else None for k in ADJOINT_GRADS), _fptr(tx), _fptr(ty), _fptr(act)) != 0:
+    if fn(model.workspace, ndir, *(ptr(got.get(k)) for k in ADJOINT_GRADS), _fptr(tx), _fptr(ty), _fptr(act)) != 0:
         raise OSQPError("Error in jvp: " + model.lib.osqp_amd_last_error().decode())
     return dict(x=tx if many else tx[0], y=ty if many else ty[0], act=act.astype(int))
 
@@ -812,7 +793,7 @@ def jacobian(model, of=("x",), wrt=("q", "l", "u"), mode="auto", out_rows=None, 
     results are placed side by side, so the result does not depend on it.  Default: as many as keep the unit vectors and
     the largest output array of one call under 256 MiB together, at least 1.  Nothing is computed on the results."""
     for name in ("osqp_amd_adjoint", "osqp_amd_jvp"):
-        _adjoint_symbol(model, name)
+        _symbol(model, name, _DERIVATIVES)
     of, wrt = tuple(of), tuple(wrt)
     if not of or len(set(of)) != len(of) or any(o not in JACOBIAN_OF for o in of):
         raise ValueError(f"of: expected a non-empty subset of {JACOBIAN_OF} without repeats, got {of!r}")
@@ -897,7 +878,7 @@ def solution(model, x=None, y=None, device=0):
         if not _is_device(a):
             raise ValueError(f"solution: {name} must be a device array (a torch CUDA tensor or a batch.DeviceArray)")
         _device_checked(name, a)
-    fn = _device_symbol(model, "osqp_amd_solution_dev")
+    fn = _symbol(model, "osqp_amd_solution_dev", _DEVICE_FORMS)
     n, m = dimensions(model)
     like = next(iter(given.values()), None)
     if like is None:
@@ -913,7 +894,7 @@ def solution(model, x=None, y=None, device=0):
 
 def device_form_calls(model):
     """Extension: osqp_amd_device_form_calls as a dict of ints -- the device-form calls this model has served so far."""
-    fn = _device_symbol(model, "osqp_amd_device_form_calls")
+    fn = _symbol(model, "osqp_amd_device_form_calls", _DEVICE_FORMS)
     out = np.zeros(len(DEVICE_FORM_FIELDS))
     if fn(model.workspace, _fptr(out), len(out)) != len(out):
         raise OSQPError("osqp_amd_device_form_calls: bad argument")
@@ -922,14 +903,14 @@ def device_form_calls(model):
 
 def adjoint_release(model):
     """Extension: drop the factor `adjoint` keeps (it is as large as a polish's)."""
-    if _adjoint_symbol(model, "osqp_amd_adjoint_release")(model.workspace) != 0:
+    if _symbol(model, "osqp_amd_adjoint_release", _DERIVATIVES)(model.workspace) != 0:
         raise OSQPError("Error in adjoint_release: " + model.lib.osqp_amd_last_error().decode())
 
 
 def adjoint_stats(model):
     """Extension: osqp_amd_adjoint_stats as a dict of ints -- factor builds and KKT solves so far, n_low / n_upp of the kept
     factor, whether one is kept, and the device bytes it holds."""
-    fn = _adjoint_symbol(model, "osqp_amd_adjoint_stats")
+    fn = _symbol(model, "osqp_amd_adjoint_stats", _DERIVATIVES)
     out = np.zeros(len(ADJOINT_STATS_FIELDS))
     if fn(model.workspace, _fptr(out), len(out)) != len(out):
         raise OSQPError("osqp_amd_adjoint_stats: bad argument")

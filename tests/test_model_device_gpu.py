@@ -223,6 +223,7 @@ def test_compact_workspace(product_lib, oracle_lib, monkeypatch):
     rc, msg = _raw_adjoint(product_lib, B, _dev(np.ones(n)), outs, act)
     print(f"refused with {rc}: {msg}")
     assert rc == 6 and "compact" in msg
+    assert "osqp_amd_adjoint_dev" in msg  # the refusal names the symbol that was called
     with pytest.raises(oq.OSQPError, match="compact"):
         oq.adjoint(B, dx=_dev(np.ones(n)), out=dict(outs, act=act))
     with pytest.raises(oq.OSQPError, match="compact"):
