@@ -4,6 +4,7 @@
 // flags the Julia side tests with `!= 0` [REF src/interface.jl:157-159].
 #include "engine.hpp"
 #include "symbolic.hpp"
+#include "direct_knobs.hpp"
 
 #include <cstring>
 #include <thread>
@@ -515,9 +516,9 @@ c_int osqp_amd_symbolic_probe(c_int n, c_int m, const c_int *Pp, const c_int *Pi
     }
     out[5] = (double)T.Fp[S.N]; out[6] = (double)T.wdoubles; out[7] = largest; out[8] = ok ? 1.0 : 0.0; out[9] = (double)inside;
     int lD, cD, kD;
-    choose_dense_top(S, 512, getenv("OSQP_AMD_DENSE_MAX") ? atoi(getenv("OSQP_AMD_DENSE_MAX")) : 12288, 1024, 32, lD, cD, kD);
-    out[10] = level_solve_cost_us(S, 512, lD, kD); out[11] = supernode_solve_cost_us(T, 256);
-    out[12] = supernodes_pay(S, T, 512, lD, kD, 256) ? 1.0 : 0.0;
+    choose_dense_top(S, kChainRows, DirectKnobs().dense_max, kDenseSparseMax, kDenseMin, lD, cD, kD);  // the back-end's own rule (direct.hip choose_dense_block)
+    out[10] = level_solve_cost_us(S, kChainRows, lD, kD); out[11] = supernode_solve_cost_us(T, kSnThreads);
+    out[12] = supernodes_pay(S, T, kChainRows, lD, kD, kSnThreads) ? 1.0 : 0.0;
     if (getenv("OSQP_AMD_PROBE_VERBOSE"))
       for (int L = 0; L < T.nlev; L++) {
         int64_t rows = 0, pre = 0, post = 0, back = 0;

@@ -48,7 +48,7 @@ void set_last_error(const std::string &m);
                              ":" + std::to_string(__LINE__));                                       \
   } while (0)
 
-// Every kernel launch goes through OQ_LAUNCH: launch errors are always checked;
+// Every kernel launch goes through OQ_LAUNCH (direct.hip's launch_sn: through post_launch itself): launch errors are always checked;
 // with OSQP_AMD_DEBUG=1 each launch is announced on stderr and synchronised, so a
 // faulting kernel is the last name printed.
 extern int g_debug_sync;
@@ -68,6 +68,13 @@ inline void post_launch(const char *name, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, block, shmem, stream, __VA_ARGS__);      \
     oq::post_launch(#kern, stream);                                         \
   } while (0)
+
+// ---- environment switches: the parse rules, one copy.  env_read: into `v` if set at all (returns that)
+inline bool env_read(const char *name, int &v) { const char *e = getenv(name); if (e) v = atoi(e); return e != nullptr; }
+inline int env_int(const char *name, int dflt) { env_read(name, dflt); return dflt; }
+inline long long env_i64(const char *name, long long dflt) { const char *e = getenv(name); return e ? atoll(e) : dflt; }
+inline double env_double(const char *name, double dflt) { const char *e = getenv(name); return e ? atof(e) : dflt; }
+inline bool env_on(const char *name) { return env_int(name, 1) != 0; }  // on unless set to 0
 
 // ---- device buffers -------------------------------------------------------
 extern size_t g_device_bytes;  // bytes currently allocated through DevBuf

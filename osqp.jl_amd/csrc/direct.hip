@@ -21,6 +21,7 @@
 
 #include "engine.hpp"
 #include "symbolic.hpp"
+#include "direct_knobs.hpp"
 #include "mfront.hpp"
 #include "mfront_big.hpp"
 
@@ -28,7 +29,6 @@ namespace oq {
 
 namespace {
 
-constexpr int kChainRows = 512;   // levels at most this wide are chained in one workgroup
 constexpr int kChainThreads = 1024;
 
 }  // namespace
@@ -46,11 +46,20 @@ namespace {
 struct Step { int kind; int a, b, G; int U = 2, L = 64; };  // L: lanes per row inside an LDS chain  // kind 0: single level, rows [a,b), G lanes per row; 1: chain of levels [a,b),
                                          // G threads per row for the part of its rows that lies before the chain
 
+// A runtime lanes-per-row count (LdlFactor::pick: 1, 4, 16, otherwise 64) as a compile-time one: f(std::integral_constant<int, G>)
+template <typename F>
+void with_lanes(int G, F &&f) {
+  if (G == 1) f(std::integral_constant<int, 1>{}); else if (G == 4) f(std::integral_constant<int, 4>{});
+  else if (G == 16) f(std::integral_constant<int, 16>{}); else f(std::integral_constant<int, 64>{});
+}
+constexpr int fewer_lanes(int LA) { return LA == 64 ? 16 : (LA == 16 ? 4 : LA); }  // one notch fewer lanes per row: where rows in flight count, not one row's latency
+
 // ------------------------------------------------------------------ factor object
 int level_limit();
 int64_t factor_limit(const Engine &e, bool forced);
 double factor_flops_limit();
 struct LdlFactor {
+  const DirectKnobs knobs{};  // every environment switch, read once per factor (before any member that uses one)
   Engine &e;
   Symbolic S;
   int N = 0, n = 0, mr = 0, nlev = 0;
@@ -67,12 +76,11 @@ struct LdlFactor {
   // The explicit inverse is formed by Gauss-Jordan sweeps without pivoting: on a block that is badly conditioned (tiny sigma /
   // delta pivots next to the 1 / sigma fill of variables without a cost term: tests/qp_zoo.py lasso_data) it can be useless where
   // the triangular solves of the same pivots still serve.  So every factorisation PROBES it: r = v - S0 (S0^-1 v) for one fixed
-  // vector, from a copy of S0 taken before the sweeps; a residual above dense_probe_tol() makes refactor return 7 and the owner
+  // vector, from a copy of S0 taken before the sweeps; a residual above knobs.dense_probe_tol makes refactor return 7 and the owner
   // builds the factor again without the block (dense_top = false).  (The blocked inverse of 512 pivots and more is not probed.)
   bool allow_dense_top = true;
   DevBuf<double> S0chk, probe_v, probe_w, probe_r;
   double dense_residual = 0.0;  // of the last factorisation
-  static double dense_probe_tol() { const char *v = getenv("OSQP_AMD_DENSE_PROBE_TOL"); return v ? atof(v) : 1e-6; }
   int ldD = 0;                  // leading dimension of the dense block's array (kD, or kD padded to 64 for the block sweeps)
   std::vector<char> long_rows;  // per level: phase 2 of the factorisation through dense work rows (k_ldl_entries_w)
   size_t w_half = 0;            // doubles in one half of W
@@ -89,7 +97,7 @@ struct LdlFactor {
     if (inject_fault) { inject_fault = false; *sn_fault_host = 1; }  // OSQP_AMD_SNODE_FAULT_TEST=1: the host side of a timed-out wait
     return *(volatile int *)sn_fault_host != 0;
   }
-  mutable bool inject_fault = getenv("OSQP_AMD_SNODE_FAULT_TEST") && atoi(getenv("OSQP_AMD_SNODE_FAULT_TEST")) == 1;
+  mutable bool inject_fault = knobs.snode_fault_test;
   bool sn_tree = false;     // the levels from sn_tree_L0 on in one launch per direction (k_sn_tree) instead of one per level
   int sn_tree_threads = 1024;  // threads per supernode of that launch (512: twice the resident workgroups, one more level fits)
   int sn_tree_grid = 0;        // persistent form: workgroups of the launch (0: one per supernode, all resident)
@@ -135,7 +143,7 @@ struct LdlFactor {
   const int *vec_pinv() const { return sn ? pinv_s.get() : pinv.get(); }
   int solve_levels() const { return sn ? T.nlev : lD; }
   // multiply-adds of a numeric factorisation WITHOUT the dense top block (sum of squared column counts of the columns below
-  // it): the block itself is inverted on the matrix cores at ~10 TFLOP/s and is bounded by dense_max()
+  // it): the block itself is inverted on the matrix cores at ~10 TFLOP/s and is bounded by knobs.dense_max
   double flops_below_dense_block() const {
     if (!kD) return S.flops;
     double f = 0.0;
@@ -148,9 +156,47 @@ struct LdlFactor {
       : e(en), sigma(sigma_), cconst(cconst_), allow_dense_top(dense_top) {
     e.fetch_host_pattern();
     e.setup_mark("  host pattern");
+    choose_ordering(row_map, mr_, limit, flops_limit);
+    if (S.too_large) return;
+    e.setup_mark("  other orderings");
+    hipStream_t s = e.stream;
+    N = S.N; n = S.n; mr = S.mr; nlev = (int)S.level_ptr.size() - 1;
+    up32(perm, S.perm); up32(pinv, S.pinv); up32(level_ptr, S.level_ptr);
+    const bool lean = S.lean;
+    lean_built = lean;
+    if (lean) { lean_device_pattern(); e.setup_mark("    scatter maps"); }
+    else {
+      up64(Lp, S.Lp); up64(Rp, S.Rp); up64(Rmap, S.Rmap);
+      up32(Li, S.Li); up32(Rj, S.Rj);
+      if (S.no_host_maps) device_scatter_maps();
+      else { up64(PtoL, S.PtoL); up64(AtoL, S.AtoL); }
+    }
+    Lcol.alloc(std::max<size_t>(1, (size_t)S.nnzL));  // the column of every entry of L: what the entry kernels of the factorisation start from
+    expand_colptr(N, Lp.get(), S.nnzL, Lcol.get(), s);
+    Lx.alloc(S.nnzL); D.alloc(N); Dinv.alloc(N); bp.alloc(N); status.alloc(2);
+    if (!lean) { choose_dense_block(); decide_supernodes(false); }
+    if (sn) { lD = nlev; cD = N; kD = 0; supernodes_on_device(); }
+    else Rx.alloc(S.nnzL);  // (the CSR copy of the values serves the level-scheduled solves only)
+    if (sn) e.setup_mark("    supernodes on the device");
+    build_mf();
+    if (mf) e.setup_mark("    fronts");
+    setup_top();
+    setup_dense_top();
+    alloc_work_rows_and_dense_block();
+    e.sync();
+    e.setup_mark("  factor pattern on the device");
+    if (!sn) build_schedule();  // (supernodal solves have their own schedule: levels of the supernode graph)
+    e.setup_mark("  solve schedule");
+    if (lean) { S.lean_rows.reset(); S.lean_state.reset(); }
+    // the big index arrays are only needed on the device from here on
+    std::vector<int>().swap(S.Li); std::vector<int>().swap(S.Rj); std::vector<int64_t>().swap(S.Rmap);
+    std::vector<int64_t>().swap(S.PtoL); std::vector<int64_t>().swap(S.AtoL);
+  }
+
+  void choose_ordering(const std::vector<int> &row_map, int mr_, int64_t limit, double flops_limit) {
     // OSQP_AMD_FIRST_ORDERING=1: nested dissection at once (a caller who knows the problem is a long banded one saves the
     // min-degree analysis that would only establish that: ~half of the setup of the control-1e6 bench workload)
-    int first_ordering = getenv("OSQP_AMD_FIRST_ORDERING") ? atoi(getenv("OSQP_AMD_FIRST_ORDERING")) : -1;  // read per setup: a process may set up problems of both kinds
+    int first_ordering = knobs.first_ordering;
     // unset (round 4): on a LARGE problem whose KKT graph is long -- a breadth-first level structure hundreds of levels
     // deep: banded, multi-stage, grid-like; random sparsity is ~log N deep -- nested dissection goes first without being
     // asked (the min-degree analysis of such a graph only finds the chain: 2 - 3 s at 2.7e6 nodes), and min-degree is the
@@ -159,8 +205,7 @@ struct LdlFactor {
     // (round 6: "long" is a level structure of 100 levels or more -- 400 until then: a 50 x 50 x 50 grid is 150 deep, and its
     // minimum-degree analysis was 2.2 of its 3.8 s of setup only to be replaced by the dissection; random sparsity at this size is
     // 10 - 20 deep.  A dissection that comes out badly is still replaced below.  OSQP_AMD_ND_DEPTH overrides.)
-    const int nd_depth = getenv("OSQP_AMD_ND_DEPTH") ? atoi(getenv("OSQP_AMD_ND_DEPTH")) : 100;
-    if (first_ordering < 0 && e.hP.cols + mr_ >= 200000) nd_by_depth = kkt_graph_depth(e.hP, e.hA, row_map, mr_) >= nd_depth;
+    if (first_ordering < 0 && e.hP.cols + mr_ >= 200000) nd_by_depth = kkt_graph_depth(e.hP, e.hA, row_map, mr_) >= knobs.nd_depth;
     if (first_ordering < 0) first_ordering = nd_by_depth ? 1 : 0;
     // Round 5: a large long problem (the class nested dissection goes first on) gets a LEAN analysis -- numbering, tree,
     // levels, counts and the unsorted rows of the pattern -- and, when the factor is a supernodal one with fronts that fit
@@ -168,12 +213,11 @@ struct LdlFactor {
     // the rows (lean_device): control-1e6 spent 1.5 of its 3 s of setup writing, sorting and uploading those arrays on the
     // host.  Any other outcome completes the analysis on the host (symbolic_complete: the same arrays as a full analysis).
     // OSQP_AMD_LEAN = 0 never, 1 whenever the row map is the identity (tests: the path on small problems).
-    const int lean_mode = getenv("OSQP_AMD_LEAN") ? atoi(getenv("OSQP_AMD_LEAN")) : -1;
     bool identity = mr_ == e.m;
     for (int i = 0; identity && i < mr_; i++) identity = row_map[i] == i;
-    const bool lean_try = lean_mode != 0 && (lean_mode == 1 || nd_by_depth) && identity;
+    const bool lean_try = knobs.lean != 0 && (knobs.lean == 1 || nd_by_depth) && identity;
     // the scatter maps of the whole KKT system (every row of A in it) are built on the device from the CSC arrays of L
-    const bool device_maps = identity && !(getenv("OSQP_AMD_DEVICE_MAPS") && atoi(getenv("OSQP_AMD_DEVICE_MAPS")) == 0);
+    const bool device_maps = identity && knobs.device_maps;
     S.no_host_maps = device_maps;
     symbolic_analyse(e.hP, e.hA, row_map, mr_, limit, flops_limit, first_ordering == 1 ? 1 : 0, S, lean_try);
     // (the depth that counts for a supernodal factor is that of the SUPERNODE graph -- up to 64 pivots a step -- which is not
@@ -197,12 +241,11 @@ struct LdlFactor {
     if (S.too_large) return;
     // A deep level schedule under min-degree (banded / multi-stage structure: the elimination tree is a chain) gets a
     // second analysis with nested dissection; the cheaper triangular solve by the model below wins.
-    const bool try_nd = !(getenv("OSQP_AMD_ND") && atoi(getenv("OSQP_AMD_ND")) == 0);
     // (not when the depth is a dense trailing block -- a dense P: no ordering shortens that, and the block is inverted
     // explicitly anyway)
     int lD0 = 0, cD0 = 0, kD0 = 0;
-    if (!S.lean) choose_dense_top(S, kChainRows, dense_max(), kDenseSparseMax, kDenseMin, lD0, cD0, kD0);
-    if (!S.lean && try_nd && first_ordering != 1 && (kD0 ? lD0 : (int)S.level_ptr.size() - 1) > 400) {
+    if (!S.lean) choose_dense_top(S, kChainRows, knobs.dense_max, kDenseSparseMax, kDenseMin, lD0, cD0, kD0);
+    if (!S.lean && knobs.nd && first_ordering != 1 && (kD0 ? lD0 : (int)S.level_ptr.size() - 1) > 400) {
       Symbolic S2;
       S2.no_host_maps = device_maps;
       symbolic_analyse(e.hP, e.hA, row_map, mr_, limit, flops_limit, 1, S2);
@@ -210,39 +253,16 @@ struct LdlFactor {
     }
     // A short level schedule is launch-bound: the tie-breaking variant of the same ordering (symbolic.hpp, ordering 2)
     // often folds it further (bound constraints: row - variable - row chains of height 2 become height 1).
-    const bool try_fifo = !(getenv("OSQP_AMD_MD_FIFO") && atoi(getenv("OSQP_AMD_MD_FIFO")) == 0);
-    if (!S.lean && try_fifo && (int)S.level_ptr.size() - 1 >= 3 && (int)S.level_ptr.size() - 1 <= 400) {
+    if (!S.lean && knobs.md_fifo && (int)S.level_ptr.size() - 1 >= 3 && (int)S.level_ptr.size() - 1 <= 400) {
       Symbolic S3;
       S3.no_host_maps = device_maps;
       symbolic_analyse(e.hP, e.hA, row_map, mr_, limit, flops_limit, 2, S3);
       if (!S3.too_large && S3.nnzL <= S.nnzL + S.nnzL / 10 && solve_cost_us(S3) < 0.9 * solve_cost_us(S)) S = std::move(S3);
     }
-    e.setup_mark("  other orderings");
+  }
+
+  void alloc_work_rows_and_dense_block() {
     hipStream_t s = e.stream;
-    N = S.N; n = S.n; mr = S.mr; nlev = (int)S.level_ptr.size() - 1;
-    auto up64 = [&](DevBuf<int64_t> &d, const std::vector<int64_t> &h) { d.alloc(h.size()); d.upload(h.data(), h.size(), s); };
-    auto up32 = [&](DevBuf<int> &d, const std::vector<int> &h) { d.alloc(h.size()); d.upload(h.data(), h.size(), s); };
-    up32(perm, S.perm); up32(pinv, S.pinv); up32(level_ptr, S.level_ptr);
-    const bool lean = S.lean;
-    lean_built = lean;
-    if (lean) { lean_device_pattern(); e.setup_mark("    scatter maps"); }
-    else {
-      up64(Lp, S.Lp); up64(Rp, S.Rp); up64(Rmap, S.Rmap);
-      up32(Li, S.Li); up32(Rj, S.Rj);
-      if (S.no_host_maps) device_scatter_maps();
-      else { up64(PtoL, S.PtoL); up64(AtoL, S.AtoL); }
-    }
-    Lcol.alloc(std::max<size_t>(1, (size_t)S.nnzL));  // the column of every entry of L: what the entry kernels of the factorisation start from
-    expand_colptr(N, Lp.get(), S.nnzL, Lcol.get(), s);
-    Lx.alloc(S.nnzL); D.alloc(N); Dinv.alloc(N); bp.alloc(N); status.alloc(2);
-    if (!lean) { choose_dense_block(); decide_supernodes(false); }
-    if (sn) { lD = nlev; cD = N; kD = 0; supernodes_on_device(); }
-    else Rx.alloc(S.nnzL);  // (the CSR copy of the values serves the level-scheduled solves only)
-    if (sn) e.setup_mark("    supernodes on the device");
-    build_mf();
-    if (mf) e.setup_mark("    fronts");
-    setup_top();
-    setup_dense_top();
     {  // levels of few columns with long rows: work rows of N doubles each, at most 256 MB
       long_rows.assign(nlev, 0);
       size_t wmax = 0;
@@ -250,7 +270,7 @@ struct LdlFactor {
         const int c0 = S.level_ptr[l], c1 = S.level_ptr[l + 1], width = c1 - c0;
         if (width == 0 || S.Lp[c1] == S.Lp[c0]) continue;
         const double mean = (double)(S.Rp[c1] - S.Rp[c0]) / (double)width;
-        if (mean >= long_row_mean() && (size_t)width * (size_t)N * sizeof(double) <= ((size_t)256 << 20)) {
+        if (mean >= knobs.long_row_mean && (size_t)width * (size_t)N * sizeof(double) <= ((size_t)256 << 20)) {
           long_rows[l] = 1;
           wmax = std::max(wmax, (size_t)width * (size_t)N);
         }
@@ -274,7 +294,7 @@ struct LdlFactor {
           e.sync();
         }
         schur_ncols = 0;
-        if (blocked && !S.Li.empty() && !(getenv("OSQP_AMD_SCHUR_DENSE") && atoi(getenv("OSQP_AMD_SCHUR_DENSE")) == 0)) {
+        if (blocked && !S.Li.empty() && knobs.schur_dense) {
           // the rank-64 form of the Schur complement when L21 is not very sparse: a rank-64 update costs (ld / 64)^2 / 2 tiles
           // whatever its columns hold; entry by entry costs a 64-lane gather round per 64 entries of a row of L21
           std::vector<int> cols;
@@ -292,38 +312,27 @@ struct LdlFactor {
         }
         x2.alloc(kD);
         // the symmetric form of the product (k_dense_apply_sym) for the blocked inverse; OSQP_AMD_DENSE_SYM=0: the full one
-        if (kD >= kDenseBlocked && ldD % kDsT == 0 && !(getenv("OSQP_AMD_DENSE_SYM") && atoi(getenv("OSQP_AMD_DENSE_SYM")) == 0)) {
+        if (kD >= kDenseBlocked && ldD % kDsT == 0 && knobs.dense_sym) {
           const size_t nb = (size_t)ldD / kDsT;
           dsP1.alloc(nb * nb * kDsT); dsP2.alloc(nb * nb * kDsT);
         }
       }
     }
-    e.sync();
-    e.setup_mark("  factor pattern on the device");
-    if (!sn) build_schedule();  // (supernodal solves have their own schedule: levels of the supernode graph)
-    e.setup_mark("  solve schedule");
-    if (lean) { S.lean_rows.reset(); S.lean_state.reset(); }
-    // the big index arrays are only needed on the device from here on
-    std::vector<int>().swap(S.Li); std::vector<int>().swap(S.Rj); std::vector<int64_t>().swap(S.Rmap);
-    std::vector<int64_t>().swap(S.PtoL); std::vector<int64_t>().swap(S.AtoL);
   }
 
   // Supernodal solves when their modelled time (a launch per level; the slowest workgroup of each level walks its
   // entries outside the blocks with 256 threads, then its s x s block) is well below the level schedule's.
   // OSQP_AMD_SNODE = 0 never, 2 always (tests), otherwise by the model.
   void decide_supernodes(bool lean) {
-    const int mode = getenv("OSQP_AMD_SNODE") ? atoi(getenv("OSQP_AMD_SNODE")) : 1;
-    if (mode == 0 || N < 2) return;
-    if (mode != 2 && nlev < 48) return;
+    if (knobs.snode == 0 || N < 2) return;
+    if (knobs.snode != 2 && nlev < 48) return;
     // the depth IS a dense block (a dense P, dense constraint rows): the few levels below it stay a level schedule (no
     // partition to build).  A block-sparse top chain taken as a block -- the separators of a dissection -- is no such case:
     // the supernodal form replaces it when its model is the cheaper one (round 5: with the one-level-structure dissection
     // the control problem with T = 400 has 44 levels below such a block and 5 supernode levels)
-    if (mode != 2 && kD > 0 && lD < 48 && kD_dense) return;
-    int smax = kSnMax;  // OSQP_AMD_SNODE_MAX: smaller supernodes (tests: many levels on small problems)
-    if (const char *v = getenv("OSQP_AMD_SNODE_MAX")) smax = std::max(1, std::min(kSnMax, atoi(v)));
-    build_supernodes(S, smax, T, false, lean);  // lean: the partition, list lengths as upper bounds from the counts
-    sn = mode == 2 || supernodes_pay(S, T, kChainRows, lD, kD, kSnThreads);
+    if (knobs.snode != 2 && kD > 0 && lD < 48 && kD_dense) return;
+    build_supernodes(S, knobs.snode_max, T, false, lean);  // lean: the partition, list lengths as upper bounds from the counts
+    sn = knobs.snode == 2 || supernodes_pay(S, T, kChainRows, lD, kD, kSnThreads);
     bool planned = false;
     if (!sn) {
       // (round 6) second look with the plan of the fronts: where it puts a dense top over the partition -- a 2-D / 3-D structure: the
@@ -345,10 +354,10 @@ struct LdlFactor {
   // Workgroups of `threads` threads of the tree kernel that one compute unit holds at once: the occupancy query (the kernel takes
   // 92 - 97 registers: one workgroup of 1024 threads, two of 512; compiled for 64 registers -- __launch_bounds__(NT, 8) -- it
   // spills 50 of them and loses: grid 700 x 700 2 405 -> 2 170 it/s, control T = 800 8.6 -> 5.5 k, measured in round 6)
-  static int tree_resident(const void *f, int threads) {
+  int tree_resident(const void *f, int threads) const {
     int api = 0;
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&api, f, threads, 0));
-    if (getenv("OSQP_AMD_SETUP_TRACE")) {
+    if (knobs.setup_trace) {
       hipFuncAttributes fa;
       if (hipFuncGetAttributes(&fa, f) == hipSuccess)
         fprintf(stderr, "[supernodes] tree kernel, %d threads: %d workgroups per compute unit (%zu B of LDS, %d registers)\n", threads, api, (size_t)fa.sharedSizeBytes, fa.numRegs);
@@ -356,16 +365,16 @@ struct LdlFactor {
     }
     return std::max(1, api);
   }
+  void up64(DevBuf<int64_t> &d, const std::vector<int64_t> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), e.stream); }
+  void up32(DevBuf<int> &d, const std::vector<int> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), e.stream); }
   // The device side of a supernodal factor: the lists of the entries outside the blocks (uploaded from a full analysis,
   // built by lean_device_lists otherwise), the counters of the one-launch tree, the arrays of the inverted blocks.
   void supernodes_on_device() {
     hipStream_t s = e.stream;
-    auto up64 = [&](DevBuf<int64_t> &d, const std::vector<int64_t> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), s); };
-    auto up32 = [&](DevBuf<int> &d, const std::vector<int> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), s); };
     const bool lean = S.lean;
     up32(sn_ptr, T.ptr); up32(sn_piv, T.piv);
     if (!lean) { up32(sn_Fj, T.Fj); up32(sn_Gi, T.Gi); }
-    sn_tree = T.nlev > 2 && !(getenv("OSQP_AMD_SNODE_TREE") && atoi(getenv("OSQP_AMD_SNODE_TREE")) == 0);
+    sn_tree = T.nlev > 2 && knobs.snode_tree;
     sn_tree_L0 = 1;
     if (sn_tree) {
       // every workgroup of the launch must be resident at once: then a waiting workgroup can never keep the one it waits
@@ -379,7 +388,7 @@ struct LdlFactor {
       HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
       per_cu_f = tree_resident((const void *)k_sn_tree<true, 1024>, 1024);
       per_cu_b = tree_resident((const void *)k_sn_tree<false, 1024>, 1024);
-      if (const char *v = getenv("OSQP_AMD_SNODE_TREE_PER_CU")) per_cu_f = per_cu_b = std::max(1, atoi(v));  // (experiments)
+      if (knobs.snode_tree_per_cu) per_cu_f = per_cu_b = knobs.snode_tree_per_cu;  // (experiments)
       // Round 6: where fronts go through global memory (a 2-D / 3-D structure: many narrow levels of large supernodes) the launch may
       // hold up to TWICE what is resident at once.  That is safe for the reason the kernel's comment gives as its second line of
       // defence -- workgroups are dispatched in block order per XCD and a workgroup only waits on lower blocks, so the lowest
@@ -387,9 +396,9 @@ struct LdlFactor {
       // full residency (the first line) was a margin, and on these structures it costs two levels of the launch: grid 700 x 700
       // 2 405 -> 2 754 it/s, 1000 x 1000 1 036 -> 1 222, no restart in any run.  The control family (fronts in LDS, 512-thread
       // variant below) is unchanged by it and keeps the margin.  OSQP_AMD_SNODE_TREE_OVERSUB = 1 restores it everywhere.
-      const int oversub = (mf_ok && mf_big_count > 0) ? (getenv("OSQP_AMD_SNODE_TREE_OVERSUB") ? std::max(1, atoi(getenv("OSQP_AMD_SNODE_TREE_OVERSUB"))) : 2) : 1;
+      const int oversub = (mf_ok && mf_big_count > 0) ? knobs.snode_tree_oversub : 1;
       const long long cap = (long long)oversub * std::min(per_cu_f, per_cu_b) * cus;
-      if (getenv("OSQP_AMD_SETUP_TRACE"))
+      if (knobs.setup_trace)
         fprintf(stderr, "[supernodes] one-launch tree: %d / %d resident workgroups of 1024 threads per compute unit (forward / backward), %d compute units, launch of at most %lld\n", per_cu_f, per_cu_b, cus, cap);
       // (a dense top over the supernodes, direct_sndense_kernels.hpp, takes the last levels out of the launch)
       const int top_end = snd_K ? snd_L0 : T.nlev, j_end = snd_K ? snd_J0 : T.count;
@@ -402,15 +411,15 @@ struct LdlFactor {
       // long rows and borders of hundreds of rows, and sixteen lanes a row instead of eight count for more than a level gained:
       // grid 700 x 700 597 -> 712 it/s, 1000 x 1000 321 -> 334; control-1e6, all fronts in LDS, keeps 512: 1 792 against 1 731)
       const bool long_rows = mf_ok && mf_big_count > 0;
-      const bool try512 = getenv("OSQP_AMD_SNODE_TREE_512") ? atoi(getenv("OSQP_AMD_SNODE_TREE_512")) != 0 : !long_rows;
+      const bool try512 = knobs.snode_tree_512 >= 0 ? knobs.snode_tree_512 != 0 : !long_rows;
       if (sn_tree_L0 > 1 && try512) {
         int pf = 0, pb = 0;
         pf = tree_resident((const void *)k_sn_tree<true, 512>, 512);
         pb = tree_resident((const void *)k_sn_tree<false, 512>, 512);
-        if (const char *v = getenv("OSQP_AMD_SNODE_TREE_PER_CU")) pf = pb = 2 * std::max(1, atoi(v));  // (experiments)
+        if (knobs.snode_tree_per_cu) pf = pb = 2 * knobs.snode_tree_per_cu;  // (experiments)
         long long cap2 = (long long)std::min(pf, pb) * cus;
-        if (getenv("OSQP_AMD_SETUP_TRACE")) fprintf(stderr, "[supernodes] one-launch tree: %d / %d resident workgroups of 512 threads per compute unit\n", pf, pb);
-        if (getenv("OSQP_AMD_SNODE_TREE_CAP")) cap2 = std::min<long long>(cap2, atoll(getenv("OSQP_AMD_SNODE_TREE_CAP")));  // (experiments: a later start)
+        if (knobs.setup_trace) fprintf(stderr, "[supernodes] one-launch tree: %d / %d resident workgroups of 512 threads per compute unit\n", pf, pb);
+        cap2 = std::min(cap2, knobs.snode_tree_cap);  // (experiments: a later start)
         int L2 = 1;
         while (L2 < top_end && (long long)(j_end - T.lvl_ptr[L2]) > cap2) L2++;
         if (L2 < sn_tree_L0) { sn_tree_L0 = L2; sn_tree_threads = 512; }
@@ -419,21 +428,19 @@ struct LdlFactor {
         // level kernels do better than 512-thread workgroups with device-scope loads; OSQP_AMD_SNODE_TREE_PERSIST=k takes the
         // levels from k on, default: off)
         sn_tree_grid = 0;
-        int persist_from = 0;
-        if (getenv("OSQP_AMD_SNODE_TREE_PERSIST")) persist_from = atoi(getenv("OSQP_AMD_SNODE_TREE_PERSIST"));
         // (It was the default for a while -- from the lowest level with at most three device-fuls of supernodes above, control-1e6
         // 1 169 -> 1 192 it/s -- until the level kernels took their entries flat (k_sn_level_f): a level of a thousand
         // supernodes is now cheaper as a plain launch than inside the launch.  Without it: control-1e6 1 704 -> 1 737 it/s,
         // control T = 8000 5.09 -> 5.56 k, T = 30 000 2.50 -> 2.67 k, T = 800 unchanged.)
-        if (persist_from >= 1 && persist_from < sn_tree_L0) {
-          sn_tree_L0 = persist_from; sn_tree_threads = 512;
+        if (knobs.snode_tree_persist >= 1 && knobs.snode_tree_persist < sn_tree_L0) {
+          sn_tree_L0 = knobs.snode_tree_persist; sn_tree_threads = 512;
           sn_tree_grid = (int)std::min<long long>(cap2, (long long)(j_end - T.lvl_ptr[sn_tree_L0]));
           sn_ticket.alloc(2);
         }
       }
       if (top_end - sn_tree_L0 < 2) sn_tree = false;  // a single level (or none) left: nothing to fuse
     }
-    if (getenv("OSQP_AMD_SETUP_TRACE"))
+    if (knobs.setup_trace)
       fprintf(stderr, "[supernodes] one-launch tree %s: from level %d of %d, %d threads, %d persistent workgroups (0: one per supernode)\n",
               sn_tree ? "on" : "off", sn_tree_L0, T.nlev, sn_tree_threads, sn_tree_grid);
     // the split of the forward rows: where the entries that point at the first level of the one-launch tree (level 1
@@ -497,12 +504,12 @@ struct LdlFactor {
   void setup_top() {
     sn_top_Jt = -1; sn_top_level = -1;
     if (!mf || !sn_tree || mf_big_count == 0) return;
-    if (getenv("OSQP_AMD_SNODE_TOP") && atoi(getenv("OSQP_AMD_SNODE_TOP")) == 0) return;  // A/B runs: rows gathered entry by entry everywhere
+    if (knobs.snode_top == 0) return;  // A/B runs: rows gathered entry by entry everywhere
     // Under a dense top (direct_sndense_kernels.hpp) the long chains of large separators -- what the front vectors were built for --
     // are gone from the launch, and for the levels that remain the plain gathers are the faster form (grid 700 x 700: 2 083 -> 2 409
     // it/s, 1000 x 1000: 920 -> 1 036 without the vectors: a supernode's hand-over is two loops over its children with a barrier
     // each and a panel product by one workgroup): off unless asked for (OSQP_AMD_SNODE_TOP=1; the tests of the vector path do)
-    if (snd_K && !(getenv("OSQP_AMD_SNODE_TOP") && atoi(getenv("OSQP_AMD_SNODE_TOP")) == 1)) return;
+    if (snd_K && knobs.snode_top != 1) return;
     // the lowest level, not below the first level of the one-launch tree, from which every supernode has a panel and a border
     // that fits the LDS the kernel has free (4096 doubles)
     int Lt = T.nlev;
@@ -531,7 +538,7 @@ struct LdlFactor {
     sn_uvec.zero(s);
     e.sync();
     sn_top_Jt = Jt; sn_top_level = Lt;
-    if (getenv("OSQP_AMD_SETUP_TRACE"))
+    if (knobs.setup_trace)
       fprintf(stderr, "[supernodes] top part by front vectors: levels %d .. %d (%d supernodes from %d on; the one-launch tree starts at level %d)\n", Lt,
               T.nlev - 1, T.count - Jt, Jt, sn_tree_L0);
   }
@@ -547,8 +554,6 @@ struct LdlFactor {
     for (int J = 0; J < snd_J0; J++)
       if (T.up[J] >= snd_J0 && mfh_bsz[J] > 0) { bch.push_back(J); boff.push_back(boff.back() + mfh_bsz[J]); }
     snd_nb = (int)bch.size();
-    auto up32 = [&](DevBuf<int> &d, const std::vector<int> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), s); };
-    auto up64 = [&](DevBuf<int64_t> &d, const std::vector<int64_t> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), s); };
     // the order of the pivots inside the dense array: the supernodes of D in postorder of their tree (children ascending), so that
     // the segments of a separator -- a chain -- and then whole subtrees are contiguous; OSQP_AMD_SN_DENSE_ORDER=0: slot order
     std::vector<int> dpos((size_t)K), dinv((size_t)K);
@@ -556,7 +561,7 @@ struct LdlFactor {
       const int nd = T.count - snd_J0;
       std::vector<int> order;
       order.reserve(nd);
-      if (getenv("OSQP_AMD_SN_DENSE_ORDER") && atoi(getenv("OSQP_AMD_SN_DENSE_ORDER")) == 0) { for (int J = snd_J0; J < T.count; J++) order.push_back(J); }
+      if (!knobs.sn_dense_order) { for (int J = snd_J0; J < T.count; J++) order.push_back(J); }
       else {
         std::vector<int> chp((size_t)nd + 1, 0), chl, stack, next((size_t)nd, 0);
         for (int J = snd_J0; J < T.count; J++) if (T.up[J] >= snd_J0) chp[(size_t)(T.up[J] - snd_J0) + 1]++;
@@ -684,7 +689,7 @@ struct LdlFactor {
     const size_t nbk = (size_t)ldD / kDsT;
     dsP1.alloc(nbk * nbk * kDsT); dsP2.alloc(nbk * nbk * kDsT);
     e.sync();
-    if (getenv("OSQP_AMD_SETUP_TRACE"))
+    if (knobs.setup_trace)
       fprintf(stderr, "[supernodes] dense top: levels %d .. %d (%d supernodes, %d pivots, %.1f MB of inverse), %d boundary children (%d one-row, %d with a front vector)\n",
               snd_L0, T.nlev - 1, T.count - snd_J0, K, 8e-6 * (double)ldD * (double)ldD, snd_nb, pend_ptr[K], snd_nv);
   }
@@ -743,20 +748,19 @@ struct LdlFactor {
     gj_tiles.alloc(std::max<size_t>(1, tiles.size())); gj_tiles.upload(tiles.data(), tiles.size(), s);
     e.sync();
     gj_sparse = true;
-    if (getenv("OSQP_AMD_SETUP_TRACE"))
+    if (knobs.setup_trace)
       fprintf(stderr, "[supernodes] dense top: block sweeps touch %.1f %% of the tiles of a full sweep (%d steps)\n",
               100.0 * (double)(tiles.size() / 2) / ((double)nt * (double)nt * (double)(nt + 1) / 2.0), nt);
   }
   void gj_invert(int K, hipStream_t s) {
-    const bool in_registers = !(getenv("OSQP_AMD_GJ_PIVOT_LDS") && atoi(getenv("OSQP_AMD_GJ_PIVOT_LDS")) == 1);   // 1: the round-5 pivot kernel (A/B, test)
-    const bool fuse = in_registers && !(getenv("OSQP_AMD_GJ_FUSE") && atoi(getenv("OSQP_AMD_GJ_FUSE")) == 0);      // 0: the pivot block a launch of its own
+    const bool fuse = !knobs.gj_pivot_lds && knobs.gj_fuse;
     // (the tile lists leave the next pivot tile to the fused workgroup: without it, full sweeps)
-    const bool sparse = gj_sparse && fuse && !(getenv("OSQP_AMD_GJ_SPARSE") && atoi(getenv("OSQP_AMD_GJ_SPARSE")) == 0);  // 0: full sweeps (A/B, test)
+    const bool sparse = gj_sparse && fuse && knobs.gj_sparse;
     if (ldD > K) OQ_LAUNCH(k_gj_pad, dim3(blocks_for(ldD - K)), dim3(kBlock), 0, s, K, ldD, S0a.get());
     const int nt = ldD / 64;
     const dim3 gu(nt, nt);
     auto pivot = [&](int p0, double *Tk) {
-      if (in_registers) OQ_LAUNCH(k_gj_pivot_r, dim3(1), dim3(kGjPivotRThreads), 0, s, K, ldD, p0, (const double *)S0a.get(), Tk, status.get());
+      if (!knobs.gj_pivot_lds) OQ_LAUNCH(k_gj_pivot_r, dim3(1), dim3(kGjPivotRThreads), 0, s, K, ldD, p0, (const double *)S0a.get(), Tk, status.get());
       else {
         // per device, not per process (the library serves several devices): set on every factorisation, as build_mf does
         HIP_CHECK(hipFuncSetAttribute((const void *)k_gj_pivot, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * 2 * kGjK * (kGjK + 1))));
@@ -768,17 +772,12 @@ struct LdlFactor {
       double *Tk = gjT.get() + (size_t)(k & 1) * kGjK * kGjK, *Tn = gjT.get() + (size_t)((k + 1) & 1) * kGjK * kGjK;
       if (k == 0 || !fuse) pivot(p0, Tk);
       const int next = (fuse && k + 1 < nt) ? (sparse ? (gj_next[k] ? 2 : 1) : 2) : 0;
-      if (sparse) {  // only the blocks coupled with the pivot block (gj_symbolic): the others see zeros in the panels
-        const int nr = gj_rptr[k + 1] - gj_rptr[k], ntl = gj_tptr[k + 1] - gj_tptr[k];
-        OQ_LAUNCH(k_gj_panel, dim3(nr), dim3(256), 0, s, ldD, p0, (const double *)S0a.get(), (const double *)Tk, gjW.get(), gjC.get(), (const int *)gj_rows.get() + gj_rptr[k]);
-        OQ_LAUNCH(k_gj_update, dim3(ntl + (next ? 1 : 0)), dim3(256), 0, s, ldD, p0, S0a.get(), (const double *)Tk, (const double *)gjW.get(), (const double *)gjC.get(),
-                  (const int *)gj_tiles.get() + 2 * (size_t)gj_tptr[k], ntl, next, Tn, K, status.get());
-      } else {
-        const int ntl = nt * (nt + 1) / 2;
-        OQ_LAUNCH(k_gj_panel, dim3(nt), dim3(256), 0, s, ldD, p0, (const double *)S0a.get(), (const double *)Tk, gjW.get(), gjC.get(), (const int *)nullptr);
-        OQ_LAUNCH(k_gj_update, dim3(ntl + (next ? 1 : 0)), dim3(256), 0, s, ldD, p0, S0a.get(), (const double *)Tk, (const double *)gjW.get(), (const double *)gjC.get(),
-                  (const int *)nullptr, ntl, next, Tn, K, status.get());
-      }
+      // sparse: only the blocks coupled with the pivot block (gj_symbolic), the others see zeros in the panels
+      const int nr = sparse ? gj_rptr[k + 1] - gj_rptr[k] : nt, ntl = sparse ? gj_tptr[k + 1] - gj_tptr[k] : nt * (nt + 1) / 2;
+      const int *rows = sparse ? gj_rows.get() + gj_rptr[k] : nullptr, *tiles = sparse ? gj_tiles.get() + 2 * (size_t)gj_tptr[k] : nullptr;
+      OQ_LAUNCH(k_gj_panel, dim3(nr), dim3(256), 0, s, ldD, p0, (const double *)S0a.get(), (const double *)Tk, gjW.get(), gjC.get(), rows);
+      OQ_LAUNCH(k_gj_update, dim3(ntl + (next ? 1 : 0)), dim3(256), 0, s, ldD, p0, S0a.get(), (const double *)Tk, (const double *)gjW.get(), (const double *)gjC.get(),
+                tiles, ntl, next, Tn, K, status.get());
     }
     OQ_LAUNCH(k_gj_mirror, gu, dim3(256), 0, s, ldD, S0a.get());
     Sinv = S0a.get();
@@ -843,7 +842,6 @@ struct LdlFactor {
   void lean_device_lists(int q_upper) {
     hipStream_t s = e.stream;
     const int64_t nnzL = S.nnzL;
-    auto up32 = [&](DevBuf<int> &d, const std::vector<int> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), s); };
     up32(mf_snof, mfh_snof); up32(mf_slot, T.slot);
     DevBuf<int> lcol(std::max<int64_t>(1, nnzL)), er(std::max<int64_t>(1, nnzL)), ec(std::max<int64_t>(1, nnzL));
     expand_colptr(N, Lp.get(), nnzL, lcol.get(), s);
@@ -877,10 +875,8 @@ struct LdlFactor {
   // and size class on the host (arrays of one entry per supernode); the two index maps that have one entry per entry of L /
   // per border row are built by device kernels.  Not taken (the level-by-level factorisation stays) when a front does not
   // fit LDS or the update matrices would need more than 8 GB.  OSQP_AMD_MF=0 switches it off.
-  static constexpr int kMfMaxFront = 192;
   bool mf_plan() {
-    const int mode = getenv("OSQP_AMD_MF") ? atoi(getenv("OSQP_AMD_MF")) : 1;
-    if (mode == 0) return false;
+    if (knobs.mf == 0) return false;
     const int count = T.count;
     snd_L0 = snd_J0 = -1; snd_q0 = 0; snd_K = 0;
     mfh_bsz.assign(count, 0); mfh_snof.assign(N, 0);
@@ -888,8 +884,6 @@ struct LdlFactor {
     mf_fmax = 0; mf_big_count = 0; mf_big_fmax = 0;
     mfh_tiles.clear(); mfh_chunks.clear();
     // tests: OSQP_AMD_MF_MAX_FRONT sends smaller fronts through the global-memory kernels too (the zoo at test sizes has none beyond 192 rows)
-    const int max_front = getenv("OSQP_AMD_MF_MAX_FRONT") ? std::min(kMfMaxFront, std::max(1, atoi(getenv("OSQP_AMD_MF_MAX_FRONT")))) : kMfMaxFront;
-    const bool big_ok = !(getenv("OSQP_AMD_MF_BIG") && atoi(getenv("OSQP_AMD_MF_BIG")) == 0);  // 0: the round-5 behaviour (A/B runs)
     // which fronts go through global memory: those beyond LDS, and -- so that the set is closed towards the root: the
     // solves treat the top of the tree by front vectors (direct_sn_kernels.hpp, SnTop), which needs a resident panel for
     // every supernode above a large front -- their ancestors (the last segments of a top separator: a few small fronts at the
@@ -897,9 +891,9 @@ struct LdlFactor {
     mf_is_big.assign(count, 0);
     for (int J = 0; J < count; J++) {
       const int top = T.piv[T.ptr[J + 1] - 1], s_ = T.ptr[J + 1] - T.ptr[J];
-      if (s_ + (S.Lp[top + 1] - S.Lp[top]) > max_front) mf_is_big[J] = 1;
+      if (s_ + (S.Lp[top + 1] - S.Lp[top]) > knobs.mf_max_front) mf_is_big[J] = 1;
     }
-    if (!(getenv("OSQP_AMD_MF_BIG_ANCESTORS") && atoi(getenv("OSQP_AMD_MF_BIG_ANCESTORS")) == 0))
+    if (knobs.mf_big_ancestors)
       for (int J = 0; J < count; J++)  // parents have larger numbers: one ascending pass
         if (mf_is_big[J] && T.up[J] >= 0 && T.ptr[T.up[J] + 1] - T.ptr[T.up[J]] <= kMfbSmax) mf_is_big[T.up[J]] = 1;
     for (int J = 0; J < count; J++) {
@@ -909,7 +903,7 @@ struct LdlFactor {
       // the whole matrix back to the level-by-level factorisation; what still does: a front beyond the 16-bit row indices of
       // `rel` / `loc`, or a supernode of more pivots than the pivot block of that kernel holds
       if (mf_is_big[J]) {
-        if (s_ + b > 65000 || s_ > kMfbSmax || !big_ok) return false;
+        if (s_ + b > 65000 || s_ > kMfbSmax || !knobs.mf_big) return false;
         mf_big_count++;
         mf_big_fmax = std::max(mf_big_fmax, s_ + (int)b);
         mfh_poff[J + 1] = (int64_t)(s_ + b) * s_;
@@ -998,20 +992,17 @@ struct LdlFactor {
   // a place of their own (their sum is small, and a million of them through a free list would be a quadratic plan).
   // mfh_uoff[J] = offset of supernode J, mfh_uoff[count] = doubles in all.  The supernodes of a dense top have no update matrix;
   // their boundary children's live to the end (the dense array is assembled after the last level).
-  static constexpr int64_t kMfShareMin = 16384;
   void place_update_matrices() {
     const int count = T.count;
-    const bool share = !(getenv("OSQP_AMD_MF_SHARE_U") && atoi(getenv("OSQP_AMD_MF_SHARE_U")) == 0);  // 0: every update matrix a place of its own (A/B, tests)
     const int j_end = snd_K ? snd_J0 : count;
-    const int64_t share_min = getenv("OSQP_AMD_MF_SHARE_MIN") ? std::max(1, atoi(getenv("OSQP_AMD_MF_SHARE_MIN"))) : kMfShareMin;  // (tests: small problems)
     auto size_of = [&](int J) { return J < j_end ? (int64_t)mfh_bsz[J] * (mfh_bsz[J] + 1) / 2 : (int64_t)0; };
     int64_t base = 0;
     for (int J = 0; J < count; J++) {
       const int64_t sz = size_of(J);
       mfh_uoff[J] = base;
-      if (!share || sz < share_min) base += sz;
+      if (!knobs.mf_share_u || sz < knobs.mf_share_min) base += sz;
     }
-    if (!share) { mfh_uoff[count] = base; return; }
+    if (!knobs.mf_share_u) { mfh_uoff[count] = base; return; }
     // the large ones: [offset, size) blocks above `base`
     std::vector<std::pair<int64_t, int64_t>> free_list;  // sorted by offset
     int64_t top = base;
@@ -1021,7 +1012,7 @@ struct LdlFactor {
     for (int L = 0; L < T.nlev; L++) {
       for (int J = T.lvl_ptr[L]; J < T.lvl_ptr[L + 1] && J < j_end; J++) {
         const int64_t sz = size_of(J);
-        if (sz < share_min) continue;
+        if (sz < knobs.mf_share_min) continue;
         size_t k = 0;
         while (k < free_list.size() && free_list[k].second < sz) k++;
         if (k < free_list.size()) {
@@ -1053,21 +1044,19 @@ struct LdlFactor {
   // with a block of their thousands of pivots.  OSQP_AMD_SN_DENSE = 0 never, 2 whenever a level fits (tests: small problems).
   void choose_dense_top_over_supernodes() {
     snd_L0 = snd_J0 = -1; snd_q0 = 0; snd_K = 0;
-    const int mode = getenv("OSQP_AMD_SN_DENSE") ? atoi(getenv("OSQP_AMD_SN_DENSE")) : 1;
-    if (mode == 0 || T.nlev < 2) return;
-    const int kmax = getenv("OSQP_AMD_SN_DENSE_MAX") ? atoi(getenv("OSQP_AMD_SN_DENSE_MAX")) : 4300;
+    if (knobs.sn_dense == 0 || T.nlev < 2) return;
     int L = T.nlev;
-    while (L - 1 >= 1 && N - T.ptr[T.lvl_ptr[L - 1]] <= kmax) L--;
+    while (L - 1 >= 1 && N - T.ptr[T.lvl_ptr[L - 1]] <= knobs.sn_dense_max) L--;
     // ... and on while the next level down is still a chain (at most four supernodes: a level of pure latency in the solves and of
     // a handful of workgroups in the factorisation), up to 8 192 pivots: the separators of a 3-D structure are planes -- a
     // 50 x 50 x 50 grid has 63 levels of one supernode each above 4 247 pivots and is still at 1.5 supernodes a level at 7 817
     // (293 -> 694 it/s for 22 -> 32 ms of refactorisation); a 700 x 700 grid is at eleven a level below its 4 137 and stops there.
     // (Not when the size was asked for explicitly.)
-    if (!getenv("OSQP_AMD_SN_DENSE_MAX"))
+    if (!knobs.sn_dense_max_set)
       while (L - 1 >= 1 && T.lvl_ptr[L] - T.lvl_ptr[L - 1] <= 4 && N - T.ptr[T.lvl_ptr[L - 1]] <= 8192) L--;
     if (L == T.nlev) return;
     const int K = N - T.ptr[T.lvl_ptr[L]];
-    if (mode != 2 && (mf_big_count == 0 || T.nlev - L < 8 || K < 256)) return;
+    if (knobs.sn_dense != 2 && (mf_big_count == 0 || T.nlev - L < 8 || K < 256)) return;
     snd_L0 = L; snd_J0 = T.lvl_ptr[L]; snd_q0 = T.ptr[snd_J0]; snd_K = K;
   }
   // size classes of the fronts: rows at most 16 / 48 (16 lanes / a wavefront each, fixed slabs), then workgroups with the
@@ -1076,13 +1065,15 @@ struct LdlFactor {
   static constexpr int kMfWideCount = 192;  // launches of at most this many workgroup-class fronts give each 1024 threads (the device is not full either way)
   static constexpr int kMfClasses = 7, kMfBig = 100;
   static constexpr int kMfClassCap[kMfClasses] = {16, 48, 64, 80, 96, 128, kMfMaxFront};
+  MfArgs mf_args(const MfLaunch &l) const {
+    return MfArgs{mf_list.get() + l.off, l.count, l.fcap, sn_ptr.get(), sn_piv.get(), mf_bsz.get(), mf_uoff.get(), mf_reloff.get(), mf_rel.get(), mf_chp.get(),
+                  mf_chl.get(), Lp.get(), mf_loc.get(), Lx.get(), D.get(), Dinv.get(), mf_U.get(), status.get(), sn_Wc.get(), sn_Wr.get(), sn_woff.get()};
+  }
   void build_mf() {
     mf = false;
     if (!sn || !mf_ok) return;
     const int count = T.count;
     hipStream_t s = e.stream;
-    auto up64 = [&](DevBuf<int64_t> &d, const std::vector<int64_t> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), s); };
-    auto up32 = [&](DevBuf<int> &d, const std::vector<int> &h) { d.alloc(std::max<size_t>(1, h.size())); d.upload(h.data(), h.size(), s); };
     if (!mf_snof.n) { up32(mf_snof, mfh_snof); up32(mf_slot, T.slot); }
     up32(mf_bsz, mfh_bsz); up32(mf_chp, mfh_chp); up32(mf_chl, mfh_chl); up32(mf_list, mfh_list);
     up64(mf_uoff, mfh_uoff); up64(mf_reloff, mfh_reloff);
@@ -1103,9 +1094,7 @@ struct LdlFactor {
     if (err) throw Error(6, "internal: the fronts of the supernodes do not cover the pattern of L (code " + std::to_string(err) + ")");
     for (const MfLaunch &l : mf_launches)  // where the 64-row pieces of the big fronts begin in the columns of L (k_mfb_rows)
       if (l.cls == kMfBig && l.chunk_count) {
-        MfArgs a{mf_list.get() + l.off, l.count, l.fcap, sn_ptr.get(), sn_piv.get(), mf_bsz.get(), mf_uoff.get(), mf_reloff.get(), mf_rel.get(),
-                 mf_chp.get(), mf_chl.get(), Lp.get(), mf_loc.get(), Lx.get(), D.get(), Dinv.get(), mf_U.get(), status.get(),
-                 sn_Wc.get(), sn_Wr.get(), sn_woff.get()};
+        const MfArgs a = mf_args(l);
         MfbSplitArgs sa{MfbArgs{a, mf_poff.get(), mf_panel.get(), nullptr}, mf_wide.get(), mf_nwide.get(), mf_chunks.get() + 2 * (size_t)l.chunk_off,
                         mf_ct0.get() + (size_t)l.chunk_off * kMfbSmax};
         OQ_LAUNCH(k_mfb_chunk_t0, dim3(blocks_for((int64_t)l.chunk_count * kMfbSmax, 256)), dim3(256), 0, s, l.chunk_count, sa);
@@ -1120,7 +1109,7 @@ struct LdlFactor {
       HIP_CHECK(hipFuncSetAttribute((const void *)k_mfb_pivot, hipFuncAttributeMaxDynamicSharedMemorySize, std::max((int)mfb_panel_lds(0), 65536)));
       HIP_CHECK(hipFuncSetAttribute((const void *)k_mfb_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kMfbSmax * 64 * sizeof(double))));
     }
-    if (getenv("OSQP_AMD_SETUP_TRACE")) {
+    if (knobs.setup_trace) {
       for (const MfLaunch &l : mf_launches) fprintf(stderr, "[fronts] class %d: %d fronts, slab for %d rows\n", l.cls, l.count, l.fcap);
       fprintf(stderr, "[fronts] beyond LDS: %d fronts (largest %d rows), %.1f MB of panels, update matrices of all fronts %.1f MB\n", mf_big_count,
               mf_big_fmax, 8e-6 * (double)mfh_poff[count], 8e-6 * (double)mfh_uoff[count]);
@@ -1128,15 +1117,12 @@ struct LdlFactor {
     std::vector<int>().swap(mfh_snof); std::vector<int>().swap(mfh_list); std::vector<int>().swap(mfh_chl);
     mf = true;
   }
-  const bool mfb_split = !(getenv("OSQP_AMD_MFB_SPLIT") && atoi(getenv("OSQP_AMD_MFB_SPLIT")) == 0);  // 0: one workgroup per big front (A/B, tests)
   void run_mf(hipStream_t s) {
     for (const MfLaunch &l : mf_launches) {
-      MfArgs a{mf_list.get() + l.off, l.count, l.fcap, sn_ptr.get(), sn_piv.get(), mf_bsz.get(), mf_uoff.get(), mf_reloff.get(), mf_rel.get(),
-               mf_chp.get(), mf_chl.get(), Lp.get(), mf_loc.get(), Lx.get(), D.get(), Dinv.get(), mf_U.get(), status.get(),
-               sn_Wc.get(), sn_Wr.get(), sn_woff.get()};
+      const MfArgs a = mf_args(l);
       if (l.cls == kMfBig) {
         MfbArgs g{a, mf_poff.get(), mf_panel.get(), mf_tiles.get() + 3 * (size_t)l.tile_off};
-        if (mfb_split) {  // the pivot blocks, then the panels in 64-row pieces (mfront_big.hpp)
+        if (knobs.mfb_split) {  // the pivot blocks, then the panels in 64-row pieces (mfront_big.hpp)
           MfbSplitArgs sa{g, mf_wide.get(), mf_nwide.get(), mf_chunks.get() + 2 * (size_t)l.chunk_off, mf_ct0.get() + (size_t)l.chunk_off * kMfbSmax};
           OQ_LAUNCH(k_mfb_pivot, dim3(l.count), dim3(kMfbPanelThreads), mfb_panel_lds(0), s, sa);
           if (l.chunk_count) OQ_LAUNCH(k_mfb_rows, dim3(l.chunk_count), dim3(256), 2 * kMfbSmax * 64 * sizeof(double), s, sa);
@@ -1150,34 +1136,29 @@ struct LdlFactor {
         // its workgroup size -- 1024 threads instead of four wavefronts on an otherwise empty unit (round 6: grid 700 x 700, 653
         // fronts of up to 187 rows in one launch, 821 us) --, one beyond 40 KB shares it with one other: 512
         const size_t slab = mf_slab_doubles(l.fcap) * sizeof(double);
-        const int wide = getenv("OSQP_AMD_MF_WIDE") ? atoi(getenv("OSQP_AMD_MF_WIDE")) : 1;  // 0: the round-5 rule (A/B)
-        if (l.count <= kMfWideCount || (wide && slab > 80 * 1024)) OQ_LAUNCH(k_mf_front<1024>, dim3(l.count), dim3(1024), slab, s, a);
-        else if (wide && slab > 40 * 1024) OQ_LAUNCH(k_mf_front<512>, dim3(l.count), dim3(512), slab, s, a);
+        if (l.count <= kMfWideCount || (knobs.mf_wide && slab > 80 * 1024)) OQ_LAUNCH(k_mf_front<1024>, dim3(l.count), dim3(1024), slab, s, a);
+        else if (knobs.mf_wide && slab > 40 * 1024) OQ_LAUNCH(k_mf_front<512>, dim3(l.count), dim3(512), slab, s, a);
         else OQ_LAUNCH(k_mf_front<256>, dim3(l.count), dim3(kMfBlock), slab, s, a);
       }
     }
   }
 
-  // rows at least this long (mean over a level) go through the work-row form of phase 2: the thread-per-entry merge
-  // of two rows of 50-300 entries is ~100 us of dependent loads, the wave-per-entry product ~7 us (control, T = 800)
-  static double long_row_mean() { const char *v = getenv("OSQP_AMD_LONG_ROW_MEAN"); return v ? atof(v) : 24.0; }
+  // rows at least knobs.long_row_mean long (mean over a level) go through the work-row form of phase 2: the thread-per-entry
+  // merge of two rows of 50-300 entries is ~100 us of dependent loads, the wave-per-entry product ~7 us (control, T = 800)
   static int pick(double mean) { return mean <= 2.0 ? 1 : (mean <= 8.0 ? 4 : (mean <= 32.0 ? 16 : 64)); }
 
-  static double solve_cost_us(const Symbolic &Y, double chain_level_us = 1.4) {
-    return level_solve_cost_us(Y, kChainRows, dense_max(), kDenseMin, chain_level_us);
+  double solve_cost_us(const Symbolic &Y, double chain_level_us = 1.4) const {
+    return level_solve_cost_us(Y, kChainRows, knobs.dense_max, kDenseMin, chain_level_us);
   }
 
   // The dense top block (symbolic.hpp, choose_dense_top)
   // Largest block: 12288 pivots (1.2 GB of inverse, a 1.2 GB product per solve -- ~0.2 ms -- against 24 000 dependent steps
   // of the chain it replaces); up to round 3 the limit was 2048 because the inversion was one pass over the array per two
   // pivots.  OSQP_AMD_DENSE_MAX overrides.
-  static constexpr int kDenseSparseMax = 1024, kDenseMin = 32, kDenseBlocked = 512;
-  static int dense_max() { static const int v = getenv("OSQP_AMD_DENSE_MAX") ? atoi(getenv("OSQP_AMD_DENSE_MAX")) : 12288; return v; }
+  static constexpr int kDenseBlocked = 512;
   void choose_dense_block() {
-    lD = nlev; cD = N; kD = 0;
-    static const bool enabled = !(getenv("OSQP_AMD_DENSE_TOP") && atoi(getenv("OSQP_AMD_DENSE_TOP")) == 0);
-    kD_dense = false;
-    if (enabled && allow_dense_top) choose_dense_top(S, kChainRows, dense_max(), kDenseSparseMax, kDenseMin, lD, cD, kD, &kD_dense);
+    lD = nlev; cD = N; kD = 0; kD_dense = false;
+    if (knobs.dense_top && allow_dense_top) choose_dense_top(S, kChainRows, knobs.dense_max, kDenseSparseMax, kDenseMin, lD, cD, kD, &kD_dense);
   }
   // columns of the block whose work rows (N doubles each) are held at once: at most 256 MB
   int dense_batch() const { return (int)std::max<size_t>(1, std::min<size_t>((size_t)kD, ((size_t)256 << 20) / ((size_t)N * sizeof(double)))); }
@@ -1275,12 +1256,13 @@ struct LdlFactor {
       const bool through_w = entries > 0 && long_rows[l];
       double *wf = through_w ? W.get() + (size_t)(half ^ 1) * w_half : nullptr, *wc = p1 > p0 ? W.get() + (size_t)half * w_half : nullptr;
       const int G = (through_w || p1 > p0) ? 64 : pick((double)(S.Rp[c1] - S.Rp[c0]) / (double)std::max(1, c1 - c0));
-      if (G == 1) OQ_LAUNCH(k_ldl_diag_g<1>, dim3(blocks_for(c1 - c0)), dim3(kBlock), 0, s, c0, c1, Lx.get(), Rp.get(), Rj.get(), Rmap.get(), D.get(), Dinv.get(), status.get());
-      else if (G == 4) OQ_LAUNCH(k_ldl_diag_g<4>, dim3(blocks_for((int64_t)(c1 - c0) * 4)), dim3(kBlock), 0, s, c0, c1, Lx.get(), Rp.get(), Rj.get(), Rmap.get(), D.get(), Dinv.get(), status.get());
-      else if (G == 16) OQ_LAUNCH(k_ldl_diag_g<16>, dim3(blocks_for((int64_t)(c1 - c0) * 16)), dim3(kBlock), 0, s, c0, c1, Lx.get(), Rp.get(), Rj.get(), Rmap.get(), D.get(), Dinv.get(), status.get());
-      else
-      OQ_LAUNCH(k_ldl_diag_w, dim3(blocks_for((int64_t)(c1 - c0 + (p1 - p0)) * 64)), dim3(kBlock), 0, s, c0, c1, N, Lx.get(), Rp.get(), Rj.get(),
-                Rmap.get(), D.get(), Dinv.get(), status.get(), wf, p0, p1, wc);
+      with_lanes(G, [&](auto g) {
+        if constexpr (g.value == 64)  // a wavefront per row, and the work rows of the previous level
+          OQ_LAUNCH(k_ldl_diag_w, dim3(blocks_for((int64_t)(c1 - c0 + (p1 - p0)) * 64)), dim3(kBlock), 0, s, c0, c1, N, Lx.get(), Rp.get(), Rj.get(),
+                    Rmap.get(), D.get(), Dinv.get(), status.get(), wf, p0, p1, wc);
+        else
+          OQ_LAUNCH(k_ldl_diag_g<g.value>, dim3(blocks_for((int64_t)(c1 - c0) * g.value)), dim3(kBlock), 0, s, c0, c1, Lx.get(), Rp.get(), Rj.get(), Rmap.get(), D.get(), Dinv.get(), status.get());
+      });
       p0 = p1 = 0;
       if (through_w) {
         OQ_LAUNCH(k_ldl_entries_w, dim3(blocks_for(entries * 64)), dim3(kBlock), 0, s, c0, c1, N, Lp.get(), Li.get(), Lx.get(),
@@ -1289,10 +1271,10 @@ struct LdlFactor {
       } else if (entries > 0) {
         // long rows, too many columns for work rows: a wavefront per entry, bisection instead of the merge
         const double mean = (double)(S.Rp[c1] - S.Rp[c0]) / (double)std::max(1, c1 - c0);
-        if (mean >= long_row_mean() && entries <= ((int64_t)1 << 18))  // few entries: the level is latency, not throughput
+        if (mean >= knobs.long_row_mean && entries <= ((int64_t)1 << 18))  // few entries: the level is latency, not throughput
           OQ_LAUNCH(k_ldl_entries_bs<64>, dim3(blocks_for(entries * 64)), dim3(kBlock), 0, s, c0, c1, Lp.get(), Li.get(), Lx.get(), Rp.get(),
                     Rj.get(), Rmap.get(), D.get(), Dinv.get(), (const int *)Lcol.get());
-        else if (mean >= long_row_mean() && entries * 16 < ((int64_t)1 << 31))
+        else if (mean >= knobs.long_row_mean && entries * 16 < ((int64_t)1 << 31))
           OQ_LAUNCH(k_ldl_entries_bs<16>, dim3(blocks_for(entries * 16)), dim3(kBlock), 0, s, c0, c1, Lp.get(), Li.get(), Lx.get(), Rp.get(),
                     Rj.get(), Rmap.get(), D.get(), Dinv.get(), (const int *)Lcol.get());
         else
@@ -1332,7 +1314,7 @@ struct LdlFactor {
         worst = std::max(worst, std::fabs(r));
       }
       dense_residual = finite ? worst / 2.5 : INFINITY;  // relative to max |v|
-      if (!(dense_residual <= dense_probe_tol())) return 7;
+      if (!(dense_residual <= knobs.dense_probe_tol)) return 7;
     }
     if (st[1] != n) return 5;
     return 0;
@@ -1389,135 +1371,104 @@ struct LdlFactor {
     OQ_LAUNCH(k_dense_apply, dim3(blocks_for((int64_t)kD * 64)), dim3(kBlock), 0, s, kD, kD, (const double *)S0chk.get(), (const double *)probe_w.get(), probe_r.get());
   }
 
-#define OQ_CHAIN_CASE(UU, LL)                                                                                                      \
-  if (t.U == UU && t.L == LL) {                                                                                                     \
-    if (fwd_) OQ_LAUNCH((k_fwd_chain_lds<UU, LL>), dim3(1), dim3(kChainThreads), 0, s, t.a, t.b, level_ptr.get(), Rsplit.get(),    \
-                        Rp.get(), Rj.get(), Rx.get(), bp.get());                                                                    \
-    else OQ_LAUNCH((k_bwd_chain_lds<UU, LL>), dim3(1), dim3(kChainThreads), 0, s, t.a, t.b, level_ptr.get(), Lp.get(),            \
-                   Lsplit.get(), Li.get(), Lx.get(), bp.get());                                                                     \
-    return;                                                                                                                         \
+  template <int U, int L>
+  void launch_chain_as(const Step &t, bool fwd_, hipStream_t s) {
+    if (fwd_) OQ_LAUNCH((k_fwd_chain_lds<U, L>), dim3(1), dim3(kChainThreads), 0, s, t.a, t.b, level_ptr.get(), Rsplit.get(),
+                        Rp.get(), Rj.get(), Rx.get(), bp.get());
+    else OQ_LAUNCH((k_bwd_chain_lds<U, L>), dim3(1), dim3(kChainThreads), 0, s, t.a, t.b, level_ptr.get(), Lp.get(),
+                   Lsplit.get(), Li.get(), Lx.get(), bp.get());
   }
   void launch_chain(const Step &t, bool fwd_, hipStream_t s) {
-    OQ_CHAIN_CASE(2, 64) OQ_CHAIN_CASE(4, 64) OQ_CHAIN_CASE(8, 64)
-    OQ_CHAIN_CASE(2, 16) OQ_CHAIN_CASE(4, 16) OQ_CHAIN_CASE(8, 16)
-    OQ_CHAIN_CASE(2, 4) OQ_CHAIN_CASE(4, 4)
+    if (t.L == 64) { if (t.U == 2) return launch_chain_as<2, 64>(t, fwd_, s); if (t.U == 4) return launch_chain_as<4, 64>(t, fwd_, s); if (t.U == 8) return launch_chain_as<8, 64>(t, fwd_, s); }
+    if (t.L == 16) { if (t.U == 2) return launch_chain_as<2, 16>(t, fwd_, s); if (t.U == 4) return launch_chain_as<4, 16>(t, fwd_, s); if (t.U == 8) return launch_chain_as<8, 16>(t, fwd_, s); }
+    if (t.L == 4) { if (t.U == 2) return launch_chain_as<2, 4>(t, fwd_, s); if (t.U == 4) return launch_chain_as<4, 4>(t, fwd_, s); }
     throw Error(6, "internal: no chain kernel for this step");
   }
-#undef OQ_CHAIN_CASE
-  void launch_fwd_chain(const Step &t, hipStream_t s) { launch_chain(t, true, s); }
-  void launch_bwd_chain(const Step &t, hipStream_t s) { launch_chain(t, false, s); }
 
-  // skip_first_fwd / skip_last_bwd: those two level steps are folded into the kernels around the solve (fused_ends)
+  // The direction-dependent operands of a supernode level, unpacked at the launch; launch_sn<kernel>: `head` are its own leading arguments
+  struct SnOperands { const int *ptr; const int64_t *woff, *Ep; const int *Ej; const double *Ex, *W, *Dinv; double *b; };
+  SnOperands sn_operands(bool fw) const {
+    return SnOperands{sn_ptr.get(), sn_woff.get(), fw ? sn_Fp.get() : sn_Gp.get(), fw ? sn_Fj.get() : sn_Gi.get(), fw ? sn_Fx.get() : sn_Gx.get(),
+                      fw ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get()};
+  }
+  template <auto kern, typename... H>
+  void launch_sn(int grid, const SnOperands &o, hipStream_t s, H... head) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSnThreads), 0, s, head..., o.ptr, o.woff, o.Ep, o.Ej, o.Ex, o.W, o.Dinv, o.b);
+    post_launch(__PRETTY_FUNCTION__, s);  // (OQ_LAUNCH's second half: the name with the instantiation in it, `kern = ...`)
+  }
   // a level of many supernodes: a wavefront each, a quarter wavefront for the small ones that come first in the level
   // (k_sn_level_w); a level of few: a workgroup each
-#define OQ_SN_LEVEL_W(LA, FWD, GS, JA, JB)                                                                                            \
-  OQ_LAUNCH((k_sn_level_w<LA, FWD, GS>), dim3(((JB) - (JA) + 4 * (64 / GS) - 1) / (4 * (64 / GS))), dim3(kSnThreads), 0, s, JA, JB, sn_ptr.get(), \
-            sn_woff.get(), FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(), FWD ? sn_Fx.get() : sn_Gx.get(),          \
-            FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get())
-#define OQ_SN_LEVEL(LA, FWD, L)                                                                                                   \
-  do {                                                                                                                            \
-    const int cnt_ = T.lvl_ptr[L + 1] - T.lvl_ptr[L];                                                                             \
-    if (cnt_ >= sn_wave_min_fixed) {                                                                                                \
-      const int mid_ = T.lvl_ptr[L] + T.lvl_small[L];                                                                             \
-      /* the single pivots the level starts with: forward nothing to do at level 0, backward a lane each */                       \
-      const int ones_ = sn_singles ? T.lvl_single[L] : 0, first_ = T.lvl_ptr[L] + ((FWD && L > 0) ? 0 : ones_);                   \
-      if (!FWD && ones_ > 0)                                                                                                      \
-        OQ_LAUNCH(k_sn_single_bwd, dim3(blocks_for(ones_)), dim3(kBlock), 0, s, T.ptr[T.lvl_ptr[L]], ones_, sn_Gp.get(),          \
-                  sn_Gi.get(), sn_Gx.get(), sn_Dinv.get(), bp.get());                                                             \
-      /* a wide level is bound by rows in flight x latency, not by the latency of one row: a notch fewer lanes per row */         \
-      if (mid_ > first_) OQ_SN_LEVEL_W((LA == 64 ? 16 : (LA == 16 ? 4 : LA)), FWD, 16, first_, mid_);                             \
-      if (T.lvl_ptr[L + 1] > mid_ && !lvl_fold.empty() && lvl_fold[L])                                                            \
-        OQ_LAUNCH((k_sn_level_wf<FWD, true>), dim3((T.lvl_ptr[L + 1] - mid_ + 3) / 4), dim3(kSnThreads), 0, s, mid_,               \
-                  T.lvl_ptr[L + 1], sn_ptr.get(), sn_woff.get(), FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(),  \
-                  FWD ? sn_Fx.get() : sn_Gx.get(), FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get());                      \
-      else if (T.lvl_ptr[L + 1] > mid_ && sn_flat && !(FWD && L == 0))                                                            \
-        OQ_LAUNCH((k_sn_level_wf<FWD, false>), dim3((T.lvl_ptr[L + 1] - mid_ + 3) / 4), dim3(kSnThreads), 0, s, mid_,              \
-                  T.lvl_ptr[L + 1], sn_ptr.get(), sn_woff.get(), FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(),  \
-                  FWD ? sn_Fx.get() : sn_Gx.get(), FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get());                      \
-      else if (T.lvl_ptr[L + 1] > mid_) OQ_SN_LEVEL_W((LA == 64 ? 16 : (LA == 16 ? 4 : LA)), FWD, 64, mid_, T.lvl_ptr[L + 1]);     \
-    } else if (sn_flat && !lvl_fold.empty() && lvl_fold[L])                                                                       \
-      OQ_LAUNCH((k_sn_level_f<FWD, true>), dim3(cnt_), dim3(kSnThreads), 0, s, T.lvl_ptr[L], sn_ptr.get(), sn_woff.get(),          \
-                FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(), FWD ? sn_Fx.get() : sn_Gx.get(),                  \
-                FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get());                                                        \
-    else if (sn_flat)                                                                                                             \
-      OQ_LAUNCH((k_sn_level_f<FWD, false>), dim3(cnt_), dim3(kSnThreads), 0, s, T.lvl_ptr[L], sn_ptr.get(), sn_woff.get(),         \
-                FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(), FWD ? sn_Fx.get() : sn_Gx.get(),                  \
-                FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get());                                                        \
-    else if (cnt_ >= kSnBusyLevel)  /* more workgroups than the device holds at once: rows in flight count, as above */         \
-      OQ_LAUNCH((k_sn_level<(LA == 64 ? 16 : (LA == 16 ? 4 : LA)), FWD>), dim3(cnt_), dim3(kSnThreads), 0, s, T.lvl_ptr[L], sn_ptr.get(), \
-                sn_woff.get(), FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(), FWD ? sn_Fx.get() : sn_Gx.get(),  \
-                FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get());                                                        \
-    else                                                                                                                          \
-      OQ_LAUNCH((k_sn_level<LA, FWD>), dim3(cnt_), dim3(kSnThreads), 0, s, T.lvl_ptr[L], sn_ptr.get(),                           \
-                sn_woff.get(), FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(), FWD ? sn_Fx.get() : sn_Gx.get(),  \
-                FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), bp.get());                                                        \
-  } while (0)
-#define OQ_SN_TREE(FWD)                                                                                                           \
-  if (sn_tree_threads == 512) OQ_SN_TREE_N(FWD, 512); else OQ_SN_TREE_N(FWD, 1024)
-#define OQ_SN_TREE_N(FWD, NT_)                                                                                                    \
-  OQ_LAUNCH((k_sn_tree<FWD, NT_>), dim3(sn_tree_grid ? sn_tree_grid : sn_j_end() - T.lvl_ptr[sn_tree_L0]), dim3(NT_), 0, s, sn_top_args(), T.lvl_ptr[sn_tree_L0], sn_j_end(), sn_ptr.get(),    \
-            sn_woff.get(), FWD ? sn_Fp.get() : sn_Gp.get(), FWD ? sn_Fsplit.get() : sn_Gp.get(), FWD ? sn_Fj.get() : sn_Gi.get(),      \
-            FWD ? sn_Fx.get() : sn_Gx.get(), FWD ? sn_Wc.get() : sn_Wr.get(), sn_Dinv.get(), sn_up.get(), sn_waits.get(),          \
-            FWD ? sn_pending.get() : sn_ready.get(), sn_fault, bp.get(), sn_tree_grid ? sn_ticket.get() + (FWD ? 0 : 1) : (int *)nullptr)
+  template <int LA, bool FWD>
+  void launch_sn_level(int L, const SnOperands &o, hipStream_t s) {
+    constexpr int LW = fewer_lanes(LA);
+    const int J0 = T.lvl_ptr[L], J1 = T.lvl_ptr[L + 1], cnt = J1 - J0;
+    const bool folded = !lvl_fold.empty() && lvl_fold[L];
+    if (cnt >= knobs.snode_wave_min) {
+      const int mid = J0 + T.lvl_small[L];
+      // the single pivots the level starts with: forward nothing to do at level 0, backward a lane each
+      const int ones = knobs.snode_single ? T.lvl_single[L] : 0, first = J0 + ((FWD && L > 0) ? 0 : ones);
+      if (!FWD && ones > 0)
+        OQ_LAUNCH(k_sn_single_bwd, dim3(blocks_for(ones)), dim3(kBlock), 0, s, T.ptr[J0], ones, o.Ep, o.Ej, o.Ex, o.Dinv, o.b);
+      // a wide level is bound by rows in flight x latency, not by the latency of one row: a notch fewer lanes per row
+      if (mid > first) launch_sn<k_sn_level_w<LW, FWD, 16>>((mid - first + 15) / 16, o, s, first, mid);
+      if (J1 > mid && folded) launch_sn<k_sn_level_wf<FWD, true>>((J1 - mid + 3) / 4, o, s, mid, J1);
+      else if (J1 > mid && knobs.snode_flat && !(FWD && L == 0)) launch_sn<k_sn_level_wf<FWD, false>>((J1 - mid + 3) / 4, o, s, mid, J1);
+      else if (J1 > mid) launch_sn<k_sn_level_w<LW, FWD, 64>>((J1 - mid + 3) / 4, o, s, mid, J1);
+    } else if (knobs.snode_flat && folded) launch_sn<k_sn_level_f<FWD, true>>(cnt, o, s, J0);
+    else if (knobs.snode_flat) launch_sn<k_sn_level_f<FWD, false>>(cnt, o, s, J0);
+    else if (cnt >= kSnBusyLevel) launch_sn<k_sn_level<LW, FWD>>(cnt, o, s, J0);  // more workgroups than the device holds at once: rows in flight count, as above
+    else launch_sn<k_sn_level<LA, FWD>>(cnt, o, s, J0);
+  }
+  template <bool FWD>
+  void launch_sn_tree(const SnOperands &o, hipStream_t s) {
+    const int J0 = T.lvl_ptr[sn_tree_L0];
+    auto launch = [&](auto nt) {
+      OQ_LAUNCH((k_sn_tree<FWD, decltype(nt)::value>), dim3(sn_tree_grid ? sn_tree_grid : sn_j_end() - J0), dim3(decltype(nt)::value), 0, s, sn_top_args(), J0,
+                sn_j_end(), o.ptr, o.woff, o.Ep, FWD ? sn_Fsplit.get() : sn_Gp.get(), o.Ej, o.Ex, o.W, o.Dinv, sn_up.get(), sn_waits.get(),
+                FWD ? sn_pending.get() : sn_ready.get(), sn_fault, o.b, sn_tree_grid ? sn_ticket.get() + (FWD ? 0 : 1) : (int *)nullptr);
+    };
+    if (sn_tree_threads == 512) launch(std::integral_constant<int, 512>{});
+    else launch(std::integral_constant<int, 1024>{});
+  }
   // the blocks of the supernodes that the wavefront form solves are kept folded (k_sn_fold / sn_block_fold); fixed at setup:
   // the levels are chosen by the same count the launches look at
-  const bool sn_fold = !(getenv("OSQP_AMD_SNODE_FOLD") && atoi(getenv("OSQP_AMD_SNODE_FOLD")) == 0) &&
-                       !(getenv("OSQP_AMD_SNODE_FLAT") && atoi(getenv("OSQP_AMD_SNODE_FLAT")) == 0);
-  const int sn_wave_min_fixed = sn_wave_min();
-  const bool sn_fold_wg = !(getenv("OSQP_AMD_SNODE_FOLD") && atoi(getenv("OSQP_AMD_SNODE_FOLD")) == 2);  // 2: wavefront-form levels only
   std::vector<char> lvl_fold;  // per level: the blocks of its larger supernodes are folded (decided once: a factor that falls
                                // back from k_sn_tree to one launch per level keeps reading them the way they are stored)
   void fold_blocks(hipStream_t s) {
-    if (!sn || !sn_fold) return;
+    if (!sn || knobs.snode_fold == 0 || !knobs.snode_flat) return;
     if (lvl_fold.empty()) {
       lvl_fold.assign(T.nlev, 0);
       for (int L = 0; L < T.nlev; L++) {
         const int cnt = T.lvl_ptr[L + 1] - T.lvl_ptr[L], mid = T.lvl_ptr[L] + T.lvl_small[L];
         // the larger supernodes of a level in the wavefront form, every supernode of a level in the workgroup form
         // (k_sn_level_f); the levels from sn_tree_L0 on are solved by k_sn_tree whatever their count: packed triangles
-        lvl_fold[L] = (cnt >= sn_wave_min_fixed ? T.lvl_ptr[L + 1] > mid : sn_fold_wg) && !(sn_tree && L >= sn_tree_L0);
+        lvl_fold[L] = (cnt >= knobs.snode_wave_min ? T.lvl_ptr[L + 1] > mid : knobs.snode_fold != 2) && !(sn_tree && L >= sn_tree_L0);
       }
     }
     for (int L = 0; L < sn_l_end(); L++) {  // (the blocks of a dense top are never formed)
       const int cnt = T.lvl_ptr[L + 1] - T.lvl_ptr[L];
-      const int mid = cnt >= sn_wave_min_fixed ? T.lvl_ptr[L] + T.lvl_small[L] : T.lvl_ptr[L];
+      const int mid = cnt >= knobs.snode_wave_min ? T.lvl_ptr[L] + T.lvl_small[L] : T.lvl_ptr[L];
       if (!lvl_fold[L]) continue;
       OQ_LAUNCH(k_sn_fold<true>, dim3(T.lvl_ptr[L + 1] - mid), dim3(64), 0, s, mid, sn_ptr.get(), sn_woff.get(), sn_Wc.get());
       OQ_LAUNCH(k_sn_fold<false>, dim3(T.lvl_ptr[L + 1] - mid), dim3(64), 0, s, mid, sn_ptr.get(), sn_woff.get(), sn_Wr.get());
     }
   }
-  const bool sn_flat = !(getenv("OSQP_AMD_SNODE_FLAT") && atoi(getenv("OSQP_AMD_SNODE_FLAT")) == 0);  // k_sn_level_f / _wf
-  const bool sn_singles = !(getenv("OSQP_AMD_SNODE_SINGLE") && atoi(getenv("OSQP_AMD_SNODE_SINGLE")) == 0);
-  // OSQP_AMD_SNODE_WAVE_MIN (tests): supernodes in a level from which the wavefront / quarter-wavefront form is used
-  static int sn_wave_min() { const char *v = getenv("OSQP_AMD_SNODE_WAVE_MIN"); return v ? atoi(v) : kSnWaveLevel; }
   int sn_l_end() const { return snd_K ? snd_L0 : T.nlev; }   // levels / supernodes below the dense top (all of them without one)
   int sn_j_end() const { return snd_K ? snd_J0 : T.count; }
   void run_supernodes() {
     hipStream_t s = e.stream;
     const bool tree = sn_tree && sn_tree_L0 < sn_l_end();
     const int plain = tree ? sn_tree_L0 : sn_l_end();  // levels [0, plain): one launch each; the rest: one launch per direction
-    for (int L = 0; L < plain; L++) switch (sn_lanes_f[L]) {
-      case 1: OQ_SN_LEVEL(1, true, L); break;
-      case 4: OQ_SN_LEVEL(4, true, L); break;
-      case 16: OQ_SN_LEVEL(16, true, L); break;
-      default: OQ_SN_LEVEL(64, true, L); break;
-    }
+    const SnOperands of = sn_operands(true), ob = sn_operands(false);
+    for (int L = 0; L < plain; L++) with_lanes(sn_lanes_f[L], [&](auto la) { launch_sn_level<decltype(la)::value, true>(L, of, s); });
     if (tree && sn_tree_grid) HIP_CHECK(hipMemsetAsync(sn_ticket.get(), 0, 2 * sizeof(int), s));
-    if (tree) { OQ_SN_TREE(true); }
+    if (tree) launch_sn_tree<true>(of, s);
     if (snd_K) solve_dense_top(s, tree);
-    if (tree) { OQ_SN_TREE(false); }
-    for (int L = plain - 1; L >= 0; L--) switch (sn_lanes_b[L]) {
-      case 1: OQ_SN_LEVEL(1, false, L); break;
-      case 4: OQ_SN_LEVEL(4, false, L); break;
-      case 16: OQ_SN_LEVEL(16, false, L); break;
-      default: OQ_SN_LEVEL(64, false, L); break;
-    }
+    if (tree) launch_sn_tree<false>(ob, s);
+    for (int L = plain - 1; L >= 0; L--) with_lanes(sn_lanes_b[L], [&](auto la) { launch_sn_level<decltype(la)::value, false>(L, ob, s); });
   }
-#undef OQ_SN_LEVEL
-#undef OQ_SN_LEVEL_W
-#undef OQ_SN_TREE
-#undef OQ_SN_TREE_N
 
+  // skip_first_fwd / skip_last_bwd: those two level steps are folded into the kernels around the solve (fused_ends)
   void run_steps(bool skip_first_fwd = false, bool skip_last_bwd = false) {
     hipStream_t s = e.stream;
     if (sn) { run_supernodes(); return; }
@@ -1528,16 +1479,11 @@ struct LdlFactor {
         const int c0 = S.level_ptr[t.a], c1 = S.level_ptr[t.b];
         if (t.G == kBlock) OQ_LAUNCH(k_fwd_far<kBlock>, dim3(c1 - c0), dim3(kBlock), 0, s, c0, c1, Rp.get(), Rsplit.get(), Rj.get(), Rx.get(), bp.get(), (double *)nullptr);
         else OQ_LAUNCH(k_fwd_far<64>, dim3(blocks_for((int64_t)(c1 - c0) * 64)), dim3(kBlock), 0, s, c0, c1, Rp.get(), Rsplit.get(), Rj.get(), Rx.get(), bp.get(), (double *)nullptr);
-        launch_fwd_chain(t, s);
+        launch_chain(t, true, s);
         continue;
       }
       dim3 grid(blocks_for((int64_t)(t.b - t.a) * t.G)), block(kBlock);
-      switch (t.G) {
-      case 1: OQ_LAUNCH(k_fwd_level<1>, grid, block, 0, s, t.a, t.b, Rp.get(), Rj.get(), Rx.get(), bp.get()); break;
-      case 4: OQ_LAUNCH(k_fwd_level<4>, grid, block, 0, s, t.a, t.b, Rp.get(), Rj.get(), Rx.get(), bp.get()); break;
-      case 16: OQ_LAUNCH(k_fwd_level<16>, grid, block, 0, s, t.a, t.b, Rp.get(), Rj.get(), Rx.get(), bp.get()); break;
-      default: OQ_LAUNCH(k_fwd_level<64>, grid, block, 0, s, t.a, t.b, Rp.get(), Rj.get(), Rx.get(), bp.get()); break;
-      }
+      with_lanes(t.G, [&](auto g) { OQ_LAUNCH(k_fwd_level<decltype(g)::value>, grid, block, 0, s, t.a, t.b, Rp.get(), Rj.get(), Rx.get(), bp.get()); });
     }
     if (kD) {  // x2 = S0^-1 (b2 - L21 y1)
       // the reduced right-hand side goes to x2, the product straight back into the block's slots of the solution
@@ -1556,16 +1502,11 @@ struct LdlFactor {
         const int c0 = S.level_ptr[t.a], c1 = S.level_ptr[t.b];
         if (t.G == kBlock) OQ_LAUNCH(k_bwd_far<kBlock>, dim3(c1 - c0), dim3(kBlock), 0, s, c0, c1, Lsplit.get(), Lp.get(), Li.get(), Lx.get(), Dinv.get(), bp.get());
         else OQ_LAUNCH(k_bwd_far<64>, dim3(blocks_for((int64_t)(c1 - c0) * 64)), dim3(kBlock), 0, s, c0, c1, Lsplit.get(), Lp.get(), Li.get(), Lx.get(), Dinv.get(), bp.get());
-        launch_bwd_chain(t, s);
+        launch_chain(t, false, s);
         continue;
       }
       dim3 grid(blocks_for((int64_t)(t.b - t.a) * t.G)), block(kBlock);
-      switch (t.G) {
-      case 1: OQ_LAUNCH(k_bwd_level<1>, grid, block, 0, s, t.a, t.b, Lp.get(), Li.get(), Lx.get(), Dinv.get(), bp.get()); break;
-      case 4: OQ_LAUNCH(k_bwd_level<4>, grid, block, 0, s, t.a, t.b, Lp.get(), Li.get(), Lx.get(), Dinv.get(), bp.get()); break;
-      case 16: OQ_LAUNCH(k_bwd_level<16>, grid, block, 0, s, t.a, t.b, Lp.get(), Li.get(), Lx.get(), Dinv.get(), bp.get()); break;
-      default: OQ_LAUNCH(k_bwd_level<64>, grid, block, 0, s, t.a, t.b, Lp.get(), Li.get(), Lx.get(), Dinv.get(), bp.get()); break;
-      }
+      with_lanes(t.G, [&](auto g) { OQ_LAUNCH(k_bwd_level<decltype(g)::value>, grid, block, 0, s, t.a, t.b, Lp.get(), Li.get(), Lx.get(), Dinv.get(), bp.get()); });
     }
   }
 
@@ -1639,6 +1580,7 @@ __global__ __launch_bounds__(kBlock) void k_direct_update_rhs(int n, int m, doub
 }
 
 struct Direct : Linsys {
+  const DirectKnobs knobs{};  // (fuse_ends, fuse2, leave_rhs: the iteration's own switches)
   Engine &e;
   std::unique_ptr<LdlFactor> F;
   explicit Direct(Engine &en) : e(en) {}
@@ -1647,10 +1589,8 @@ struct Direct : Linsys {
   int fused_step() override {
     hipStream_t s = e.stream;
     const int N = e.n + e.m;
-    static const bool fuse_ends = !(getenv("OSQP_AMD_FUSE_ENDS") && atoi(getenv("OSQP_AMD_FUSE_ENDS")) == 0);
-    const bool f1 = fuse_ends && F->can_fuse_fwd1(), b0 = fuse_ends && F->can_fuse_bwd0();
-    static const bool fuse2 = !(getenv("OSQP_AMD_FUSE2") && atoi(getenv("OSQP_AMD_FUSE2")) == 0);
-    if (fuse_ends && fuse2 && F->can_fuse2()) {
+    const bool f1 = knobs.fuse_ends && F->can_fuse_fwd1(), b0 = knobs.fuse_ends && F->can_fuse_bwd0();
+    if (knobs.fuse_ends && knobs.fuse2 && F->can_fuse2()) {
       const int l1 = F->S.level_ptr[1];
       OQ_LAUNCH(k_direct2_fwd, dim3(blocks_for(N - l1)), dim3(kBlock), 0, s, e.n, N, e.st.sigma, F->perm.get(), l1, F->Rp.get(), F->Rj.get(),
                 F->Rx.get(), F->Dinv.get(), e.x.get(), e.q.get(), e.z.get(), e.rho_inv.get(), e.y.get(), F->bp.get());
@@ -1672,7 +1612,7 @@ struct Direct : Linsys {
       OQ_LAUNCH(k_direct_bwd0_update, dim3(blocks_for(N)), dim3(kBlock), 0, s, e.n, e.m, e.st.alpha, F->pinv.get(), F->S.level_ptr[1],
                 F->Lp.get(), F->Li.get(), F->Lx.get(), F->Dinv.get(), F->bp.get(), e.rho.get(), e.rho_inv.get(), e.l.get(), e.u.get(),
                 e.x.get(), e.z.get(), e.y.get(), e.dx.get(), e.dy.get());
-    else if (next_follows && !f1 && leave_rhs) {
+    else if (next_follows && !f1 && knobs.leave_rhs) {
       OQ_LAUNCH(k_direct_update_rhs, dim3(blocks_for(N)), dim3(kBlock), 0, s, e.n, e.m, e.st.alpha, e.st.sigma, F->vec_pinv(), F->bp.get(),
                 e.q.get(), e.rho.get(), e.rho_inv.get(), e.l.get(), e.u.get(), e.x.get(), e.z.get(), e.y.get(), e.dx.get(), e.dy.get());
       rhs_left = true;  // (only ever true between two steps of one capture: the last step of a chunk has next_follows = false)
@@ -1682,7 +1622,6 @@ struct Direct : Linsys {
     return 0;
   }
   bool rhs_left = false;  // the previous step of this capture left this step's right-hand side in the factor's vector
-  const bool leave_rhs = !(getenv("OSQP_AMD_DIRECT_LEAVE_RHS") && atoi(getenv("OSQP_AMD_DIRECT_LEAVE_RHS")) == 0);
   // a supernode waited 200 ms for its children: the factor goes back to one launch per level (no waiting inside a
   // kernel); 6 tells the engine that the iterations since the last test cannot be trusted (TreeFault: the solve restarts)
   void invalidate() override { rhs_left = false; }
@@ -1749,20 +1688,9 @@ struct Direct : Linsys {
   }
 };
 
-double factor_flops_limit() {
-  if (const char *v = getenv("OSQP_AMD_FLOPS_LIMIT")) return atof(v);
-  return 5e8;
-}
-int level_limit() {
-  if (const char *v = getenv("OSQP_AMD_LEVEL_LIMIT")) return atoi(v);
-  return 3000;
-}
-
-int64_t factor_limit(const Engine &e, bool forced) {
-  if (const char *v = getenv("OSQP_AMD_NNZL_LIMIT")) return atoll(v);
-  (void)e;
-  return forced ? (int64_t)2000000000LL : (int64_t)400000000LL;  // 4e8 entries = 9.6 GB of L (both copies)
-}
+double factor_flops_limit() { return env_double("OSQP_AMD_FLOPS_LIMIT", 5e8); }
+int level_limit() { return env_int("OSQP_AMD_LEVEL_LIMIT", 3000); }
+int64_t factor_limit(const Engine &, bool forced) { return env_i64("OSQP_AMD_NNZL_LIMIT", forced ? 2000000000LL : 400000000LL); }  // 4e8 entries = 9.6 GB of L (both copies)
 
 // The factor of the delta-regularised reduced KKT matrix of an active set (polish, the adjoint), factorised; without the dense
 // top block where its explicit inverse fails the probe.  *rc: 0, -1 too large, else refactor's code.
@@ -1863,7 +1791,7 @@ int polish_run(Engine &e) {
   // the reduced KKT system is assembled from the CSR arrays, which a compact workspace has released: iterative form (pcg.hip)
   // OSQP_AMD_POLISH_ITERATIVE=1 (tests): the iterative form wherever the indirect back-end runs, so that it can be compared
   // with a factorisation-based polish on problems small enough to have one
-  const bool force_iterative = getenv("OSQP_AMD_POLISH_ITERATIVE") && atoi(getenv("OSQP_AMD_POLISH_ITERATIVE")) != 0;
+  const bool force_iterative = env_int("OSQP_AMD_POLISH_ITERATIVE", 0) != 0;
   if (e.compact || e.comm || (force_iterative && e.lin && e.lin->kind() == 2)) return polish_run_pcg(e);  // a row block has no reduced KKT matrix either
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;

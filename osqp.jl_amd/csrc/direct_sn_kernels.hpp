@@ -3,6 +3,7 @@
 // for reviewability -- direct.hip keeps the factor object (LdlFactor), the back-end (Direct) and the set-up decisions.
 #pragma once
 #include "engine.hpp"
+#include "direct_knobs.hpp"  // kSnMax, kSnThreads, kSnWaveLevel: shared with the set-up decisions and the symbolic probe
 
 namespace oq {
 namespace {
@@ -13,9 +14,7 @@ namespace {
 //   forward   t = b_J - F_J y (entries of the rows of J outside its block),  y_J = W t
 //   backward  u = D_J^-1 y_J - G_J x (entries of the columns of J outside its block),  x_J = W' u
 // A deep elimination tree (nested dissection of a long banded problem: 300 pivot levels) is 15 such levels.
-constexpr int kSnMax = 64, kSnThreads = 256;
 constexpr int kSnBusyLevel = 2048;   // supernodes in a level from which its workgroups no longer fit the device at once
-constexpr int kSnWaveLevel = 16384;  // supernodes in a level from which each gets a wavefront instead of a workgroup (below: the device is not full either way and a workgroup finishes its supernode sooner)
 
 __global__ __launch_bounds__(kSnThreads) void k_sn_invert(const int *__restrict__ ptr, const int64_t *__restrict__ woff,
                                                           const int64_t *__restrict__ wmap, const double *__restrict__ Lx,

@@ -60,7 +60,6 @@ constexpr int kSortN = 4096;        // power of two >= kTileRowsMax: per-tile or
 constexpr int64_t kLenMax = 0x7FFFF;  // longest (row, panel) cell the 32-bit sort key of that ordering can hold (19 bits above the 12 of the row)
 
 // tunables (defaults from the sweep in profiles/r01_e_panel_sweep.md; overridable for experiments)
-int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
 int panel_shift() { return env_int("OSQP_AMD_PANEL_SHIFT", 14); }           // W = 16384 columns = 128 KB of fp64 in LDS
 int panel_tile_nnz() { return env_int("OSQP_AMD_PANEL_TILE_NNZ", 65536); }  // non-zeros per workgroup tile
 
