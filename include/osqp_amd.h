@@ -705,8 +705,10 @@ c_int osqp_amd_device_copy(void *dst, const void *src, c_int bytes, c_int kind, 
  *   gradient wanted with dx and dy both NULL, nothing wanted at all, no current solution (no osqp_solve yet, or a data
  *   update, warm start or osqp_amd_iterate after the last one: call osqp_solve), the last solve did not end with status
  *   OSQP_SOLVED (solved inaccurate is refused too); 6 a compact or a row-sharded workspace (no CSR arrays, no reduced KKT
- *   matrix; an iterative adjoint on the operator of the indirect back-end is not built), a reduced factor that is too
- *   large; 4 a failed numeric factorisation. */
+ *   matrix) and a reduced factor that is too large -- under the default method; osqp_amd_derivative_method(work, 1, 0, 0)
+ *   serves the compact workspace and the factor that does not fit with the iterative adjoint on the operator of the indirect
+ *   back-end (below), a row-sharded workspace stays refused --; 4 a failed numeric factorisation, or an iterative solve that
+ *   did not converge. */
 c_int osqp_amd_adjoint(OSQPWorkspace *work, c_int ncot,
                        const c_float *dx /* [ncot x n] or NULL = 0 */, const c_float *dy /* [ncot x m] or NULL = 0 */,
                        c_float *dq /* [ncot x n] */, c_float *dl /* [ncot x m] */, c_float *du /* [ncot x m] */,
@@ -734,8 +736,10 @@ c_int osqp_amd_adjoint(OSQPWorkspace *work, c_int ncot,
  *
  *   Returns 0, or non-zero with the reason in osqp_amd_last_error and no output written, with osqp_amd_adjoint's codes: 7
  *   NULL workspace; 1 ndir < 1, tx or ty wanted with all five tangents NULL, nothing wanted at all, no current solution, a
- *   status other than OSQP_SOLVED; 6 a compact or a row-sharded workspace, a reduced factor that is too large; 4 a failed
- *   numeric factorisation. */
+ *   status other than OSQP_SOLVED; 6 a compact or a row-sharded workspace, a reduced factor that is too large (the default
+ *   method; osqp_amd_derivative_method(work, 1, 0, 0) serves the first and the last iteratively, with tq, tl, tu on a compact
+ *   workspace: tPx / tAx are refused with 6 there, their products on the sliced copy are not built); 4 a failed numeric
+ *   factorisation, or an iterative solve that did not converge. */
 c_int osqp_amd_jvp(OSQPWorkspace *work, c_int ndir,
                    const c_float *tq /* [ndir x n] or NULL = 0 */, const c_float *tl /* [ndir x m] */, const c_float *tu /* [ndir x m] */,
                    const c_float *tPx /* [ndir x nnz(triu P)] */, const c_float *tAx /* [ndir x nnz(A)] */,
@@ -749,6 +753,40 @@ c_int osqp_amd_adjoint_release(OSQPWorkspace *work);
  * OSQP_AMD_ADJOINT_STATS_COUNT), 0 on a NULL argument. */
 #define OSQP_AMD_ADJOINT_STATS_COUNT 6
 c_int osqp_amd_adjoint_stats(const OSQPWorkspace *work, c_float *out, c_int count);
+
+/* ---- The KKT solve behind osqp_amd_adjoint / _jvp and their _dev forms: factor or iteration ----
+ *
+ * osqp_amd_derivative_method chooses per workspace.  method 0, direct (the default): the kept factor, with the refusals
+ * above.  1, auto: the kept factor wherever method 0 builds one; the iterative form on a compact workspace and where the
+ * reduced factor is too large.  2, iterative: always the iterative form.  The iterative form needs the indirect back-end
+ * (linsys_solver = pcg) on one device, with OSQP_AMD_PCG_ASYNC and OSQP_AMD_PCG_SR at their defaults: method 2 on another
+ * workspace returns 6 and says what is missing (a row-sharded workspace stays refused under every method).
+ *
+ *   The iterative form solves K [s_x; s_a] = [b1; b2] on the scaled data as polish does on such a workspace: conjugate
+ *   gradients on (P + d I + Aa' Aa / d) with d = max(delta, 1e-3), relative tolerance 1e-6, start vector zero, the
+ *   multipliers s_a = (Aa s_x - r2) / d, and outer steps on the residual of the UNREGULARISED system until it has dropped by
+ *   rel_drop (0: 1e-10), after more than polish_refine_iter and at most max_outer (0: 40) steps.  Its kept state holds no
+ *   factor: the side of every row (classified on the device), the caller-unit solution and scratch of n + m doubles; it is
+ *   created by the first adjoint or jvp after a solve, used by both, dropped by what drops the factor, and reported by
+ *   osqp_amd_adjoint_stats (entries 0 and 1 then count builds and outer steps).  Pair c (direction d) of a call has the bits
+ *   of a call with it alone, a NULL tangent those of zeros, the device form those of the host form.  "The call changes
+ *   nothing else" holds: rho, sigma, the preconditioner, the CG settings, start vectors, carried products and the iteration
+ *   total of the indirect back-end are saved and put back, also when a launch throws; the derivative's CG iterations are
+ *   counted below and not in osqp_amd_get_stats.  On a compact workspace dPx / dAx are computed on the sliced copy (scratch
+ *   of one double per stored slot of one matrix for the length of the call) and the matrix tangents tPx / tAx are refused.
+ *
+ *   A solve that does not reach rel_drop in max_outer steps (or whose CG refuses) makes the call return 4 with the reached
+ *   rn / first_norm in osqp_amd_last_error.  Host form: nothing has been delivered.  Device form: the outputs of earlier
+ *   pairs / directions of the same call may already have been written.
+ *
+ *   The call drops the derivative state the current solution keeps (as osqp_amd_adjoint_release).  Returns 0; 7 NULL
+ *   workspace; 1 method outside 0..2, max_outer < 0, rel_drop outside [0, 1); 6 as above. */
+c_int osqp_amd_derivative_method(OSQPWorkspace *work, c_int method, c_int max_outer, c_float rel_drop);
+/* Fills out[0..count): 0 iterative states built so far, 1 outer steps so far, 2 CG iterations so far (the derivative's own),
+ * 3 outer steps of the last pass, 4 rn / first_norm of the last pass, 5 1 if the kept state is the iterative one, 6 device
+ * bytes it holds.  Returns the number of entries written (at most OSQP_AMD_DERIVATIVE_ITER_STATS_COUNT), 0 on a NULL argument. */
+#define OSQP_AMD_DERIVATIVE_ITER_STATS_COUNT 7
+c_int osqp_amd_derivative_iter_stats(const OSQPWorkspace *work, c_float *out, c_int count);
 
 /* ---- Device-pointer forms of a single model's life cycle ----
  *

@@ -905,6 +905,31 @@ c_int osqp_amd_adjoint_stats(const OSQPWorkspace *w, c_float *out, c_int count) 
   return k;
 }
 
+// ---- which KKT solve the derivatives of a single model use ----
+c_int osqp_amd_derivative_method(OSQPWorkspace *w, c_int method, c_int max_outer, c_float rel_drop) {
+  const char *who = "osqp_amd_derivative_method";
+  return on_workspace(w, who, [&](Engine &e) {
+    const std::string name = std::string(who) + ": ";
+    if (method < 0 || method > 2) throw Error(1, name + "method must be 0 (direct), 1 (auto) or 2 (iterative)");
+    if (max_outer < 0 || max_outer > 1000000) throw Error(1, name + "max_outer must be 0 (the default, 40) or a positive count");
+    if (!(rel_drop >= 0.0) || rel_drop >= 1.0) throw Error(1, name + "rel_drop must be 0 (the default, 1e-10) or lie in (0, 1)");
+    if (method == 2) kkt_iter_refuse(e, who);
+    model_adjoint_release(e);
+    e.deriv_method = (int)method;
+    e.deriv_max_outer = max_outer ? (int)max_outer : 40;
+    e.deriv_rel_drop = rel_drop > 0.0 ? (double)rel_drop : 1e-10;
+    return 0;
+  });
+}
+c_int osqp_amd_derivative_iter_stats(const OSQPWorkspace *w, c_float *out, c_int count) {
+  if (!w || !out) return 0;
+  double v[OSQP_AMD_DERIVATIVE_ITER_STATS_COUNT];
+  model_adjoint_iter_stats(*E(w), v);
+  c_int k = 0;
+  for (; k < count && k < OSQP_AMD_DERIVATIVE_ITER_STATS_COUNT; k++) out[k] = v[k];
+  return k;
+}
+
 c_int osqp_amd_set_device(c_int device) {
   return guarded([&]() { HIP_CHECK(hipSetDevice((int)device)); return 0; });
 }

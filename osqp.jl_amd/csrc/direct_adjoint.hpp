@@ -7,6 +7,9 @@
 // factorised once per solution and KEPT, the right-hand side c D g_x and (E g_y)_a, r_x = D r~, r_y = E s / c.
 // Every kernel is one thread per output word, consecutive lanes on consecutive words, gathers through L2, no atomics: two calls
 // give the same bits.
+// Section 17 (osqp_amd_derivative_method): the same drivers on a kept state WITHOUT a factor -- the solve is kkt_iter_solve of
+// pcg.hip on the operator of the indirect back-end, the multipliers stay at full length m (act_rows / slot the identity), and
+// the matrix gradients of a compact matrix come from a sampled outer product on its sliced copy (panel_outer) and a gather.
 #pragma once
 #include "engine.hpp"
 
@@ -78,7 +81,9 @@ __global__ __launch_bounds__(kBlock) void k_adj_dA(int64_t nnz, const int64_t *_
 
 // what one solution keeps: the factor, the active set in its three forms, the caller-unit solution, the scratch of the solves
 struct AdjointKept {
-  std::unique_ptr<LdlFactor> F;
+  std::unique_ptr<LdlFactor> F;                 // null: the iterative state of section 17 -- no factor, multipliers at full length
+  bool iterative = false;                       // (mr = m, act_rows and slot the identity: the kernels above serve both)
+  bool h_side_current = true;                   // iterative: h_side is downloaded by the first host-form call that wants `act`
   int n_low = 0, n_upp = 0, mr = 0;
   std::vector<double> h_side;                   // [m] -1 lower, 0 inactive, 1 upper (the `act` output)
   DevBuf<int> act_rows, slot;                   // [mr] rows in the order of the reduced matrix; [m] row -> position, -1
@@ -98,6 +103,12 @@ struct ModelAdjoint {
   DevBuf<int> Ppos2k, Apos2k;
   bool jvp_maps = false;
   long long builds = 0, solves = 0;
+  // the iterative form (osqp_amd_derivative_iter_stats): states built, outer steps, CG iterations of its own, the last pass
+  long long it_builds = 0, it_outer = 0, it_cg = 0;
+  int last_outer = 0;
+  double last_drop = 0.0;
+  const char *who = "";            // the exported symbol of the call in progress (kept_state)
+  KktIter *session = nullptr;      // the indirect back-end is borrowed for the passes of the call in progress (IterSession)
 };
 void model_adjoint_destroy(ModelAdjoint *a) { delete a; }
 
@@ -116,11 +127,24 @@ void model_adjoint_stats(const Engine &e, double out[6]) {
   out[5] = k ? (double)k->bytes : 0.0;
 }
 
+void model_adjoint_iter_stats(const Engine &e, double out[7]) {
+  const ModelAdjoint *a = e.adj.get();
+  const AdjointKept *k = a ? a->kept.get() : nullptr;
+  out[0] = a ? (double)a->it_builds : 0.0;
+  out[1] = a ? (double)a->it_outer : 0.0;
+  out[2] = a ? (double)a->it_cg : 0.0;
+  out[3] = a ? (double)a->last_outer : 0.0;
+  out[4] = a ? a->last_drop : 0.0;
+  out[5] = k && k->iterative ? 1.0 : 0.0;
+  out[6] = k && k->iterative ? (double)k->bytes : 0.0;
+}
+
 namespace {
 
 // classify the rows on the scaled (z, y, l, u) of the solution -- polish's rule, and a row with l == u is always active and
 // counts as lower --, analyse and factorise the reduced matrix, set up what every later call on this solution reuses
-void adjoint_build(Engine &e, ModelAdjoint &A, const char *who, const char *form) {
+// too_large (auto method): a factor that does not fit is reported there instead of refused, and nothing is built
+void adjoint_build(Engine &e, ModelAdjoint &A, const char *who, const char *form, bool *too_large = nullptr) {
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
   const size_t bytes0 = g_device_bytes;
@@ -145,8 +169,10 @@ void adjoint_build(Engine &e, ModelAdjoint &A, const char *who, const char *form
   }
   int frc = 0;
   K->F = reduced_factor(e, row_map, mr, &frc);
+  if (frc == -1 && too_large) { *too_large = true; return; }
   if (frc == -1)
-    throw Error(6, std::string(who) + ": the factor of the reduced KKT matrix of the active set is too large for the device (an iterative " + form + " is not built)");
+    throw Error(6, std::string(who) + ": the factor of the reduced KKT matrix of the active set is too large for the device (the iterative " + form +
+                       " is opt-in: osqp_amd_derivative_method(work, 1, 0, 0) takes it where the factor does not fit)");
   if (frc != 0)
     throw Error(4, std::string(who) + ": the numeric factorisation of the regularised KKT matrix of the active set failed");
   const int nr = n + mr;
@@ -173,6 +199,20 @@ void adjoint_build(Engine &e, ModelAdjoint &A, const char *who, const char *form
 // the REGULARISED matrix: the answer is the regularised one, to working accuracy.
 void kept_solve(Engine &e, ModelAdjoint &A) {
   AdjointKept &K = *A.kept;
+  if (K.iterative) {  // section 17: rhs_red = [b1; b2] and sol = [s_x; s_y] at full length n + m
+    KktIterResult res;
+    const int rc = kkt_iter_solve(A.session, K.rhs_red.get(), K.rhs_red.get() + e.n, K.sol.get(), K.sol.get() + e.n, e.deriv_max_outer,
+                                  e.deriv_rel_drop, &res);
+    A.solves += res.outer; A.it_outer += res.outer; A.it_cg += res.cg;
+    A.last_outer = res.outer; A.last_drop = res.drop;
+    if (rc) {
+      char buf[64];
+      snprintf(buf, sizeof buf, "%.3e", res.drop);
+      throw Error(4, std::string(A.who) + ": the iterative KKT solve of the derivative did not converge: residual drop rn / first_norm = " + buf + " after " +
+                         std::to_string(res.outer) + " outer steps (osqp_amd_derivative_method sets max_outer and rel_drop)");
+    }
+    return;
+  }
   const bool regularised = e.st.polish_refine_iter == 0;
   A.solves += kkt_solve_refine(e, *K.F, K.act_rows.get(), K.mr, K.rhs_red.get(), K.sol.get(),
                                RefineScratch{K.rhs.get(), K.yfull.get(), K.Axv.get(), K.px.get(), K.ared_x.get()},
@@ -187,23 +227,102 @@ void adjoint_pass(Engine &e, ModelAdjoint &A, const double *gx, const double *gy
   kept_solve(e, A);
 }
 
+bool workspace_compact(const Engine &e) {
+  return e.compact || e.A.compact || e.At.compact || e.Pf.compact || (e.nnzPtriu > 0 && e.Pi_keep.n == 0);
+}
+
 // no CSR arrays and no reduced KKT matrix: what polish_run hands to its iterative form
 void adjoint_needs_csr(const Engine &e, const char *who, const char *form) {
   if (e.comm)
-    throw Error(6, std::string(who) + ": not available on a row-sharded workspace (a row block has no reduced KKT matrix; an iterative " + form + " is not built)");
-  if (e.compact || e.A.compact || e.At.compact || e.Pf.compact || (e.nnzPtriu > 0 && e.Pi_keep.n == 0))
+    throw Error(6, std::string(who) + ": not available on a row-sharded workspace (a row block has no reduced KKT matrix; the iterative " + form +
+                       " of osqp_amd_derivative_method runs on one device only)");
+  if (workspace_compact(e))
     throw Error(6, std::string(who) + ": not available on a compact workspace (its CSR arrays are released, there is no reduced KKT matrix to factorise; "
-                   "an iterative " + form + " is not built; OSQP_AMD_COMPACT_NNZ=-1 at setup keeps the arrays)");
+                   "the iterative " + form + " is opt-in: osqp_amd_derivative_method(work, 1, 0, 0); OSQP_AMD_COMPACT_NNZ=-1 at setup keeps the arrays)");
 }
+
+// ---- the iterative kept state ----
+// side by the rule of adjoint_build, on the device; low / upp: 1.0 where the row is lower / upper (summed for the counts)
+__global__ __launch_bounds__(kBlock) void k_adj_classify(int m, const double *__restrict__ z, const double *__restrict__ y, const double *__restrict__ l,
+                                                         const double *__restrict__ u, double *__restrict__ side, double *__restrict__ low_ind,
+                                                         double *__restrict__ upp_ind, int *__restrict__ ident_a, int *__restrict__ ident_b) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= m) return;
+  const bool low = (z[i] - l[i] < -y[i]) || l[i] == u[i];
+  const bool upp = !low && (u[i] - z[i] < y[i]);
+  side[i] = low ? -1.0 : (upp ? 1.0 : 0.0);
+  low_ind[i] = low ? 1.0 : 0.0;
+  upp_ind[i] = upp ? 1.0 : 0.0;
+  ident_a[i] = i; ident_b[i] = i;
+}
+
+// no factor: the side array (classified and counted on the device: no m-vector comes to the host), the caller-unit solution,
+// right-hand side and solution at full length n + m, act_rows and slot the identity
+void adjoint_build_iter(Engine &e, ModelAdjoint &A) {
+  hipStream_t s = e.stream;
+  const int n = e.n, m = e.m;
+  const size_t bytes0 = g_device_bytes, m1 = m ? m : 1;
+  std::unique_ptr<AdjointKept> K(new AdjointKept());
+  K->iterative = true;
+  K->mr = m;
+  K->act_rows.alloc(m1); K->slot.alloc(m1); K->side.alloc(m1);
+  K->xc.alloc(n); K->yc.alloc(m1);
+  K->rhs_red.alloc((size_t)n + m); K->sol.alloc((size_t)n + m); K->rx.alloc(n); K->ry.alloc(m1);
+  if (m > 0) {
+    // the indicator arrays live in scratch that the first pass overwrites (rhs_red is n + m long, ry m)
+    double *low_ind = K->rhs_red.get() + n, *upp_ind = K->ry.get();
+    OQ_LAUNCH(k_adj_classify, dim3(blocks_for(m)), dim3(kBlock), 0, s, m, e.z.get(), e.y.get(), e.l.get(), e.u.get(), K->side.get(), low_ind, upp_ind,
+              K->act_rows.get(), K->slot.get());
+    double h_keep[2] = {e.h_slots[S_T2], e.h_slots[S_T3]};
+    reduce_sum(low_ind, m, e.partials.get(), e.slots.get() + S_T2, s);
+    reduce_sum(upp_ind, m, e.partials.get(), e.slots.get() + S_T3, s);
+    e.fetch_slots(S_T2, 2, 3u);
+    K->n_low = (int)e.h_slots[S_T2]; K->n_upp = (int)e.h_slots[S_T3];
+    e.h_slots[S_T2] = h_keep[0]; e.h_slots[S_T3] = h_keep[1];
+  }
+  K->h_side_current = m == 0;
+  OQ_LAUNCH(k_adj_unscale, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), e.x.get(), e.y.get(),
+            K->xc.get(), K->yc.get());
+  e.sync();
+  K->bytes = g_device_bytes > bytes0 ? g_device_bytes - bytes0 : 0;
+  A.kept = std::move(K);
+  A.builds++; A.it_builds++;
+}
+
+// the indirect back-end borrowed for the passes of one call and handed back at the end of the scope, whatever ends it
+struct IterSession {
+  ModelAdjoint &A;
+  std::unique_ptr<KktIter, KktIterDeleter> it;
+  IterSession(Engine &e, ModelAdjoint &A_) : A(A_) {
+    if (!A.kept->iterative) return;
+    it.reset(kkt_iter_begin(e, A.kept->side.get()));
+    A.session = it.get();
+  }
+  ~IterSession() { A.session = nullptr; }
+};
 
 // ---- the driver model_adjoint_run and model_jvp_run (direct_jvp.hpp) share ----
 // the workspace's derivative state with what the current solution keeps present (built by the first call after a solve);
-// who: the exported symbol that was called, form: what its refusals say is not built
+// who: the exported symbol that was called, form: what its refusals name.  The method of osqp_amd_derivative_method decides
+// which state is built: 0 the factor (and today's refusals), 1 the factor where today's code builds one and the iterative
+// state on a compact workspace or where the factor does not fit, 2 the iterative state always.
 ModelAdjoint &kept_state(Engine &e, const char *who, const char *form) {
-  adjoint_needs_csr(e, who, form);
   if (!e.adj) e.adj.reset(new ModelAdjoint());
-  if (!e.adj->kept) adjoint_build(e, *e.adj, who, form);
-  return *e.adj;
+  ModelAdjoint &A = *e.adj;
+  A.who = who;
+  if (A.kept) return A;
+  bool iterative = e.deriv_method == 2 || (e.deriv_method == 1 && !e.comm && workspace_compact(e));
+  if (!iterative) {
+    adjoint_needs_csr(e, who, form);
+    bool too_large = false;
+    adjoint_build(e, A, who, form, e.deriv_method == 1 ? &too_large : nullptr);
+    iterative = too_large;
+  }
+  if (iterative) {
+    kkt_iter_refuse(e, who);
+    adjoint_build_iter(e, A);
+  }
+  return A;
 }
 
 // The operands of one call as device arrays.  Device form: the caller's arrays themselves.  Host form: in() gives an uploaded
@@ -242,6 +361,12 @@ struct Staged {
 template <typename F>
 void with_tree_retry(Engine &e, ModelAdjoint &A, F &&passes) {
   AdjointKept &K = *A.kept;
+  if (K.iterative) {  // no factor, no tree: the passes run inside a session on the borrowed indirect back-end
+    IterSession session(e, A);
+    passes();
+    e.sync();
+    return;
+  }
   const long long solves0 = A.solves;
   passes();
   e.sync();
@@ -256,10 +381,44 @@ void with_tree_retry(Engine &e, ModelAdjoint &A, F &&passes) {
 }
 
 // the `act` output: [m] -1 lower, 0 inactive, 1 upper
-void write_act(Engine &e, const AdjointKept &K, double *act, bool dev) {
+void write_act(Engine &e, AdjointKept &K, double *act, bool dev) {
   if (!act) return;
-  if (dev) { e.copy_dev(act, K.side.get(), (size_t)e.m); e.sync(); }
-  else std::copy(K.h_side.begin(), K.h_side.end(), act);
+  if (dev) { e.copy_dev(act, K.side.get(), (size_t)e.m); e.sync(); return; }
+  if (!K.h_side_current) {  // the iterative state classified on the device: the one m-vector a host-form caller asks for
+    K.h_side.resize((size_t)e.m);
+    K.side.download(K.h_side.data(), (size_t)e.m, e.stream);
+    e.sync();
+    K.h_side_current = true;
+  }
+  std::copy(K.h_side.begin(), K.h_side.end(), act);
+}
+
+// the matrix gradients of a compact matrix (section 17): entry k of the caller's array gathers its slot of the sampled outer
+// product g (panel_outer); a map entry of all ones is no slot (P_k2up on the diagonal), a slot beyond `padded` is not read
+__global__ __launch_bounds__(kBlock) void k_adj_gather_A(int64_t nnz, const int64_t *__restrict__ to_sorted, const uint32_t *__restrict__ k2slot,
+                                                         size_t padded, const double *__restrict__ g, double *__restrict__ dA) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nnz) return;
+  const uint32_t sl = k2slot[to_sorted ? to_sorted[k] : k];
+  dA[k] = sl < padded ? g[sl] : 0.0;
+}
+__global__ __launch_bounds__(kBlock) void k_adj_gather_P(int64_t nnz, const uint32_t *__restrict__ k2lo, const uint32_t *__restrict__ k2up,
+                                                         size_t padded, const double *__restrict__ g, double *__restrict__ dP) {
+  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nnz) return;
+  const uint32_t lo = k2lo[k], up = k2up[k];
+  const bool has_lo = lo < padded, has_up = up < padded && up != lo;
+  dP[k] = has_lo && has_up ? g[lo] + g[up] : (has_lo ? g[lo] : (has_up ? g[up] : 0.0));
+}
+
+// which statement of dPx / dAx this workspace can run; refusals before the first kernel
+void matrix_gradient_paths(const Engine &e, const char *who, bool wantP, bool wantA, bool &slicedP, bool &slicedA) {
+  slicedP = wantP && e.nnzPtriu > 0 && e.Pf.compact;
+  slicedA = wantA && e.nnzA > 0 && e.A.compact;
+  if (wantP && e.nnzPtriu > 0 && !slicedP && e.Pi_keep.n == 0)
+    throw Error(6, std::string(who) + ": dPx is not available: the workspace released the pattern of P while its sliced copy keeps CSR arrays");
+  if (wantA && e.nnzA > 0 && !slicedA && e.At.compact)
+    throw Error(6, std::string(who) + ": dAx is not available: A' is compact while A keeps its CSR arrays");
 }
 
 }  // namespace
@@ -270,13 +429,21 @@ int model_adjoint_run(Engine &e, const char *who, bool dev, int ncot, const doub
   AdjointKept &K = *A.kept;
   hipStream_t s = e.stream;
   const int n = e.n, m = e.m;
-  if ((dPx || dAx) && !A.patterns) {
+  bool slicedP = false, slicedA = false;
+  matrix_gradient_paths(e, who, dPx != nullptr, dAx != nullptr, slicedP, slicedA);
+  const bool csrP = dPx && e.nnzPtriu > 0 && !slicedP, csrA = dAx && e.nnzA > 0 && !slicedA;
+  if ((dPx || dAx) && !A.patterns && !workspace_compact(e)) {
     A.Pcol.alloc(std::max<int64_t>(1, e.nnzPtriu)); A.Acol.alloc(std::max<int64_t>(1, e.nnzA));
     expand_colptr(n, e.Pp_keep.get(), e.nnzPtriu, A.Pcol.get(), s);
     expand_colptr(n, e.At.rowptr.get(), e.nnzA, A.Acol.get(), s);
     e.device_A_to_sorted();
     e.sync();
     A.patterns = true;
+  }
+  if (workspace_compact(e)) {  // some matrices compact, others not: the column arrays of those that still go the CSR way
+    if (csrP && A.Pcol.n == 0) { A.Pcol.alloc((size_t)e.nnzPtriu); expand_colptr(n, e.Pp_keep.get(), e.nnzPtriu, A.Pcol.get(), s); }
+    if (csrA && A.Acol.n == 0) { A.Acol.alloc((size_t)e.nnzA); expand_colptr(n, e.At.rowptr.get(), e.nnzA, A.Acol.get(), s); }
+    e.sync();
   }
   if (dq || dl || du || dPx || dAx) {
     const size_t nc = (size_t)ncot, nzP = (size_t)e.nnzPtriu, nzA = (size_t)e.nnzA;
@@ -289,12 +456,29 @@ int model_adjoint_run(Engine &e, const char *who, bool dev, int ncot, const doub
         adjoint_pass(e, A, gx ? gx + c * n : nullptr, gy ? gy + c * m : nullptr);
         OQ_LAUNCH(k_adj_vectors, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), K.slot.get(), K.side.get(),
                   K.sol.get(), K.rx.get(), K.ry.get(), oq_ ? oq_ + c * n : nullptr, ol ? ol + c * m : nullptr, ou ? ou + c * m : nullptr);
-        if (dPx && e.nnzPtriu > 0)
+        if (csrP)
           OQ_LAUNCH(k_adj_dP, dim3(blocks_for(e.nnzPtriu)), dim3(kBlock), 0, s, e.nnzPtriu, e.Pi_keep.get(), A.Pcol.get(), K.rx.get(), K.xc.get(),
                     oP + c * nzP);
-        if (dAx && e.nnzA > 0)
+        if (csrA)
           OQ_LAUNCH(k_adj_dA, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, to_sorted,
                     e.At.col.get(), A.Acol.get(), K.rx.get(), K.ry.get(), K.xc.get(), K.yc.get(), oA + c * nzA);
+        // compact matrices: the sampled outer product on the slices, then the gather through the slot maps; the scratch g
+        // (panel.padded doubles) lives for one matrix of one cotangent
+        if (slicedP) {
+          DevBuf<double> g(e.Pf.panel.padded);
+          panel_outer(e.Pf, K.rx.get(), K.xc.get(), false, g.get(), s);  // -(r_x,i x_j) at (i, j): the two halves add up in the gather
+          OQ_LAUNCH(k_adj_gather_P, dim3(blocks_for(e.nnzPtriu)), dim3(kBlock), 0, s, e.nnzPtriu, (const uint32_t *)e.P_k2lo.get(),
+                    (const uint32_t *)e.P_k2up.get(), e.Pf.panel.padded, (const double *)g.get(), oP + c * nzP);
+          e.sync();
+        }
+        if (slicedA) {
+          DevBuf<double> g(e.A.panel.padded);
+          panel_outer(e.A, K.yc.get(), K.rx.get(), false, g.get(), s);  // -(y_i r_x,j)
+          panel_outer(e.A, K.ry.get(), K.xc.get(), true, g.get(), s);   // - r_y,i x_j: the second pass (one staged vector at a time)
+          OQ_LAUNCH(k_adj_gather_A, dim3(blocks_for(e.nnzA)), dim3(kBlock), 0, s, e.nnzA, to_sorted, (const uint32_t *)e.A_k2pos.get(), e.A.panel.padded,
+                    (const double *)g.get(), oA + c * nzA);
+          e.sync();
+        }
       }
     });
     st.deliver();

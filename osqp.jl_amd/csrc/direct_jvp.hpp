@@ -7,6 +7,8 @@
 // right-hand side: products with tangent MATRICES given as value arrays in the caller's nnz order, read through two maps from
 // CSR position back to the caller's entry.  G lanes per row as in k_spmv (kernels.hip), G from the pattern alone, no atomics:
 // direction d of a call has the bits of a call with that direction alone, and a missing tangent those of a tangent of zeros.
+// On the iterative kept state of section 17 (mr = m, identity act_rows / slot) the same kernels run over all m rows and the
+// solve masks the inactive ones; a compact workspace has no CSR arrays for the tangent products: tPx / tAx are refused there.
 #pragma once
 #include "engine.hpp"
 
@@ -147,6 +149,10 @@ int model_jvp_run(Engine &e, const char *who, bool dev, int ndir, const double *
   if (m == 0) { tl = tu = nullptr; }
   if (e.nnzPtriu == 0) tPx = nullptr;
   if (e.nnzA == 0) tAx = nullptr;
+  // section 17: the products with tangent matrices read the CSR arrays through Ppos2k / Apos2k; on the slices they are not built
+  if ((tPx && (e.Pf.compact || e.Pi_keep.n == 0)) || (tAx && (e.A.compact || e.At.compact)))
+    throw Error(6, std::string(who) + ": matrix tangents (tPx, tAx) are not available on a compact workspace (its CSR arrays are released and the products on the "
+                       "sliced copy are not built; tq, tl, tu are served, and osqp_amd_adjoint gives dPx / dAx there)");
   if ((tPx || tAx) && !A.jvp_maps) {
     A.Ppos2k.alloc(std::max<int64_t>(1, e.Pf.nnz)); A.Apos2k.alloc(std::max<int64_t>(1, e.nnzA));
     A.Ppos2k.zero(s); A.Apos2k.zero(s);  // (every position is written below; an index that is read is in range in any case)

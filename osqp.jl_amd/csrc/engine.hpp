@@ -139,6 +139,10 @@ struct Engine {
   // settings or the iterate); the kept factor and its counters (created by the first call, direct_adjoint.hpp)
   bool solution_current = false;
   std::unique_ptr<ModelAdjoint, ModelAdjointDeleter> adj;
+  // osqp_amd_derivative_method: 0 direct (the kept factor, the default), 1 auto, 2 iterative (the
+  // KKT solve on the operator of the indirect back-end, kkt_iter_* below); outer-step cap and drop of the iterative form
+  int deriv_method = 0, deriv_max_outer = 40;
+  double deriv_rel_drop = 1e-10;
 
   // PCG tolerance rule state
   double sc_pri = 0, sc_dua = 0, lambda0 = 0.015, lambda = 0.015, g_ref = 0;
@@ -286,6 +290,23 @@ int model_jvp_run(Engine &e, const char *who, bool dev, int ndir, const double *
                   const double *tPx, const double *tAx, double *tx, double *ty, double *act);
 void model_adjoint_release(Engine &e);  // drops the kept factor (the counters stay)
 void model_adjoint_stats(const Engine &e, double out[6]);
+void model_adjoint_iter_stats(const Engine &e, double out[7]);  // osqp_amd_derivative_iter_stats
+
+// The KKT solve of the derivatives without a factorisation (pcg.hip): [P, Aa'; Aa, 0] [s_x; s_a] = [b1; b2]
+// on the scaled data, a = the rows with side != 0, by the scheme of polish_run_pcg.  A session borrows the indirect back-end:
+// kkt_iter_begin saves everything a later osqp_solve reads (rho, sigma, the preconditioner, the CG settings, start vectors,
+// carried products and their marks, the iteration total, the host slots) and installs rho = mask / delta_in, sigma = delta_in;
+// kkt_iter_end puts all of it back (it is the deleter of the session: an exception out of a launch restores as well).
+struct KktIter;
+struct KktIterResult { int outer = 0; long long cg = 0; double drop = 0.0; };
+void kkt_iter_refuse(const Engine &e, const char *who);  // throws Error(6) unless the indirect back-end on one device, default CG modes
+KktIter *kkt_iter_begin(Engine &e, const double *side);
+// b1 [n], b2 [m] (read on the active rows only) -> sx [n], sy [m] (0 off the active rows); every solve starts from the same CG
+// state (start vector zero).  0, or 4: the residual of the unregularised system did not drop by rel_drop in max_outer steps
+// (or the CG refused); res is filled either way
+int kkt_iter_solve(KktIter *it, const double *b1, const double *b2, double *sx, double *sy, int max_outer, double rel_drop, KktIterResult *res);
+void kkt_iter_end(KktIter *it) noexcept;
+struct KktIterDeleter { void operator()(KktIter *it) const { kkt_iter_end(it); } };
 const char *last_error_cstr();
 
 // device generators (gen.hip)

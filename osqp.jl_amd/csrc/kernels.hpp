@@ -76,6 +76,12 @@ void panel_scale(DevCsr &M, const double *r, const double *c, int order, double 
 void panel_diag(const DevCsr &M, double *diag, int row0, hipStream_t s);
 void panel_scale_norm(DevCsr &M, const double *r, const double *c, int order, double pre, int row0, double *norm, hipStream_t s);
 void spmv_panel_squared(const DevCsr &M, const double *x, double *y, double gamma, const double *v, hipStream_t s);
+// Sampled outer product on the sliced-ELL copy (LDS-staged panels; the matrix gradients of osqp_amd_adjoint on a compact
+// workspace): for every slot of a row's cell, g[slot] = -(ra[row] * cb[col]) (accumulate = false) or
+// g[slot] - ra[row] * cb[col] (true: the second rank-1 term, a second pass with another staged column vector).  g holds
+// M.panel.padded doubles; a padding slot receives the product with the cell's local column 0 (nobody gathers it), the
+// slots of an empty lane are not written.  One thread per slot, no atomics.
+void panel_outer(const DevCsr &M, const double *ra, const double *cb, bool accumulate, double *g, hipStream_t s);
 
 // ---------------- K0: Ruiz equilibration pieces ----------------
 void csr_row_absmax(const DevCsr &M, double *out, bool accumulate, hipStream_t s);  // out[i] = max(|row i|) (or max with old)

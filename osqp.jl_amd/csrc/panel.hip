@@ -777,6 +777,66 @@ __global__ __launch_bounds__(kThreads) void k_sell_scale_norm(int rows, int cols
   double *out = partial + (size_t)g * rows + r0;
   for (int i = threadIdx.x; i < nrows; i += kThreads) out[i] = ys[i];
 }
+// Sampled outer product over the sliced-ELL copy (panel_outer): g[slot] = -(ra[row] * cb[col]), or g[slot] - ra[row] * cb[col]
+// with `accumulate` (the second rank-1 term of dAx, a pass of its own: one staged column vector of W doubles is 128 KB of the
+// 160 KB a workgroup has, two do not fit).  The structure of k_sell_scale_norm: same tiles and units, lane = row, the column
+// vector through LDS panel by panel, kBatch entries in flight; only the 2-byte column ids are read and 8 B per slot written.
+// A padding slot (local column 0) gets a product nobody gathers; an empty lane writes nothing.
+template <typename ColT>
+__global__ __launch_bounds__(kThreads) void k_sell_outer(int rows, int cols, int shift, int B, int Gp, const int *__restrict__ tile_g,
+                                                         const int *__restrict__ tile_r0, const int *__restrict__ unit_s0,
+                                                         const int *__restrict__ unit_ns, const uint32_t *__restrict__ slice_base,
+                                                         const int *__restrict__ slice_len, const uint16_t *__restrict__ slice_rows,
+                                                         const ColT *__restrict__ scol, const double *__restrict__ ra,
+                                                         const double *__restrict__ cb, int accumulate, double *__restrict__ g) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int t = blockIdx.x, gq = tile_g[t];
+  const int W = 1 << shift;
+  const int r0 = tile_r0[t];
+  double *cs = lds;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  bool first = true;
+  for (int j = 0; j < Gp; j++) {
+    const int b = gq * Gp + j;
+    if (b >= B) break;
+    const int s0 = unit_s0[(size_t)t * Gp + j], ns = unit_ns[(size_t)t * Gp + j];
+    if (ns == 0) continue;  // (uniform over the workgroup: the barriers below are met by all or by none)
+    const int c0 = b << shift;
+    if (!first) __syncthreads();
+    const int wlen = cols - c0 < W ? cols - c0 : W;
+    for (int i = threadIdx.x; i < wlen; i += kThreads) cs[i] = cb[c0 + i];
+    __syncthreads();
+    first = false;
+    for (int sl = s0 + wave; sl < s0 + ns; sl += kWaves) {
+      const uint16_t ent = slice_rows[(size_t)sl * 64 + lane];
+      if (ent == kLaneEmpty) continue;
+      const int row = r0 + (int)ent;
+      if (row >= rows) continue;
+      const size_t base = (size_t)slice_base[sl] + lane;
+      const int L = slice_len[sl];
+      const double rs = ra[row];
+      const ColT *cc_ = scol + base;
+      double *o = g + base;
+      for (int k = 0; k < L; k += kBatch) {
+        ColT cc[kBatch];
+        double old[kBatch];
+#pragma unroll
+        for (int u = 0; u < kBatch; u++) {
+          const bool in = k + u < L;
+          cc[u] = in ? cc_[(size_t)(k + u) * 64] : (ColT)0;
+          old[u] = (in && accumulate) ? o[(size_t)(k + u) * 64] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; u++) {
+          if (k + u >= L) break;
+          const int lc = (int)cc[u];
+          const double prod = rs * (lc < wlen ? cs[lc] : 0.0);
+          o[(size_t)(k + u) * 64] = accumulate ? old[u] - prod : -prod;
+        }
+      }
+    }
+  }
+}
 __global__ __launch_bounds__(kBlock) void k_panel_reduce_max(int rows, int NG, const double *__restrict__ partial, double *__restrict__ out,
                                                              int accumulate) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -1080,6 +1140,15 @@ void panel_scale_norm(DevCsr &M, const double *r, const double *c, int order, do
             P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(), P.slice_len.get(),
             P.slice_rows.get(), P.scol.get(), P.sval.get(), r, c, order, pre, row0, P.partial.get());
   OQ_LAUNCH(k_panel_reduce_max, dim3(blocks_for(M.rows)), dim3(kBlock), 0, s, M.rows, P.NG, P.partial.get(), norm, 0);
+}
+void panel_outer(const DevCsr &M, const double *ra, const double *cb, bool accumulate, double *g, hipStream_t s) {
+  const DevPanel &P = M.panel;
+  if (!P.active || P.wide) throw Error(6, "internal: the sampled outer product needs LDS-staged panels");
+  if (P.ntiles <= 0) return;
+  const size_t lds = sizeof(double) << P.shift;
+  HIP_CHECK(hipFuncSetAttribute((const void *)k_sell_outer<uint16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  OQ_LAUNCH((k_sell_outer<uint16_t>), dim3(P.ntiles), dim3(kThreads), lds, s, M.rows, M.cols, P.shift, P.B, P.Gp, P.tile_g.get(), P.tile_r0.get(),
+            P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(), P.slice_len.get(), P.slice_rows.get(), P.scol.get(), ra, cb, accumulate ? 1 : 0, g);
 }
 void panel_diag(const DevCsr &M, double *diag, int row0, hipStream_t s) {
   const DevPanel &P = M.panel;

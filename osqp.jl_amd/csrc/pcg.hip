@@ -970,4 +970,150 @@ int polish_run_pcg(Engine &e) {
   return 1;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The KKT solve of osqp_amd_adjoint / _jvp without a factorisation: the scheme above with another
+// right-hand side, [P, Aa'; Aa, 0] [s_x; s_a] = [b1; b2], a = the rows with side != 0.  A function of its own next to
+// polish_run_pcg, which stays as it is: polish ends a solve and may reset the CG state, a derivative call lies between two
+// solves and may not -- what it borrows (KktIter) goes back bit for bit.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_iter_rho(int m, double delta_in, const double *__restrict__ side, double *__restrict__ rho) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < m) rho[i] = side[i] != 0.0 ? 1.0 / delta_in : 0.0;
+}
+// r2 = mask .* (b2 - A s_x)  (mask = rho > 0; Asx null: s_x = 0)
+__global__ __launch_bounds__(kBlock) void k_iter_r2(int m, const double *__restrict__ rho, const double *__restrict__ b2,
+                                                    const double *__restrict__ Asx, double *__restrict__ r2) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < m) r2[i] = rho[i] > 0.0 ? (Asx ? b2[i] - Asx[i] : b2[i]) : 0.0;
+}
+
+struct KktIter {
+  Engine &e;
+  Pcg *P;
+  double delta_in = 1e-3;
+  // what the session borrowed
+  DevBuf<double> rho_keep, dinv_keep, xs_keep, xs0_keep, Axs_keep, Mxs_keep, Axs0_keep, Mxs0_keep, t_keep;
+  double sigma_keep, rel_keep;
+  bool extrap_keep, carried_keep, prev_keep, rhs_keep;
+  int iter_keep, refresh_keep;
+  long long total_keep;
+  std::vector<double> h_slots_keep;
+  bool installed = false;
+  // scratch of the solves
+  DevBuf<double> xz, tmp, r2, Asx;
+  KktIter(Engine &en, Pcg *p) : e(en), P(p) {}
+};
+
+void kkt_iter_refuse(const Engine &e, const char *who) {
+  const std::string name = std::string(who) + ": the iterative derivative (osqp_amd_derivative_method) ";
+  if (e.comm) throw Error(6, name + "is not available on a row-sharded workspace (one device only)");
+  const Pcg *P = e.lin && e.lin->kind() == 2 ? dynamic_cast<const Pcg *>(e.lin.get()) : nullptr;
+  if (!P) throw Error(6, name + "needs the indirect back-end (linsys_solver = pcg at setup); this workspace runs the direct back-end");
+  if (P->async_on) throw Error(6, name + "is not available under OSQP_AMD_PCG_ASYNC=1 (the enqueued steps hold state it cannot put back)");
+  if (P->sr_on) throw Error(6, name + "is not available under OSQP_AMD_PCG_SR=1 (the single-reduction recurrence carries state it cannot put back)");
+}
+
+KktIter *kkt_iter_begin(Engine &e, const double *side) {
+  Pcg *P = dynamic_cast<Pcg *>(e.lin.get());
+  if (!P || e.comm || P->async_on || P->sr_on) throw Error(6, "internal: kkt_iter_begin on a workspace kkt_iter_refuse turns away");
+  if (int rc = P->flush()) throw Error(rc, "the indirect back-end reported an error left from the last solve");
+  std::unique_ptr<KktIter, KktIterDeleter> it(new KktIter(e, P));
+  KktIter &S = *it;
+  hipStream_t s = e.stream;
+  const size_t n = e.n, m = e.m, m1 = m ? m : 1;
+  S.delta_in = std::max((double)e.st.delta, 1e-3);
+  auto keep = [&](DevBuf<double> &dst, const DevBuf<double> &src, size_t count) {
+    if (src.n == 0 || count == 0) return;
+    dst.alloc(count);
+    vec_copy(dst.get(), src.get(), (int)count, s);
+  };
+  keep(S.rho_keep, e.rho, m); keep(S.dinv_keep, P->dinv, n);
+  keep(S.xs_keep, P->xs, n); keep(S.Mxs_keep, P->Mxs, n); keep(S.Axs_keep, P->Axs, m);
+  keep(S.xs0_keep, P->xs0, n); keep(S.Mxs0_keep, P->Mxs0, n); keep(S.Axs0_keep, P->Axs0, m);
+  keep(S.t_keep, P->t, m);
+  S.sigma_keep = e.st.sigma; S.rel_keep = P->rel_tol; S.extrap_keep = P->extrapolate; S.iter_keep = P->max_iter;
+  S.carried_keep = P->carried_valid; S.prev_keep = P->have_prev; S.rhs_keep = P->rhs_ready; S.refresh_keep = P->since_refresh;
+  S.total_keep = P->total_iters;
+  S.h_slots_keep.assign(e.h_slots, e.h_slots + S_COUNT + 8);
+  S.xz.alloc(n + m); S.tmp.alloc(n); S.r2.alloc(m1); S.Asx.alloc(m1);
+  S.installed = true;  // from here on kkt_iter_end has something to put back
+  if (m > 0) OQ_LAUNCH(k_iter_rho, dim3(blocks_for(m)), dim3(kBlock), 0, s, (int)m, S.delta_in, side, e.rho.get());
+  e.st.sigma = S.delta_in;
+  P->precond();
+  P->extrapolate = false; P->rel_tol = 1e-6; P->max_iter = 2000;
+  return it.release();
+}
+
+int kkt_iter_solve(KktIter *it, const double *b1, const double *b2, double *sx, double *sy, int max_outer, double rel_drop, KktIterResult *res) {
+  KktIter &S = *it;
+  Engine &e = S.e;
+  Pcg *P = S.P;
+  hipStream_t s = e.stream;
+  const int n = e.n, m = e.m;
+  const long long iters0 = P->total_iters;
+  HIP_CHECK(hipMemsetAsync(sx, 0, sizeof(double) * (size_t)n, s));
+  if (m > 0) HIP_CHECK(hipMemsetAsync(sy, 0, sizeof(double) * (size_t)m, s));
+  double first_norm = -1.0, rn = 0.0;
+  bool ok = false;
+  int step = 0;
+  for (; step < max_outer && !ok; step++) {
+    // residual of the unregularised system at (s_x, s_y): r1 = b1 - (P s_x + A' s_y), r2 = (b2 - A s_x) on the active rows
+    vec_copy(S.xz.get(), b1, n, s);
+    if (step > 0) {
+      spmv(e.Pf, sx, S.tmp.get(), nullptr, 0.0, 0.0, nullptr, s);
+      vec_axpy(S.xz.get(), -1.0, S.tmp.get(), n, s);
+    }
+    if (m > 0) {
+      if (step > 0) {
+        spmv(e.At, sy, S.tmp.get(), nullptr, 0.0, 0.0, nullptr, s);
+        vec_axpy(S.xz.get(), -1.0, S.tmp.get(), n, s);
+        spmv(e.A, sx, S.Asx.get(), nullptr, 0.0, 0.0, nullptr, s);
+      }
+      OQ_LAUNCH(k_iter_r2, dim3(blocks_for(m)), dim3(kBlock), 0, s, m, (const double *)e.rho.get(), b2, step > 0 ? (const double *)S.Asx.get() : (const double *)nullptr,
+                S.r2.get());
+      vec_copy(S.xz.get() + n, S.r2.get(), m, s);
+    }
+    P->xs.zero(s);
+    P->carried_valid = false; P->have_prev = false; P->since_refresh = 0;
+    if (P->solve(S.xz.get(), -1.0)) break;
+    rn = e.h_slots[S_T5];  // ||r1 + A' rho r2||inf of the system just solved: how far (s_x, s_y) was from the solution
+    vec_axpy(sx, 1.0, S.xz.get(), n, s);
+    if (m > 0) OQ_LAUNCH(k_polish_dual, dim3(blocks_for(m)), dim3(kBlock), 0, s, m, S.delta_in, (const double *)e.rho.get(), (const double *)(S.xz.get() + n),
+                         (const double *)S.r2.get(), sy, 1);
+    if (first_norm < 0.0) first_norm = rn;
+    ok = step + 1 > e.st.polish_refine_iter && rn <= rel_drop * first_norm;
+  }
+  if (res) {
+    res->outer = step;
+    res->cg = P->total_iters - iters0;
+    res->drop = first_norm > 0.0 ? rn / first_norm : (first_norm == 0.0 ? 0.0 : 1.0);
+  }
+  return ok ? 0 : 4;
+}
+
+void kkt_iter_end(KktIter *it) noexcept {
+  if (!it) return;
+  std::unique_ptr<KktIter> S(it);
+  if (!S->installed) return;
+  try {
+    Engine &e = S->e;
+    Pcg *P = S->P;
+    hipStream_t s = e.stream;
+    auto back = [&](DevBuf<double> &dst, const DevBuf<double> &src) {
+      if (src.n) vec_copy(dst.get(), src.get(), (int)src.n, s);
+    };
+    back(e.rho, S->rho_keep); back(P->dinv, S->dinv_keep);
+    back(P->xs, S->xs_keep); back(P->Mxs, S->Mxs_keep); back(P->Axs, S->Axs_keep);
+    back(P->xs0, S->xs0_keep); back(P->Mxs0, S->Mxs0_keep); back(P->Axs0, S->Axs0_keep);
+    back(P->t, S->t_keep);
+    e.st.sigma = S->sigma_keep;
+    P->rel_tol = S->rel_keep; P->extrapolate = S->extrap_keep; P->max_iter = S->iter_keep;
+    P->carried_valid = S->carried_keep; P->have_prev = S->prev_keep; P->rhs_ready = S->rhs_keep; P->since_refresh = S->refresh_keep;
+    P->total_iters = S->total_keep;
+    e.sync();  // the copies read buffers this session frees
+    std::copy(S->h_slots_keep.begin(), S->h_slots_keep.end(), e.h_slots);
+  } catch (...) {
+  }
+}
+
 }  // namespace oq

@@ -777,6 +777,14 @@ def jvp(model, q=None, l=None, u=None, Px=None, Ax=None, out=None):
     return dict(x=tx if many else tx[0], y=ty if many else ty[0], act=act.astype(int))
 
 
+def _any_compact(model):
+    """Whether one of A, A', P of the workspace has released its CSR arrays (`spmv_layout`: "compact")."""
+    out = np.zeros(len(SPMV_LAYOUT_FIELDS))
+    at = SPMV_LAYOUT_FIELDS.index("compact")
+    fn = getattr(model.lib, "osqp_amd_spmv_layout", None)
+    return fn is not None and any(fn(model.workspace, which, _fptr(out), len(out)) == len(out) and out[at] != 0 for which in (0, 1, 2))
+
+
 JACOBIAN_OF = ("x", "y")
 JACOBIAN_BUDGET = 256 << 20  # bytes: the unit vectors and the largest output of one call of `jacobian` (default chunk)
 
@@ -825,6 +833,9 @@ def jacobian(model, of=("x",), wrt=("q", "l", "u"), mode="auto", out_rows=None, 
         raise ValueError("jacobian: no output component or no data column is asked for")
     if mode == "auto":
         mode = "reverse" if n_rev <= n_fwd else "forward"
+        # a compact workspace serves dPx / dAx (reverse) but not the matrix tangents (forward)
+        if mode == "forward" and ("Px" in wrt or "Ax" in wrt) and _any_compact(model):
+            mode = "reverse"
     reverse = mode == "reverse"
     total = n_rev if reverse else n_fwd
     if chunk is None:
@@ -915,3 +926,37 @@ def adjoint_stats(model):
     if fn(model.workspace, _fptr(out), len(out)) != len(out):
         raise OSQPError("osqp_amd_adjoint_stats: bad argument")
     return {name: int(v) for name, v in zip(ADJOINT_STATS_FIELDS, out)}
+
+
+DERIVATIVE_METHODS = ("direct", "auto", "iterative")
+DERIVATIVE_ITER_STATS_FIELDS = ("builds", "outer_steps", "cg_iters", "last_outer_steps", "last_drop", "kept", "bytes")
+
+
+def derivative_method(model, method="direct", max_outer=None, rel_drop=None):
+    """Extension: osqp_amd_derivative_method -- which KKT solve `adjoint`, `jvp`, `jacobian` and `qp_layer.QPLayer` use on
+    this model.  "direct" (the default): the kept factor; a compact workspace and a factor that does not fit are refused.
+    "auto": the factor where "direct" builds one, the iterative solve on the operator of the indirect back-end on a compact
+    workspace and where the factor does not fit.  "iterative": always the iterative solve (needs `linsys_solver="pcg"` on one
+    device).  max_outer (default 40) caps its outer steps, rel_drop (default 1e-10) is the drop of the residual of the
+    unregularised system they run to; a solve that misses it makes the derivative call raise.  Drops the derivative state
+    the current solution keeps."""
+    if method not in DERIVATIVE_METHODS:
+        raise ValueError(f"method: expected one of {DERIVATIVE_METHODS}, got {method!r}")
+    if max_outer is not None and (not isinstance(max_outer, (int, np.integer)) or isinstance(max_outer, bool) or max_outer < 1):
+        raise ValueError(f"max_outer: expected a positive integer or None, got {max_outer!r}")
+    if rel_drop is not None and not (isinstance(rel_drop, (float, np.floating)) and 0.0 < rel_drop < 1.0):
+        raise ValueError(f"rel_drop: expected a float in (0, 1) or None, got {rel_drop!r}")
+    fn = _symbol(model, "osqp_amd_derivative_method", _DERIVATIVES)
+    if fn(model.workspace, DERIVATIVE_METHODS.index(method), 0 if max_outer is None else int(max_outer), 0.0 if rel_drop is None else float(rel_drop)) != 0:
+        raise OSQPError("Error in derivative_method: " + model.lib.osqp_amd_last_error().decode())
+
+
+def derivative_iter_stats(model):
+    """Extension: osqp_amd_derivative_iter_stats as a dict -- iterative states built, outer steps and CG iterations of the
+    derivatives so far, outer steps and reached residual drop ("last_drop", a float) of the last pass, whether the kept
+    state is the iterative one, and the device bytes it holds."""
+    fn = _symbol(model, "osqp_amd_derivative_iter_stats", _DERIVATIVES)
+    out = np.zeros(len(DERIVATIVE_ITER_STATS_FIELDS))
+    if fn(model.workspace, _fptr(out), len(out)) != len(out):
+        raise OSQPError("osqp_amd_derivative_iter_stats: bad argument")
+    return {name: (float(v) if name == "last_drop" else int(v)) for name, v in zip(DERIVATIVE_ITER_STATS_FIELDS, out)}

@@ -170,6 +170,31 @@ function adjoint_stats(model::OSQP.Model)
     return (builds = Int(out[1]), solves = Int(out[2]), n_low = Int(out[3]), n_upp = Int(out[4]), kept = out[5] == 1.0, bytes = Int(out[6]))
 end
 
+"""
+    derivative_method!(model, method = :direct; max_outer = 0, rel_drop = 0.0)
+
+Which KKT solve `adjoint` and `jvp` use (osqp_amd_derivative_method, DESIGN.md section 17): `:direct` the kept factor,
+`:auto` the factor where it can be built and the iterative solve on the operator of the indirect back-end on a compact
+workspace or where the factor does not fit, `:iterative` always the iterative solve.  0 keeps the defaults (40 outer steps,
+a drop of 1e-10).  Drops the derivative state the current solution keeps.
+"""
+function derivative_method!(model::OSQP.Model, method::Symbol = :direct; max_outer::Integer = 0, rel_drop::Real = 0.0)
+    code = findfirst(==(method), (:direct, :auto, :iterative))
+    code === nothing && error("derivative_method!: expected :direct, :auto or :iterative, got $(method)")
+    flag = ccall((:osqp_amd_derivative_method, lib), Cc_int, (Ptr{OSQP.Workspace}, Cc_int, Cc_int, Cdouble), model.workspace, code - 1, max_outer, rel_drop)
+    flag == 0 || error("Error in derivative_method!: $(last_error())")
+    return nothing
+end
+
+"(builds, outer_steps, cg_iters, last_outer_steps, last_drop, kept, bytes) of the iterative derivatives (osqp_amd_derivative_iter_stats)."
+function derivative_iter_stats(model::OSQP.Model)
+    out = zeros(Float64, 7)  # OSQP_AMD_DERIVATIVE_ITER_STATS_COUNT (include/osqp_amd.h)
+    k = ccall((:osqp_amd_derivative_iter_stats, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Cc_int), model.workspace, out, length(out))
+    k == length(out) || error("osqp_amd_derivative_iter_stats: bad argument")
+    return (builds = Int(out[1]), outer_steps = Int(out[2]), cg_iters = Int(out[3]), last_outer_steps = Int(out[4]), last_drop = out[5],
+            kept = out[6] == 1.0, bytes = Int(out[7]))
+end
+
 # ---- device-pointer forms of a single model's life cycle (include/osqp_amd.h, DESIGN.md section 16) ----
 # Every array is a DEVICE address on the model's device, as a `Ptr{Cdouble}` (`C_NULL`: not given / not wanted) -- for an
 # AMDGPU.jl array `Ptr{Cdouble}(UInt(pointer(a)))`; the package itself does not depend on a GPU array type.  The library runs

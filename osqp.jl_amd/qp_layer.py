@@ -320,11 +320,15 @@ class QPLayer(torch.nn.Module):
     """`layer(q=None, l=None, u=None, Px=None, Ax=None) -> (x, y)` on the single model `model` (set up, direct back-end, not
     compact); `layer.info` is the `Info` of the last forward.  Px / Ax: full value arrays in the nnz order of `update`.
     Tensors on the model's device stay there (device-pointer forms, no host hop; x, y and the gradients come back as CUDA
-    tensors); CPU tensors go the host way and give CPU tensors; both at once is a ValueError."""
+    tensors); CPU tensors go the host way and give CPU tensors; both at once is a ValueError.
+    derivative_method: "direct" (the kept factor, the default), "auto" or "iterative" -- `interface.derivative_method`,
+    called once here; the last two serve a model on the indirect back-end, compact ones included."""
 
-    def __init__(self, model):
+    def __init__(self, model, derivative_method="direct"):
         super().__init__()
         self.model, self.info = model, None
+        if derivative_method != "direct":
+            _iface.derivative_method(model, derivative_method)
 
     def forward(self, q=None, l=None, u=None, Px=None, Ax=None):
         try:
