@@ -333,7 +333,8 @@ c_int osqp_amd_get_stats(const OSQPWorkspace *work, c_float *out, c_int count);
  * own stream; returns the mean milliseconds per launch, <0 on error.
  * which: 0 SpMV A*x, 1 SpMV A'*y, 2 SpMV P*x, 3 forward+backward trisolve,
  *        4 fused ADMM vector update, 5 one whole ADMM iteration of the back-end in use without the residual
- *        evaluation (advances the iterate), 7 one all-gather of an n-vector (sharded workspaces). */
+ *        evaluation (advances the iterate), 7 one all-gather of an n-vector (sharded workspaces), 8 the active-set check
+ *        of osqp_amd_adjoint_retain on the kept derivative factor (<0 without one or with m = 0; changes nothing). */
 c_float osqp_amd_time_kernel(OSQPWorkspace *work, c_int which, c_int reps);
 
 /* ---- Row-sharded workspaces: ONE large QP over several GPUs, indirect back-end ----
@@ -750,9 +751,45 @@ c_int osqp_amd_adjoint_release(OSQPWorkspace *work);
  * Fills out[0..count): 0 factor builds so far, 1 KKT solves so far (1 + polish_refine_iter per pair or direction; 2 at polish_refine_iter = 0), 2, 3 n_low and
  * n_upp of the kept factor (0 if none), 4 1 if a factor is kept, 5 device bytes the kept factor holds with its index
  * arrays and scratch.  Like osqp_amd_get_stats it returns the number of entries written (at most
- * OSQP_AMD_ADJOINT_STATS_COUNT), 0 on a NULL argument. */
+ * OSQP_AMD_ADJOINT_STATS_COUNT), 0 on a NULL argument.  Under osqp_amd_adjoint_retain(work, 1) a state that is stale
+ * (held over from the previous solution, awaiting its check) is still a kept factor: entry 4 is 1 and entries 2, 3 and 5
+ * are those of what is held. */
 #define OSQP_AMD_ADJOINT_STATS_COUNT 6
 c_int osqp_amd_adjoint_stats(const OSQPWorkspace *work, c_float *out, c_int count);
+
+/* ---- Keep the derivative factor while the active set holds ----
+ *
+ * By default the kept factor belongs to ONE solution.  osqp_amd_adjoint_retain(work, 1) lets it outlive the solution, for
+ * the loop update - solve - differentiate: the calls that move the model on -- osqp_solve, osqp_update_lin_cost /
+ * _bounds / _lower_bound / _upper_bound / _P / _A / _P_A, osqp_warm_start*, osqp_amd_iterate, osqp_amd_time_kernel id 5 and
+ * the _dev forms of these -- no longer drop a kept FACTOR, they mark it stale.  osqp_update_P / _A / _P_A and
+ * osqp_amd_update_values_dev also mark its values dirty, and they do so also when they return non-zero.  The first
+ * osqp_amd_adjoint / _jvp (or _dev form) that passes its checks on the next solution classifies the rows on the device
+ * against the kept side of every row (one pass over z, y, l, u and the kept side; the host reads one word, no m-vector comes
+ * to the host) and then
+ *   - no row changed side, values clean: the factor is reused as it is; only the caller-unit solution is refreshed;
+ *   - no row changed side, values dirty: the kept structure is factorised numerically again (no classification on the
+ *     host, no analysis); a factorisation that returns non-zero (a failed probe of the dense top block included) falls
+ *     back to a full build;
+ *   - otherwise: the state is dropped and built as by default, with the default's refusals and codes.
+ * The results have the bits of the default life cycle: the same kernels on the same values in the same structure.
+ *
+ *   What still drops the state, stale or not: every settings update (delta is inside the matrix), osqp_amd_derivative_method,
+ *   osqp_amd_adjoint_release, osqp_cleanup.  The iterative state of osqp_amd_derivative_method is never retained (it is cheap
+ *   to build).  A derivative call that is refused for want of a current solution, or after a solve that did not end
+ *   OSQP_SOLVED, is refused exactly as by default and leaves a stale state where it is.  mode 0 (the default) drops a stale
+ *   state at once and leaves a current one alone.  With the mode never set nothing changes: not a launch, not a bit.
+ *
+ *   Returns 0; 1 on another mode; 7 on a NULL workspace. */
+c_int osqp_amd_adjoint_retain(OSQPWorkspace *work, c_int mode);
+/* Fills out[0..count): 0 the mode, 1 checks made (derivative calls that found a stale kept factor and classified the new
+ * solution against it), 2 reused as it was, 3 reused after a numeric refactorisation, 4 rebuilt because the active set
+ * differed, 5 rebuilt because the numeric refactorisation of the kept structure returned non-zero, 6 rows whose side
+ * differed at the last check, 7 1 while the kept state is stale (awaiting a check; osqp_amd_adjoint_stats reports it as
+ * kept, with its bytes, n_low and n_upp).  Full builds stay in entry 0 of osqp_amd_adjoint_stats.  Returns the number of
+ * entries written (at most OSQP_AMD_ADJOINT_RETAIN_STATS_COUNT), 0 on a NULL argument. */
+#define OSQP_AMD_ADJOINT_RETAIN_STATS_COUNT 8
+c_int osqp_amd_adjoint_retain_stats(const OSQPWorkspace *work, c_float *out, c_int count);
 
 /* ---- The KKT solve behind osqp_amd_adjoint / _jvp and their _dev forms: factor or iteration ----
  *

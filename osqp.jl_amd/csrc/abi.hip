@@ -43,10 +43,13 @@ const Engine *E(const OSQPWorkspace *w) { return &((const Impl *)w->impl)->eng; 
 
 // The factor osqp_amd_adjoint keeps belongs to one solution under one set of settings (delta is inside its matrix): every entry
 // that changes the data, the iterate or a setting drops it; the first two also end the solution's being current.
-void adjoint_moved_on(OSQPWorkspace *w, bool solution_too) {
+// osqp_amd_adjoint_retain changes the first two: the state stays, stale (values: P or A changed as
+// well), until the next derivative call has seen the next solution.  A setting still drops it.
+void adjoint_moved_on(OSQPWorkspace *w, bool solution_too, bool values = false) {
   Engine &e = *E(w);
   if (solution_too) e.solution_current = false;
-  model_adjoint_release(e);
+  if (solution_too) model_adjoint_moved_on(e, values);
+  else model_adjoint_release(e);
 }
 
 }  // namespace
@@ -163,10 +166,11 @@ c_int on_workspace(OSQPWorkspace *w, const char *who, F &&f) {
   return guarded([&]() { return f(*E(w)); });
 }
 
-// a call that moves the model on (new data, a new iterate): the solution stops being current, the kept factor goes, then the body
+// a call that moves the model on (new data, a new iterate): the solution stops being current, the kept factor goes (or
+// turns stale: adjoint_moved_on; values: the call writes P or A, whatever it returns), then the body
 template <typename F>
-c_int moving_on(OSQPWorkspace *w, F &&body) {
-  return on_workspace(w, nullptr, [&](Engine &e) { adjoint_moved_on(w, true); return body(e); });
+c_int moving_on(OSQPWorkspace *w, F &&body, bool values = false) {
+  return on_workspace(w, nullptr, [&](Engine &e) { adjoint_moved_on(w, true, values); return body(e); });
 }
 
 // ---- device-pointer forms of a single model's life cycle (Engine::update_vectors_dev ...) ----
@@ -177,11 +181,11 @@ void dev_form_needs_whole_model(const Engine &e, const char *who) {
 // the device form of a call that moves the model on; nothing_given (every array NULL): 0 and the model stays where it is.
 // call: its place in Engine::dev_calls, counted when the body returns 0
 template <typename F>
-c_int dev_moving_on(OSQPWorkspace *w, const char *who, int call, bool nothing_given, F &&body) {
+c_int dev_moving_on(OSQPWorkspace *w, const char *who, int call, bool nothing_given, F &&body, bool values = false) {
   return on_workspace(w, who, [&](Engine &e) {
     dev_form_needs_whole_model(e, who);
     if (nothing_given) return 0;
-    adjoint_moved_on(w, true);
+    adjoint_moved_on(w, true, values);
     const int rc = body(e);
     if (rc == 0) e.dev_calls[call]++;
     return rc;
@@ -627,14 +631,14 @@ c_int osqp_update_upper_bound(OSQPWorkspace *w, const c_float *u_new) {
   return moving_on(w, [&](Engine &e) { return e.update_bounds(nullptr, u_new); });
 }
 c_int osqp_update_P(OSQPWorkspace *w, const c_float *Px_new, const c_int *Px_new_idx, c_int P_new_n) {
-  return moving_on(w, [&](Engine &e) { return e.update_PA(Px_new, Px_new_idx, P_new_n, nullptr, nullptr, 0, true, false); });
+  return moving_on(w, [&](Engine &e) { return e.update_PA(Px_new, Px_new_idx, P_new_n, nullptr, nullptr, 0, true, false); }, true);
 }
 c_int osqp_update_A(OSQPWorkspace *w, const c_float *Ax_new, const c_int *Ax_new_idx, c_int A_new_n) {
-  return moving_on(w, [&](Engine &e) { return e.update_PA(nullptr, nullptr, 0, Ax_new, Ax_new_idx, A_new_n, false, true); });
+  return moving_on(w, [&](Engine &e) { return e.update_PA(nullptr, nullptr, 0, Ax_new, Ax_new_idx, A_new_n, false, true); }, true);
 }
 c_int osqp_update_P_A(OSQPWorkspace *w, const c_float *Px_new, const c_int *Px_new_idx, c_int P_new_n, const c_float *Ax_new,
                       const c_int *Ax_new_idx, c_int A_new_n) {
-  return moving_on(w, [&](Engine &e) { return e.update_PA(Px_new, Px_new_idx, P_new_n, Ax_new, Ax_new_idx, A_new_n, true, true); });
+  return moving_on(w, [&](Engine &e) { return e.update_PA(Px_new, Px_new_idx, P_new_n, Ax_new, Ax_new_idx, A_new_n, true, true); }, true);
 }
 
 c_int osqp_update_rho(OSQPWorkspace *w, c_float rho_new) {
@@ -747,6 +751,7 @@ c_float osqp_amd_time_kernel(OSQPWorkspace *w, c_int which, c_int reps) {
     Engine &e = *E(w);
     hipStream_t s = e.stream;
     if (which == 3) { result = e.lin->time_solve((int)reps); return 0; }
+    if (which == 8) { result = model_adjoint_time_check(e, (int)reps); return 0; }
     if (which == 5) adjoint_moved_on(w, true);  // advances the iterate, as osqp_amd_iterate does
     // sharded: the local block's product on whatever the gather buffers hold (exchange timed separately, id 7)
     const double *xin = e.comm ? e.gn.get() : e.x.get(), *yin = e.comm ? e.gm.get() : e.y.get();
@@ -871,7 +876,7 @@ c_int osqp_amd_update_vectors_dev(OSQPWorkspace *w, const c_float *q, const c_fl
   });
 }
 c_int osqp_amd_update_values_dev(OSQPWorkspace *w, const c_float *Px, const c_float *Ax) {
-  return dev_moving_on(w, "osqp_amd_update_values_dev", 1, !Px && !Ax, [&](Engine &e) { return e.update_values_dev(Px, Ax); });
+  return dev_moving_on(w, "osqp_amd_update_values_dev", 1, !Px && !Ax, [&](Engine &e) { return e.update_values_dev(Px, Ax); }, true);
 }
 c_int osqp_amd_warm_start_dev(OSQPWorkspace *w, const c_float *x, const c_float *y) {
   return dev_moving_on(w, "osqp_amd_warm_start_dev", 2, !x && !y, [&](Engine &e) { return e.warm_start(x, y, true); });
@@ -902,6 +907,24 @@ c_int osqp_amd_adjoint_stats(const OSQPWorkspace *w, c_float *out, c_int count) 
   model_adjoint_stats(*E(w), v);
   c_int k = 0;
   for (; k < count && k < OSQP_AMD_ADJOINT_STATS_COUNT; k++) out[k] = v[k];
+  return k;
+}
+
+// ---- a kept factor that outlives its solution while the active set holds ----
+c_int osqp_amd_adjoint_retain(OSQPWorkspace *w, c_int mode) {
+  const char *who = "osqp_amd_adjoint_retain";
+  return on_workspace(w, who, [&](Engine &e) {
+    if (mode != 0 && mode != 1) throw Error(1, std::string(who) + ": mode must be 0 (off, the default) or 1 (on)");
+    model_adjoint_retain(e, (int)mode);
+    return 0;
+  });
+}
+c_int osqp_amd_adjoint_retain_stats(const OSQPWorkspace *w, c_float *out, c_int count) {
+  if (!w || !out) return 0;
+  double v[OSQP_AMD_ADJOINT_RETAIN_STATS_COUNT];
+  model_adjoint_retain_stats(*E(w), v);
+  c_int k = 0;
+  for (; k < count && k < OSQP_AMD_ADJOINT_RETAIN_STATS_COUNT; k++) out[k] = v[k];
   return k;
 }
 

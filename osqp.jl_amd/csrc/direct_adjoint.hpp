@@ -10,6 +10,9 @@
 // Section 17 (osqp_amd_derivative_method): the same drivers on a kept state WITHOUT a factor -- the solve is kkt_iter_solve of
 // pcg.hip on the operator of the indirect back-end, the multipliers stay at full length m (act_rows / slot the identity), and
 // the matrix gradients of a compact matrix come from a sampled outer product on its sliced copy (panel_outer) and a gather.
+// Section 18 (osqp_amd_adjoint_retain): opt-in, the kept factor outlives its solution -- what moves the model on marks it
+// stale, and the next derivative call counts on the device the rows that changed side (k_adj_side_changed) and reuses the
+// factor, factorises the kept structure numerically again, or drops it and builds as ever.
 #pragma once
 #include "engine.hpp"
 
@@ -90,6 +93,9 @@ struct AdjointKept {
   DevBuf<double> side, xc, yc;                  // [m], [n], [m]
   DevBuf<double> rhs_red, sol, rhs, yfull, Axv, px, ared_x, rx, ry;
   size_t bytes = 0;                             // device bytes held (factor, index arrays, scratch)
+  // section 18 (osqp_amd_adjoint_retain): the model moved on and the state was kept for the next solution to be checked
+  // against it; values_dirty: P or A changed meanwhile, the kept structure needs its numeric factorisation again
+  bool stale = false, values_dirty = false;
 };
 
 }  // namespace
@@ -109,11 +115,44 @@ struct ModelAdjoint {
   double last_drop = 0.0;
   const char *who = "";            // the exported symbol of the call in progress (kept_state)
   KktIter *session = nullptr;      // the indirect back-end is borrowed for the passes of the call in progress (IterSession)
+  // osqp_amd_adjoint_retain (section 18): the mode, and what became of the stale states that were checked
+  int retain = 0;
+  long long rt_checks = 0, rt_reused = 0, rt_refactorised = 0, rt_rebuilt_set = 0, rt_rebuilt_failed = 0;
+  int rt_last_changed = 0;
 };
 void model_adjoint_destroy(ModelAdjoint *a) { delete a; }
 
 void model_adjoint_release(Engine &e) {
   if (e.adj && e.adj->kept) { e.sync(); e.adj->kept.reset(); }
+}
+
+// the model moved on (a solve, new data, a new iterate).  Default: the kept state goes.  Retain mode, and the state holds a
+// factor: it stays, marked stale, and the first derivative call on the next solution decides what it is still good for
+void model_adjoint_moved_on(Engine &e, bool values_changed) {
+  ModelAdjoint *a = e.adj.get();
+  if (!a || !a->kept) return;
+  if (a->retain != 1 || !a->kept->F) { model_adjoint_release(e); return; }
+  a->kept->stale = true;
+  a->kept->values_dirty = a->kept->values_dirty || values_changed;
+}
+
+void model_adjoint_retain(Engine &e, int mode) {
+  if (!e.adj) e.adj.reset(new ModelAdjoint());
+  e.adj->retain = mode;
+  if (mode == 0 && e.adj->kept && e.adj->kept->stale) model_adjoint_release(e);  // from here on the default's invariants hold
+}
+
+void model_adjoint_retain_stats(const Engine &e, double out[8]) {
+  const ModelAdjoint *a = e.adj.get();
+  const AdjointKept *k = a ? a->kept.get() : nullptr;
+  out[0] = a ? (double)a->retain : 0.0;
+  out[1] = a ? (double)a->rt_checks : 0.0;
+  out[2] = a ? (double)a->rt_reused : 0.0;
+  out[3] = a ? (double)a->rt_refactorised : 0.0;
+  out[4] = a ? (double)a->rt_rebuilt_set : 0.0;
+  out[5] = a ? (double)a->rt_rebuilt_failed : 0.0;
+  out[6] = a ? (double)a->rt_last_changed : 0.0;
+  out[7] = k && k->stale ? 1.0 : 0.0;
 }
 
 void model_adjoint_stats(const Engine &e, double out[6]) {
@@ -301,6 +340,67 @@ struct IterSession {
   ~IterSession() { A.session = nullptr; }
 };
 
+// ---- a kept factor that outlives its solution (osqp_amd_adjoint_retain) ----
+// How many rows of the new solution lie on another side than the kept state was built for: the rule of adjoint_build to the
+// letter (subtractions and comparisons only: the host and the device cannot disagree) against side[i].  A streaming pass over
+// five m-vectors, consecutive lanes on consecutive doubles, grid-stride beyond kSideGrid workgroups; the count goes through
+// the wavefront, then the four waves of the block, then ONE integer add per workgroup into a word the caller zeroed.
+constexpr int kSideGrid = 2048;
+__global__ __launch_bounds__(kBlock) void k_adj_side_changed(int m, const double *__restrict__ z, const double *__restrict__ y,
+                                                             const double *__restrict__ l, const double *__restrict__ u,
+                                                             const double *__restrict__ side, int *__restrict__ count) {
+  int mine = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
+    const double zi = z[i], yi = y[i], li = l[i], ui = u[i];
+    const bool low = (zi - li < -yi) || li == ui;
+    const bool upp = !low && (ui - zi < yi);
+    mine += (low ? -1.0 : (upp ? 1.0 : 0.0)) != side[i];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  __shared__ int sm[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int total = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+    if (total) atomicAdd(count, total);
+  }
+}
+
+void launch_side_changed(Engine &e, const AdjointKept &K) {
+  OQ_LAUNCH(k_adj_side_changed, dim3(std::min(blocks_for(e.m), kSideGrid)), dim3(kBlock), 0, e.stream, e.m, e.z.get(), e.y.get(), e.l.get(), e.u.get(),
+            K.side.get(), e.flag.get());
+}
+
+// The stale kept state against the solution the workspace holds now; true: it serves (A.kept is current again), false: it
+// is gone and the caller builds as ever.  The host reads one word (m > 0; m = 0 has nothing to classify).  An unchanged
+// active set leaves the structure as it is -- act_rows, slot, side, h_side, the scratch, the factor's choice of solve -- and
+// only the caller-unit solution is written again; where P or A changed meanwhile the kept structure is factorised
+// numerically first (LdlFactor's constructor reads the pattern alone: every choice it takes holds for the new values, and
+// the probe of a dense top block is part of refactor).
+bool retained_state_serves(Engine &e, ModelAdjoint &A) {
+  AdjointKept &K = *A.kept;
+  hipStream_t s = e.stream;
+  const int n = e.n, m = e.m;
+  int changed = 0;
+  A.rt_checks++;
+  if (m > 0) {
+    e.flag.zero(s);
+    launch_side_changed(e, K);
+    e.flag.download(&changed, 1, s);
+    e.sync();
+  }
+  A.rt_last_changed = changed;
+  if (changed > 0) { A.rt_rebuilt_set++; model_adjoint_release(e); return false; }
+  if (K.values_dirty && K.F->refactor(nullptr) != 0) { A.rt_rebuilt_failed++; model_adjoint_release(e); return false; }
+  OQ_LAUNCH(k_adj_unscale, dim3(blocks_for((int64_t)n + m)), dim3(kBlock), 0, s, n, m, e.c, e.D.get(), e.E.get(), e.x.get(), e.y.get(),
+            K.xc.get(), K.yc.get());
+  e.sync();
+  if (K.values_dirty) A.rt_refactorised++; else A.rt_reused++;
+  K.stale = K.values_dirty = false;
+  return true;
+}
+
 // ---- the driver model_adjoint_run and model_jvp_run (direct_jvp.hpp) share ----
 // the workspace's derivative state with what the current solution keeps present (built by the first call after a solve);
 // who: the exported symbol that was called, form: what its refusals name.  The method of osqp_amd_derivative_method decides
@@ -310,7 +410,8 @@ ModelAdjoint &kept_state(Engine &e, const char *who, const char *form) {
   if (!e.adj) e.adj.reset(new ModelAdjoint());
   ModelAdjoint &A = *e.adj;
   A.who = who;
-  if (A.kept) return A;
+  if (A.kept && !A.kept->stale) return A;
+  if (A.kept && retained_state_serves(e, A)) return A;  // section 18 (only a state with a factor is ever stale)
   bool iterative = e.deriv_method == 2 || (e.deriv_method == 1 && !e.comm && workspace_compact(e));
   if (!iterative) {
     adjoint_needs_csr(e, who, form);
@@ -485,6 +586,28 @@ int model_adjoint_run(Engine &e, const char *who, bool dev, int ncot, const doub
   }
   write_act(e, K, act, dev);
   return 0;
+}
+
+// osqp_amd_time_kernel id 8: the check kernel of section 18 by itself on the kept state (stale or current), HIP events on the
+// engine's stream; -1 without a kept factor or with m = 0.  It writes the engine's flag word only.
+float model_adjoint_time_check(Engine &e, int reps) {
+  const AdjointKept *K = e.adj ? e.adj->kept.get() : nullptr;
+  if (!K || !K->F || e.m == 0) return -1.0f;
+  hipStream_t s = e.stream;
+  hipEvent_t a, b;
+  HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
+  e.flag.zero(s);
+  launch_side_changed(e, *K);  // warm
+  HIP_CHECK(hipEventRecord(a, s));
+  for (int i = 0; i < reps; i++) launch_side_changed(e, *K);
+  HIP_CHECK(hipEventRecord(b, s));
+  HIP_CHECK(hipEventSynchronize(b));
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+  (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+  e.flag.zero(s);
+  e.sync();
+  return ms / (float)reps;
 }
 
 }  // namespace oq

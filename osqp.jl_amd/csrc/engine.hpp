@@ -289,6 +289,13 @@ int model_adjoint_run(Engine &e, const char *who, bool dev, int ncot, const doub
 int model_jvp_run(Engine &e, const char *who, bool dev, int ndir, const double *tq, const double *tl, const double *tu,
                   const double *tPx, const double *tAx, double *tx, double *ty, double *act);
 void model_adjoint_release(Engine &e);  // drops the kept factor (the counters stay)
+// osqp_amd_adjoint_retain: a call that moves the model on drops the kept state, or under mode 1 marks
+// a state with a factor stale (values_changed: P or A changed, the factor needs its numeric part again) for the next
+// derivative call to check against the new solution
+void model_adjoint_moved_on(Engine &e, bool values_changed);
+void model_adjoint_retain(Engine &e, int mode);
+void model_adjoint_retain_stats(const Engine &e, double out[8]);
+float model_adjoint_time_check(Engine &e, int reps);  // osqp_amd_time_kernel id 8
 void model_adjoint_stats(const Engine &e, double out[6]);
 void model_adjoint_iter_stats(const Engine &e, double out[7]);  // osqp_amd_derivative_iter_stats
 

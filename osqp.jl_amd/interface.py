@@ -928,6 +928,34 @@ def adjoint_stats(model):
     return {name: int(v) for name, v in zip(ADJOINT_STATS_FIELDS, out)}
 
 
+ADJOINT_RETAIN_STATS_FIELDS = ("mode", "checks", "reused", "refactorised", "rebuilt_active_set", "rebuilt_failed", "last_rows_changed", "stale")
+
+
+def adjoint_retain(model, on=True):
+    """Extension: osqp_amd_adjoint_retain -- with on=True the factor `adjoint` / `jvp` keep outlives its solution: updates,
+    warm starts and solves mark it stale instead of dropping it, and the first derivative call on the next solution checks
+    on the device whether any row changed its side.  None did: the factor is reused (after a numeric refactorisation where
+    P or A changed); otherwise it is rebuilt as by default.  Settings updates, `derivative_method` and `adjoint_release`
+    still drop it.  on=False (the default of every model) drops a stale factor at once.  The results have the bits of the
+    default life cycle."""
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"on: expected a bool, got {on!r}")
+    fn = _symbol(model, "osqp_amd_adjoint_retain", _DERIVATIVES)
+    if fn(model.workspace, 1 if on else 0) != 0:
+        raise OSQPError("Error in adjoint_retain: " + model.lib.osqp_amd_last_error().decode())
+
+
+def adjoint_retain_stats(model):
+    """Extension: osqp_amd_adjoint_retain_stats as a dict of ints -- the mode, the checks of a stale factor made so far and
+    what became of them (reused, refactorised, rebuilt_active_set, rebuilt_failed), the rows that had changed side at the
+    last check, and whether the kept factor is stale now."""
+    fn = _symbol(model, "osqp_amd_adjoint_retain_stats", _DERIVATIVES)
+    out = np.zeros(len(ADJOINT_RETAIN_STATS_FIELDS))
+    if fn(model.workspace, _fptr(out), len(out)) != len(out):
+        raise OSQPError("osqp_amd_adjoint_retain_stats: bad argument")
+    return {name: int(v) for name, v in zip(ADJOINT_RETAIN_STATS_FIELDS, out)}
+
+
 DERIVATIVE_METHODS = ("direct", "auto", "iterative")
 DERIVATIVE_ITER_STATS_FIELDS = ("builds", "outer_steps", "cg_iters", "last_outer_steps", "last_drop", "kept", "bytes")
 

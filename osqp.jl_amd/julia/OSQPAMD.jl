@@ -195,6 +195,29 @@ function derivative_iter_stats(model::OSQP.Model)
             kept = out[6] == 1.0, bytes = Int(out[7]))
 end
 
+"""
+    adjoint_retain!(model, on = true)
+
+Let the factor `adjoint` and `jvp` keep outlive its solution (osqp_amd_adjoint_retain, DESIGN.md section 18): updates, warm
+starts and solves mark it stale instead of dropping it, and the first derivative call on the next solution checks on the
+device whether a row changed its side.  None did: the factor is reused (after a numeric refactorisation where P or A
+changed); otherwise it is rebuilt as by default.  `on = false` drops a stale factor at once.
+"""
+function adjoint_retain!(model::OSQP.Model, on::Bool = true)
+    flag = ccall((:osqp_amd_adjoint_retain, lib), Cc_int, (Ptr{OSQP.Workspace}, Cc_int), model.workspace, on ? 1 : 0)
+    flag == 0 || error("Error in adjoint_retain!: $(last_error())")
+    return nothing
+end
+
+"(mode, checks, reused, refactorised, rebuilt_active_set, rebuilt_failed, last_rows_changed, stale) of the retained factor (osqp_amd_adjoint_retain_stats)."
+function adjoint_retain_stats(model::OSQP.Model)
+    out = zeros(Float64, 8)  # OSQP_AMD_ADJOINT_RETAIN_STATS_COUNT (include/osqp_amd.h)
+    k = ccall((:osqp_amd_adjoint_retain_stats, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Cc_int), model.workspace, out, length(out))
+    k == length(out) || error("osqp_amd_adjoint_retain_stats: bad argument")
+    return (mode = Int(out[1]), checks = Int(out[2]), reused = Int(out[3]), refactorised = Int(out[4]), rebuilt_active_set = Int(out[5]),
+            rebuilt_failed = Int(out[6]), last_rows_changed = Int(out[7]), stale = out[8] == 1.0)
+end
+
 # ---- device-pointer forms of a single model's life cycle (include/osqp_amd.h, DESIGN.md section 16) ----
 # Every array is a DEVICE address on the model's device, as a `Ptr{Cdouble}` (`C_NULL`: not given / not wanted) -- for an
 # AMDGPU.jl array `Ptr{Cdouble}(UInt(pointer(a)))`; the package itself does not depend on a GPU array type.  The library runs

@@ -322,13 +322,17 @@ class QPLayer(torch.nn.Module):
     Tensors on the model's device stay there (device-pointer forms, no host hop; x, y and the gradients come back as CUDA
     tensors); CPU tensors go the host way and give CPU tensors; both at once is a ValueError.
     derivative_method: "direct" (the kept factor, the default), "auto" or "iterative" -- `interface.derivative_method`,
-    called once here; the last two serve a model on the indirect back-end, compact ones included."""
+    called once here; the last two serve a model on the indirect back-end, compact ones included.
+    retain_factor: True calls `interface.adjoint_retain(model)` once here -- the factor of one backward serves the next
+    step while the active set holds (a training loop); the default leaves the model's life cycle as it is."""
 
-    def __init__(self, model, derivative_method="direct"):
+    def __init__(self, model, derivative_method="direct", retain_factor=False):
         super().__init__()
         self.model, self.info = model, None
         if derivative_method != "direct":
             _iface.derivative_method(model, derivative_method)
+        if retain_factor:
+            _iface.adjoint_retain(model, True)
 
     def forward(self, q=None, l=None, u=None, Px=None, Ax=None):
         try:

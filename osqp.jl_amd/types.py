@@ -199,6 +199,9 @@ EXT_SYMBOLS = {
     "osqp_amd_device_form_calls": (c_int, [Workspace_p, c_float_p, c_int]),
     "osqp_amd_adjoint_release": (c_int, [Workspace_p]),
     "osqp_amd_adjoint_stats": (c_int, [Workspace_p, c_float_p, c_int]),
+    # the kept factor outlives its solution while the active set holds: mode 0 off / 1 on; what became of the stale states
+    "osqp_amd_adjoint_retain": (c_int, [Workspace_p, c_int]),
+    "osqp_amd_adjoint_retain_stats": (c_int, [Workspace_p, c_float_p, c_int]),
     # which KKT solve the derivatives use: method 0 direct / 1 auto / 2 iterative, max_outer, rel_drop (0 = default)
     "osqp_amd_derivative_method": (c_int, [Workspace_p, c_int, c_int, c_float]),
     "osqp_amd_derivative_iter_stats": (c_int, [Workspace_p, c_float_p, c_int]),
