@@ -339,6 +339,7 @@ struct Pcg : Linsys {
   int *h_ctl = nullptr;
   double cand_dev = -2.0;           // what dctl[0] holds
   long long issued = 0;             // steps enqueued since the last flush
+  std::vector<int> since_log;       // since_refresh after each of them: where the count stands when one of them stalls
   int spec = 2;                     // CG iterations enqueued per step
   std::map<int, hipGraphExec_t> graphs;
   // slots: (S_T0 r'z, S_T1 ||r||inf) and (S_T2, S_T3) alternate between iterations, S_T4 p'Mp, S_T5 ||b1||inf
@@ -730,17 +731,19 @@ struct Pcg : Linsys {
     }
     issued++;
     if (refresh) { carried_valid = true; since_refresh = 0; } else since_refresh++;
+    since_log.push_back(since_refresh);
     if (extrapolate) have_prev = true;
     if (issued >= 64) (void)flush_keep_error();
   }
   int deferred = 0;
+  void window_done() { issued = 0; since_log.clear(); }
   int flush_keep_error() { int rc = flush(); if (rc) deferred = rc; return rc; }
 
   // Wait for what was enqueued; finish a stalled solve on the host loop and re-issue the steps behind it.
   int flush() override {
     rhs_ready = false;
     if (!async_on) return 0;
-    if (deferred) { int rc = deferred; deferred = 0; issued = 0; return rc; }
+    if (deferred) { int rc = deferred; deferred = 0; window_done(); return rc; }
     hipStream_t s = e.stream;
     int guard = 0;
     while (issued > 0) {
@@ -751,23 +754,28 @@ struct Pcg : Linsys {
       const int stall_it = h_ctl[C_STALL_IT];
       total_iters += iters;
       HIP_CHECK(hipMemsetAsync(ctl.get(), 0, sizeof(int) * C_COUNT, s));
-      if (err) { issued = 0; carried_valid = false; have_prev = false; return 5; }
+      if (err) { window_done(); carried_valid = false; have_prev = false; return 5; }
       if (!stalled) {
         // speculation depth for the next window: one more than the mean needed
         const double mean = steps > 0 ? (double)iters / (double)steps : 0.0;
         int want = (int)std::ceil(mean) + 1;
         spec = std::min(kMaxSpec, std::max(1, std::max(want, spec - 1)));
-        issued = 0;
+        window_done();
         break;
       }
       // the step after `steps` completed ones ran out of enqueued iterations: its CG state is intact
       const long long behind = issued - steps - 1;
       int rc = finish_on_host(stall_it);
-      if (rc) { issued = 0; return rc; }
+      // The steps behind the stall fell through: their bookkeeping is redone from where the count stood after the stalled step
+      // (which ran, its refresh included).  Not since_refresh - behind: a refresh among the steps that fell through had set the
+      // count back to zero, the difference then lost every step before it -- and with it, when each window stalls before its
+      // refresh comes up, every refresh.
+      const int since_stalled = (size_t)steps < since_log.size() ? since_log[(size_t)steps] : 0;
+      if (rc) { window_done(); return rc; }
       finish_step();
       spec = std::min(kMaxSpec, spec + 1);
-      issued = 0;
-      since_refresh = (int)std::max<long long>(0, since_refresh - behind);  // the steps behind the stall fell through: their bookkeeping is redone
+      window_done();
+      since_refresh = since_stalled;
       for (long long i = 0; i < behind; i++) issue(spec, have_prev, since_refresh + 1 >= kRefresh);
       if (++guard > 1000) throw Error(6, "internal: the asynchronous CG path does not make progress");
     }

@@ -41,7 +41,6 @@ forward error in w / its share of the (a') bound (worst of two runs; the estimat
   dense-sym-0: equality-600 3.8e-10 / 280 / 2.1e-10 / 0.011;  equality-1100 1.5e-10 / 390 / 2.0e-10 / 0.0091
   dense-sym-1: equality-600 3.0e-10 / 180 / 2.9e-10 / 0.023;  equality-1100 1.5e-10 / 290 / 2.7e-10 / 0.011
 The module takes 9 - 11 s with an MI355X, host work included (9.5 s in the last run)."""
-import ctypes as C
 import re
 import zlib
 
@@ -49,15 +48,11 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import kkt_reference as kr
-import osqp_jl_amd as oq
 import qp_zoo
+from kkt_events import Workspace as _Workspace  # the event driver (shared with test_pcg_reference_gpu.py)
 from test_multifrontal_gpu import _random_problem
 
 pytestmark = pytest.mark.gpu
-
-RHO0, RHO1, RHO2 = 0.1, 0.731, 0.2
-PRODUCTS = 1e-12  # ops 0 / 1 / 2, componentwise relative to |M| |v|
 
 STRUCTURES = {
     "control": lambda: qp_zoo.control(nx=8, nu=4, T=400),
@@ -155,170 +150,6 @@ BY_CONDITION = {
     ("dense-sym-0", "equality-600"), ("dense-sym-0", "equality-1100"), ("dense-sym-1", "equality-600"), ("dense-sym-1", "equality-1100"),
     ("default", "lp"), ("default", "dense-row-and-column"),
 }
-
-
-def _fptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _apply(m, op, v, nout):
-    v = np.ascontiguousarray(v, dtype=np.float64)
-    out = np.empty(nout)
-    assert m.lib.osqp_amd_apply(m.workspace, op, _fptr(v), _fptr(out)) == 0
-    return out
-
-
-def _canonical(M):
-    M = sp.csc_matrix(M, dtype=np.float64, copy=True)
-    M.sum_duplicates()
-    M.sort_indices()
-    return M
-
-
-def _entries(M):
-    """Row and column of every stored entry, in storage order (the order of the nnz indices of an update)."""
-    return M.indices, np.repeat(np.arange(M.shape[1]), np.diff(M.indptr))
-
-
-class _Workspace:
-    """One workspace and the data it must hold: every event updates both, then the solve is checked against the data."""
-
-    def __init__(self, lib, prob, what, seed, by_condition):
-        self.by_condition = by_condition
-        P = sp.csc_matrix(prob["P"])
-        if sp.tril(P, -1).nnz:
-            P = sp.triu(P, format="csc")
-        self.P = _canonical(P)
-        n = self.P.shape[0]
-        self.A = _canonical(prob["A"]) if prob.get("A") is not None else sp.csc_matrix((0, n))
-        self.l = np.asarray(prob.get("l", np.zeros(0)), dtype=np.float64).copy()
-        self.u = np.asarray(prob.get("u", np.zeros(0)), dtype=np.float64).copy()
-        self.rho = RHO0
-        self.rng = np.random.default_rng(seed)
-        self.m = oq.Model(lib)
-        oq.setup(self.m, P=self.P, q=prob["q"], A=self.A, l=self.l, u=self.u, linsys_solver="direct", verbose=False, scaling=0,
-                 adaptive_rho=False, rho=RHO0)
-        self.factorizations = 1
-        st = self.stats()
-        self.what = f"{what} (supernode levels {int(st[19])}, dense block {int(st[25])})"
-
-    def stats(self):
-        return oq.stats(self.m)
-
-    def check(self, event):
-        n, mm = self.A.shape[1], self.A.shape[0]
-        ref = kr.Reference(self.P, self.A, kr.rho_vector(self.l, self.u, self.rho))
-        b = self.rng.standard_normal(n + mm)
-        out = np.empty_like(b)
-        assert self.m.lib.osqp_amd_apply(self.m.workspace, 3, _fptr(b), _fptr(out)) == 0
-        ref.check(b, out, kr.BACKWARD, kr.IDENTITY, kr.FORWARD, what=f"{self.what} / {event}", by_condition=self.by_condition)
-        assert self.stats()[8] == self.factorizations, (self.what, event, self.stats()[8], self.factorizations)
-
-    def check_products(self, event):
-        n, mm = self.A.shape[1], self.A.shape[0]
-        x, y = self.rng.standard_normal(n), self.rng.standard_normal(mm)
-        for op, M, v in ((0, self.A, x), (1, self.A.T.tocsc(), y), (2, kr.full_P(self.P), x)):
-            if M.shape[0] == 0 or M.shape[1] == 0:
-                continue
-            err = kr.ratio(np.abs(_apply(self.m, op, v, M.shape[0]) - M @ v), abs(M) @ np.abs(v))
-            assert err <= PRODUCTS, (self.what, event, op, err)
-
-    def rho_update(self, rho, event):
-        oq.update_settings(self.m, rho=rho)
-        self.rho = rho
-        self.factorizations += 1
-        self.check(event)
-
-    def _update(self, Px, Px_idx, Ax, Ax_idx, event):
-        Px = None if Px is None or len(Px) == 0 else Px
-        Ax = None if Ax is None or len(Ax) == 0 else Ax
-        assert Px is not None or Ax is not None
-        oq.update(self.m, Px=Px, Px_idx=None if Px is None else Px_idx, Ax=Ax, Ax_idx=None if Ax is None else Ax_idx)
-        for M, vals, idx in ((self.P, Px, Px_idx), (self.A, Ax, Ax_idx)):
-            if vals is not None:
-                M.data[slice(None) if idx is None else idx] = vals
-        self.factorizations += 1
-        self.check(event)
-        self.check_products(event)
-
-    def full_update(self, event):
-        """P -> D P D, A -> A o (1 + 0.3 xi); explicitly stored zeros become non-zero (a diagonal one d_i^2, an off-diagonal one a
-        quarter of the geometric mean of its two new diagonal entries, A's a value in +-[0.5, 1.5])."""
-        n = self.P.shape[0]
-        r, c = _entries(self.P)
-        d = self.rng.uniform(0.5, 2.0, n)
-        Px = d[r] * d[c] * self.P.data
-        zero = self.P.data == 0
-        Px[zero & (r == c)] = d[r[zero & (r == c)]] ** 2
-        dpos = np.full(n, -1)
-        dpos[c[r == c]] = np.flatnonzero(r == c)
-        off = np.flatnonzero(zero & (r != c) & (dpos[r] >= 0) & (dpos[c] >= 0))
-        Px[off] = 0.25 * np.sqrt(Px[dpos[r[off]]] * Px[dpos[c[off]]])
-        Ax = self.A.data * (1.0 + 0.3 * self.rng.uniform(-1.0, 1.0, self.A.nnz))
-        za = self.A.data == 0
-        Ax[za] = self.rng.choice([-1.0, 1.0], int(za.sum())) * self.rng.uniform(0.5, 1.5, int(za.sum()))
-        self._update(Px, None, Ax, None, event)
-
-    def subset_update(self, event):
-        n = self.P.shape[0]
-        S = self.rng.choice(n, max(1, n // 10), replace=False)
-        d = np.ones(n)
-        d[S] = self.rng.uniform(0.5, 2.0, len(S))
-        r, c = _entries(self.P)
-        pidx = self.rng.permutation(np.flatnonzero(np.isin(r, S) | np.isin(c, S)))
-        aidx = self.rng.choice(self.A.nnz, max(1, self.A.nnz // 3), replace=False) if self.A.nnz else np.zeros(0, dtype=np.int64)
-        Px = d[r[pidx]] * d[c[pidx]] * self.P.data[pidx]
-        Ax = self.A.data[aidx] * (1.0 + 0.3 * self.rng.uniform(-1.0, 1.0, len(aidx)))
-        self._update(Px, pidx, Ax, aidx, event)
-
-    def bounds_update(self, event):
-        """A tenth of the inequality rows become equalities, another tenth free; a third of the equality rows inequalities."""
-        t = kr.row_classes(self.l, self.u)
-        l, u = self.l.copy(), self.u.copy()
-        ineq, eq = self.rng.permutation(np.flatnonzero(t == 0)), self.rng.permutation(np.flatnonzero(t == 1))
-        k = max(1, len(ineq) // 10) if len(ineq) >= 2 else 0
-        to_eq, to_free, to_ineq = ineq[:k], ineq[k:2 * k], eq[:max(1, len(eq) // 3)] if len(eq) else eq
-        v = np.where(np.isfinite(l[to_eq]), l[to_eq], np.where(np.isfinite(u[to_eq]), u[to_eq], 0.0))
-        l[to_eq], u[to_eq] = v, v
-        l[to_free], u[to_free] = -np.inf, np.inf
-        l[to_ineq] -= 1.0
-        u[to_ineq] += 1.0
-        want = t.copy()
-        want[to_eq], want[to_free], want[to_ineq] = 1, -1, 0
-        assert np.array_equal(kr.row_classes(l, u), want) and not np.array_equal(want, t)
-        oq.update(self.m, l=l, u=u)
-        self.l, self.u = l, u
-        self.factorizations += 1
-        self.check(event)
-
-    def refuses_an_indefinite_P(self):
-        """The last stored diagonal entry of P far below -(rho |A_j|^2 + |P_j|): the reduced matrix P + sigma I + A' R A is
-        indefinite, and with it the KKT matrix's inertia is wrong."""
-        r, c = _entries(self.P)
-        diag = np.flatnonzero(r == c)
-        if len(diag) == 0:
-            return False
-        k = diag[np.argmax(c[diag])]
-        j = c[k]
-        Aj = self.A[:, [j]]
-        rho = kr.rho_vector(self.l, self.u, self.rho)
-        v = -1e3 * (1.0 + float(np.sum(rho[Aj.indices] * Aj.data ** 2)) + float(abs(kr.full_P(self.P)[:, [j]]).sum()))
-        with pytest.raises(oq.OSQPError):
-            oq.update(self.m, Px=np.array([v]), Px_idx=np.array([k]))
-        return True
-
-    def run(self):
-        self.check("setup")
-        self.rho_update(RHO1, "rho update")
-        self.full_update("P and A update")
-        self.subset_update("update of an index subset")
-        if self.A.shape[0]:
-            self.bounds_update("bounds update (row classes)")
-        self.rho_update(RHO2, "second rho update")
-        return self.refuses_an_indefinite_P()
-
-    def close(self):
-        oq.clean(self.m)
 
 
 def _run_case(lib, monkeypatch, capfd, env, form_ran, traces, prob, form, structure):
