@@ -325,8 +325,10 @@ c_int osqp_amd_setup_generated(OSQPWorkspace **workp, c_int kind, c_int n, c_int
  *    back to hipMalloc; 128 TiB per process)
  * 25 pivots of the dense top block of the direct back-end (its Schur complement is inverted explicitly: block sweeps on the
  *    fp64 matrix cores from 512 pivots on); 0: none
+ * 26 whole-matrix products issued by residual evaluations so far (A x, P x and A' y per evaluation; osqp_amd_iterate evaluates
+ *    every check_termination iterations and at its last iteration, once each)
  * Returns the number of entries written (at most OSQP_AMD_STATS_COUNT). */
-#define OSQP_AMD_STATS_COUNT 26
+#define OSQP_AMD_STATS_COUNT 27
 c_int osqp_amd_get_stats(const OSQPWorkspace *work, c_float *out, c_int count);
 
 /* Time `reps` launches of one hot-path kernel with HIP events on the engine's
@@ -398,9 +400,13 @@ c_int osqp_amd_apply(OSQPWorkspace *work, c_int op, const c_float *in, c_float *
  *  2 panel shift (panels of 2^shift columns)   3 panels B   4 panels per group Gp   5 groups NG (the reduction depth)
  *  6 tiles   7 slices   8 padded entries of the sliced copy   9 stored entries (nnz)
  * 10 compact (the CSR column / value arrays of this matrix released) 0 / 1
- * Entries 2-8 are 0 when the matrix runs on the CSR kernel.  Returns the number of entries written (at most
+ * 11 fused: the single product adds up its group sums inside the product launch (k_spmv_sell_fused) 0 / 1
+ * 12 rshift: reduce blocks of 2^rshift rows (LDS-staged panels)
+ * 13 products of this matrix that ran on k_spmv_sell_fused so far (a product onto its own input keeps two kernels and is not
+ *    counted, nor is any launch of the two-kernel form)
+ * Entries 2-8 and 11-13 are 0 when the matrix runs on the CSR kernel.  Returns the number of entries written (at most
  * OSQP_AMD_LAYOUT_COUNT), 0 on a bad argument. */
-#define OSQP_AMD_LAYOUT_COUNT 11
+#define OSQP_AMD_LAYOUT_COUNT 14
 c_int osqp_amd_spmv_layout(const OSQPWorkspace *work, c_int which, c_float *out, c_int count);
 
 /* Which kernel the last batched solve of this process ran (tests, benchmarks): -1 the 512-thread kernel (one QP per eight

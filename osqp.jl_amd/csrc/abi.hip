@@ -738,6 +738,7 @@ c_int osqp_amd_get_stats(const OSQPWorkspace *w, c_float *out, c_int count) {
   v[23] = e.lin->lean_setup();
   v[24] = (c_float)dev_va_reserved();
   v[25] = e.lin->dense_block();
+  v[26] = (c_float)e.residual_products;
   c_int k = 0;
   for (; k < count && k < OSQP_AMD_STATS_COUNT; k++) out[k] = v[k];
   return k;
@@ -831,6 +832,7 @@ c_int osqp_amd_spmv_layout(const OSQPWorkspace *w, c_int which, c_float *out, c_
   if (P.active) {
     v[2] = (c_float)P.shift; v[3] = (c_float)P.B; v[4] = (c_float)P.Gp; v[5] = (c_float)P.NG;
     v[6] = (c_float)P.ntiles; v[7] = (c_float)P.slice_base.n; v[8] = (c_float)P.padded;
+    v[11] = P.fused ? 1.0 : 0.0; v[12] = (c_float)P.rshift; v[13] = (c_float)P.fused_launches;
   }
   v[9] = (c_float)M.nnz;
   v[10] = M.compact ? 1.0 : 0.0;

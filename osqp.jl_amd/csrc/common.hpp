@@ -161,6 +161,12 @@ struct DevPanel {
   DevBuf<uint32_t> scol32;                   // their local column ids
   DevBuf<double> partial;                    // [NG * rows] per-group row sums, reduced in fixed order
   size_t padded = 0;                         // stored entries including padding
+  // Reduce blocks of R = 2^rshift rows (LDS-staged layouts): need[k] = tiles, over all groups, whose rows meet block k;
+  // arrived[k] counts them during a fused product and is back at 0 when the launch ends (panel.hip, k_spmv_sell_fused).
+  int rshift = 0;
+  bool fused = false;                        // the single product adds up its group sums inside the product launch
+  DevBuf<int> need, arrived;
+  mutable long long fused_launches = 0;      // products that ran on k_spmv_sell_fused (osqp_amd_spmv_layout: tests, records)
 };
 
 struct DevCsr {

@@ -974,6 +974,7 @@ void Engine::residual_evaluation() {
   spmv(A, xg, Ax.get(), nullptr, 0.0, 0.0, nullptr, stream);
   spmv(Pf, xg, Px_.get(), nullptr, 0.0, 0.0, nullptr, stream);
   if (m > 0) spmv(At, full_m(y.get()), Aty.get(), nullptr, 0.0, 0.0, nullptr, stream);
+  residual_products += m > 0 ? 3 : 2;
   residual_norms(n, m, x.get(), z.get(), Ax.get(), Px_.get(), Aty.get(), q.get(), Dinv.get(), Einv.get(), slots.get(),
                  partials.get(), stream);
   fetch_slots(0, 16, (1u << S_XPX) | (1u << S_QX));
@@ -1355,12 +1356,15 @@ double Engine::obj_from_slots_fresh() {
 int Engine::iterate(long long iters) {
   tic();
   lin->set_guess(x.get());
+  long long evaluated_at = -1;
   for (long long it = 1; it <= iters; it++) {
     if (can_chunk(it, iters)) { run_chunk(); it += chunk_k() - 1; }
     else admm_step();
-    if (st.check_termination && (it % st.check_termination == 0)) update_info(it, false);
+    // the last iteration of the call is evaluated once, with the objective: a second evaluation of the same iterate would
+    // repeat three whole-matrix products for numbers the first one has (the objective comes from the same slots)
+    if (st.check_termination && (it % st.check_termination == 0)) { update_info(it, it == iters); evaluated_at = it; }
   }
-  update_info(iters, true);
+  if (evaluated_at != iters) update_info(iters, true);
   sync();
   if (deferred_error) { int rc = deferred_error; deferred_error = 0; return rc; }
   return 0;

@@ -153,6 +153,7 @@ struct Engine {
   int deferred_error = 0;  // an asynchronous back-end met negative curvature some iterations ago (reported at the next check)
   // statistics
   long long admm_iters_total = 0;
+  long long residual_products = 0;  // whole-matrix products issued by residual evaluations (A x, P x, A' y each time)
   // graph of `check_termination` iterations (direct back-end)
   hipGraphExec_t chunk_exec = nullptr;
   int chunk_len = 0;

@@ -12,7 +12,8 @@
 // is two-dimensional -- a matrix whose density varies along its columns stays balanced).  A
 // workgroup walks the Gp panels of its tile one after the other with the row sums staying in LDS,
 // and writes them once per group to an [NG x rows] buffer that a second kernel adds up in group
-// order (fixed order => reproducible) together with the SpMV epilogue.
+// order (fixed order => reproducible) together with the SpMV epilogue.  On a layout of many tiles per compute unit the single
+// product does that adding itself: the tile that arrives last at a block of rows adds up the block (k_spmv_sell_fused).
 //
 // Inside a tile the entries are laid out as sliced ELL:
 //   * the rows of the tile are ordered by their length inside the panel, longest first;
@@ -174,6 +175,17 @@ __global__ __launch_bounds__(kBlock) void k_tile_ends(int rows, int ntiles, cons
   const int t = blockIdx.x * kBlock + threadIdx.x;
   if (t >= ntiles) return;
   tile_r1[t] = (t + 1 < ntiles && tile_b[t + 1] == tile_b[t]) ? tile_r0[t + 1] : rows;
+}
+
+// need[k] = tiles, over all groups, whose rows [r0, r1) meet reduce block k = rows [k << rshift, (k + 1) << rshift): what the
+// arrival counter of block k reaches in a fused product.  A tile's blocks follow from r0 and r1; no per-tile list.
+__global__ __launch_bounds__(kBlock) void k_block_need(int ntiles, int rshift, const int *__restrict__ tile_r0, const int *__restrict__ tile_r1,
+                                                       int *__restrict__ need) {
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= ntiles) return;
+  const int r0 = tile_r0[t], r1 = tile_r1[t];
+  if (r1 <= r0) return;
+  for (int k = r0 >> rshift; k <= (r1 - 1) >> rshift; k++) atomicAdd(need + k, 1);
 }
 
 // The rows of a tile ordered by length inside the panel, longest first, ties by row id: bitonic sort of
@@ -394,7 +406,8 @@ __global__ __launch_bounds__(kFillWaves * 64) void k_sell_fill_lds(int rows, int
 // ---------------------------------------------------------------------------------------------
 // kSquare: y = (M .* M) x -- the Jacobi diagonal of A' diag(rho) A is this product of A' with rho (compact mode)
 // kNT: non-temporal loads for the matrix stream and the slice descriptors (sell_nt()); x, LDS and the row sums as ever
-template <typename ColT, bool kStageX, bool kSquare, bool kNT>
+// kSc1Out: the row sums go out as agent-scope (write-through) stores: another workgroup of this launch reads them (k_spmv_sell_fused)
+template <typename ColT, bool kStageX, bool kSquare, bool kNT, bool kSc1Out = false>
 __device__ __forceinline__ void sell_tile(int t, int rows, int cols, int shift, int B, int Gp, const int *__restrict__ tile_g,
                                           const int *__restrict__ tile_r0, const int *__restrict__ tile_r1,
                                           const int *__restrict__ unit_s0, const int *__restrict__ unit_ns,
@@ -484,7 +497,10 @@ __device__ __forceinline__ void sell_tile(int t, int rows, int cols, int shift, 
   }
   __syncthreads();
   double *out = partial + (size_t)g * rows + r0;
-  for (int i = threadIdx.x; i < nrows; i += kThreads) out[i] = ys[i];
+  for (int i = threadIdx.x; i < nrows; i += kThreads) {
+    if constexpr (kSc1Out) __hip_atomic_store(out + i, ys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through
+    else out[i] = ys[i];
+  }
 }
 template <typename ColT, bool kStageX, bool kSquare, bool kNT>
 __global__ __launch_bounds__(kThreads) void k_spmv_sell(int rows, int cols, int shift, int B, int Gp, const int *__restrict__ tile_g,
@@ -521,38 +537,54 @@ __global__ __launch_bounds__(kThreads) void k_spmv_sell_pair(SellSide a, SellSid
                                          m.partial);
 }
 
-// y[i] = (rscale ? rscale[i] : 1) * sum_g partial[g][i] + beta * y[i] + gamma * v[i]   (group order is fixed)
+// One row of the reduce: y[i] = (rscale ? rscale[i] : 1) * sum_g partial[g][i] + beta * y[i] + gamma * v[i], the groups added in
+// their fixed order in 8-wide, 4-wide and scalar pieces; y2[i] = s2[i] * (the raw sum) when asked for.  Returns y[i].  The ONE
+// source of the expression: the reduce kernels and the last arriver of a fused product (below) give the same bits.
+// kAgent: the partial sums were stored by other workgroups of THIS launch -- agent-scope loads, past the L1 of this CU.
+template <bool kAgent>
+__device__ __forceinline__ double ld_partial(const double *p) {
+  if constexpr (kAgent) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return *p;
+}
+template <bool kAgent>
+__device__ __forceinline__ double panel_reduce_row(int i, int rows, int B, const double *partial, double *y, const double *rscale, double beta,
+                                                   double gamma, const double *v, double *y2, const double *s2) {
+  double acc = 0.0;
+  int b = 0;
+  for (; b + 8 <= B; b += 8) {  // eight loads in flight, added in group order
+    double t[8];
+#pragma unroll
+    for (int u = 0; u < 8; u++) t[u] = ld_partial<kAgent>(partial + (size_t)(b + u) * rows + i);
+#pragma unroll
+    for (int u = 0; u < 8; u++) acc += t[u];
+  }
+  if (b + 4 <= B) {
+    double t[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) t[u] = ld_partial<kAgent>(partial + (size_t)(b + u) * rows + i);
+#pragma unroll
+    for (int u = 0; u < 4; u++) acc += t[u];
+    b += 4;
+  }
+  for (; b < B; b++) acc += ld_partial<kAgent>(partial + (size_t)b * rows + i);
+  if (y2) y2[i] = s2[i] * acc;
+  if (rscale) acc *= rscale[i];
+  if (beta != 0.0) acc += beta * y[i];
+  if (v) acc += gamma * v[i];
+  y[i] = acc;
+  return acc;
+}
 // Grid of at most kReduceBlocks blocks, grid-stride over the rows -- the thread-to-row assignment of the two-stage
 // reductions (k_dot_partial), so that the optional dot product of the result with another vector lands in the same
 // partials, in the same order, as a separate reduce_dot would form (SpmvExtra).
+// kFromY: y is finished (a fused product wrote it); only the sums over rows are formed, from y[i] read back.
+template <bool kFromY>
 __device__ __forceinline__ void panel_reduce_rows(int vb, int vg, int rows, int B, const double *__restrict__ partial, double *__restrict__ y,
                                                   const double *__restrict__ rscale, double beta, double gamma,
                                                   const double *__restrict__ v, const SpmvExtra &ex) {
   double dot = 0.0, mx = 0.0, num = 0.0, den = 0.0;
   for (int i = vb * kBlock + threadIdx.x; i < rows; i += vg * kBlock) {
-    double acc = 0.0;
-    int b = 0;
-    for (; b + 8 <= B; b += 8) {  // eight loads in flight, added in group order
-      double t[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) t[u] = partial[(size_t)(b + u) * rows + i];
-#pragma unroll
-      for (int u = 0; u < 8; u++) acc += t[u];
-    }
-    if (b + 4 <= B) {
-      double t[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) t[u] = partial[(size_t)(b + u) * rows + i];
-#pragma unroll
-      for (int u = 0; u < 4; u++) acc += t[u];
-      b += 4;
-    }
-    for (; b < B; b++) acc += partial[(size_t)b * rows + i];
-    if (ex.y2) ex.y2[i] = ex.s2[i] * acc;
-    if (rscale) acc *= rscale[i];
-    if (beta != 0.0) acc += beta * y[i];
-    if (v) acc += gamma * v[i];
-    y[i] = acc;
+    const double acc = kFromY ? y[i] : panel_reduce_row<false>(i, rows, B, partial, y, rscale, beta, gamma, v, ex.y2, ex.s2);
     if (ex.dotv) dot += ex.dotv[i] * acc;
     if (ex.absmax_slot) mx = nanmax(mx, fabs(acc));
     if (ex.e2_partials) {
@@ -583,7 +615,73 @@ __global__ __launch_bounds__(kBlock) void k_panel_reduce(int rows, int B, const 
                                                          const double *__restrict__ rscale, double beta, double gamma,
                                                          const double *__restrict__ v, SpmvExtra ex, const int *__restrict__ skip) {
   if (skip && *skip) return;
-  panel_reduce_rows(blockIdx.x, gridDim.x, rows, B, partial, y, rscale, beta, gamma, v, ex);
+  panel_reduce_rows<false>(blockIdx.x, gridDim.x, rows, B, partial, y, rscale, beta, gamma, v, ex);
+}
+// The sums over rows of a product whose y the fused launch has finished (dot_partials, absmax_slot, e2_partials): they are
+// sums over rows strided by the reduce grid, which a row block cannot form in that order.  The grid and the thread-to-row
+// assignment of k_panel_reduce, y[i] read back (16-32 MB from cache): the partials are bit for bit those of the two-kernel form.
+__global__ __launch_bounds__(kBlock) void k_panel_row_sums(int rows, double *__restrict__ y, SpmvExtra ex, const int *__restrict__ skip) {
+  if (skip && *skip) return;
+  panel_reduce_rows<true>(blockIdx.x, gridDim.x, rows, 0, nullptr, y, nullptr, 0.0, 0.0, nullptr, ex);
+}
+
+// The single product with the reduce inside the launch.  A tile's row sums are final when the tile ends; the tile that arrives
+// last at a block of R = 2^rshift rows adds up that block, in the fixed group order, while the other compute units keep
+// streaming.  Arrival is a ticket: the tile's row sums go to `partial` as agent-scope write-through stores, every wave waits for
+// its own to complete, the workgroup meets, and lane j of wave 0 draws a ticket from arrived[k0 + j] (one agent-scope fetch_add
+// per block the tile meets, k0 its first); the ticket need[k] - 1 is the last.  (The write-through stores stand in for a release
+// fence before the ticket, as in k_pcg_sr: the fence writes back every dirty line of the XCD's L2 and cost ~7 us per tile here,
+// 1.77 -> 1.86 ms per product)  The last arriver acquires at agent scope, reads the NG partial rows of
+// the block with agent-scope loads (other XCDs wrote them during this launch), applies panel_reduce_row and sets arrived[k]
+// back to 0: the launch can be replayed as it is.  No workgroup waits for another: no polling, nothing that can hang.
+// A tile has at most kTileRowsMax rows and R >= 64, so it meets at most 63 blocks: one ballot holds "last at block k0 + j".
+// y (and y2) must not overlap x: rows are finished while other tiles still read x (spmv_panel checks).
+template <bool kNT>
+__global__ __launch_bounds__(kThreads) void k_spmv_sell_fused(int rows, int cols, int shift, int B, int Gp, int NG, const int *__restrict__ tile_g,
+                                                              const int *__restrict__ tile_r0, const int *__restrict__ tile_r1,
+                                                              const int *__restrict__ unit_s0, const int *__restrict__ unit_ns,
+                                                              const uint32_t *__restrict__ slice_base, const int *__restrict__ slice_len,
+                                                              const uint16_t *__restrict__ slice_rows, const uint16_t *__restrict__ scol,
+                                                              const double *__restrict__ sval, const double *__restrict__ x, double *partial,
+                                                              int rshift, const int *__restrict__ need, int *arrived, double *y,
+                                                              const double *rscale, double beta, double gamma, const double *v, double *y2,
+                                                              const double *s2, const int *__restrict__ skip) {
+  if (skip && *skip) return;  // every workgroup of the launch takes this branch or none: arrived stays as it is
+  const int t = blockIdx.x;
+  sell_tile<uint16_t, true, false, kNT, true>(t, rows, cols, shift, B, Gp, tile_g, tile_r0, tile_r1, unit_s0, unit_ns, slice_base, slice_len,
+                                         slice_rows, scol, sval, x, partial);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its stores of the tile's row sums are complete
+  __syncthreads();                                   // ... and the staged x panel is no longer read
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  unsigned long long *last = reinterpret_cast<unsigned long long *>(lds);  // in place of the x panel: all LDS stays in the one dynamic array
+  const int r0 = tile_r0[t], r1 = tile_r1[t];
+  if (r1 <= r0) return;
+  const int k0 = r0 >> rshift, nb = ((r1 - 1) >> rshift) - k0 + 1;
+  if (threadIdx.x < 64) {
+    bool mine = false;
+    if ((int)threadIdx.x < nb) {
+      const int ticket = __hip_atomic_fetch_add(arrived + k0 + threadIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      mine = ticket == need[k0 + threadIdx.x] - 1;
+    }
+    const unsigned long long m = __ballot(mine);
+    if (m) {  // wave-uniform.  Only wave 0 fences.  The other waves rely on ld_partial<true>: after the barrier they read
+              // `partial` with agent-scope (sc1) loads alone, which are coherent across the device without a fence of their
+              // own.  Plain loads there would need this acquire in every wave.
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    if (threadIdx.x == 0) *last = m;
+  }
+  __syncthreads();
+  unsigned long long m = *last;
+  while (m) {
+    const int j = __builtin_ctzll(m);
+    m &= m - 1;
+    const int k = k0 + j;
+    const int lo = k << rshift, hi = min(rows, lo + (1 << rshift));
+    for (int i = lo + (int)threadIdx.x; i < hi; i += kThreads) panel_reduce_row<true>(i, rows, NG, partial, y, rscale, beta, gamma, v, y2, s2);
+    if (threadIdx.x == 0) __hip_atomic_store(arrived + k, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 // the reduces of a pair launch: blocks [0, ga) are the grid of the first, the rest that of the second
 struct ReduceSide {
@@ -598,7 +696,7 @@ __global__ __launch_bounds__(kBlock) void k_panel_reduce_pair(ReduceSide a, Redu
   if (skip && *skip) return;
   const bool first = (int)blockIdx.x < a.grid;
   const ReduceSide &m = first ? a : b;
-  panel_reduce_rows(first ? (int)blockIdx.x : (int)blockIdx.x - a.grid, m.grid, m.rows, m.B, m.partial, m.y, nullptr, 0.0, m.gamma, m.v, m.ex);
+  panel_reduce_rows<false>(first ? (int)blockIdx.x : (int)blockIdx.x - a.grid, m.grid, m.rows, m.B, m.partial, m.y, nullptr, 0.0, m.gamma, m.v, m.ex);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -892,6 +990,25 @@ static int panel_group_size(const DevCsr &M, int B) {
   return 1;
 }
 
+// Rows per reduce block of the fused single product, as a shift: OSQP_AMD_PANEL_RBLOCK rounded up to a power of two, at least
+// 64 (a tile of kTileRowsMax rows then meets at most 63 blocks: one ballot in k_spmv_sell_fused).  Default 2048: the 16 group
+// rows of a block are 256 KB for the last arriver, two rows per thread.
+static int reduce_block_shift() {
+  const int want = std::max(64, std::min(env_int("OSQP_AMD_PANEL_RBLOCK", 2048), 1 << 24));
+  int sh = 6;
+  while ((1 << sh) < want) sh++;
+  return sh;
+}
+// OSQP_AMD_PANEL_FUSED_REDUCE (read when a layout is built): 1 on, 0 off; unset: on when the layout has at least four tiles per
+// compute unit -- the block reductions then hide under tiles that still stream (rand-1e6: ~15 rounds of tiles); a layout of one
+// round or less (rand-1e5: 153-217 tiles) would only lengthen its tiles by the ticket, and keeps the two-kernel form.
+static bool fused_reduce_wanted(int ntiles) {
+  if (const char *e = getenv("OSQP_AMD_PANEL_FUSED_REDUCE")) return atoi(e) != 0;
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return ntiles >= 4 * cus;
+}
+
 // 0: plain CSR kernel; 1: panels of 2^shift columns staged in LDS; 2: wide panels of 2^18 columns left to L2
 // width of the wide panels: 2^18 columns (2 MB of x, half an L2), up to 2^20 when the rows are so thin that a narrower
 // panel holds fewer than ~3.5 entries of a row (measured at n = 4e6 / 150 per row: 2^16..2^18 equal, 2^19 +25 %, 2^20 +55 %;
@@ -995,6 +1112,16 @@ void panel_build(DevCsr &M, hipStream_t s, uint32_t *slot, bool will_compact, co
   P.tile_g.alloc((size_t)ntiles); P.tile_r0.alloc((size_t)ntiles); P.tile_r1.alloc((size_t)ntiles);
   OQ_LAUNCH(k_tile_fill, dim3(blocks_for(gcells)), dim3(kBlock), 0, s, M.rows, gcells, gcnt.get(), tid.get(), P.tile_g.get(), P.tile_r0.get());
   OQ_LAUNCH(k_tile_ends, dim3(blocks_for(ntiles)), dim3(kBlock), 0, s, M.rows, P.ntiles, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get());
+  P.fused = false;
+  P.fused_launches = 0;
+  if (!P.wide) {  // reduce blocks and their arrival counts: what the fused single product needs (k_spmv_sell_fused)
+    P.rshift = reduce_block_shift();
+    const size_t nblocks = (size_t)(((int64_t)M.rows + (1LL << P.rshift) - 1) >> P.rshift);
+    P.need.alloc(nblocks); P.arrived.alloc(nblocks);
+    P.need.zero(s); P.arrived.zero(s);
+    OQ_LAUNCH(k_block_need, dim3(blocks_for(ntiles)), dim3(kBlock), 0, s, P.ntiles, P.rshift, P.tile_r0.get(), P.tile_r1.get(), P.need.get());
+    P.fused = fused_reduce_wanted(P.ntiles);
+  }
   const int64_t nunits = ntiles * P.Gp;
   DevBuf<int> ub((size_t)nunits), u0((size_t)nunits), u1((size_t)nunits);
   OQ_LAUNCH(k_expand_units, dim3(blocks_for(nunits)), dim3(kBlock), 0, s, P.ntiles, P.B, P.Gp, P.tile_g.get(), P.tile_r0.get(),
@@ -1063,6 +1190,24 @@ void spmv_panel(const DevCsr &M, const double *x, double *y, const double *rscal
                 hipStream_t s, const SpmvExtra *extra) {
   const DevPanel &P = M.panel;
   const SpmvExtra ex = extra ? *extra : SpmvExtra();
+  // The fused form finishes rows of y (and y2) while other tiles still read x: a product onto its own input keeps two kernels.
+  auto overlaps = [](const double *a, size_t na, const double *b, size_t nb) { return a && b && a < b + nb && b < a + na; };
+  if (P.fused && !P.wide && !overlaps(x, (size_t)M.cols, y, (size_t)M.rows) && !overlaps(x, (size_t)M.cols, ex.y2, (size_t)M.rows)) {
+    with_sell_nt([&](auto nt) {
+      constexpr bool kNT = decltype(nt)::value;
+      static size_t allowed[64] = {0};
+      allow_dynamic_lds((const void *)k_spmv_sell_fused<kNT>, spmv_lds_bytes(P.shift), allowed);
+      OQ_LAUNCH(k_spmv_sell_fused<kNT>, dim3(P.ntiles), dim3(kThreads), spmv_lds_bytes(P.shift), s, M.rows, M.cols, P.shift, P.B, P.Gp, P.NG,
+                P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(), P.slice_len.get(),
+                P.slice_rows.get(), P.scol.get(), P.sval.get(), x, P.partial.get(), P.rshift, (const int *)P.need.get(), P.arrived.get(), y, rscale,
+                beta, gamma, v, ex.y2, ex.s2, g_skip);
+    });
+    P.fused_launches++;
+    // sums over rows keep the order of the reduce grid: one light pass over the finished y, only for a product that carries one
+    if (ex.dot_partials || ex.absmax_slot || ex.e2_partials)
+      OQ_LAUNCH(k_panel_row_sums, dim3(reduce_grid(M.rows)), dim3(kBlock), 0, s, M.rows, y, ex, g_skip);
+    return;
+  }
   if (P.wide) {  // default-policy loads: its x is served by the L2 the matrix stream passes through
     OQ_LAUNCH((k_spmv_sell<uint32_t, false, false, false>), dim3(P.ntiles), dim3(kThreads), sizeof(double) * kTileRowsMax, s, M.rows, M.cols,
               P.shift, P.B, P.Gp, P.tile_g.get(), P.tile_r0.get(), P.tile_r1.get(), P.unit_s0.get(), P.unit_ns.get(), P.slice_base.get(),

@@ -597,14 +597,15 @@ def warm_start(model, x=None, y=None):
         warm_start_y(model, y)
 
 
-def stats(model, count=26):
+def stats(model, count=27):
     """Extension: osqp_amd_get_stats as a list of floats."""
     out = np.zeros(count)
     k = model.lib.osqp_amd_get_stats(model.workspace, _fptr(out), count)
     return out[:k]
 
 
-SPMV_LAYOUT_FIELDS = ("kernel", "G", "shift", "B", "Gp", "NG", "tiles", "slices", "padded", "nnz", "compact")
+SPMV_LAYOUT_FIELDS = ("kernel", "G", "shift", "B", "Gp", "NG", "tiles", "slices", "padded", "nnz", "compact", "fused", "rshift",
+                      "fused_launches")
 
 
 def spmv_layout(model, which):
