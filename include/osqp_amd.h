@@ -660,6 +660,21 @@ c_int osqp_amd_batch_jvp_launches(void);
 /* The same for the certificate kernel: one launch per osqp_amd_batch_resolve / _resolve_rows, none by osqp_amd_batch_certificates or by the
  * one-shot entries. */
 c_int osqp_amd_batch_cert_launches(void);
+/* Primal objective, dual objective and duality gap of every instance of a resident handle (definitions: "Dual objective,
+ * duality gap and a gap stopping rule" below): out [count x 3] doubles (host or device by `where`), row
+ * i = prim_obj, dual_obj, gap of the pair (x, y) instance i's last resolve returned (the polished pair where polish was
+ * accepted), in the caller's units; a NaN row where that resolve left no solution (infeasible, non-convex).  A launch of
+ * a kernel of its own (one workgroup per instance, sums in a fixed order) that reads the records, the raw data and the
+ * pattern: the handle is only read, a resolve after the call has the bits of one without it.  Every instance must be
+ * current (resolved after its last update or warm start), as for osqp_amd_batch_adjoint: otherwise 1, and the message
+ * names the first that is not.  _rows: the k selected instances, out [k x 3], row j of instance rows[j], equal to row
+ * rows[j] of the whole call; only they must be current.  Returns 0; 1 NULL or foreign handle, NULL out, a bad selection, a
+ * stale instance.
+ * Out of scope: the gap as a stopping rule inside the batched solve kernels (k_batch_quad runs at 168 registers without
+ * scratch; a third test in its termination check is not risked), the one-shot entries (osqp_amd_batch_solve,
+ * _solve_generated) and osqp_amd_batch_mpc_*: they return x and y, from which the caller can form the three numbers. */
+c_int osqp_amd_batch_duality(osqp_amd_batch *batch, c_float *out /* [count x 3] */, c_int where);
+c_int osqp_amd_batch_duality_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *out /* [k x 3] */, c_int where);
 
 /* Device memory for callers without an allocator of their own (the packed result array above): plain hipMalloc / hipFree /
  * hipMemcpy on `device`.  copy kind: 0 device -> host, 1 host -> device, 2 device -> device; blocking. */
@@ -896,6 +911,37 @@ c_int osqp_amd_jvp_dev(OSQPWorkspace *work, c_int ndir,
                        c_float *tx /* [ndir x n] or NULL */, c_float *ty /* [ndir x m] or NULL */, c_float *act /* [m] or NULL */);
 #define OSQP_AMD_DEVICE_FORM_COUNT 6
 c_int osqp_amd_device_form_calls(const OSQPWorkspace *work, c_float *out, c_int count);
+
+/* ---- Dual objective, duality gap and a gap stopping rule (after OSQP 1.0's check_dualgap) ----
+ *
+ * For min 1/2 x'Px + q'x s.t. l <= Ax <= u and a pair (x, y): yh is y projected onto the polar of the recession cone of
+ * [l, u] (0 where both bounds are infinite, min(y, 0) where only u is, max(y, 0) where only l is, y otherwise; "infinite"
+ * is the test of the primal-infeasibility check on the scaled bound; y itself is not modified),
+ *   SC       = sum_i u_i max(yh_i, 0) + l_i min(yh_i, 0)     (an infinite bound adds 0; 0 when m = 0)
+ *   prim_obj = 1/2 x'Px + q'x        dual_obj = -1/2 x'Px - SC        gap = x'Px + q'x + SC = prim_obj - dual_obj
+ *   eps_gap  = eps_abs + eps_rel max(|x'Px|, |q'x|, |SC|)              rule: |gap| < eps_gap.
+ *
+ * osqp_amd_duality_gap_check(work, on): on = 1 adds the rule to the termination test of every later osqp_solve: Solved and
+ *   Solved inaccurate (there with 10 eps, as for the residuals) then need the primal-residual, the dual-residual and the gap
+ *   test to hold.  The gap and the three magnitudes are taken in the units of the residual tests: the caller's with
+ *   scaling && !scaled_termination, the scaled problem's otherwise.  The infeasibility tests, Non_convex, adaptive rho and
+ *   the tolerance rule of the indirect back-end stay as they are.  With the rule on every residual evaluation makes one more
+ *   pass over y, l, u, and SC comes back in the read-back of the residual norms; off (the default) a solve launches exactly
+ *   what it launched before.  Callable any time after setup; it does not move the iterate, rho, the ADMM factor or a kept
+ *   derivative factor.  Returns 0; 7 NULL workspace; 1 `on` other than 0 or 1; 6 row-sharded workspace.
+ * osqp_amd_duality(work, out, count) fills out[0..min(count, OSQP_AMD_DUALITY_COUNT)), caller's units:
+ *   0 prim_obj, 1 dual_obj, 2 gap -- of the (x, y) the workspace holds: what the last osqp_solve returned (the polished pair
+ *     when polish was accepted, the final iterate at Max_iter / Time_limit), or the current iterate after osqp_amd_iterate.
+ *     Computed by the call, rule on or off: one product with P, two dots, the support pass, in scratch of its own.  Where
+ *     the status carries no solution (infeasible, non-convex) 1 and 2 are NaN and 0 is info->obj_val.
+ *   3 eps_gap of the last termination check the rule took part in (units of that check; NaN if there was none),
+ *   4 1 if the rule is on, 5 checks so far at which both residual tests held and the gap alone refused.
+ *   The call changes nothing: solve, duality, solve has the bits and counts of solve, solve.  Returns 0; 7 NULL workspace;
+ *   1 before any osqp_solve / osqp_amd_iterate or NULL out; 6 row-sharded workspace.
+ * Both serve the direct and the indirect back-end, compact workspaces included. */
+#define OSQP_AMD_DUALITY_COUNT 6
+c_int osqp_amd_duality_gap_check(OSQPWorkspace *work, c_int on);
+c_int osqp_amd_duality(OSQPWorkspace *work, c_float *out, c_int count);
 
 /* Select the HIP device for workspaces created afterwards by this process
  * (one process per GPU: pass LOCAL_RANK). */

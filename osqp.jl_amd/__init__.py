@@ -17,6 +17,6 @@ from .interface import (  # noqa: F401
     warm_start_x, warm_start_y, warm_start_x_y, update_q, update_l, update_u, update_bounds, update_P, update_A,
     update_P_A, clean, version, dimensions, default_settings, make_settings, stats, ManagedCcsc, ccsc_to_scipy,
     spmv_layout, adjoint, adjoint_release, adjoint_stats, jvp, jacobian, solution, device_form_calls,
-    derivative_method, derivative_iter_stats, adjoint_retain, adjoint_retain_stats,
+    derivative_method, derivative_iter_stats, adjoint_retain, adjoint_retain_stats, duality_gap_check, duality,
 )
 from .types import load_library, PRODUCT_LIB_PATH, ORACLE_LIB_PATH  # noqa: F401

@@ -267,7 +267,7 @@ class ResidentBatch:
     `warm_start=False` in the settings: from zero).  P (upper triangle) and A are scipy matrices giving the pattern; the
     *_all arrays are [count x .] as for `solve_batch`.  Array arguments of `update` / `warm_start` and the `out` of `solve`
     may be numpy arrays (host form) or device arrays (`DeviceArray`, torch tensors: no host hop).
-    `update`, `warm_start`, `solve`, `adjoint`, `jvp`, `certificates` and `polish_status` take `rows=`: a selection of the instances (`selection` above: integers in any order,
+    `update`, `warm_start`, `solve`, `adjoint`, `jvp`, `certificates`, `polish_status` and `duality` take `rows=`: a selection of the instances (`selection` above: integers in any order,
     or a boolean mask; always host data).  Their arrays are then compact, [k x .], row j for instance rows[j]; a selected
     instance gets the bits of the whole-batch call, every other instance is left exactly as it was -- data, record,
     certificates, polish status (include/osqp_amd.h, "*_rows")."""
@@ -479,6 +479,30 @@ class ResidentBatch:
             raise ValueError("out: no certificate was asked for")
         self._call("certificates", certs(ptrs[0], ptrs[1], 1))
         return (None if self.m == 0 else out[0]), out[1]
+
+    def duality(self, out=None, rows=None):
+        """[count x 3]: prim_obj, dual_obj and gap = prim_obj - dual_obj of the pair (x, y) every instance's last `solve()`
+        returned, in the caller's units (osqp_amd_batch_duality); a NaN row where that solve left no
+        solution.  Every instance served must be current (solved after its last update or warm start).  out=None: a numpy
+        array; out = a device array [count x 3] of float64: filled in place and returned.  rows: a selection (`selection`);
+        the result is [k x 3], row j for instance rows[j], and only these must be current.  Only reads the handle."""
+        sel = None if rows is None else selection(rows, self.count)
+        k = self.count if sel is None else len(sel)
+
+        def dual(ptr, where):
+            if sel is None:
+                return self.lib.osqp_amd_batch_duality(self.handle, ptr, where)
+            return self.lib.osqp_amd_batch_duality_rows(self.handle, _iptr(sel), k, ptr, where)
+
+        if out is None:
+            res = np.empty((k, 3))
+            self._call("duality", dual(res.ctypes.data, 0))
+            return res
+        if not hasattr(out, "data_ptr"):
+            raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
+        ptr = _batch_array("out", out, (k, 3))[1]
+        self._call("duality", dual(ptr, 1))
+        return out
 
     ADJOINT_WANT = ("q", "l", "u", "Px", "Ax")
 

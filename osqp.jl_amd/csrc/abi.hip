@@ -606,6 +606,7 @@ c_int osqp_solve(OSQPWorkspace *w) {
   return moving_on(w, [&](Engine &e) {
     const int rc = e.solve();
     e.solves_run++;
+    e.have_iterate = true;
     e.solution_current = rc == 0;
     return rc;
   });
@@ -787,7 +788,7 @@ c_float osqp_amd_time_kernel(OSQPWorkspace *w, c_int which, c_int reps) {
 }
 
 c_int osqp_amd_iterate(OSQPWorkspace *w, c_int iters) {
-  return moving_on(w, [&](Engine &e) { return e.iterate(iters); });
+  return moving_on(w, [&](Engine &e) { e.have_iterate = true; return e.iterate(iters); });
 }
 
 c_int osqp_amd_get_iterate(OSQPWorkspace *w, c_float *x_out, c_float *y_out) {
@@ -953,6 +954,37 @@ c_int osqp_amd_derivative_iter_stats(const OSQPWorkspace *w, c_float *out, c_int
   c_int k = 0;
   for (; k < count && k < OSQP_AMD_DERIVATIVE_ITER_STATS_COUNT; k++) out[k] = v[k];
   return k;
+}
+
+// ---- dual objective, duality gap and the gap stopping rule ----
+static void duality_needs_whole_model(const Engine &e, const char *who) {
+  if (e.comm)
+    throw Error(6, std::string(who) + ": not available on a row-sharded workspace (the support term and the gap are sums over all rows; a rank holds a row block)");
+}
+c_int osqp_amd_duality_gap_check(OSQPWorkspace *w, c_int on) {
+  const char *who = "osqp_amd_duality_gap_check";
+  return on_workspace(w, who, [&](Engine &e) {
+    if (on != 0 && on != 1) throw Error(1, std::string(who) + ": on must be 0 (off, the default) or 1 (on)");
+    duality_needs_whole_model(e, who);
+    e.gap_rule = on == 1;  // read by the next residual evaluation: nothing of the iteration, the factor or a captured chunk depends on it
+    return 0;
+  });
+}
+c_int osqp_amd_duality(OSQPWorkspace *w, c_float *out, c_int count) {
+  const char *who = "osqp_amd_duality";
+  return on_workspace(w, who, [&](Engine &e) {
+    duality_needs_whole_model(e, who);
+    if (!out || count < 0) throw Error(1, std::string(who) + ": no output array");
+    if (!e.have_iterate) throw Error(1, std::string(who) + ": neither osqp_solve nor osqp_amd_iterate has run on this workspace yet");
+    double v[OSQP_AMD_DUALITY_COUNT] = {NAN, NAN, NAN, e.gap_eps, e.gap_rule ? 1.0 : 0.0, (double)e.gap_refusals};
+    const c_int st = w->info->status_val;
+    const bool no_solution = st == OSQP_PRIMAL_INFEASIBLE || st == OSQP_PRIMAL_INFEASIBLE_INACCURATE || st == OSQP_DUAL_INFEASIBLE ||
+                             st == OSQP_DUAL_INFEASIBLE_INACCURATE || st == OSQP_NON_CVX;
+    if (no_solution) v[0] = w->info->obj_val;  // +-OSQP_INFTY or NaN, as osqp_solve left it; no pair to take a dual objective of
+    else e.duality(v);
+    for (c_int k = 0; k < count && k < OSQP_AMD_DUALITY_COUNT; k++) out[k] = v[k];
+    return 0;
+  });
 }
 
 c_int osqp_amd_set_device(c_int device) {

@@ -20,6 +20,8 @@
 //                     launch of its own on request (osqp_amd_batch_jvp): one factorisation per instance, one solve per direction;
 //   batch_cert.hpp    k_batch_cert -- the infeasibility certificates of the resident batch, a launch of its own after every
 //                     ADMM launch of osqp_amd_batch_resolve: normalises the directions that launch left in the records (RES_CERT);
+//   batch_gap.hpp     k_batch_gap -- primal objective, dual objective and duality gap of the resident batch, a launch of its own on
+//                     request (osqp_amd_batch_duality); reads the records, the raw data and the pattern, writes three doubles;
 //   this file         the small kernels (warm start, rho fill, bound check, the row scatter and gather of a selection, MPC generator), the
 //                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
@@ -36,6 +38,7 @@
 #include "batch_adjoint.hpp"
 #include "batch_jvp.hpp"
 #include "batch_cert.hpp"
+#include "batch_gap.hpp"
 #include "batch_polish.hpp"
 #include "batch_quad.hpp"
 #include "batch_sched.hpp"
@@ -1139,6 +1142,39 @@ c_int osqp_amd_batch_certificates_rows(osqp_amd_batch *handle, const c_int *rows
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
+}
+
+// osqp_amd_batch_duality (subset false) and osqp_amd_batch_duality_rows: one launch of k_batch_gap (batch_gap.hpp), one
+// workgroup per served instance; row j of out is of instance j, or of rows[j].  Only reads the handle (the selection and the
+// staging of a host-pointer call are per-call scratch, as for the certificates).
+static c_int batch_duality(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, c_float *out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!out) { set_last_error("invalid batch data: no output array"); return 1; }
+  if (!subset && !holds_current(*b, nullptr)) return 1;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (subset) {  // only the selected instances must be current; nothing is launched when one is not
+      if (!select_rows(*b, rows, k, s)) return 1;
+      if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
+    }
+    const int launch = subset ? (int)k : b->count;
+    const size_t len = (size_t)launch * 3;
+    if (!where && b->adj_out.n < len) b->adj_out.alloc(len);
+    gap::Args a;
+    a.Px = b->Px.get(); a.q = b->q.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
+    a.out = where ? out : b->adj_out.get();
+    a.info_stride = 6; a.rec_stride = b->rec_stride; a.sel = subset ? b->sel.get() : nullptr;
+    OQ_LAUNCH(gap::k_batch_gap, dim3(launch), dim3(gap::GT), 0, s, b->dp.P, launch, a);
+    if (!where) HIP_CHECK(hipMemcpyAsync(out, a.out, len * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+c_int osqp_amd_batch_duality(osqp_amd_batch *handle, c_float *out, c_int where) { return batch_duality(handle, false, nullptr, 0, out, where); }
+c_int osqp_amd_batch_duality_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *out, c_int where) {
+  return batch_duality(handle, true, rows, k, out, where);
 }
 
 c_int osqp_amd_batch_destroy(osqp_amd_batch *handle) {

@@ -188,6 +188,7 @@ enum Slot {
   S_PRI = 0, S_PRI_UNS, S_Z, S_AX, S_Z_UNS, S_AX_UNS,
   S_DUA, S_DUA_UNS, S_Q, S_ATY, S_PX, S_Q_UNS, S_ATY_UNS, S_PX_UNS,
   S_XPX, S_QX,
+  S_SC,                                 // support term of the dual objective, right behind the 16 residual slots: one read-back (duality-gap rule)
   S_T0, S_T1, S_T2, S_T3, S_T4, S_T5,   // scratch slots (infeasibility tests, scaling, PCG)
   S_COUNT = 32
 };

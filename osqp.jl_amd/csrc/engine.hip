@@ -977,7 +977,11 @@ void Engine::residual_evaluation() {
   residual_products += m > 0 ? 3 : 2;
   residual_norms(n, m, x.get(), z.get(), Ax.get(), Px_.get(), Aty.get(), q.get(), Dinv.get(), Einv.get(), slots.get(),
                  partials.get(), stream);
-  fetch_slots(0, 16, (1u << S_XPX) | (1u << S_QX));
+  if (gap_rule) {  // SC rides behind the 16 residual slots (the finish kernel above has consumed the partials: stream order)
+    dual_support(m, y.get(), l.get(), u.get(), partials.get(), slots.get() + S_SC, stream);
+    fetch_slots(0, 17, (1u << S_XPX) | (1u << S_QX) | (1u << S_SC));
+  } else
+    fetch_slots(0, 16, (1u << S_XPX) | (1u << S_QX));
   // the read-back has drained the stream: a wait that timed out in the iterations that were still in flight at the
   // test above shows now, before anything is decided from these numbers
   if (lin->flush() == 6) throw TreeFault();
@@ -987,6 +991,7 @@ void Engine::update_info(long long iter, bool compute_objective) {
   OSQPInfo *info = ws->info;
   residual_evaluation();
   memcpy(res, h_slots, sizeof(double) * 16);
+  if (gap_rule) res_sc = h_slots[S_SC];
   const bool uns = st.scaling && !st.scaled_termination;
   info->iter = iter;
   if (compute_objective) info->obj_val = obj_from_slots();
@@ -1078,6 +1083,14 @@ int Engine::check_termination(bool approximate) {
   if (info->dua_res < eps_dual) dual_res_check = true;
   else dual_inf_check = is_dual_infeasible(eps_dual_inf);
 
+  if (gap_rule && prim_res_check && dual_res_check) {
+    // third test: |gap| < eps_abs + eps_rel max(|x'Px|, |q'x|, |SC|), in the units of the residual tests
+    const double k = uns ? cinv : 1.0;
+    const double xpx = k * res[S_XPX], qx = k * res[S_QX], sc = k * res_sc;
+    const double gap = xpx + qx + sc;
+    gap_eps = eps_abs + eps_rel * std::max(std::fabs(xpx), std::max(std::fabs(qx), std::fabs(sc)));
+    if (!(std::fabs(gap) < gap_eps)) { gap_refusals++; return 0; }
+  }
   if (prim_res_check && dual_res_check) {
     update_status(info, approximate ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED);
     return 1;
@@ -1340,6 +1353,24 @@ int Engine::solve_attempt(bool restarted) {
   store_solution();
   *ws->settings = st;
   return 0;
+}
+
+// Primal objective, dual objective and gap of the current (x, y), on demand: one product with P, two dots, the support pass
+// (DESIGN.md section 19).  Scratch of its own and a plain copy back: neither the slot array (the CG keeps state there) nor its
+// host mirror nor any vector of the iteration is written, so a solve after this call runs as if it had not been made.
+void Engine::duality(double out[3]) {
+  DevBuf<double> px((size_t)std::max(n, 1)), sums(3);
+  spmv(Pf, x.get(), px.get(), nullptr, 0.0, 0.0, nullptr, stream);
+  reduce_dot(x.get(), px.get(), n, partials.get(), sums.get() + 0, stream);
+  reduce_dot(q.get(), x.get(), n, partials.get(), sums.get() + 1, stream);
+  dual_support(m, y.get(), l.get(), u.get(), partials.get(), sums.get() + 2, stream);
+  double h[3] = {0, 0, 0};
+  sums.download(h, 3, stream);
+  sync();
+  const double k = st.scaling ? cinv : 1.0;
+  out[0] = (0.5 * h[0] + h[1]) * k;
+  out[1] = (-0.5 * h[0] - h[2]) * k;
+  out[2] = (h[0] + h[1] + h[2]) * k;
 }
 
 // objective at the current x (Px recomputed: the last residual evaluation may be older than x)

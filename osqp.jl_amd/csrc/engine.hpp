@@ -11,6 +11,7 @@
 // come back to the host.
 #pragma once
 #include <chrono>
+#include <cmath>
 #include <memory>
 
 #include "comm.hpp"
@@ -149,6 +150,15 @@ struct Engine {
   long long it_ref = 0;
   bool have_res = false, have_ref = false, have_seed = false;
   double g_seed = 0;
+
+  // duality-gap stopping rule (osqp_amd_duality_gap_check); off: no launch and no slot more than before.
+  // On: every residual evaluation leaves SC (scaled sum) in res_sc, check_termination adds |gap| < eps_gap to the two
+  // residual tests; gap_refusals counts the checks at which the gap alone refused, gap_eps is the bound of the last check.
+  bool gap_rule = false;
+  bool have_iterate = false;  // an osqp_solve or osqp_amd_iterate has run (osqp_amd_duality refuses before)
+  double res_sc = 0.0, gap_eps = NAN;
+  long long gap_refusals = 0;
+  void duality(double out[3]);  // prim_obj, dual_obj, gap of the current (x, y) in the caller's units; reads only
 
   int deferred_error = 0;  // an asynchronous back-end met negative curvature some iterations ago (reported at the next check)
   // statistics

@@ -889,6 +889,26 @@ void prim_infeas_prep(int m, double *dy, const double *l, const double *u, const
   OQ_LAUNCH(k_prim_infeas_prep, dim3(kReduceBlocks), dim3(kBlock), 0, s, m, dy, l, u, E, slots, partials);
   OQ_LAUNCH(k_sum_partials, dim3(1), dim3(kBlock), 0, s, partials, slots + S_T1, g_skip);
 }
+// The support term of the dual objective: SC = sum_i u_i max(yh_i, 0) + l_i min(yh_i, 0), yh = y
+// projected as k_prim_infeas_prep projects delta_y -- an infinite bound never meets a non-zero factor, so it adds 0.  y is
+// only read.  Block partials, then k_sum_partials: no atomics, the same bits on every call.
+__global__ __launch_bounds__(kBlock) void k_dual_support(int m, const double *__restrict__ y, const double *__restrict__ l,
+                                                         const double *__restrict__ u, double *__restrict__ partials) {
+  double sum = 0.0;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < m; i += gridDim.x * kBlock) {
+    const double yi = y[i], li = l[i], ui = u[i];
+    const bool u_inf = ui > INF_SCALED, l_inf = li < -INF_SCALED;
+    const double up = u_inf ? 0.0 : ui * fmax(yi, 0.0);
+    const double lo = l_inf ? 0.0 : li * fmin(yi, 0.0);
+    sum += up + lo;
+  }
+  sum = block_sum(sum);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+void dual_support(int m, const double *y, const double *l, const double *u, double *partials, double *slot, hipStream_t s) {
+  OQ_LAUNCH(k_dual_support, dim3(kReduceBlocks), dim3(kBlock), 0, s, m, y, l, u, partials);
+  OQ_LAUNCH(k_sum_partials, dim3(1), dim3(kBlock), 0, s, partials, slot, g_skip);
+}
 __global__ __launch_bounds__(kBlock) void k_dual_infeas_rows(int m, const double *__restrict__ Adx, const double *__restrict__ Einv,
                                                              const double *__restrict__ l, const double *__restrict__ u, double thr,
                                                              double *__restrict__ slots) {

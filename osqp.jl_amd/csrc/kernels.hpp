@@ -140,6 +140,9 @@ void residual_norms(int n, int m, const double *x, const double *z, const double
 // slots[S_T0] = ||E.*dy||inf (E may be null), slots[S_T1] = u'max(dy,0) + l'min(dy,0)
 void prim_infeas_prep(int m, double *dy, const double *l, const double *u, const double *E, double *slots,
                       double *partials, hipStream_t s);
+// *slot = u'max(yh,0) + l'min(yh,0), yh = y projected onto the same cone (y is not modified; an infinite bound adds 0);
+// partials: kReduceBlocks doubles
+void dual_support(int m, const double *y, const double *l, const double *u, double *partials, double *slot, hipStream_t s);
 // slots[S_T2] = number of rows violating the dual-infeasibility sign conditions
 void dual_infeas_rows(int m, const double *Adx, const double *Einv, const double *l, const double *u, double thr,
                       double *slots, hipStream_t s);

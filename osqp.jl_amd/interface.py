@@ -989,3 +989,34 @@ def derivative_iter_stats(model):
     if fn(model.workspace, _fptr(out), len(out)) != len(out):
         raise OSQPError("osqp_amd_derivative_iter_stats: bad argument")
     return {name: (float(v) if name == "last_drop" else int(v)) for name, v in zip(DERIVATIVE_ITER_STATS_FIELDS, out)}
+
+
+DUALITY_FIELDS = ("prim_obj", "dual_obj", "gap", "eps_gap", "rule", "gap_refusals")
+_DUALITY = "the dual objective and the duality gap are"
+
+
+def duality_gap_check(model, on=True):
+    """Extension: osqp_amd_duality_gap_check -- with on=True every later `solve` also needs the duality gap
+    |x'Px + q'x + SC(y)| < eps_abs + eps_rel max(|x'Px|, |q'x|, |SC|) to hold before it ends Solved (10 eps for Solved
+    inaccurate), besides the two residual tests (OSQP 1.0's check_dualgap).  Off by default.  The call
+    does not move the iterate, rho, the factor or a kept derivative factor."""
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"on: expected a bool, got {on!r}")
+    fn = _symbol(model, "osqp_amd_duality_gap_check", _DUALITY)
+    if fn(model.workspace, 1 if on else 0) != 0:
+        raise OSQPError("Error in duality_gap_check: " + model.lib.osqp_amd_last_error().decode())
+
+
+def duality(model):
+    """Extension: osqp_amd_duality as a dict -- "prim_obj", "dual_obj" and "gap" = prim_obj - dual_obj of the (x, y) the
+    model holds (what the last `solve` returned, or the current iterate after `iterate`; NaN dual_obj and gap where the
+    status carries no solution), "eps_gap" of the last termination check the rule took part in (NaN: none), "rule" (bool)
+    and "gap_refusals": the checks at which both residual tests held and the gap alone refused.  Changes nothing."""
+    fn = _symbol(model, "osqp_amd_duality", _DUALITY)
+    out = np.zeros(len(DUALITY_FIELDS))
+    if fn(model.workspace, _fptr(out), len(out)) != 0:
+        raise OSQPError("Error in duality: " + model.lib.osqp_amd_last_error().decode())
+    res = {name: float(v) for name, v in zip(DUALITY_FIELDS, out)}
+    res["rule"] = bool(out[4])
+    res["gap_refusals"] = int(out[5])
+    return res

@@ -218,6 +218,27 @@ function adjoint_retain_stats(model::OSQP.Model)
             rebuilt_failed = Int(out[6]), last_rows_changed = Int(out[7]), stale = out[8] == 1.0)
 end
 
+"""
+    duality_gap_check!(model, on = true)
+
+Add the duality gap |x'Px + q'x + SC(y)| < eps_abs + eps_rel max(|x'Px|, |q'x|, |SC|) to the termination test of every later
+`OSQP.solve!` (osqp_amd_duality_gap_check, DESIGN.md section 19; OSQP 1.0's check_dualgap).  Off by default.  The call does
+not move the iterate, rho, the factor or a kept derivative factor.
+"""
+function duality_gap_check!(model::OSQP.Model, on::Bool = true)
+    flag = ccall((:osqp_amd_duality_gap_check, lib), Cc_int, (Ptr{OSQP.Workspace}, Cc_int), model.workspace, on ? 1 : 0)
+    flag == 0 || error("Error in duality_gap_check!: $(last_error())")
+    return nothing
+end
+
+"(prim_obj, dual_obj, gap, eps_gap, rule, gap_refusals) of the pair (x, y) the model holds (osqp_amd_duality); changes nothing."
+function duality(model::OSQP.Model)
+    out = zeros(Float64, 6)  # OSQP_AMD_DUALITY_COUNT (include/osqp_amd.h)
+    flag = ccall((:osqp_amd_duality, lib), Cc_int, (Ptr{OSQP.Workspace}, Ptr{Cdouble}, Cc_int), model.workspace, out, length(out))
+    flag == 0 || error("Error in duality: $(last_error())")
+    return (prim_obj = out[1], dual_obj = out[2], gap = out[3], eps_gap = out[4], rule = out[5] == 1.0, gap_refusals = Int(out[6]))
+end
+
 # ---- device-pointer forms of a single model's life cycle (include/osqp_amd.h, DESIGN.md section 16) ----
 # Every array is a DEVICE address on the model's device, as a `Ptr{Cdouble}` (`C_NULL`: not given / not wanted) -- for an
 # AMDGPU.jl array `Ptr{Cdouble}(UInt(pointer(a)))`; the package itself does not depend on a GPU array type.  The library runs
@@ -723,6 +744,39 @@ function batch_certificates(b::ResidentBatch, rows::AbstractVector{<:Integer}, p
                  b.handle, r, length(r), p, d, 1)
     flag == 0 || error("Error in batched certificates: $(last_error())")
     return nothing
+end
+
+"""
+    batch_duality(b) -> [3 x count]
+
+prim_obj, dual_obj and gap = prim_obj - dual_obj of the pair every instance's last `batch_solve!` returned (osqp_amd_batch_duality,
+DESIGN.md section 19): column i is of instance i, NaN where its solve left no solution.  Every instance must be current.
+"""
+function batch_duality(b::ResidentBatch)
+    out = Matrix{Float64}(undef, 3, b.count)
+    GC.@preserve out begin
+        flag = ccall((:osqp_amd_batch_duality, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), b.handle, pointer(out), 0)
+    end
+    flag == 0 || error("Error in batched duality: $(last_error())")
+    return out
+end
+
+"The same into a device array (a pointer to 3 * count doubles on the handle's device)."
+function batch_duality(b::ResidentBatch, out::Ptr{Cdouble})
+    flag = ccall((:osqp_amd_batch_duality, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), b.handle, out, 1)
+    flag == 0 || error("Error in batched duality: $(last_error())")
+    return nothing
+end
+
+"The instances `rows` only (osqp_amd_batch_duality_rows) -> [3 x k]; column j is of instance rows[j]; only they must be current."
+function batch_duality(b::ResidentBatch, rows::AbstractVector{<:Integer})
+    r = _batch_rows(rows)
+    out = Matrix{Float64}(undef, 3, length(r))
+    GC.@preserve out begin
+        flag = ccall((:osqp_amd_batch_duality_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Cc_int), b.handle, r, length(r), pointer(out), 0)
+    end
+    flag == 0 || error("Error in batched duality: $(last_error())")
+    return out
 end
 
 const AdjointArg = Union{Nothing,Matrix{Float64},Array{Float64,3},Ptr{Cdouble}}

@@ -472,6 +472,14 @@ class Optimizer:
         rawobj = self.results.info.obj_val + self.objconstant
         return -rawobj if self.sense == MAX_SENSE else rawobj
 
+    def dual_objective_value(self):
+        """MOI.DualObjectiveValue: -1/2 x'Px - SC(y) of the returned pair (`interface.duality`) plus
+        the objective constant, in the sense of the model.  The attribute the reference's conformance run excludes [REF
+        test/MOI_wrapper.jl:36-37] because its engine cannot supply it.  NaN where the status carries no solution."""
+        self._check_result()
+        rawobj = oq.duality(self.inner)["dual_obj"] + self.objconstant
+        return -rawobj if self.sense == MAX_SENSE else rawobj
+
     def solve_time_sec(self):
         self._check_has_results()
         return self.results.info.run_time

@@ -205,6 +205,9 @@ EXT_SYMBOLS = {
     # which KKT solve the derivatives use: method 0 direct / 1 auto / 2 iterative, max_outer, rel_drop (0 = default)
     "osqp_amd_derivative_method": (c_int, [Workspace_p, c_int, c_int, c_float]),
     "osqp_amd_derivative_iter_stats": (c_int, [Workspace_p, c_float_p, c_int]),
+    # dual objective, duality gap and the gap stopping rule: on 0 / 1; out = prim_obj, dual_obj, gap, eps_gap, rule, refusals
+    "osqp_amd_duality_gap_check": (c_int, [Workspace_p, c_int]),
+    "osqp_amd_duality": (c_int, [Workspace_p, c_float_p, c_int]),
     "osqp_amd_batch_solve": (
         c_int,
         [c_int, c_int, c_int, c_int_p, c_int_p, c_float_p, c_int_p, c_int_p, c_float_p,
@@ -260,6 +263,9 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_adjoint_multi_rows": (c_int, [C.c_void_p, c_int_p, c_int, c_int] + [C.c_void_p] * 9 + [c_int]),
     "osqp_amd_batch_polish_status_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, c_int]),
     "osqp_amd_batch_certificates_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, C.c_void_p, c_int]),
+    # prim_obj, dual_obj, gap of every instance ([count x 3]) or of a selection ([k x 3]); host or device output by `where`
+    "osqp_amd_batch_duality": (c_int, [C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_duality_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, c_int]),
     "osqp_amd_device_alloc": (C.c_void_p, [c_int, c_int]),
     "osqp_amd_device_free": (c_int, [C.c_void_p, c_int]),
     "osqp_amd_device_copy": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int]),
