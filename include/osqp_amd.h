@@ -670,11 +670,27 @@ c_int osqp_amd_batch_cert_launches(void);
  * names the first that is not.  _rows: the k selected instances, out [k x 3], row j of instance rows[j], equal to row
  * rows[j] of the whole call; only they must be current.  Returns 0; 1 NULL or foreign handle, NULL out, a bad selection, a
  * stale instance.
- * Out of scope: the gap as a stopping rule inside the batched solve kernels (k_batch_quad runs at 168 registers without
- * scratch; a third test in its termination check is not risked), the one-shot entries (osqp_amd_batch_solve,
- * _solve_generated) and osqp_amd_batch_mpc_*: they return x and y, from which the caller can form the three numbers. */
+ * Out of scope: the one-shot entries (osqp_amd_batch_solve, _solve_generated) and osqp_amd_batch_mpc_*: they return x and
+ * y, from which the caller can form the three numbers. */
 c_int osqp_amd_batch_duality(osqp_amd_batch *batch, c_float *out /* [count x 3] */, c_int where);
 c_int osqp_amd_batch_duality_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *out /* [k x 3] */, c_int where);
+/* The gap as a stopping rule of the resident batch (the rule of osqp_amd_duality_gap_check below, inside
+ * the batched solve kernels).  on = 1: from the next osqp_amd_batch_resolve / _resolve_rows an instance ends Solved
+ * (Solved_inaccurate in the approximate pass at the iteration limit, at 10 eps) only where, next to the two residual tests,
+ * |gap| < eps_abs + eps_rel max(|x'Px|, |q'x|, |SC|) holds, in the units of the residual tests (the caller's unless
+ * scaled_termination); a NaN fails it.  The test is evaluated only at checks where both residual tests hold; a check that
+ * it alone refuses goes on iterating (the infeasibility tests did not run at that check; adaptive rho proceeds as at any
+ * other) and adds one to the instance's refusal count.  Instances whose gap holds where their residuals do stop where they
+ * stopped before, with the same bits.  on = 0, the default: the solve of a handle that never had the rule.  The call drops
+ * nothing -- iterate, rho, which instances are current, certificates and polish status stay -- and sets every refusal count
+ * to zero.  Polish, certificates, adjoint, JVP and osqp_amd_batch_duality work on whatever point a solve stopped at.
+ * osqp_amd_batch_gap_refusals: out [count] doubles (host or device by `where`), out[i] = the checks of instance i's own last
+ * resolve that the gap test alone refused; zeros while the rule is off.  _rows: out [k], out[j] of instance rows[j].
+ * The one-shot entries (osqp_amd_batch_solve, _solve_generated) and osqp_amd_batch_mpc_* run without the rule.
+ * Return 0; 1 NULL or foreign (non-resident) handle, NULL out, a bad selection. */
+c_int osqp_amd_batch_duality_gap_check(osqp_amd_batch *batch, c_int on);
+c_int osqp_amd_batch_gap_refusals(osqp_amd_batch *batch, c_float *out /* [count] */, c_int where);
+c_int osqp_amd_batch_gap_refusals_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *out /* [k] */, c_int where);
 
 /* Device memory for callers without an allocator of their own (the packed result array above): plain hipMalloc / hipFree /
  * hipMemcpy on `device`.  copy kind: 0 device -> host, 1 host -> device, 2 device -> device; blocking. */

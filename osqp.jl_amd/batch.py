@@ -267,10 +267,11 @@ class ResidentBatch:
     `warm_start=False` in the settings: from zero).  P (upper triangle) and A are scipy matrices giving the pattern; the
     *_all arrays are [count x .] as for `solve_batch`.  Array arguments of `update` / `warm_start` and the `out` of `solve`
     may be numpy arrays (host form) or device arrays (`DeviceArray`, torch tensors: no host hop).
-    `update`, `warm_start`, `solve`, `adjoint`, `jvp`, `certificates`, `polish_status` and `duality` take `rows=`: a selection of the instances (`selection` above: integers in any order,
-    or a boolean mask; always host data).  Their arrays are then compact, [k x .], row j for instance rows[j]; a selected
-    instance gets the bits of the whole-batch call, every other instance is left exactly as it was -- data, record,
-    certificates, polish status (include/osqp_amd.h, "*_rows")."""
+    `update`, `warm_start`, `solve`, `adjoint`, `jvp`, `certificates`, `polish_status`, `duality` and `gap_refusals`
+    take `rows=`: a selection of the instances (`selection` above: integers in any order, or a boolean mask; always
+    host data). Their arrays are then compact, [k x .], row j for instance rows[j]; a selected instance gets the
+    bits of the whole-batch call, every other instance is left exactly as it was -- data, record, certificates,
+    polish status (include/osqp_amd.h, "*_rows")."""
 
     def __init__(self, lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, **settings):
         import scipy.sparse as sp
@@ -502,6 +503,37 @@ class ResidentBatch:
             raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
         ptr = _batch_array("out", out, (k, 3))[1]
         self._call("duality", dual(ptr, 1))
+        return out
+
+    def duality_gap_check(self, on=True):
+        """The duality gap as a third termination test of every later `solve()`, whole or `rows=`
+        (osqp_amd_batch_duality_gap_check): |gap| < eps_abs + eps_rel max(|x'Px|, |q'x|, |SC|), evaluated
+        inside the solve kernels at the checks where both residual tests hold.  An instance whose gap holds there stops where
+        it stopped before, with the same bits; the others iterate on.  Off by default.  Drops nothing of the handle (iterate,
+        rho, which instances are current, certificates, polish status); the refusal counts start from zero."""
+        self._call("duality_gap_check", self.lib.osqp_amd_batch_duality_gap_check(self.handle, 1 if on else 0))
+
+    def gap_refusals(self, out=None, rows=None):
+        """[count]: how many checks of every instance's own last `solve()` the gap test alone refused
+        (osqp_amd_batch_gap_refusals); zeros while the rule is off.  out=None: a numpy array of float64; out = a device array
+        [count] of float64: filled in place and returned.  rows: a selection (`selection`); the result is [k], entry j for
+        instance rows[j].  Only reads the handle."""
+        sel = None if rows is None else selection(rows, self.count)
+        k = self.count if sel is None else len(sel)
+
+        def refusals(ptr, where):
+            if sel is None:
+                return self.lib.osqp_amd_batch_gap_refusals(self.handle, ptr, where)
+            return self.lib.osqp_amd_batch_gap_refusals_rows(self.handle, _iptr(sel), k, ptr, where)
+
+        if out is None:
+            res = np.empty(k)
+            self._call("gap_refusals", refusals(res.ctypes.data, 0))
+            return res
+        if not hasattr(out, "data_ptr"):
+            raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
+        ptr = _batch_array("out", out, (k,))[1]
+        self._call("gap_refusals", refusals(ptr, 1))
         return out
 
     ADJOINT_WANT = ("q", "l", "u", "Px", "Ax")

@@ -83,10 +83,17 @@ __global__ __launch_bounds__(256) void k_batch_warm(Pattern P, int count, const 
   }
 }
 
-// the rho of osqp_amd_batch_update_setting("rho") into every record, as osqp_update_rho rebuilds rho_vec; the iterate stays
-__global__ __launch_bounds__(256) void k_batch_fill_rho(int count, double rho, double *__restrict__ rec_all, int rec_stride) {
+// one header slot of every record: the rho of osqp_amd_batch_update_setting("rho") into REC_RHO, as osqp_update_rho rebuilds
+// rho_vec, or a zero into REC_GAPREF when the gap rule is switched (osqp_amd_batch_duality_gap_check); the iterate stays
+__global__ __launch_bounds__(256) void k_batch_fill_hdr(int count, int slot, double value, double *__restrict__ rec_all, int rec_stride) {
   const int inst = blockIdx.x * 256 + threadIdx.x;
-  if (inst < count) rec_all[(size_t)inst * rec_stride + REC_RHO] = rho;
+  if (inst < count) rec_all[(size_t)inst * rec_stride + slot] = value;
+}
+// out[p] = the refusal count in the record of instance sel[p] (sel == nullptr: p), or 0 while the rule is off
+__global__ __launch_bounds__(256) void k_batch_gap_refusals(const int *__restrict__ sel, int k, int on, const double *__restrict__ rec_all,
+                                                            int rec_stride, double *__restrict__ out) {
+  const int pos = blockIdx.x * 256 + threadIdx.x;
+  if (pos < k) out[pos] = on ? rec_all[(size_t)(sel ? sel[pos] : pos) * rec_stride + REC_GAPREF] : 0.0;
 }
 
 // rows with l > u, counted per launch (osqp_amd_batch_update_bounds refuses the update when there is one)
@@ -349,6 +356,9 @@ struct BatchPlan : BatchData {
   // after every resolve
   DevBuf<double> pcert, dcert;
   bool rec_raw = false;  // a solve launched with RES_CERT whose k_batch_cert has not been launched (osqp_amd_batch_resolve)
+  // osqp_amd_batch_duality_gap_check: every resolve carries RES_GAP, and slot REC_GAPREF of a record is the refusal count of
+  // the instance's own last resolve since the rule was switched on (the switch zeroes the slot of every record)
+  bool gap_rule = false;
 };
 
 // The checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings], shared by the
@@ -844,7 +854,7 @@ c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_
     // (a resolve that failed between its solve launch and k_batch_cert may have left directions where the records of
     // infeasible instances hold zeros: the next one starts every instance from zero and rewrites every record)
     io.rec = b->rec.get(); io.rec_stride = b->rec_stride;
-    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0);
+    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0) | (b->gap_rule ? RES_GAP : 0);
     b->rec_raw = true;
     launch_batch(b->dp, b->st, b->count, io, s);
     launch_cert(*b, io, b->count, s);  // before anything else reads the records: it puts them back as a solve without RES_CERT leaves them
@@ -960,7 +970,7 @@ c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *handle, const c_int *rows, c_i
     io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : b->info_out.get();
     io.x_stride = b->n; io.y_stride = b->m; io.info_stride = io.info_cols = 6;
     io.rec = b->rec.get(); io.rec_stride = b->rec_stride; io.sel = b->sel.get();
-    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0);  // rec_raw: as osqp_amd_batch_resolve
+    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0) | (b->gap_rule ? RES_GAP : 0);  // rec_raw: as osqp_amd_batch_resolve
     b->rec_raw = true;
     launch_batch(b->dp, b->st, cnt, io, s);
     launch_cert(*b, io, cnt, s);
@@ -1086,7 +1096,7 @@ c_int osqp_amd_batch_update_setting(osqp_amd_batch *handle, const char *name, c_
       DeviceScope on_dev(b->device);
       hipStream_t s = nullptr;
       st.rho = std::min(std::max(st.rho, (c_float)B_RHO_MIN), (c_float)B_RHO_MAX);
-      OQ_LAUNCH(k_batch_fill_rho, dim3(blocks_for(b->count, 256)), dim3(256), 0, s, b->count, (double)st.rho, b->rec.get(), b->rec_stride);
+      OQ_LAUNCH(k_batch_fill_hdr, dim3(blocks_for(b->count, 256)), dim3(256), 0, s, b->count, (int)REC_RHO, (double)st.rho, b->rec.get(), b->rec_stride);
       HIP_CHECK(hipStreamSynchronize(s));
     }
     b->st = st;  // acts from the next resolve; data and iterate are unchanged: `current`, the certificates and polish_status stay
@@ -1175,6 +1185,47 @@ static c_int batch_duality(osqp_amd_batch *handle, bool subset, const c_int *row
 c_int osqp_amd_batch_duality(osqp_amd_batch *handle, c_float *out, c_int where) { return batch_duality(handle, false, nullptr, 0, out, where); }
 c_int osqp_amd_batch_duality_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *out, c_int where) {
   return batch_duality(handle, true, rows, k, out, where);
+}
+
+// The gap stopping rule of the resident batch: the switch is host state that the next resolve, whole
+// or _rows, turns into RES_GAP; the iterate, rho, `current`, the certificates and the polish status stay.  The refusal counts
+// start from zero at every switch.
+c_int osqp_amd_batch_duality_gap_check(osqp_amd_batch *handle, c_int on) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    OQ_LAUNCH(k_batch_fill_hdr, dim3(blocks_for(b->count, 256)), dim3(256), 0, s, b->count, (int)REC_GAPREF, 0.0, b->rec.get(), b->rec_stride);
+    HIP_CHECK(hipStreamSynchronize(s));
+    b->gap_rule = on != 0;
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+// osqp_amd_batch_gap_refusals (subset false) and _rows: out[j] = the checks of the own last resolve of instance j (rows[j])
+// that the gap test alone refused; zeros while the rule is off.  Only reads the handle.
+static c_int batch_gap_refusals(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, c_float *out, c_int where) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return 1;
+  if (!out) { set_last_error("invalid batch data: no output array"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    if (subset && !select_rows(*b, rows, k, s)) return 1;
+    const int launch = subset ? (int)k : b->count;
+    if (!where && b->adj_out.n < (size_t)launch) b->adj_out.alloc((size_t)launch);
+    double *const dev = where ? out : b->adj_out.get();
+    OQ_LAUNCH(k_batch_gap_refusals, dim3(blocks_for(launch, 256)), dim3(256), 0, s, subset ? (const int *)b->sel.get() : (const int *)nullptr, launch,
+              (int)b->gap_rule, (const double *)b->rec.get(), b->rec_stride, dev);
+    if (!where) HIP_CHECK(hipMemcpyAsync(out, dev, (size_t)launch * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+c_int osqp_amd_batch_gap_refusals(osqp_amd_batch *handle, c_float *out, c_int where) { return batch_gap_refusals(handle, false, nullptr, 0, out, where); }
+c_int osqp_amd_batch_gap_refusals_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *out, c_int where) {
+  return batch_gap_refusals(handle, true, rows, k, out, where);
 }
 
 c_int osqp_amd_batch_destroy(osqp_amd_batch *handle) {

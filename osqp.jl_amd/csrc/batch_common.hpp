@@ -102,8 +102,9 @@ __device__ __forceinline__ double opaque_s(double v) {
 }
 
 // the nrm[] block both kernels keep in LDS: the 14 norms (Slot order of the large-problem path), then these.  N_RECORD: the
-// four-wavefront kernel only (the 512-thread kernel uses 18 .. 23 as scratch)
-enum { N_PRI = 14, N_DUA = 15, N_OBJ = 16, N_STATUS = 17, N_RECORD = 18, N_COUNT = 24 };
+// four-wavefront kernel only (the 512-thread kernel uses 18 .. 23 as scratch), and so are N_XPX, N_QX (the two sums of the
+// objective, kept for the gap test)
+enum { N_PRI = 14, N_DUA = 15, N_OBJ = 16, N_STATUS = 17, N_RECORD = 18, N_XPX = 19, N_QX = 20, N_COUNT = 24 };
 extern __shared__ __attribute__((aligned(16))) double lds_raw[];
 
 // ---------------------------------------------------------------------------------------------------------
@@ -125,27 +126,54 @@ extern __shared__ __attribute__((aligned(16))) double lds_raw[];
 //                   loads again from the kernel arguments there, so a launch without the bit runs the code it ran before up
 //                   to the store.  In k_batch_solve, whose certificate store is a call that takes everything from LDS, the
 //                   bit travels in bit 0 of the parked record pointer (records are 16-byte aligned).
+//   RES_GAP         (with RES_SOLVE; the resolves of a handle with osqp_amd_batch_duality_gap_check on) the duality gap is a
+//                   third termination test, evaluated where both residual tests hold: cold code of the
+//                   residual evaluation, nothing in the ADMM loop proper.  It travels as RES_CERT does: k_batch_quad /
+//                   k_batch_quad2 test the bit of res_mode itself on that branch and in the epilogue, k_batch_solve finds it in
+//                   bit 1 of the parked record pointer.  The epilogue leaves the number of checks the gap alone refused in
+//                   header slot REC_GAPREF of the record (the `-` above); without the bit the slot keeps its zero
+//                   (k_batch_solve does not write it, the four-wavefront kernels write the zero they counted).
 // ---------------------------------------------------------------------------------------------------------
-enum { RES_SOLVE = 1, RES_WARM = 2, RES_SCALE_ONLY = 4, RES_CERT = 8 };
-enum { REC_C = 0, REC_RHO = 1, REC_FLAG = 2, REC_HDR = 4 };
+enum { RES_SOLVE = 1, RES_WARM = 2, RES_SCALE_ONLY = 4, RES_CERT = 8, RES_GAP = 16 };
+enum { REC_C = 0, REC_RHO = 1, REC_FLAG = 2, REC_GAPREF = 3, REC_HDR = 4 };
 __host__ __device__ constexpr int rec_D(int, int) { return REC_HDR; }
 __host__ __device__ constexpr int rec_x(int n, int) { return REC_HDR + n; }
 __host__ __device__ constexpr int rec_E(int n, int) { return REC_HDR + 2 * n; }
 __host__ __device__ constexpr int rec_z(int n, int m) { return REC_HDR + 2 * n + m; }
 __host__ __device__ constexpr int rec_y(int n, int m) { return REC_HDR + 2 * n + 2 * m; }
 __host__ __device__ constexpr int rec_doubles(int n, int m) { return (REC_HDR + 2 * n + 3 * m + 1) & ~1; }
-// a pointer parked in LDS by the prologue, back as a wave-uniform value; k_batch_solve parks RES_CERT in bit 0 (park_rec)
+// a pointer parked in LDS by the prologue, back as a wave-uniform value; k_batch_solve parks RES_CERT in bit 0 and RES_GAP
+// in bit 1 (park_rec)
 typedef __attribute__((address_space(3))) unsigned long long lu64;
 __device__ __forceinline__ unsigned long long park_rec(const double *rec, int res_mode) {
-  return (res_mode & RES_SOLVE) ? ((unsigned long long)rec | ((res_mode & RES_CERT) ? 1ull : 0ull)) : 0ull;
+  return (res_mode & RES_SOLVE) ? ((unsigned long long)rec | ((res_mode & RES_CERT) ? 1ull : 0ull) | ((res_mode & RES_GAP) ? 2ull : 0ull)) : 0ull;
 }
 __device__ __forceinline__ double *parked_ptr(unsigned long long v) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
   return (double *)(((unsigned long long)hi << 32) | (lo & ~7u));
 }
 __device__ __forceinline__ bool parked_cert(unsigned long long v) { return (__builtin_amdgcn_readfirstlane((int)(unsigned)v) & 1) != 0; }
+__device__ __forceinline__ bool parked_gap(unsigned long long v) { return (__builtin_amdgcn_readfirstlane((int)(unsigned)v) & 2) != 0; }
 __host__ __device__ inline bool status_prim_inf(int s) { return s == OSQP_PRIMAL_INFEASIBLE || s == OSQP_PRIMAL_INFEASIBLE_INACCURATE; }
 __host__ __device__ inline bool status_dual_inf(int s) { return s == OSQP_DUAL_INFEASIBLE || s == OSQP_DUAL_INFEASIBLE_INACCURATE; }
+
+// ---- the duality gap: THE statement of a row's support term and of the third termination test, shared
+// by the reading kernel (batch_gap.hpp) and the stopping rule inside k_batch_quad / k_batch_solve -------------------------------
+// u max(y, 0) + l min(y, 0) of one row, y projected onto the polar of the recession cone of [l, u]: a bound is infinite when
+// the SCALED bound (l_s, u_s: the bound times the row's factor E) passes B_INF, and then adds 0.  l, u, y in one system of
+// units, the caller's or the scaled one (there l_s = l, u_s = u).
+__device__ __forceinline__ double support_term(double l, double u, double y, double l_s, double u_s) {
+  const double up = u_s > B_INF ? 0.0 : u * fmax(y, 0.0);
+  const double lo = l_s < -B_INF ? 0.0 : l * fmin(y, 0.0);
+  return up + lo;
+}
+// |gap| < eps_abs + eps_rel max(|x'Px|, |q'x|, |SC|) on the scaled sums, k = 1 / c when the tests are in the caller's units
+// (the scaled sums are c times the caller's), 1 otherwise; a NaN fails
+__device__ __forceinline__ bool gap_test(double sxpx, double sqx, double ssc, double k, double ea, double er) {
+  const double xpx = k * sxpx, qx = k * sqx, sc = k * ssc;
+  const double gap = xpx + qx + sc;
+  return fabs(gap) < ea + er * fmax(fabs(xpx), fmax(fabs(qx), fabs(sc)));
+}
 
 // the shape of the MPC family (BASELINE.json config 5; the generator is mpc_fill in batch.hip): both kernels have an
 // instantiation with it compiled in

@@ -66,10 +66,7 @@ __global__ __launch_bounds__(GT) void k_batch_gap(Pattern P, int count, Args a) 
   for (int i = tid; i < m; i += GT) {
     const double e = E[i], yi = cinv * e * ys[i];
     const double li = fmax(a.l[(size_t)inst * m + i], -OSQP_INFTY), ui = fmin(a.u[(size_t)inst * m + i], OSQP_INFTY);
-    const bool u_inf = ui * e > B_INF, l_inf = li * e < -B_INF;
-    const double up = u_inf ? 0.0 : ui * fmax(yi, 0.0);
-    const double lo = l_inf ? 0.0 : li * fmin(yi, 0.0);
-    sc += up + lo;
+    sc += support_term(li, ui, yi, li * e, ui * e);
   }
   xpx = block_sum(xpx, red);
   qx = block_sum(qx, red);

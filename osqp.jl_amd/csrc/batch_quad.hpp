@@ -52,6 +52,8 @@ namespace quad {
 #endif
 
 constexpr int QT = 256;    // threads per QP
+constexpr int kGapRefShift = 16;  // where the refusal count of the gap test rides in the counter of the rho updates
+constexpr int kRhoCountMax = (1 << kGapRefShift) - 1, kGapRefMax = 0x7FFF;  // where the two counts saturate
 constexpr int RECB = 64;   // bytes of a row record
 enum { F_Z = 0, F_Y = 8, F_L = 16, F_U = 24, F_RHO = 32, F_RHOI = 40, F_ZT = 48, F_E = 56 };
 
@@ -615,6 +617,10 @@ __device__ __forceinline__ void quad_body(
   const double sigma = st.sigma;
   const int max_iter = (int)st.max_iter;
   double pri_res = 0.0, dua_res = 0.0, obj = 0.0;
+  // rho_updates: the rho updates in its low 16 bits, the checks the gap test refused (RES_GAP) in the 15 bits above -- one
+  // scalar register across the ADMM loop instead of two.  Each count stops at its largest value (65535 rho updates, 32767
+  // refusals: one per evaluation at most, so only a solve of more than 32767 evaluations can reach either) instead of
+  // carrying into its neighbour or into the sign.
   int status = OSQP_UNSOLVED, iter = 0, rho_updates = 0;
   bool need_factor = true;
   double U[NH], nsc = 0.0;
@@ -626,7 +632,14 @@ __device__ __forceinline__ void quad_body(
       // reads -- and clears -- its own column of the rows of its half, registers k CH/2 + r.  The windows are unrolled:
       // compile-time register indices, every register assigned exactly once.  The window aliases the row words.
       for (int e = tid(); e < CH * n + 1; e += QT) sd(lds, L.roww + e * 8, 0.0);
-      if (tid() == 0) st2at(lds, L.cst, 1.0, sigma);
+      if (tid() == 0) {
+        // the two constants are made HERE, from an immediate and a scalar register: as plain operands the pair is a loop
+        // invariant that holds four vector registers across the whole ADMM loop (the room the gap test of RES_GAP needs)
+        double one = 1.0, sg = opaque_s(sigma);
+        asm volatile("" : "+v"(one));
+        asm volatile("" : "+v"(sg));
+        st2at(lds, L.cst, one, sg);
+      }
       __syncthreads();
       // the term words of a window are fetched (L2) behind the terms of the window before, so that their latency runs under
       // the two barriers and the read-out of that window; NSM: compile-time bound of the slots per thread
@@ -1003,7 +1016,10 @@ __device__ __forceinline__ void quad_body(
         const double xj = owner ? ld(lds, L.cx + j * 8) : 0.0;
         double sm[2] = {xj * px, qj * xj};
         quad_reduce<2, 1>(sm, lds, L.red, flip, wvs);
-        if (t == 0) *(ldouble *)(nrm + 8 * N_OBJ) = cinv * (0.5 * sm[0] + sm[1]);
+        if (t == 0) {
+          *(ldouble *)(nrm + 8 * N_OBJ) = cinv * (0.5 * sm[0] + sm[1]);
+          sd(nrm, 8 * N_XPX, sm[0]); sd(nrm, 8 * N_QX, sm[1]);  // the two sums themselves: the gap test (RES_GAP) reads them
+        }
       }
       __syncthreads();
     }
@@ -1087,7 +1103,26 @@ __device__ __forceinline__ void quad_body(
           __syncthreads();
         }
       }
-      if (pc && dc) code = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
+      // third test (RES_GAP), only where both residual tests hold: the duality gap, at the eps of this
+      // pass.  x'Px and q'x are the sums of the objective (nrm[N_XPX], nrm[N_QX]); SC is one pass over the row records, every
+      // thread its rows in index order, then the fixed order of quad_reduce.  A refusal means "go on": neither infeasibility
+      // test ran at this check, adaptive rho proceeds as at any other.  res_mode is read from the kernel arguments here.
+      bool gc = true;
+      if (pc && dc && (res_mode & RES_GAP)) {
+        double s1[1] = {0.0};
+        for (int i = t; i < m; i += QT) {
+          const unsigned r = (unsigned)i * RECB;
+          const d2_t lu = ld2at(lds, L.rec + r + F_L);
+          s1[0] += support_term(lu.x, lu.y, ld(lds, L.rec + r + F_Y), lu.x, lu.y);
+        }
+        quad_reduce<1, 1>(s1, lds, L.red, flip, wvs);
+        // (eps of this pass read again from the kernel arguments: ea, er of the residual tests would otherwise stay in
+        // vector registers through the infeasibility tests above, next to the inverse)
+        const double k10 = approx ? 10.0 : 1.0;
+        gc = uni((int)gap_test(NRM(N_XPX), NRM(N_QX), s1[0], uns ? cinv : 1.0, k10 * opaque_s(st.eps_abs), k10 * opaque_s(st.eps_rel))) != 0;
+        if (!gc && rho_updates < (kGapRefMax << kGapRefShift)) rho_updates += 1 << kGapRefShift;  // saturates
+      }
+      if (pc && dc) { if (gc) code = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED; }
       else if (pinf) code = approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE;
       else if (dinf) code = approx ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE;
     }
@@ -1101,7 +1136,8 @@ __device__ __forceinline__ void quad_body(
       const double du = NRM(6) / (nmax(nmax(NRM(8), NRM(9)), NRM(10)) + 1e-10);
       const double est = uni(fmin(fmax(rho * sqrt(pr / (du + 1e-10)), B_RHO_MIN), B_RHO_MAX));
       if (est > rho * st.adaptive_rho_tolerance || est < rho / st.adaptive_rho_tolerance) {
-        rho = est; rho_updates++;
+        rho = est;
+        if ((rho_updates & kRhoCountMax) != kRhoCountMax) rho_updates++;  // saturates below the refusal count
         __syncthreads();
         set_rho(false);
         need_factor = true;
@@ -1124,7 +1160,7 @@ __device__ __forceinline__ void quad_body(
     if (me.t == 0) {
       double *o = info_out + (size_t)row * info_stride;
       o[0] = (double)iter; o[1] = (double)status; o[2] = pri_res; o[3] = dua_res;
-      if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)rho_updates; }
+      if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)(rho_updates & kRhoCountMax); }
     }
     const unsigned long long parked = *(const lu64 *)(lds + L.nrm + 8 * N_RECORD);
     if (double *const rec = parked_ptr(parked)) {  // the scaled iterate and rho stay: the next solve starts from them
@@ -1138,7 +1174,10 @@ __device__ __forceinline__ void quad_body(
         const d2_t zy = ld2at(lds, L.rec + (unsigned)i * RECB + F_Z);
         rec[rec_z(n, m) + i] = has_sol ? zy.x : 0.0; rec[rec_y(n, m) + i] = has_sol ? zy.y : (pcert ? ld(lds, L.dy + i * 8) : 0.0);
       }
-      if (me.t == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; }
+      // (REC_GAPREF: the checks the gap alone refused -- zero without RES_GAP, which is what the slot holds from setup on.
+      // Written with the other header slots, not under a test of res_mode of its own: that test put a frame object of 36
+      // bytes on the instantiations with a selection)
+      if (me.t == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; rec[REC_GAPREF] = (double)(rho_updates >> kGapRefShift); }
     }
   }
 #undef ME

@@ -551,6 +551,11 @@ __device__ __noinline__ void residual_phase(CheckArgs a) {
     __syncthreads();
   }
   const double pri_res = nrm[N_PRI], dua_res = nrm[N_DUA];
+  // RES_GAP (batch_common.hpp): the duality gap as a third test, only where both residual tests hold.  The bit rides in the
+  // parked record pointer; the two sums of the objective are taken out of tmp[] here, before the infeasibility tests of a
+  // first pass reuse the slots
+  const bool gap_rule = parked_gap(*(const lu64 *)(s.gjc + 2 * 4 * 128 + 56));
+  const double sxpx = tmp[0], sqx = tmp[1];
   // ---- termination tests: the requested accuracy when a check is due or the iteration limit is reached,
   //      then -- at the limit only -- the 10x-relaxed ones ----
   int status = 0;
@@ -615,7 +620,16 @@ __device__ __noinline__ void residual_phase(CheckArgs a) {
         }
       }
     }
-    if (pc && dc) status = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED;
+    bool gc = true;
+    if (pc && dc && gap_rule) {  // SC: every thread its rows in index order, then the fixed order of block_reduce_to
+      double sm[1] = {0.0};
+      for (int i = tid; i < m; i += NT) sm[0] += support_term(s.l[i], s.u[i], s.y[i], s.l[i], s.u[i]);
+      block_reduce_to<1>(sm, 1, s.red, tmp + 2);
+      gc = gap_test(sxpx, sqx, tmp[2], uns ? cinv : 1.0, ea, er);
+      // a refusal means "go on" (neither infeasibility test ran at this check); counted behind the parked pointer
+      if (!gc && tid == 0) s.gjc[2 * 4 * 128 + 57] += 1.0;
+    }
+    if (pc && dc) { if (gc) status = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED; }
     else if (pinf) status = approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE;
     else if (dinf) status = approx ? OSQP_DUAL_INFEASIBLE_INACCURATE : OSQP_DUAL_INFEASIBLE;
   }
@@ -693,7 +707,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   // where the epilogue finds the record (0: nothing to leave behind): parked behind the pivot buffers of the inversion
   // instead of scalar registers that would stay live across the whole ADMM loop
   // (and a defined status code for the RES_CERT block of the epilogue, should the loop end before its first residual phase)
-  if (tid == 0) { *(lu64 *)(s.gjc + 2 * 4 * 128 + 56) = park_rec(rec, res_mode); s.nrm[N_STATUS] = 0.0; }
+  // (behind it, slot 57: the checks the gap test refused, RES_GAP only)
+  if (tid == 0) { *(lu64 *)(s.gjc + 2 * 4 * 128 + 56) = park_rec(rec, res_mode); s.gjc[2 * 4 * 128 + 57] = 0.0; s.nrm[N_STATUS] = 0.0; }
   __syncthreads();
   PROF(0)
   // ---- K0: Ruiz equilibration + cost scaling --------------------------------
@@ -933,6 +948,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     for (int j = tid; j < n; j += NT) rec[rec_x(n, m) + j] = has_sol ? x[j] : 0.0;
     for (int i = tid; i < m; i += NT) { rec[rec_z(n, m) + i] = has_sol ? z[i] : 0.0; rec[rec_y(n, m) + i] = has_sol ? s.y[i] : 0.0; }
     if (tid == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; }
+    if (parked_gap(*(const lu64 *)(s.gjc + 2 * 4 * 128 + 56)) && tid == 0) rec[REC_GAPREF] = s.gjc[2 * 4 * 128 + 57];  // the checks the gap alone refused
   }
   leave_certificate<CN, CM, CA, CF>(n, m, P.nnzA, P.nnzF, regs);
 }

@@ -779,6 +779,41 @@ function batch_duality(b::ResidentBatch, rows::AbstractVector{<:Integer})
     return out
 end
 
+"""
+    batch_duality_gap_check!(b, on = true)
+
+The duality gap as a third termination test of every later `batch_solve!`, whole or `rows`, inside the batched solve kernels
+(osqp_amd_batch_duality_gap_check, DESIGN.md section 19): evaluated where both residual tests hold; an instance it refuses
+iterates on, the others stop where they stopped before.  Off by default.  Drops nothing of the handle; the refusal counts
+start from zero.
+"""
+function batch_duality_gap_check!(b::ResidentBatch, on::Bool = true)
+    flag = ccall((:osqp_amd_batch_duality_gap_check, lib), Cc_int, (Ptr{Cvoid}, Cc_int), b.handle, on ? 1 : 0)
+    flag == 0 || error("Error in batch_duality_gap_check!: $(last_error())")
+    return nothing
+end
+
+"[count]: the checks of every instance's own last `batch_solve!` that the gap test alone refused (osqp_amd_batch_gap_refusals); zeros while the rule is off."
+function batch_gap_refusals(b::ResidentBatch)
+    out = Vector{Float64}(undef, b.count)
+    GC.@preserve out begin
+        flag = ccall((:osqp_amd_batch_gap_refusals, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), b.handle, pointer(out), 0)
+    end
+    flag == 0 || error("Error in batched gap refusals: $(last_error())")
+    return out
+end
+
+"The instances `rows` only (osqp_amd_batch_gap_refusals_rows) -> [k]; entry j is of instance rows[j]."
+function batch_gap_refusals(b::ResidentBatch, rows::AbstractVector{<:Integer})
+    r = _batch_rows(rows)
+    out = Vector{Float64}(undef, length(r))
+    GC.@preserve out begin
+        flag = ccall((:osqp_amd_batch_gap_refusals_rows, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cc_int}, Cc_int, Ptr{Cdouble}, Cc_int), b.handle, r, length(r), pointer(out), 0)
+    end
+    flag == 0 || error("Error in batched gap refusals: $(last_error())")
+    return out
+end
+
 const AdjointArg = Union{Nothing,Matrix{Float64},Array{Float64,3},Ptr{Cdouble}}
 _batch_ptr(a::Array{Float64,3}) = pointer(a)
 

@@ -188,11 +188,15 @@ class BatchQPFunction(torch.autograd.Function):
 class BatchQPLayer(torch.nn.Module):
     """`layer(q=None, l=None, u=None, Px=None, Ax=None, rows=None) -> (x, y)` on the resident batch `rb`; `layer.info` is the
     info array [count x 6] of the last forward.  rows: a selection of the instances (`batch.selection`); the tensors, x, y
-    and `layer.info` are then [k x .], row j for instance rows[j], and every other instance is left as it was."""
+    and `layer.info` are then [k x .], row j for instance rows[j], and every other instance is left as it was.
+    duality_gap_check=True calls `rb.duality_gap_check()` once here: every forward then also needs the duality gap below its
+    bound before an instance ends Solved, and the backward differentiates at that point."""
 
-    def __init__(self, rb):
+    def __init__(self, rb, duality_gap_check=False):
         super().__init__()
         self.rb, self.info = rb, None
+        if duality_gap_check:
+            rb.duality_gap_check(True)
 
     def forward(self, q=None, l=None, u=None, Px=None, Ax=None, rows=None):
         if rows is None:

@@ -266,6 +266,10 @@ EXT_SYMBOLS = {
     # prim_obj, dual_obj, gap of every instance ([count x 3]) or of a selection ([k x 3]); host or device output by `where`
     "osqp_amd_batch_duality": (c_int, [C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_duality_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, c_int]),
+    # the gap stopping rule of the resident batch: on 0 / 1; refusal counts of every instance ([count]) or of a selection ([k])
+    "osqp_amd_batch_duality_gap_check": (c_int, [C.c_void_p, c_int]),
+    "osqp_amd_batch_gap_refusals": (c_int, [C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_batch_gap_refusals_rows": (c_int, [C.c_void_p, c_int_p, c_int, C.c_void_p, c_int]),
     "osqp_amd_device_alloc": (C.c_void_p, [c_int, c_int]),
     "osqp_amd_device_free": (c_int, [C.c_void_p, c_int]),
     "osqp_amd_device_copy": (c_int, [C.c_void_p, C.c_void_p, c_int, c_int, c_int]),
