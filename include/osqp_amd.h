@@ -422,6 +422,26 @@ c_int osqp_amd_batch_last_kernel(void);
  * is 0.  Returns the number of entries written. */
 c_int osqp_amd_batch_last_schedule(c_int *out, c_int count);
 
+/* Instances with 128 < n <= 256: an opt-in, process-wide switch, 0 at start; returns the previous
+ * value.  While it is 0 nothing differs from a library without it: n > 128 is refused with the message that names 128.
+ * While it is 1, osqp_amd_batch_solve and osqp_amd_batch_setup accept 128 < n <= 256 and serve it with k_batch_solve_large:
+ * one QP per 512-thread workgroup and compute unit, the inverse of the reduced KKT matrix left in the instance's n x n
+ * scratch in global memory and read from there every iteration -- several times slower per iteration than the register
+ * kernels, hence a switch.  n > 256 is refused with a message that names 256; a pattern whose LDS need exceeds 160 KB with the
+ * usual message; every pattern with n <= 128 goes where it went before, with the same bits.  A resident handle remembers at
+ * setup which path it was built on; later changes of the switch do not touch it.  On such a handle every call of the
+ * resident surface works except polish, adjoint and JVP: their capacity check refuses every such handle ("instance too
+ * large to polish ...": they keep M in LDS and at most 128 variables per instance), before anything is launched or written;
+ * polish = 1 is refused at setup.  osqp_amd_batch_last_kernel and out[0] of osqp_amd_batch_last_schedule report -2 for this kernel (with its LDS
+ * bytes in out[9]; before any launch they are 0). */
+c_int osqp_amd_batch_large(c_int on);
+/* What that kernel needs for a shape, on the host alone (no device is touched; the function the launcher uses): nnzF is the
+ * number of stored entries of the FULL symmetric P (both triangles).  out[0] = bytes of LDS per workgroup, out[1] = bytes of
+ * scratch per instance (8 n^2: the inverse every iteration reads), out[2] = 16 x 16 tiles per wavefront of the inversion.
+ * Returns 0 when the shape is accepted; otherwise 1 with the reason in osqp_amd_last_error (n <= 128, n > 256, too much
+ * LDS) and out untouched.  It does not look at the switch. */
+c_int osqp_amd_batch_large_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out);
+
 /* Batched path: `count` independent QPs that
  * share one sparsity pattern.  P (upper triangle) and A are given once as
  * patterns; values are [count x nnz] row-major; q,l,u are [count x n|m].
@@ -698,7 +718,8 @@ void *osqp_amd_device_alloc(c_int bytes, c_int device);
 c_int osqp_amd_device_free(void *ptr, c_int device);
 c_int osqp_amd_device_copy(void *dst, const void *src, c_int bytes, c_int kind, c_int device);
 
-/* Differences between the batched path and osqp_setup / osqp_solve: instances share one sparsity pattern, n <= 128,
+/* Differences between the batched path and osqp_setup / osqp_solve: instances share one sparsity pattern, n <= 128
+ * (n <= 256 while osqp_amd_batch_large is on),
  * fewer than 65536 rows and non-zeros, everything must fit 160 KB of LDS; `adaptive_rho_interval` = 0 (automatic) means
  * every 100 iterations (there is no per-instance clock); `time_limit`, `verbose` and `linsys_solver` are ignored (the
  * reduced KKT system is factorised on chip); data and settings are validated as by osqp_setup (1 = data, 2 = settings).

@@ -21,9 +21,42 @@ MPC_N, MPC_M = 100, 200
 INFO_COLS = 4  # iter, status_val, pri_res, dua_res
 
 
-def solve_batch(lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, **settings):
+class _large_switch:
+    """osqp_amd_batch_large set to `on` for the length of one call, then put back to what it was."""
+
+    def __init__(self, lib, on):
+        self.lib, self.on = lib, 1 if on else 0
+
+    def __enter__(self):
+        self.before = self.lib.osqp_amd_batch_large(self.on)
+
+    def __exit__(self, *exc):
+        self.lib.osqp_amd_batch_large(self.before)
+        return False
+
+
+def large_plan(lib, P, A):
+    """What the kernel of the opt-in path for 128 < n <= 256 needs for the pattern of P (upper triangle) and A
+    (osqp_amd_batch_large_plan; host only, no device is touched): a dict with `lds_bytes` per workgroup, `scratch_bytes` per
+    instance (8 n^2: the inverse that every iteration reads) and `tiles_per_wave` of the inversion.  A pattern the kernel
+    does not take raises OSQPError with the library's reason."""
+    import scipy.sparse as sp
+
+    P = sp.csc_matrix(sp.triu(P)); P.sort_indices()
+    A = sp.csc_matrix(A); A.sort_indices()
+    n, m = A.shape[1], A.shape[0]
+    ndiag = int(np.count_nonzero(P.tocoo().row == P.tocoo().col))
+    out = np.zeros(3, dtype=np.int64)
+    if lib.osqp_amd_batch_large_plan(n, m, A.nnz, 2 * P.nnz - ndiag, out.ctypes.data) != 0:
+        raise OSQPError("Error in batched plan: " + lib.osqp_amd_last_error().decode())
+    return {"lds_bytes": int(out[0]), "scratch_bytes": int(out[1]), "tiles_per_wave": int(out[2])}
+
+
+def solve_batch(lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, large=False, **settings):
     """Host-pointer entry point (osqp_amd_batch_solve).  P (upper triangle) and A are
-    scipy CSC matrices giving the shared pattern; the *_all arrays are [count x .]."""
+    scipy CSC matrices giving the shared pattern; the *_all arrays are [count x .].
+    large: accept 128 < n <= 256 for this call (osqp_amd_batch_large: the inverse of the reduced KKT matrix read from global
+    memory every iteration, slower per iteration than the register kernels); n <= 128 runs as without it."""
     import scipy.sparse as sp
 
     P = sp.csc_matrix(sp.triu(P)); P.sort_indices()
@@ -39,8 +72,9 @@ def solve_batch(lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, **sett
     stgs = make_settings(lib, settings)
     x = np.empty((count, n)); y = np.empty((count, m))
     infos = (T.CInfo * count)()
-    rc = lib.osqp_amd_batch_solve(count, n, m, _iptr(Pp), _iptr(Pi), _fptr(Px_all), _iptr(Ap), _iptr(Ai), _fptr(Ax_all),
-                                  _fptr(q_all), _fptr(l_all), _fptr(u_all), C.byref(stgs), _fptr(x), _fptr(y), infos, device)
+    with _large_switch(lib, large):
+        rc = lib.osqp_amd_batch_solve(count, n, m, _iptr(Pp), _iptr(Pi), _fptr(Px_all), _iptr(Ap), _iptr(Ai), _fptr(Ax_all),
+                                      _fptr(q_all), _fptr(l_all), _fptr(u_all), C.byref(stgs), _fptr(x), _fptr(y), infos, device)
     if rc != 0:
         raise OSQPError("Error in batched solve: " + lib.osqp_amd_last_error().decode())
     info = np.array([[i.iter, i.status_val, i.pri_res, i.dua_res, i.obj_val, i.rho_updates] for i in infos])
@@ -52,7 +86,7 @@ SCHEDULE_FIELDS = ("entry", "p1_top", "p1_bot", "bw", "ns", "kew0", "kew1", "kew
 
 def last_schedule(lib):
     """The schedule of the last batched launch of this process (osqp_amd_batch_last_schedule) as a dict: `entry` (-1 the
-    512-thread kernel, -2 none yet), `p1_top`, `p1_bot`, `bw`, `ns`, `kew` (the four wavefronts' longest rows), `lds_bytes`,
+    512-thread kernel, -2 the kernel for 128 < n <= 256 -- or, with `lds_bytes` 0, none yet), `p1_top`, `p1_bot`, `bw`, `ns`, `kew` (the four wavefronts' longest rows), `lds_bytes`,
     `instances`."""
     out = np.zeros(len(SCHEDULE_FIELDS), dtype=np.int64)
     got = lib.osqp_amd_batch_last_schedule(out.ctypes.data, len(out))
@@ -273,7 +307,9 @@ class ResidentBatch:
     bits of the whole-batch call, every other instance is left exactly as it was -- data, record, certificates,
     polish status (include/osqp_amd.h, "*_rows")."""
 
-    def __init__(self, lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, **settings):
+    def __init__(self, lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, large=False, **settings):
+        """large: accept 128 < n <= 256 (osqp_amd_batch_large, set for the setup call only: the handle remembers its path).
+        On such a handle polish, `adjoint` and `jvp` raise the library's capacity refusal ("instance too large to polish ...")."""
         import scipy.sparse as sp
 
         P = sp.csc_matrix(sp.triu(P)); P.sort_indices()
@@ -299,8 +335,9 @@ class ResidentBatch:
         Ap, Ai = np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int64)
         stgs = make_settings(lib, settings)
         self.polish_refine_iter = int(stgs.polish_refine_iter)
-        rc = lib.osqp_amd_batch_setup(C.byref(self.handle), count, self.n, self.m, _iptr(Pp), _iptr(Pi), _fptr(Px), _iptr(Ap), _iptr(Ai),
-                                      _fptr(Ax), _fptr(q), _fptr(l), _fptr(u), C.byref(stgs), self.device)
+        with _large_switch(lib, large):
+            rc = lib.osqp_amd_batch_setup(C.byref(self.handle), count, self.n, self.m, _iptr(Pp), _iptr(Pi), _fptr(Px), _iptr(Ap), _iptr(Ai),
+                                          _fptr(Ax), _fptr(q), _fptr(l), _fptr(u), C.byref(stgs), self.device)
         if rc != 0:
             self.handle = C.c_void_p()
             raise OSQPError("Error in batched setup: " + lib.osqp_amd_last_error().decode())

@@ -9,6 +9,9 @@
 //                     of the table -- the MPC family of the benchmark among them;
 //   batch_solve.hpp   k_batch_solve (rounds 1-3) -- one QP per 512-thread workgroup, two per compute unit, for every other
 //                     pattern with n <= 128 (run-time shapes, dense P, long rows);
+//   batch_large.hpp  k_batch_solve_large -- the same phases for 128 < n <= 256 with the inverse left in the instance's global
+//                     scratch and read from there every iteration; only while osqp_amd_batch_large is on (opt-in: slower per
+//                     iteration than the register kernels);
 //   batch_sched.hpp   host side: the analysis of the shared pattern (HostPattern), its device copy and the schedule of the
 //                     four-wavefront kernel for the first table entry it fits (DevicePattern);
 //   batch_polish.hpp  k_batch_polish -- solution polishing for the resident batch, a launch of its own after the ADMM launch
@@ -43,6 +46,7 @@
 #include "batch_quad.hpp"
 #include "batch_sched.hpp"
 #include "batch_solve.hpp"
+#include "batch_large.hpp"
 #include "rng.hpp"
 
 namespace oq {
@@ -52,7 +56,9 @@ int g_batch_polish_launches = 0;  // launches of k_batch_polish by this process 
 int g_batch_jvp_launches = 0;      // launches of k_batch_jvp by this process (osqp_amd_batch_jvp_launches)
 int g_batch_adjoint_launches = 0;  // launches of k_batch_adjoint by this process (osqp_amd_batch_adjoint_launches)
 int g_batch_cert_launches = 0;  // launches of k_batch_cert by this process (osqp_amd_batch_cert_launches)
-int g_batch_last_kernel = -2;  // what launch_batch launched last: -1 the 512-thread kernel, >= 0 the number of the entry of OQ_QUAD_ENTRIES
+int g_batch_last_kernel = -2;  // what launch_batch launched last: -1 the 512-thread kernel, >= 0 the number of the entry of OQ_QUAD_ENTRIES,
+                               // -2 k_batch_solve_large (also the value before any launch: the LDS bytes of the schedule are 0 then)
+int g_batch_large = 0;         // osqp_amd_batch_large: 128 < n <= 256 is accepted and served by k_batch_solve_large
 // the schedule of that launch (osqp_amd_batch_last_schedule): entry, p1_top, p1_bot, bw, ns, kew[0..3], LDS bytes, instances
 constexpr int kSchedWords = 11;
 int g_batch_last_schedule[kSchedWords] = {-2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -244,8 +250,33 @@ void launch_kernel_quad(K kern, const DevicePattern &dp, const OSQPSettings &st,
             io.x_stride, io.y_stride, io.info_stride, io.info_cols, io.rec, io.rec_stride, io.res_mode, io.sel);
 }
 
+// What k_batch_solve_large needs for a shape (osqp_amd_batch_large_plan and the launcher both ask here); a shape it does not
+// take is an Error with the reason.
+struct LargePlan { size_t lds_bytes, scratch_bytes; int tiles_per_wave; };
+LargePlan large_plan(long long n, long long m, long long nnzA, long long nnzF) {
+  if (n > kLargeMaxN || m > 65535 || nnzA > 65535 || nnzF > 65535)
+    throw Error(1, "the batched path supports n <= 256 (osqp_amd_batch_large on) and fewer than 65536 rows / non-zeros");
+  if (n <= kPivotW || m < 0 || nnzA < 0 || nnzF < 0)
+    throw Error(1, "k_batch_solve_large serves 128 < n <= 256; a pattern with n <= 128 runs the register kernels (n = " + std::to_string(n) + ")");
+  const size_t bytes = large_lds_bytes((int)n, (int)m, (int)nnzA, (int)nnzF);
+  if (bytes > 160 * 1024) throw Error(1, "instance too large for the LDS-resident batched path (needs " + std::to_string(bytes) + " bytes of LDS)");
+  return LargePlan{bytes, (size_t)n * (size_t)n * sizeof(double), large_tiles_per_wave((int)n)};
+}
+void launch_batch_large(const DevicePattern &dp, const OSQPSettings &st, int count, const BatchIO &io, hipStream_t s) {
+  const Pattern &P = dp.P;
+  const LargePlan lp = large_plan(P.n, P.m, P.nnzA, P.nnzF);
+  const size_t need = (size_t)count * P.n * P.n;  // M, then M^-1, of every position of the launch: read every iteration
+  if (dp.scratch.n < need) { HIP_CHECK(hipStreamSynchronize(s)); dp.scratch.alloc(need); }
+  g_batch_last_kernel = -2;
+  const int sched[kSchedWords] = {-2, 0, 0, 0, 0, 0, 0, 0, 0, (int)lp.lds_bytes, count};
+  std::copy(sched, sched + kSchedWords, g_batch_last_schedule);
+  if (io.sel) launch_kernel_solve(k_batch_solve_large<true>, lp.lds_bytes, dp, st, count, io, s);
+  else launch_kernel_solve(k_batch_solve_large<false>, lp.lds_bytes, dp, st, count, io, s);
+}
+
 void launch_batch(const DevicePattern &dp, const OSQPSettings &st, int count, const BatchIO &io, hipStream_t s) {
   const Pattern &P = dp.P;
+  if (dp.large) { launch_batch_large(dp, st, count, io, s); return; }  // built while osqp_amd_batch_large was on, n > 128
   const size_t bytes = lds_bytes(P.n, P.m, P.nnzA, P.nnzF, sparse_fits(P));
   if (P.n > 128 || P.m > 65535 || P.nnzA > 65535 || P.nnzF > 65535) throw Error(1, "the batched path supports n <= 128 and fewer than 65536 rows / non-zeros");
   if (bytes > 160 * 1024) throw Error(1, "instance too large for the LDS-resident batched path (needs " + std::to_string(bytes) + " bytes of LDS)");
@@ -372,8 +403,10 @@ c_int validate_batch_data(const BatchProblem &p, bool outputs_ok) {
     set_last_error("invalid batch data"); return 1;
   }
   if (validate_settings(settings)) { set_last_error("invalid settings"); return 2; }
-  if (n > 128 || m > 65535 || Pp[0] != 0 || Ap[0] != 0 || Pp[n] < 0 || Ap[n] < 0 || Pp[n] > 65535 || Ap[n] > 65535) {
-    set_last_error("the batched path supports n <= 128 and fewer than 65536 rows / non-zeros"); return 1;
+  if (n > (g_batch_large ? kLargeMaxN : kPivotW) || m > 65535 || Pp[0] != 0 || Ap[0] != 0 || Pp[n] < 0 || Ap[n] < 0 || Pp[n] > 65535 || Ap[n] > 65535) {
+    set_last_error(g_batch_large ? "the batched path supports n <= 256 (osqp_amd_batch_large on) and fewer than 65536 rows / non-zeros"
+                                 : "the batched path supports n <= 128 and fewer than 65536 rows / non-zeros");
+    return 1;
   }
   for (c_int j = 0; j < n; j++) {
     if (Pp[j + 1] < Pp[j] || Ap[j + 1] < Ap[j]) { set_last_error("column pointers must not decrease"); return 1; }
@@ -464,6 +497,11 @@ void polish_check_fits(const Pattern &P) {
   if (L.total > polish::kLdsLimit)
     throw Error(1, "instance too large to polish on the LDS-resident batched path (needs " + std::to_string(L.total) + " bytes of LDS, " +
                        std::to_string(polish::kLdsLimit) + " available); set polish = 0");
+  // a handle of the opt-in path for n > 128 whose M would still fit the LDS (n < ~190): the substitutions of the polish,
+  // adjoint and JVP kernels hold the vector as two entries per lane of one wavefront (factor_solve, batch_polish.hpp)
+  if (P.n > kPivotW)
+    throw Error(1, "instance too large to polish on the LDS-resident batched path (n = " + std::to_string(P.n) +
+                       ": the polish, adjoint and JVP kernels hold at most 128 variables); set polish = 0");
 }
 // polish() of the oracle on every Solved instance of the launch that has just written io.x / io.y / io.info and the records
 // (`count` workgroups, instance by io.sel)
@@ -626,6 +664,18 @@ c_int osqp_amd_batch_last_schedule(c_int *out, c_int count) {
   for (c_int i = 0; i < k; i++) out[i] = g_batch_last_schedule[i];
   return k;
 }
+c_int osqp_amd_batch_large(c_int on) {
+  const c_int before = g_batch_large;
+  g_batch_large = on ? 1 : 0;
+  return before;
+}
+c_int osqp_amd_batch_large_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out) {
+  try {
+    const LargePlan lp = large_plan(n, m, nnzA, nnzF);
+    if (out) { out[0] = (c_int)lp.lds_bytes; out[1] = (c_int)lp.scratch_bytes; out[2] = lp.tiles_per_wave; }
+    return 0;
+  } OQ_BATCH_CATCH
+}
 c_int osqp_amd_batch_polish_launches(void) { return g_batch_polish_launches; }
 c_int osqp_amd_batch_adjoint_launches(void) { return g_batch_adjoint_launches; }
 c_int osqp_amd_batch_jvp_launches(void) { return g_batch_jvp_launches; }
@@ -641,6 +691,7 @@ c_int osqp_amd_batch_solve(c_int count, c_int n, c_int m, const c_int *Pp, const
     hipStream_t s = nullptr;
     DevicePattern dp;
     dp.build(host_pattern(prob), s);
+    dp.large = n > kPivotW;  // past validate_batch_data only while osqp_amd_batch_large is on
     BatchData d;
     d.upload(prob, dp.P, s);
     DevBuf<double> dx((size_t)count * n), dy((size_t)count * m), dinfo((size_t)count * 6);
@@ -745,6 +796,7 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, 
     b->resident = true; b->device = (int)device; b->total = b->count = (int)count; b->st = *settings;
     b->n = (int)n; b->m = (int)m; b->nnzP = (int)Pp[n]; b->nnzA = (int)Ap[n]; b->rec_stride = rec_doubles((int)n, (int)m);
     b->dp.build(host_pattern(prob), s);
+    b->dp.large = n > kPivotW;  // the handle stays on the path it was built on, whatever the switch does later
     if (settings->polish) polish_check_fits(b->dp.P);
     const size_t cnt = (size_t)count;
     b->upload(prob, b->dp.P, s);

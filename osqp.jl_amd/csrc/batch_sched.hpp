@@ -76,6 +76,7 @@ void upload_vec(DevBuf<T> &d, const std::vector<T> &h, hipStream_t s) { d.alloc(
 struct DevicePattern {
   Pattern P;
   bool mpc = false;                 // HostPattern::mpc
+  bool large = false;               // n > 128, built while osqp_amd_batch_large was on: launch_batch runs k_batch_solve_large (set by build's caller)
   DevBuf<int> Ap, Ai, Rp, Rc, Rmap, Fp, Fc, Fmap, Tp;
   DevBuf<unsigned short> Ti, Tj, Tr, Ta, Tb;
   mutable DevBuf<double> scratch;  // [instances x n x n]: where a workgroup assembles its reduced KKT matrix (launch_batch sizes it)

@@ -33,8 +33,15 @@ constexpr int NW = NT / 64;
 constexpr int KT = 4, KR = 6;  // entries per lane: 4 lanes per column of A (A' v), 2 lanes per row (A v)
 constexpr int KRW = 8;         // dwords per thread of the row-side words (6 used: a 16-byte and an 8-byte read)
 
+// The pivot buffers of the MFMA inversion (Lds::gjc) as a layout: GW doubles per pivot row -- 128 for the kernels of this file,
+// 256 for k_batch_solve_large (batch_large.hpp) -- and what sits behind them.  Every user takes its offsets from here.
+constexpr int kPivotW = 128;
+__host__ __device__ constexpr int gjc_pivot(int gw) { return 2 * 4 * gw; }    // where the 2 x 32 of the pivot block start
+__host__ __device__ constexpr int gjc_parked(int gw) { return 2 * 4 * gw + 56; }  // the parked record pointer; + 1: the gap refusals
+__host__ __device__ constexpr int gjc_doubles(int gw) { return 2 * 4 * gw + 64; }
+
 struct Lds {
-  ldouble *gjc;  // 2 x (4 x 128): the four pivot rows of a block step of the MFMA inversion, double-buffered; behind them
+  ldouble *gjc;  // 2 x (4 x GW): the four pivot rows of a block step of the MFMA inversion, double-buffered; behind them
                  // 2 x 32: the inverse of the 4 x 4 pivot block and its positive-definite flag
   ldouble *bb, *Av, *Pv, *q, *l, *u, *D, *E, *rho, *rhoi, *x, *z, *y, *xp, *zp, *xt, *zt, *dx, *dy, *Ax, *Px, *Aty, *tn, *tm, *red, *ldinv, *nrm;
   lint *ctype;
@@ -44,16 +51,17 @@ struct Lds {
   int ld;
 };
 // Av carries one more double than A has entries: a zero that padded entries point at
-__host__ __device__ inline size_t lds_doubles(int n, int m, int nnzA, int nnzF) {
-  return (size_t)n + nnzA + 1 + nnzF + 10 * (size_t)n + 12 * (size_t)m + 16 * NW + 24 + 2 * 4 * 128 + 64 + 1;  // + 1: alignment slack
+__host__ __device__ inline size_t lds_doubles(int n, int m, int nnzA, int nnzF, int gw = kPivotW) {
+  return (size_t)n + nnzA + 1 + nnzF + 10 * (size_t)n + 12 * (size_t)m + 16 * NW + 24 + gjc_doubles(gw) + 1;  // + 1: alignment slack
 }
 __host__ __device__ inline size_t lds_shorts(int n, int m, int nnzA, int nnzF) {
   return 2 * ((size_t)n + 1) + ((size_t)m + 1) + 3 * (size_t)nnzA + (size_t)nnzF + 8;
 }
-__host__ __device__ inline size_t lds_bytes(int n, int m, int nnzA, int nnzF, bool words) {
-  return lds_doubles(n, m, nnzA, nnzF) * 8 + (((size_t)m * 4 + 15) / 16) * 16 + (words ? (size_t)NT * (KT + KRW) * 4 : 0) +
+__host__ __device__ inline size_t lds_bytes(int n, int m, int nnzA, int nnzF, bool words, int gw = kPivotW) {
+  return lds_doubles(n, m, nnzA, nnzF, gw) * 8 + (((size_t)m * 4 + 15) / 16) * 16 + (words ? (size_t)NT * (KT + KRW) * 4 : 0) +
          lds_shorts(n, m, nnzA, nnzF) * 2 + 16;
 }
+template <int GW = kPivotW>
 __device__ __forceinline__ Lds carve(ldouble *base, const Pattern &P, bool words) {
   Lds s;
   const int n = P.n, m = P.m;
@@ -67,7 +75,7 @@ __device__ __forceinline__ Lds carve(ldouble *base, const Pattern &P, bool words
   s.zp = p; p += m; s.zt = p; p += m; s.dy = p; p += m; s.Ax = p; p += m; s.tm = p; p += m;
   s.red = p; p += 16 * NW;  // NW * K doubles of block_reduce, K <= 14
   s.nrm = p; p += 24;
-  s.gjc = p; p += 2 * 4 * 128 + 64;
+  s.gjc = p; p += gjc_doubles(GW);
   p += (p - base) & 1;  // what follows starts on a 16-byte boundary
   s.ctype = (lint *)p;
   luint *w = (luint *)((lchar *)p + (((size_t)m * 4 + 15) / 16) * 16);  // 16-byte aligned: the words are read four at a time
@@ -196,9 +204,9 @@ __device__ __forceinline__ void assemble_scratch(const Pattern &P, const Lds &s,
 // v_readlane per 25 multiply-adds, ~10 % of the fp64 rate).  The array stays symmetric, so only the tiles on and below
 // the diagonal are kept, TPW per wavefront in accumulator layout (lane: column lane & 15, rows (lane >> 4) + 4 r);
 // indices >= n are padded with the identity and never swept.  One barrier per block step: the pivot rows go through two
-// alternating 4 x 128 LDS buffers.  In: M in the instance's scratch (both triangles, ld = n); out: M^-1 there.
+// alternating 4 x GW LDS buffers (GW >= 16 ceil(n / 16)).  In: M in the instance's scratch (both triangles, ld = n); out: M^-1 there.
 typedef double d4_t __attribute__((ext_vector_type(4)));
-template <int TPW>
+template <int TPW, int GW = kPivotW>
 __device__ __forceinline__ bool invert_mfma(int n, double *scratch, ldouble *cb) {
   scratch = opaque(scratch);
   const int lane = mytid() & 63, wave = uni(mytid() >> 6);
@@ -226,18 +234,18 @@ __device__ __forceinline__ bool invert_mfma(int n, double *scratch, ldouble *cb)
     for (int tq = 0; tq < 4; tq++) {
       const int step = tb * 4 + tq;
       if (step < steps) {
-        ldouble *C = cb + (step & 1) * 512;  // C[a][j] at a * 128 + j
-        ldouble *Gs = cb + 1024 + (step & 1) * 32;
+        ldouble *C = cb + (step & 1) * (4 * GW);  // C[a][j] at a * GW + j
+        ldouble *Gs = cb + gjc_pivot(GW) + (step & 1) * 32;
         // publish rows k0 .. k0 + 3: left of and inside block tb from the tiles of row block tb (register tq of every
         // lane), right of it from column k0 + a of the tiles below (the array is symmetric).  The wavefront that owns the
         // diagonal tile also inverts the 4 x 4 pivot block -- it sits in register tq of its lanes 16 a + 4 tq + b -- while
         // the others wait at the barrier: one Gauss-Jordan per block step instead of one per wavefront.
 #pragma unroll
         for (int s = 0; s < TPW; s++) {
-          if (TI[s] == tb) C[lr * 128 + TJ[s] * 16 + lc] = acc[s][tq];
+          if (TI[s] == tb) C[lr * GW + TJ[s] * 16 + lc] = acc[s][tq];
           if (TJ[s] == tb && TI[s] > tb && (lc >> 2) == tq) {
 #pragma unroll
-            for (int r = 0; r < 4; r++) C[(lc & 3) * 128 + TI[s] * 16 + lr + 4 * r] = acc[s][r];
+            for (int r = 0; r < 4; r++) C[(lc & 3) * GW + TI[s] * 16 + lr + 4 * r] = acc[s][r];
           }
           if (TI[s] == tb && TJ[s] == tb) {
             double g[4][4];
@@ -281,12 +289,12 @@ __device__ __forceinline__ bool invert_mfma(int n, double *scratch, ldouble *cb)
 #pragma unroll
         for (int s = 0; s < TPW; s++) {
           if (TI[s] < 0) continue;
-          const double aop = -C[lr * 128 + TI[s] * 16 + lc];  // A[i = lane & 15][k = lane >> 4] = -C[k][row i of block I]
+          const double aop = -C[lr * GW + TI[s] * 16 + lc];  // A[i = lane & 15][k = lane >> 4] = -C[k][row i of block I]
           const ldouble *cj = C + TJ[s] * 16 + lc;
           double bop = gl[0] * cj[0];                          // B[k = lane >> 4][j = lane & 15] = (G C)[k][column j of block J]
-          bop = __builtin_fma(gl[1], cj[128], bop);
-          bop = __builtin_fma(gl[2], cj[256], bop);
-          bop = __builtin_fma(gl[3], cj[384], bop);
+          bop = __builtin_fma(gl[1], cj[GW], bop);
+          bop = __builtin_fma(gl[2], cj[2 * GW], bop);
+          bop = __builtin_fma(gl[3], cj[3 * GW], bop);
           acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, bop, acc[s], 0, 0, 0);
           if (TI[s] == tb) acc[s][tq] = (TJ[s] == tb && (lc >> 2) == tq) ? -gdiag : bop;  // rows K: G C, and -G inside the block
           if (TJ[s] == tb && (lc >> 2) == tq) {                                              // columns K: the mirror
@@ -295,9 +303,9 @@ __device__ __forceinline__ bool invert_mfma(int n, double *scratch, ldouble *cb)
               if (TI[s] == tb && r == tq) continue;  // rows K of the diagonal tile were set above
               const ldouble *ci = C + TI[s] * 16 + lr + 4 * r;
               double w = gc[0] * ci[0];
-              w = __builtin_fma(gc[1], ci[128], w);
-              w = __builtin_fma(gc[2], ci[256], w);
-              w = __builtin_fma(gc[3], ci[384], w);
+              w = __builtin_fma(gc[1], ci[GW], w);
+              w = __builtin_fma(gc[2], ci[2 * GW], w);
+              w = __builtin_fma(gc[3], ci[3 * GW], w);
               acc[s][r] = w;
             }
           }
@@ -306,12 +314,16 @@ __device__ __forceinline__ bool invert_mfma(int n, double *scratch, ldouble *cb)
     }
   }
   // the sweeps leave -M^-1; both triangles back into the scratch
+  // (the wide instantiations take the pointer and the lane afresh: the 4 TPW addresses of the load above are otherwise kept
+  // for this loop -- spilled before the sweeps and fetched back after them)
+  int sr = lr, sc = lc;
+  if constexpr (GW > kPivotW) { scratch = opaque(scratch); const int l2 = mytid() & 63; sr = l2 >> 4; sc = l2 & 15; }
 #pragma unroll
   for (int s = 0; s < TPW; s++) {
     if (TI[s] < 0) continue;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const int row = TI[s] * 16 + lr + 4 * r, col = TJ[s] * 16 + lc;
+      const int row = TI[s] * 16 + sr + 4 * r, col = TJ[s] * 16 + sc;
       if (row < n && col < n) {
         const double v = -acc[s][r];
         scratch[row + (size_t)col * n] = v;
@@ -503,11 +515,11 @@ __device__ __forceinline__ void block_reduce_to(double *v, int op, ldouble *red,
   __syncthreads();
 }
 
-template <int CN, int CM, int CA, int CF>
+template <int CN, int CM, int CA, int CF, int GW = kPivotW>
 __device__ __noinline__ void residual_phase(CheckArgs a) {
   Pattern P;
   P.n = CN ? CN : a.n; P.m = CN ? CM : a.m; P.nnzA = CN ? CA : a.nnzA; P.nnzF = CN ? CF : a.nnzF;
-  const Lds s = carve((ldouble *)lds_raw, P, a.words != 0);
+  const Lds s = carve<GW>((ldouble *)lds_raw, P, a.words != 0);
   const int n = P.n, m = P.m, tid = mytid();
   ldouble *x = a.swapped ? s.xp : s.x, *z = a.swapped ? s.zp : s.z;
   ldouble *nrm = s.nrm, *tmp = s.nrm + 18;  // tmp: 6 scratch results of the small reductions
@@ -554,7 +566,7 @@ __device__ __noinline__ void residual_phase(CheckArgs a) {
   // RES_GAP (batch_common.hpp): the duality gap as a third test, only where both residual tests hold.  The bit rides in the
   // parked record pointer; the two sums of the objective are taken out of tmp[] here, before the infeasibility tests of a
   // first pass reuse the slots
-  const bool gap_rule = parked_gap(*(const lu64 *)(s.gjc + 2 * 4 * 128 + 56));
+  const bool gap_rule = parked_gap(*(const lu64 *)(s.gjc + gjc_parked(GW)));
   const double sxpx = tmp[0], sqx = tmp[1];
   // ---- termination tests: the requested accuracy when a check is due or the iteration limit is reached,
   //      then -- at the limit only -- the 10x-relaxed ones ----
@@ -627,7 +639,7 @@ __device__ __noinline__ void residual_phase(CheckArgs a) {
       block_reduce_to<1>(sm, 1, s.red, tmp + 2);
       gc = gap_test(sxpx, sqx, tmp[2], uns ? cinv : 1.0, ea, er);
       // a refusal means "go on" (neither infeasibility test ran at this check); counted behind the parked pointer
-      if (!gc && tid == 0) s.gjc[2 * 4 * 128 + 57] += 1.0;
+      if (!gc && tid == 0) s.gjc[gjc_parked(GW) + 1] += 1.0;
     }
     if (pc && dc) { if (gc) status = approx ? OSQP_SOLVED_INACCURATE : OSQP_SOLVED; }
     else if (pinf) status = approx ? OSQP_PRIMAL_INFEASIBLE_INACCURATE : OSQP_PRIMAL_INFEASIBLE;
@@ -645,12 +657,12 @@ __device__ __noinline__ void residual_phase(CheckArgs a) {
 // reason: everything it needs is in LDS -- the parked record pointer with the RES_CERT bit, the status code where the
 // residual phase left it (a loop that ended on a failed factorisation left 0 there: no certificate), delta_y and delta_x --
 // so the kernel keeps no register for it and its own code stays what it was.
-template <int CN, int CM, int CA, int CF>
+template <int CN, int CM, int CA, int CF, int GW = kPivotW>
 __device__ __noinline__ void leave_certificate(int n_, int m_, int nnzA, int nnzF, int words) {
   Pattern P;
   P.n = CN ? CN : n_; P.m = CN ? CM : m_; P.nnzA = CN ? CA : nnzA; P.nnzF = CN ? CF : nnzF;
-  const Lds s = carve((ldouble *)lds_raw, P, words != 0);
-  const unsigned long long parked = *(const lu64 *)(s.gjc + 2 * 4 * 128 + 56);
+  const Lds s = carve<GW>((ldouble *)lds_raw, P, words != 0);
+  const unsigned long long parked = *(const lu64 *)(s.gjc + gjc_parked(GW));
   if (!parked_cert(parked)) return;
   double *const rec = parked_ptr(parked);
   const int n = P.n, m = P.m, code = uni((int)s.nrm[N_STATUS]);
@@ -708,7 +720,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
   // instead of scalar registers that would stay live across the whole ADMM loop
   // (and a defined status code for the RES_CERT block of the epilogue, should the loop end before its first residual phase)
   // (behind it, slot 57: the checks the gap test refused, RES_GAP only)
-  if (tid == 0) { *(lu64 *)(s.gjc + 2 * 4 * 128 + 56) = park_rec(rec, res_mode); s.gjc[2 * 4 * 128 + 57] = 0.0; s.nrm[N_STATUS] = 0.0; }
+  if (tid == 0) { *(lu64 *)(s.gjc + gjc_parked(kPivotW)) = park_rec(rec, res_mode); s.gjc[gjc_parked(kPivotW) + 1] = 0.0; s.nrm[N_STATUS] = 0.0; }
   __syncthreads();
   PROF(0)
   // ---- K0: Ruiz equilibration + cost scaling --------------------------------
@@ -942,13 +954,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     o[0] = (double)iter; o[1] = (double)status; o[2] = pri_res; o[3] = dua_res;
     if (info_cols > 4) { o[4] = status == OSQP_NON_CVX ? NAN : obj; o[5] = (double)rho_updates; }
   }
-  if (double *const rec = parked_ptr(*(const lu64 *)(s.gjc + 2 * 4 * 128 + 56))) {  // the scaled iterate and rho stay: the next solve starts from them
+  if (double *const rec = parked_ptr(*(const lu64 *)(s.gjc + gjc_parked(kPivotW)))) {  // the scaled iterate and rho stay: the next solve starts from them
     // (an instance without a solution -- infeasible, non-convex -- starts its next solve from zero, as the oracle's
     // store_solution cold-starts it; rho stays)
     for (int j = tid; j < n; j += NT) rec[rec_x(n, m) + j] = has_sol ? x[j] : 0.0;
     for (int i = tid; i < m; i += NT) { rec[rec_z(n, m) + i] = has_sol ? z[i] : 0.0; rec[rec_y(n, m) + i] = has_sol ? s.y[i] : 0.0; }
     if (tid == 0) { rec[REC_RHO] = rho; rec[REC_FLAG] = 3.0; }
-    if (parked_gap(*(const lu64 *)(s.gjc + 2 * 4 * 128 + 56)) && tid == 0) rec[REC_GAPREF] = s.gjc[2 * 4 * 128 + 57];  // the checks the gap alone refused
+    if (parked_gap(*(const lu64 *)(s.gjc + gjc_parked(kPivotW))) && tid == 0) rec[REC_GAPREF] = s.gjc[gjc_parked(kPivotW) + 1];  // the checks the gap alone refused
   }
   leave_certificate<CN, CM, CA, CF>(n, m, P.nnzA, P.nnzF, regs);
 }

@@ -793,6 +793,34 @@ function batch_duality_gap_check!(b::ResidentBatch, on::Bool = true)
     return nothing
 end
 
+"""
+    batch_large!(on = true) -> Bool
+
+The opt-in path for instances with 128 < n <= 256 (osqp_amd_batch_large, DESIGN.md section 13.1): a process-wide switch, off
+at start; returns the previous value.  While it is on, the batched solve and the setup of a resident batch accept such
+patterns and serve them with a kernel that reads the inverse of the reduced KKT matrix from global memory every iteration
+(slower per iteration than the register kernels); every pattern with n <= 128 runs as before.  A resident batch remembers
+the path it was set up on.
+"""
+function batch_large!(on::Bool = true)
+    return ccall((:osqp_amd_batch_large, lib), Cc_int, (Cc_int,), on ? 1 : 0) != 0
+end
+
+"""
+    batch_large_plan(n, m, nnzA, nnzF) -> (lds_bytes, scratch_bytes, tiles_per_wave)
+
+What that kernel needs for a shape (osqp_amd_batch_large_plan; host only, no device is touched): nnzF counts the stored
+entries of the full symmetric P.  A shape it does not take raises with the library's reason.
+"""
+function batch_large_plan(n::Integer, m::Integer, nnzA::Integer, nnzF::Integer)
+    out = zeros(Cc_int, 3)
+    GC.@preserve out begin
+        flag = ccall((:osqp_amd_batch_large_plan, lib), Cc_int, (Cc_int, Cc_int, Cc_int, Cc_int, Ptr{Cc_int}), n, m, nnzA, nnzF, pointer(out))
+    end
+    flag == 0 || error("Error in batched plan: $(last_error())")
+    return (lds_bytes = Int(out[1]), scratch_bytes = Int(out[2]), tiles_per_wave = Int(out[3]))
+end
+
 "[count]: the checks of every instance's own last `batch_solve!` that the gap test alone refused (osqp_amd_batch_gap_refusals); zeros while the rule is off."
 function batch_gap_refusals(b::ResidentBatch)
     out = Vector{Float64}(undef, b.count)

@@ -190,11 +190,15 @@ class BatchQPLayer(torch.nn.Module):
     info array [count x 6] of the last forward.  rows: a selection of the instances (`batch.selection`); the tensors, x, y
     and `layer.info` are then [k x .], row j for instance rows[j], and every other instance is left as it was.
     duality_gap_check=True calls `rb.duality_gap_check()` once here: every forward then also needs the duality gap below its
-    bound before an instance ends Solved, and the backward differentiates at that point."""
+    bound before an instance ends Solved, and the backward differentiates at that point.
+    large=True states that `rb` was built with `ResidentBatch(..., large=True)` for 128 < n <= 256 (it is also set when rb.n >
+    128): such a layer is FORWARD ONLY -- the adjoint and JVP kernels keep M in LDS, and `backward` / `jacobian` raise the
+    library's refusal ("instance too large to polish ...")."""
 
-    def __init__(self, rb, duality_gap_check=False):
+    def __init__(self, rb, duality_gap_check=False, large=False):
         super().__init__()
         self.rb, self.info = rb, None
+        self.large = bool(large) or rb.n > 128
         if duality_gap_check:
             rb.duality_gap_check(True)
 
