@@ -430,9 +430,9 @@ c_int osqp_amd_batch_last_schedule(c_int *out, c_int count);
  * kernels, hence a switch.  n > 256 is refused with a message that names 256; a pattern whose LDS need exceeds 160 KB with the
  * usual message; every pattern with n <= 128 goes where it went before, with the same bits.  A resident handle remembers at
  * setup which path it was built on; later changes of the switch do not touch it.  On such a handle every call of the
- * resident surface works except polish, adjoint and JVP: their capacity check refuses every such handle ("instance too
- * large to polish ...": they keep M in LDS and at most 128 variables per instance), before anything is launched or written;
- * polish = 1 is refused at setup.  osqp_amd_batch_last_kernel and out[0] of osqp_amd_batch_last_schedule report -2 for this kernel (with its LDS
+ * resident surface works; polish, adjoint and JVP work once osqp_amd_batch_large_factor (below) has been switched on for the
+ * handle.  By default their capacity check refuses every such handle ("instance too large to polish ...": they keep M in LDS
+ * and at most 128 variables per instance), before anything is launched or written; polish = 1 is refused at setup either way.  osqp_amd_batch_last_kernel and out[0] of osqp_amd_batch_last_schedule report -2 for this kernel (with its LDS
  * bytes in out[9]; before any launch they are 0). */
 c_int osqp_amd_batch_large(c_int on);
 /* What that kernel needs for a shape, on the host alone (no device is touched; the function the launcher uses): nnzF is the
@@ -709,6 +709,22 @@ c_int osqp_amd_batch_duality_rows(osqp_amd_batch *batch, const c_int *rows, c_in
  * The one-shot entries (osqp_amd_batch_solve, _solve_generated) and osqp_amd_batch_mpc_* run without the rule.
  * Return 0; 1 NULL or foreign (non-resident) handle, NULL out, a bad selection. */
 c_int osqp_amd_batch_duality_gap_check(osqp_amd_batch *batch, c_int on);
+
+/* Polish, adjoint and JVP on a resident handle with 128 < n <= 256: an opt-in switch PER HANDLE, 0
+ * after setup; returns the previous value, or -1 with the reason in osqp_amd_last_error for a NULL handle, a handle that
+ * osqp_amd_batch_setup did not create, or a handle with n <= 128.  While it is 1 the three kernels run forms that keep the
+ * Cholesky factor of M in the instance's n x n block of the handle's global scratch (blocked factorisation, panels of
+ * out[2] columns in LDS) instead of in LDS; everything else they do -- ncot cotangents, ndir directions, *_rows, host and
+ * device forms, statuses, acceptance rule -- is what they do for n <= 128.  The shape is checked against the LDS need of that
+ * layout wherever polish is asked for and at every adjoint / JVP call, before anything is launched or written ("instance too
+ * large to polish ... (needs N bytes of LDS ...").  The call launches nothing and touches nothing on the device.  To polish:
+ * set up with polish = 0, switch on, osqp_amd_batch_update_polish(handle, 1, ...).  Switching off puts the refusals back and
+ * sets the handle's polish to 0. */
+c_int osqp_amd_batch_large_factor(osqp_amd_batch *batch, c_int on);
+/* What those forms need for a shape, on the host alone (the function their launchers ask): out[0] = bytes of LDS per workgroup,
+ * out[1] = bytes of scratch per launched instance (8 n^2), out[2] = NB, the columns per panel.  Returns 0 when the shape is
+ * accepted; otherwise 1 with the reason in osqp_amd_last_error (n <= 128, n > 256, too much LDS) and out untouched. */
+c_int osqp_amd_batch_large_factor_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out);
 c_int osqp_amd_batch_gap_refusals(osqp_amd_batch *batch, c_float *out /* [count] */, c_int where);
 c_int osqp_amd_batch_gap_refusals_rows(osqp_amd_batch *batch, const c_int *rows, c_int k, c_float *out /* [k] */, c_int where);
 

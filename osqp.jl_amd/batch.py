@@ -52,6 +52,23 @@ def large_plan(lib, P, A):
     return {"lds_bytes": int(out[0]), "scratch_bytes": int(out[1]), "tiles_per_wave": int(out[2])}
 
 
+def large_factor_plan(lib, P, A):
+    """What polish, adjoint and JVP need for the pattern of P (upper triangle) and A on a handle with 128 < n <= 256 and
+    `large_factor` on (osqp_amd_batch_large_factor_plan; host only): a dict with `lds_bytes` per workgroup, `scratch_bytes`
+    per launched instance (8 n^2: the factor) and `nb`, the columns per panel of the blocked factorisation.  A pattern they do
+    not take raises OSQPError with the library's reason."""
+    import scipy.sparse as sp
+
+    P = sp.csc_matrix(sp.triu(P)); P.sort_indices()
+    A = sp.csc_matrix(A); A.sort_indices()
+    n, m = A.shape[1], A.shape[0]
+    ndiag = int(np.count_nonzero(P.tocoo().row == P.tocoo().col))
+    out = np.zeros(3, dtype=np.int64)
+    if lib.osqp_amd_batch_large_factor_plan(n, m, A.nnz, 2 * P.nnz - ndiag, out.ctypes.data) != 0:
+        raise OSQPError("Error in batched plan: " + lib.osqp_amd_last_error().decode())
+    return {"lds_bytes": int(out[0]), "scratch_bytes": int(out[1]), "nb": int(out[2])}
+
+
 def solve_batch(lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, large=False, **settings):
     """Host-pointer entry point (osqp_amd_batch_solve).  P (upper triangle) and A are
     scipy CSC matrices giving the shared pattern; the *_all arrays are [count x .].
@@ -307,9 +324,12 @@ class ResidentBatch:
     bits of the whole-batch call, every other instance is left exactly as it was -- data, record, certificates,
     polish status (include/osqp_amd.h, "*_rows")."""
 
-    def __init__(self, lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, large=False, **settings):
+    def __init__(self, lib, P, A, Px_all, Ax_all, q_all, l_all, u_all, device=0, large=False, large_factor=False, **settings):
         """large: accept 128 < n <= 256 (osqp_amd_batch_large, set for the setup call only: the handle remembers its path).
-        On such a handle polish, `adjoint` and `jvp` raise the library's capacity refusal ("instance too large to polish ...")."""
+        By default polish, `adjoint` and `jvp` raise the library's capacity refusal on such a handle ("instance too large to
+        polish ..."); large_factor=True (or `large_factor()` later) switches on the forms of those kernels that keep their factor
+        in global scratch.  With it, `polish=True` is set up in the order the library asks for: setup
+        with polish = 0, the switch, then `update_polish(True)`."""
         import scipy.sparse as sp
 
         P = sp.csc_matrix(sp.triu(P)); P.sort_indices()
@@ -333,6 +353,9 @@ class ResidentBatch:
         self.lib, self.device, self.handle = lib, int(device), C.c_void_p()
         Pp, Pi = np.ascontiguousarray(P.indptr, dtype=np.int64), np.ascontiguousarray(P.indices, dtype=np.int64)
         Ap, Ai = np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int64)
+        polish_after = bool(large_factor and self.n > 128 and settings.get("polish"))
+        if polish_after:
+            settings = dict(settings, polish=False)
         stgs = make_settings(lib, settings)
         self.polish_refine_iter = int(stgs.polish_refine_iter)
         with _large_switch(lib, large):
@@ -341,6 +364,25 @@ class ResidentBatch:
         if rc != 0:
             self.handle = C.c_void_p()
             raise OSQPError("Error in batched setup: " + lib.osqp_amd_last_error().decode())
+        if large_factor and self.n > 128:
+            try:
+                self.large_factor(True)
+                if polish_after:
+                    self.update_polish(True)
+            except Exception:
+                self.close()
+                raise
+
+    def large_factor(self, on=True):
+        """Polish, `adjoint`, `jvp` and `jacobian` on a handle with 128 < n <= 256 (osqp_amd_batch_large_factor, DESIGN.md section
+        13.2): off after setup; returns the previous value.  While it is on those kernels keep the factor of M in the
+        instance's block of global scratch instead of in LDS; a shape whose other LDS needs exceed the limit is refused where
+        polish is asked for and at every derivative call.  Launches nothing.  Switching off puts the refusals back and sets
+        polish off.  A handle with n <= 128 raises."""
+        before = self.lib.osqp_amd_batch_large_factor(self.handle, 1 if on else 0)
+        if before < 0:
+            raise OSQPError("Error in batched large_factor: " + self.lib.osqp_amd_last_error().decode())
+        return bool(before)
 
     def _call(self, what, rc):
         if rc != 0:

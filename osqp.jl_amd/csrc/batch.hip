@@ -14,6 +14,8 @@
 //                     iteration than the register kernels);
 //   batch_sched.hpp   host side: the analysis of the shared pattern (HostPattern), its device copy and the schedule of the
 //                     four-wavefront kernel for the first table entry it fits (DevicePattern);
+//   batch_large_factor.hpp  the factor of the polish / adjoint / JVP kernels in the instance's global scratch, for handles with
+//                     128 < n <= 256 and osqp_amd_batch_large_factor on: the LARGE instantiations of the three kernels below;
 //   batch_polish.hpp  k_batch_polish -- solution polishing for the resident batch, a launch of its own after the ADMM launch
 //                     when the handle's settings.polish is 1; the solve kernels know nothing of it;
 //   batch_adjoint.hpp k_batch_adjoint -- adjoint derivatives of the solutions of the resident batch, a launch of its own on
@@ -390,6 +392,9 @@ struct BatchPlan : BatchData {
   // osqp_amd_batch_duality_gap_check: every resolve carries RES_GAP, and slot REC_GAPREF of a record is the refusal count of
   // the instance's own last resolve since the rule was switched on (the switch zeroes the slot of every record)
   bool gap_rule = false;
+  // osqp_amd_batch_large_factor (handles with n > 128 only): polish, adjoint and JVP run their LARGE instantiations, the factor
+  // in dp.scratch; off: they are refused as a large handle always refused them
+  bool large_factor = false;
 };
 
 // The checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings], shared by the
@@ -490,9 +495,22 @@ bool holds_current(const BatchPlan &b, const std::vector<int> *rows) {
   }
   return true;
 }
+// What the LARGE instantiations of k_batch_polish / _adjoint / _jvp need for a shape (osqp_amd_batch_large_factor_plan and
+// polish_check_fits, which every launcher of the three asks, both ask here); a shape they do not take is an Error.
+struct LargeFactorPlan { size_t lds_bytes, scratch_bytes; int nb; };
+LargeFactorPlan large_factor_plan(long long n, long long m, long long nnzA, long long nnzF) {
+  if (n <= kPivotW || n > polish::lf::kMaxN || m < 0 || m > 65535 || nnzA < 0 || nnzA > 65535 || nnzF < 0 || nnzF > 65535)
+    throw Error(1, "the factor in global scratch serves 128 < n <= 256 and fewer than 65536 rows / non-zeros (n = " + std::to_string(n) + ")");
+  const polish::Layout L = polish::make_layout((int)n, (int)m, (int)nnzA, (int)nnzF, true);
+  if (L.total > polish::kLdsLimit)
+    throw Error(1, "instance too large to polish on the LDS-resident batched path (needs " + std::to_string(L.total) + " bytes of LDS, " +
+                       std::to_string(polish::kLdsLimit) + " available, with the factor in global scratch); set polish = 0");
+  return LargeFactorPlan{(size_t)L.total, (size_t)n * (size_t)n * sizeof(double), polish::lf::NB};
+}
 // the LDS a polish launch of this pattern needs; a pattern it cannot serve is refused where polish is asked for (setup,
-// osqp_amd_batch_update_polish), never skipped
-void polish_check_fits(const Pattern &P) {
+// osqp_amd_batch_update_polish), never skipped.  large_factor: the handle's switch (a handle with n <= 128 ignores it)
+void polish_check_fits(const Pattern &P, bool large_factor = false) {
+  if (large_factor && P.n > kPivotW) { large_factor_plan(P.n, P.m, P.nnzA, P.nnzF); return; }
   const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
   if (L.total > polish::kLdsLimit)
     throw Error(1, "instance too large to polish on the LDS-resident batched path (needs " + std::to_string(L.total) + " bytes of LDS, " +
@@ -503,21 +521,31 @@ void polish_check_fits(const Pattern &P) {
     throw Error(1, "instance too large to polish on the LDS-resident batched path (n = " + std::to_string(P.n) +
                        ": the polish, adjoint and JVP kernels hold at most 128 variables); set polish = 0");
 }
+// the n x n block per launch position of the LARGE instantiations: the scratch of the handle's solve launches, grown as
+// launch_batch_large grows it
+double *large_factor_scratch(const DevicePattern &dp, int launch, hipStream_t s) {
+  const size_t need = (size_t)launch * dp.P.n * dp.P.n;
+  if (dp.scratch.n < need) { HIP_CHECK(hipStreamSynchronize(s)); dp.scratch.alloc(need); }
+  return dp.scratch.get();
+}
 // polish() of the oracle on every Solved instance of the launch that has just written io.x / io.y / io.info and the records
 // (`count` workgroups, instance by io.sel)
 void launch_polish(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
   const Pattern &P = b.dp.P;
-  polish_check_fits(P);
-  const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
+  const bool large = b.large_factor && b.dp.large;
+  polish_check_fits(P, large);
+  const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, large);
   polish::Args a;
   a.Px = io.Px; a.Ax = io.Ax; a.q = io.q; a.l = io.l; a.u = io.u;
   a.x = io.x; a.y = io.y; a.info = io.info; a.rec = io.rec; a.status = b.pstat.get();
   a.x_stride = io.x_stride; a.y_stride = io.y_stride; a.info_stride = io.info_stride; a.rec_stride = io.rec_stride;
   a.refine = (int)b.st.polish_refine_iter; a.unscaled = b.st.scaling && !b.st.scaled_termination;
   a.delta = b.st.delta; a.sel = io.sel;
-  HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_polish, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+  if (large) a.scratch = large_factor_scratch(b.dp, count, s);
+  auto *const kern = large ? polish::k_batch_polish<true> : polish::k_batch_polish<false>;
+  HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
   g_batch_polish_launches++;
-  OQ_LAUNCH(polish::k_batch_polish, dim3(count), dim3(polish::PT), (size_t)L.total, s, P, count, L, a);
+  OQ_LAUNCH(kern, dim3(count), dim3(polish::PT), (size_t)L.total, s, P, count, L, a);
 }
 // the certificates of the launch that has just written io.info and, under RES_CERT, left the directions in the records
 void launch_cert(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
@@ -531,7 +559,7 @@ void launch_cert(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
 // polish / polish_refine_iter of a resident handle (osqp_amd_batch_update_polish, osqp_amd_batch_update_setting); the values
 // have passed their rules
 void set_polish(BatchPlan &b, c_int polish_new, c_int refine_new) {
-  if (polish_new) polish_check_fits(b.dp.P);
+  if (polish_new) polish_check_fits(b.dp.P, b.large_factor);
   b.st.polish = polish_new; b.st.polish_refine_iter = refine_new;
 }
 #define OQ_BATCH_CATCH                                                                          \
@@ -557,7 +585,8 @@ c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_in
       if (!select_rows(*b, rows, k, s)) return 1;
       if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
     }
-    polish_check_fits(P);
+    const bool large = b->large_factor && b->dp.large;
+    polish_check_fits(P, large);
     const int launch = subset ? (int)k : b->count;
     const size_t cnt = (size_t)launch, nc = (size_t)ncot, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
     if (!lm) { dy = nullptr; dl = du = act_out = nullptr; }
@@ -582,10 +611,12 @@ c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_in
     a.dq = dev[0]; a.dl = dev[1]; a.du = dev[2]; a.dPx = dev[3]; a.dAx = dev[4]; a.act = dev[5]; a.status = dev[6];
     a.ncot = (int)ncot; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
     a.sel = subset ? b->sel.get() : nullptr;
-    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
-    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, large);
+    if (large) a.scratch = large_factor_scratch(b->dp, launch, s);
+    auto *const kern = large ? polish::k_batch_adjoint<true> : polish::k_batch_adjoint<false>;
+    HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
     g_batch_adjoint_launches++;
-    OQ_LAUNCH(polish::k_batch_adjoint, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
+    OQ_LAUNCH(kern, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
     if (!where)
       for (int j = 0; j < 7; j++) if (host[j]) HIP_CHECK(hipMemcpyAsync(host[j], dev[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -611,7 +642,8 @@ c_int batch_jvp(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k,
       if (!select_rows(*b, rows, k, s)) return 1;
       if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
     }
-    polish_check_fits(P);
+    const bool large = b->large_factor && b->dp.large;
+    polish_check_fits(P, large);
     const int launch = subset ? (int)k : b->count;
     const size_t cnt = (size_t)launch, nd = (size_t)ndir, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
     if (!lm) { tl = tu = nullptr; ty_out = act_out = nullptr; }
@@ -639,10 +671,12 @@ c_int batch_jvp(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k,
     a.tx = dev[0]; a.ty = dev[1]; a.act = dev[2]; a.status = dev[3];
     a.ndir = (int)ndir; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
     a.sel = subset ? b->sel.get() : nullptr;
-    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF);
-    HIP_CHECK(hipFuncSetAttribute((const void *)polish::k_batch_jvp, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, large);
+    if (large) a.scratch = large_factor_scratch(b->dp, launch, s);
+    auto *const kern = large ? polish::k_batch_jvp<true> : polish::k_batch_jvp<false>;
+    HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
     g_batch_jvp_launches++;
-    OQ_LAUNCH(polish::k_batch_jvp, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
+    OQ_LAUNCH(kern, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
     if (!where)
       for (int j = 0; j < 4; j++) if (host[j]) HIP_CHECK(hipMemcpyAsync(host[j], dev[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -675,6 +709,28 @@ c_int osqp_amd_batch_large_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int 
     if (out) { out[0] = (c_int)lp.lds_bytes; out[1] = (c_int)lp.scratch_bytes; out[2] = lp.tiles_per_wave; }
     return 0;
   } OQ_BATCH_CATCH
+}
+c_int osqp_amd_batch_large_factor_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out) {
+  try {
+    const LargeFactorPlan lp = large_factor_plan(n, m, nnzA, nnzF);
+    if (out) { out[0] = (c_int)lp.lds_bytes; out[1] = (c_int)lp.scratch_bytes; out[2] = lp.nb; }
+    return 0;
+  } OQ_BATCH_CATCH
+}
+// The switch of a handle with n > 128: host state that the next polish / adjoint / JVP launch reads; nothing is launched,
+// nothing of the handle changes.  Switching off while settings.polish is 1 would leave a handle whose next resolve refuses: the
+// polish setting goes off with it.
+c_int osqp_amd_batch_large_factor(osqp_amd_batch *handle, c_int on) {
+  BatchPlan *b = resident_plan(handle);
+  if (!b) return -1;
+  if (!b->dp.large) {
+    set_last_error("osqp_amd_batch_large_factor is for handles with 128 < n <= 256 (n = " + std::to_string(b->n) + " keeps its factor in LDS)");
+    return -1;
+  }
+  const c_int before = b->large_factor ? 1 : 0;
+  b->large_factor = on != 0;
+  if (!b->large_factor) b->st.polish = 0;
+  return before;
 }
 c_int osqp_amd_batch_polish_launches(void) { return g_batch_polish_launches; }
 c_int osqp_amd_batch_adjoint_launches(void) { return g_batch_adjoint_launches; }

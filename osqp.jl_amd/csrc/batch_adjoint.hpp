@@ -43,6 +43,7 @@ struct AdjointArgs {
   // "of the handle" above is addressed with the instance, what is "of the call" with the position (row c * k + p of a
   // cotangent-major array).  nullptr: the identity
   const int *sel = nullptr;
+  double *scratch = nullptr;  // LARGE (batch_polish.hpp): n x n doubles per launch position, the handle's solve scratch
 };
 
 // the rows of the call (at position pos of the `count` launched) of an instance that is not differentiated: zeros in every
@@ -62,6 +63,7 @@ __device__ __forceinline__ void adjoint_zero_rows(const Pattern &P, const Adjoin
   if (a.act) for (int i = tid; i < m; i += PT) a.act[(size_t)pos * m + i] = 0.0;
 }
 
+template <bool LARGE>
 __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layout L, AdjointArgs a) {
   const int pos = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
   if (pos >= count) return;
@@ -71,7 +73,8 @@ __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layo
     if (tid == 0 && a.status) a.status[pos] = 0.0;
     return;
   }
-  const Slots S = make_slots(L);
+  Slots S = make_slots(L);
+  if constexpr (LARGE) S.G = a.scratch + (size_t)pos * n * n;
   ldouble *const q = S.q, *const x = S.x, *const xc = S.col, *const l = S.l, *const y = S.y, *const ry = S.ry, *const z = S.z, *const act = S.act;
   const double *const rec = a.rec + (size_t)inst * a.rec_stride;
   const double *const D = rec + rec_D(n, m), *const E = rec + rec_E(n, m);
@@ -90,8 +93,7 @@ __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layo
     y[i] = 0.0;  // the inactive rows stay zero through every cotangent
     z[i] = cinv * e * yi;
   }
-  assemble_M(P, S, delta);
-  if (!cholesky(n, S.M, S.rdg, S.col)) {
+  if (!assemble_and_factor<LARGE>(P, S, delta)) {
     adjoint_zero_rows(P, a, count, pos);
     if (tid == 0 && a.status) a.status[pos] = -1.0;
     return;
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(PT) void k_batch_adjoint(Pattern P, int count, Layo
       l[i] = g; ry[i] = g;
     }
     __syncthreads();  // kkt_step's first loop reads the ry of other threads' rows (and xc is complete for the output stage)
-    for (int it = 0; it <= a.refine; it++) kkt_step<false>(P, S, it, delta);
+    for (int it = 0; it <= a.refine; it++) kkt_step<false, LARGE>(P, S, it, delta);
 
     // ---- back to the caller's units: x <- r_x = D r~_x, ry <- r_y = E s / c (y is zero on the inactive rows) ----
     for (int j = tid; j < n; j += PT) x[j] = D[j] * x[j];

@@ -38,6 +38,7 @@ struct JvpArgs {
   // "of the handle" above is addressed with the instance, what is "of the call" with the position (row d * k + p of a
   // direction-major array).  nullptr: the identity
   const int *sel = nullptr;
+  double *scratch = nullptr;  // LARGE (batch_polish.hpp): n x n doubles per launch position, the handle's solve scratch
 };
 
 // the rows of the call (at position pos of the `count` launched) of an instance that is not differentiated: zeros in every
@@ -52,6 +53,7 @@ __device__ __forceinline__ void jvp_zero_rows(const Pattern &P, const JvpArgs &a
   if (a.act) for (int i = tid; i < m; i += PT) a.act[(size_t)pos * m + i] = 0.0;
 }
 
+template <bool LARGE>
 __global__ __launch_bounds__(PT) void k_batch_jvp(Pattern P, int count, Layout L, JvpArgs a) {
   const int pos = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
   if (pos >= count) return;
@@ -61,7 +63,8 @@ __global__ __launch_bounds__(PT) void k_batch_jvp(Pattern P, int count, Layout L
     if (tid == 0 && a.status) a.status[pos] = 0.0;
     return;
   }
-  const Slots S = make_slots(L);
+  Slots S = make_slots(L);
+  if constexpr (LARGE) S.G = a.scratch + (size_t)pos * n * n;
   ldouble *const q = S.q, *const x = S.x, *const xc = S.col, *const l = S.l, *const y = S.y, *const ry = S.ry, *const z = S.z, *const act = S.act;
   const double *const rec = a.rec + (size_t)inst * a.rec_stride;
   const double *const D = rec + rec_D(n, m), *const E = rec + rec_E(n, m);
@@ -78,8 +81,7 @@ __global__ __launch_bounds__(PT) void k_batch_jvp(Pattern P, int count, Layout L
     y[i] = 0.0;  // the inactive rows stay zero through every direction
     z[i] = cinv * e * yi;
   }
-  assemble_M(P, S, delta);
-  if (!cholesky(n, S.M, S.rdg, S.col)) {
+  if (!assemble_and_factor<LARGE>(P, S, delta)) {
     jvp_zero_rows(P, a, count, pos);
     if (tid == 0 && a.status) a.status[pos] = -1.0;
     return;
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(PT) void k_batch_jvp(Pattern P, int count, Layout L
       l[i] = g; ry[i] = g;
     }
     __syncthreads();
-    for (int it = 0; it <= a.refine; it++) kkt_step<false>(P, S, it, delta);
+    for (int it = 0; it <= a.refine; it++) kkt_step<false, LARGE>(P, S, it, delta);
 
     // ---- back to the caller's units: tx = D x~, ty = E s / c (y is zero on the inactive rows) ----
     if (a.tx) for (int j = tid; j < n; j += PT) a.tx[row * n + j] = D[j] * x[j];

@@ -17,8 +17,14 @@
 // consecutive words), the scaled values of A and of the full P, 1 / pivot [n], the pivot column [n], q, x, t (right-hand side
 // / correction) [n each], l, u, y, r_y, z, act [m each], and a small block for reductions.  Nothing of an instance touches
 // global scratch.  tests/batch_polish_ref.py is the numpy model of this file.
+//
+// LARGE (a template argument of the three kernels and of kkt_step; handles with 128 < n <= 256 and osqp_amd_batch_large_factor
+// on): M and its factor live in the n x n block of global scratch of the launch position instead
+// (batch_large_factor.hpp: lf::assemble, lf::cholesky, lf::solve in place of assemble_M, cholesky, factor_solve), and the slot
+// of M in the layout holds that file's panel.  Everything else is this file's code, instantiated twice.
 #pragma once
 #include "batch_common.hpp"
+#include "batch_large_factor.hpp"
 
 namespace oq {
 namespace {
@@ -26,13 +32,14 @@ namespace polish {
 
 constexpr int PT = 256;  // threads per workgroup
 constexpr int PW = PT / 64;
+static_assert(PT == lf::LT, "batch_large_factor.hpp deals its rows to the threads of these kernels");
 
 struct Layout { int M, Av, Pv, rdg, col, q, x, t, l, u, y, ry, z, act, red, total; };  // offsets in doubles; total in bytes
-inline Layout make_layout(int n, int m, int nnzA, int nnzF) {
+inline Layout make_layout(int n, int m, int nnzA, int nnzF, bool large = false) {  // large: the panel of lf:: in the slot of M
   Layout L;
   int o = 0;
   auto take = [&o](int k) { const int at = o; o += (k + 1) & ~1; return at; };
-  L.M = take(n * (n + 1) / 2); L.Av = take(nnzA); L.Pv = take(nnzF);
+  L.M = take(large ? lf::lds_doubles(n) : n * (n + 1) / 2); L.Av = take(nnzA); L.Pv = take(nnzF);
   L.rdg = take(n); L.col = take(n); L.q = take(n); L.x = take(n); L.t = take(n);
   L.l = take(m); L.u = take(m); L.y = take(m); L.ry = take(m); L.z = take(m); L.act = take(m);
   L.red = take(4 * PW);
@@ -48,6 +55,7 @@ struct Args {
   int refine, unscaled;  // unscaled: scaling on and scaled_termination off (residuals in the caller's units)
   double delta;
   const int *sel;  // the instance of each workgroup (nullptr: its own number); the x / y / info rows are the workgroups'
+  double *scratch = nullptr;  // LARGE: n x n doubles per launch position (the handle's solve scratch)
 };
 
 __device__ __forceinline__ int tri(int i, int j) { return ((i * (i + 1)) >> 1) + j; }  // i >= j
@@ -91,11 +99,11 @@ __device__ __forceinline__ void factor_solve(int n, const ldouble *M, const ldou
 
 // ---- what k_batch_polish and k_batch_adjoint (batch_adjoint.hpp) share: the views of the LDS slots, the scaled matrices, the
 // classification of a row, the assembly of M, its factorisation and one solve / refinement step ----
-struct Slots { ldouble *M, *Av, *Pv, *rdg, *col, *q, *x, *t, *l, *u, *y, *ry, *z, *act, *red; };
+struct Slots { ldouble *M, *Av, *Pv, *rdg, *col, *q, *x, *t, *l, *u, *y, *ry, *z, *act, *red; double *G; };  // G: LARGE only
 __device__ __forceinline__ Slots make_slots(const Layout &L) {
   ldouble *const lds = (ldouble *)lds_raw;
   return Slots{lds + L.M, lds + L.Av, lds + L.Pv, lds + L.rdg, lds + L.col, lds + L.q, lds + L.x, lds + L.t,
-               lds + L.l, lds + L.u, lds + L.y, lds + L.ry, lds + L.z, lds + L.act, lds + L.red};
+               lds + L.l, lds + L.u, lds + L.y, lds + L.ry, lds + L.z, lds + L.act, lds + L.red, nullptr};
 }
 
 // column j of the scaled A and row j of the scaled full P (as the solve prologue forms them) into Av / Pv
@@ -155,11 +163,22 @@ __device__ __forceinline__ bool cholesky(int n, ldouble *M, ldouble *rdg, ldoubl
   }
   return true;
 }
+// M and its factor where the instantiation keeps them: false as cholesky
+template <bool LARGE>
+__device__ __forceinline__ bool assemble_and_factor(const Pattern &P, const Slots &S, double delta) {
+  if constexpr (LARGE) {
+    lf::assemble(P, S.Av, S.Pv, S.act, delta, S.G);
+    return lf::cholesky(P.n, S.G, lf::make_work(S.M, P.n));
+  } else {
+    assemble_M(P, S, delta);
+    return cholesky(P.n, S.M, S.rdg, S.col);
+  }
+}
 
 // One solve with the factor: step `it` = 0 solves [P + delta I, Aa'; Aa, -delta I] [x; y] = [g; b] from the ry the caller
 // staged (b on the active rows, zero elsewhere); a step it > 0 refines x, y against the unregularised [P, Aa'; Aa, 0].
 // POLISH: g = -q and b = l on the lower rows, u on the upper ones; otherwise (the adjoint) g = q and b = l on every active row.
-template <bool POLISH>
+template <bool POLISH, bool LARGE>
 __device__ __forceinline__ void kkt_step(const Pattern &P, const Slots &S, int it, double delta) {
   const int tid = threadIdx.x, n = P.n, m = P.m;
   ldouble *const Av = S.Av, *const Pv = S.Pv, *const x = S.x, *const y = S.y, *const t = S.t, *const ry = S.ry, *const act = S.act;
@@ -184,7 +203,8 @@ __device__ __forceinline__ void kkt_step(const Pattern &P, const Slots &S, int i
     t[j] = rx + ar / delta;
   }
   __syncthreads();
-  factor_solve(n, S.M, S.rdg, t);
+  if constexpr (LARGE) lf::solve(n, S.G, lf::make_work(S.M, n), t);
+  else factor_solve(n, S.M, S.rdg, t);
   __syncthreads();
   for (int i = tid; i < m; i += PT) {  // d_y = (Aa d_x - r_y) / delta
     if (act[i] == 0.0) continue;
@@ -197,6 +217,7 @@ __device__ __forceinline__ void kkt_step(const Pattern &P, const Slots &S, int i
   __syncthreads();
 }
 
+template <bool LARGE>
 __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layout L, Args a) {
   const int pos = blockIdx.x, tid = threadIdx.x, n = P.n, m = P.m;
   if (pos >= count) return;
@@ -206,7 +227,8 @@ __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layou
     if (tid == 0) a.status[inst] = 0.0;
     return;
   }
-  const Slots S = make_slots(L);
+  Slots S = make_slots(L);
+  if constexpr (LARGE) S.G = a.scratch + (size_t)pos * n * n;
   ldouble *const Av = S.Av, *const Pv = S.Pv, *const q = S.q, *const x = S.x, *const l = S.l, *const u = S.u;
   ldouble *const y = S.y, *const ry = S.ry, *const z = S.z, *const act = S.act, *const red = S.red;
   double *const rec = a.rec + (size_t)inst * a.rec_stride;
@@ -231,14 +253,13 @@ __global__ __launch_bounds__(PT) void k_batch_polish(Pattern P, int count, Layou
     ry[i] = on < 0.0 ? li : (on > 0.0 ? ui : 0.0);  // the right-hand side of the first solve: [-q; l_low; u_upp]
     y[i] = 0.0;
   }
-  assemble_M(P, S, delta);
-  if (!cholesky(n, S.M, S.rdg, S.col)) {  // as a failed direct_init in the oracle
+  if (!assemble_and_factor<LARGE>(P, S, delta)) {  // as a failed direct_init in the oracle
     if (tid == 0) a.status[inst] = -1.0;
     return;
   }
 
   // ---- solve with [-q; b_act], then `refine` steps against the unregularised [P, Aa'; Aa, 0] ----
-  for (int it = 0; it <= a.refine; it++) kkt_step<true>(P, S, it, delta);
+  for (int it = 0; it <= a.refine; it++) kkt_step<true, LARGE>(P, S, it, delta);
 
   // ---- z = A x, (z, y) onto the normal cone of [l, u]; residuals and objective as the termination check defines them ----
   double pri = 0.0, dua = 0.0, obj = 0.0;

@@ -821,6 +821,34 @@ function batch_large_plan(n::Integer, m::Integer, nnzA::Integer, nnzF::Integer)
     return (lds_bytes = Int(out[1]), scratch_bytes = Int(out[2]), tiles_per_wave = Int(out[3]))
 end
 
+"""
+    batch_large_factor!(b, on = true) -> Bool
+
+Polish, adjoint and JVP on a resident batch with 128 < n <= 256 (osqp_amd_batch_large_factor, DESIGN.md section 13.2): a switch
+per handle, off after setup; returns the previous value.  While it is on the three kernels keep the factor of M in the
+instance's block of global scratch.  A batch with n <= 128 raises.
+"""
+function batch_large_factor!(b::ResidentBatch, on::Bool = true)
+    before = ccall((:osqp_amd_batch_large_factor, lib), Cc_int, (Ptr{Cvoid}, Cc_int), b.handle, on ? 1 : 0)
+    before >= 0 || error("Error in batch_large_factor!: $(last_error())")
+    return before != 0
+end
+
+"""
+    batch_large_factor_plan(n, m, nnzA, nnzF) -> (lds_bytes, scratch_bytes, nb)
+
+What those kernels need for a shape (osqp_amd_batch_large_factor_plan; host only): nnzF counts the stored entries of the full
+symmetric P.  A shape they do not take raises with the library's reason.
+"""
+function batch_large_factor_plan(n::Integer, m::Integer, nnzA::Integer, nnzF::Integer)
+    out = zeros(Cc_int, 3)
+    GC.@preserve out begin
+        flag = ccall((:osqp_amd_batch_large_factor_plan, lib), Cc_int, (Cc_int, Cc_int, Cc_int, Cc_int, Ptr{Cc_int}), n, m, nnzA, nnzF, pointer(out))
+    end
+    flag == 0 || error("Error in batched plan: $(last_error())")
+    return (lds_bytes = Int(out[1]), scratch_bytes = Int(out[2]), nb = Int(out[3]))
+end
+
 "[count]: the checks of every instance's own last `batch_solve!` that the gap test alone refused (osqp_amd_batch_gap_refusals); zeros while the rule is off."
 function batch_gap_refusals(b::ResidentBatch)
     out = Vector{Float64}(undef, b.count)

@@ -192,13 +192,17 @@ class BatchQPLayer(torch.nn.Module):
     duality_gap_check=True calls `rb.duality_gap_check()` once here: every forward then also needs the duality gap below its
     bound before an instance ends Solved, and the backward differentiates at that point.
     large=True states that `rb` was built with `ResidentBatch(..., large=True)` for 128 < n <= 256 (it is also set when rb.n >
-    128): such a layer is FORWARD ONLY -- the adjoint and JVP kernels keep M in LDS, and `backward` / `jacobian` raise the
-    library's refusal ("instance too large to polish ...")."""
+    128): by default such a layer is forward only -- the adjoint and JVP kernels keep M in LDS, and `backward` / `jacobian`
+    raise the library's refusal ("instance too large to polish ...").  large_factor=True calls `rb.large_factor()` once here:
+    backward and forward mode then run the forms of those kernels that keep the factor in global scratch (DESIGN.md section
+    13.2)."""
 
-    def __init__(self, rb, duality_gap_check=False, large=False):
+    def __init__(self, rb, duality_gap_check=False, large=False, large_factor=False):
         super().__init__()
         self.rb, self.info = rb, None
         self.large = bool(large) or rb.n > 128
+        if large_factor:
+            rb.large_factor(True)
         if duality_gap_check:
             rb.duality_gap_check(True)
 

@@ -250,6 +250,8 @@ EXT_SYMBOLS = {
     # the opt-in path for 128 < n <= 256: the switch (returns the previous value) and the host-only plan of a shape
     "osqp_amd_batch_large": (c_int, [c_int]),
     "osqp_amd_batch_large_plan": (c_int, [c_int, c_int, c_int, c_int, C.c_void_p]),
+    "osqp_amd_batch_large_factor": (c_int, [C.c_void_p, c_int]),
+    "osqp_amd_batch_large_factor_plan": (c_int, [c_int, c_int, c_int, c_int, C.c_void_p]),
     "osqp_amd_batch_adjoint": (c_int, [C.c_void_p] + [C.c_void_p] * 9 + [c_int]),
     "osqp_amd_batch_polish_launches": (c_int, []),
     "osqp_amd_batch_adjoint_launches": (c_int, []),
