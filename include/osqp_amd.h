@@ -996,6 +996,54 @@ c_int osqp_amd_device_form_calls(const OSQPWorkspace *work, c_float *out, c_int 
 c_int osqp_amd_duality_gap_check(OSQPWorkspace *work, c_int on);
 c_int osqp_amd_duality(OSQPWorkspace *work, c_float *out, c_int count);
 
+/* ---- The shared batch: ONE MODEL, MANY RIGHT-HAND SIDES on a shared KKT inverse --------------------
+ * A shared batch is one model (P, A, base vectors q0, l0, u0, settings) and `count` instances that differ in q, l and u
+ * only: MPC of one plant from many states, scenario trees, a QP layer with fixed matrices.  Instance i is, by definition,
+ *   osqp_setup(P, q0, A, l0, u0, settings); osqp_update_lin_cost(q_i); osqp_update_bounds(l_i, u_i); osqp_solve
+ * on a fresh model, and later updates and re-solves act on that same model.  Three rules make one inverse serve all:
+ *   scaling  D, E and c come from setup (P, A, q0) and are not recomputed on vector updates, as in libosqp;
+ *   rho      settings->adaptive_rho must be 0 (setup returns 2 with a message otherwise); rho is settings->rho and changes
+ *            through update_setting("rho") at the cost of one re-factorisation;
+ *   kinds    every row of every instance must have the kind it has under (l0, u0) on the SCALED bounds: loose where
+ *            l < -OSQP_INFTY * 1e-4 and u > OSQP_INFTY * 1e-4, an equality where u - l < 1e-4, an inequality otherwise (the
+ *            rule osqp_update_bounds re-derives rho by).  An update that breaks this, or has l > u, is refused before
+ *            anything is written; the message names the first offending instance and row.
+ * plan()     host only: out[0] = T, the instances per workgroup, chosen from the shape alone (never from count); out[1] the LDS
+ *            bytes of a workgroup; out[2] the bytes of the model block (scaling, scaled values, the padded inverse); out[3] the
+ *            bytes of device state per instance.  nnzF counts the stored entries of the full symmetric P.  n <= 256; a shape
+ *            whose layout exceeds 160 KB of LDS is refused ("needs N bytes of LDS").
+ * setup()    one scaling and one inversion (k_shared_factor, one workgroup); every instance then holds (q0, l0, u0) and a zero
+ *            iterate.  A reduced KKT matrix that is not positive definite ends setup with the OSQP_NON_CVX message.
+ * update_lin_cost() / update_bounds()  q_all [count x n]; l_all, u_all [count x m], both given.
+ * warm_start()  x_all [count x n] and / or y_all [count x m] in the caller's units, NULL = zero; sets warm_start = 1.
+ * resolve()  ONE launch of k_batch_solve_shared: T instances per workgroup, the dense step on the fp64 matrix cores.  x_out
+ *            [count x n], y_out [count x m], info_out [count x 6] (iter, status_val, pri_res, dua_res, obj_val, 0): the columns
+ *            of the resident batch.  An instance stops at ITS OWN check and reports its own iteration count; its bits do not
+ *            depend on count, on its position or on the other instances.  Instances without a solution get NaN rows and
+ *            restart from zero.  With warm_start = 1 (the default) a resolve starts from the iterate the last one left.
+ *            osqp_amd_batch_last_kernel reports -3 afterwards; osqp_amd_shared_batch_launches counts these launches.
+ * update_setting()  max_iter, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, alpha, check_termination, scaled_termination, rho
+ *            (one k_shared_factor launch; the carried iterates stay, as with osqp_update_rho).  Any other name is refused.
+ * device_bytes()  the device memory the handle holds, staging included.
+ * where: 0 host pointers, 1 device pointers on the handle's device.  Every call blocks until done; 0 = success, otherwise
+ * osqp_amd_last_error has the reason.  The handle has no polish, derivatives, certificates or `rows` entries, and its
+ * matrices cannot be updated: a new model is a new handle. */
+typedef struct osqp_amd_shared_batch osqp_amd_shared_batch;
+c_int osqp_amd_shared_batch_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out /* [4] */);
+c_int osqp_amd_shared_batch_setup(osqp_amd_shared_batch **out, c_int count, c_int n, c_int m,
+                                  const c_int *Pp, const c_int *Pi, const c_float *Px,
+                                  const c_int *Ap, const c_int *Ai, const c_float *Ax,
+                                  const c_float *q0, const c_float *l0, const c_float *u0,
+                                  const OSQPSettings *settings, c_int device);
+c_int osqp_amd_shared_batch_update_lin_cost(osqp_amd_shared_batch *batch, const c_float *q_all, c_int where);
+c_int osqp_amd_shared_batch_update_bounds(osqp_amd_shared_batch *batch, const c_float *l_all, const c_float *u_all, c_int where);
+c_int osqp_amd_shared_batch_warm_start(osqp_amd_shared_batch *batch, const c_float *x_all, const c_float *y_all, c_int where);
+c_int osqp_amd_shared_batch_resolve(osqp_amd_shared_batch *batch, c_float *x_out, c_float *y_out, c_float *info_out, c_int where);
+c_int osqp_amd_shared_batch_update_setting(osqp_amd_shared_batch *batch, const char *name, c_float value);
+c_int osqp_amd_shared_batch_device_bytes(osqp_amd_shared_batch *batch);
+c_int osqp_amd_shared_batch_launches(void);
+c_int osqp_amd_shared_batch_destroy(osqp_amd_shared_batch *batch);
+
 /* Select the HIP device for workspaces created afterwards by this process
  * (one process per GPU: pass LOCAL_RANK). */
 c_int osqp_amd_set_device(c_int device);

@@ -932,5 +932,144 @@ class ResidentBatch:
             pass
 
 
+def _pattern_sizes(P, A):
+    import scipy.sparse as sp
+
+    P = sp.csc_matrix(sp.triu(P)); P.sort_indices()
+    A = sp.csc_matrix(A); A.sort_indices()
+    ndiag = int(np.count_nonzero(P.tocoo().row == P.tocoo().col))
+    return P, A, A.shape[1], A.shape[0], 2 * P.nnz - ndiag
+
+
+def shared_plan(lib, P, A):
+    """What a shared batch needs for the pattern of P (upper triangle) and A (osqp_amd_shared_batch_plan; host only, no device
+    is touched): a dict with `T`, the instances per workgroup -- chosen from the shape alone, never from the number of
+    instances --, `lds_bytes` per workgroup, `model_bytes` (scaling, scaled values and the padded inverse, once per handle) and
+    `instance_bytes` of device state per instance.  A shape it does not take raises OSQPError with the library's reason."""
+    P, A, n, m, nnzF = _pattern_sizes(P, A)
+    out = np.zeros(4, dtype=np.int64)
+    if lib.osqp_amd_shared_batch_plan(n, m, A.nnz, nnzF, out.ctypes.data) != 0:
+        raise OSQPError("Error in batched plan: " + lib.osqp_amd_last_error().decode())
+    return {"T": int(out[0]), "lds_bytes": int(out[1]), "model_bytes": int(out[2]), "instance_bytes": int(out[3])}
+
+
+def shared_launches(lib):
+    """Launches of the shared solve kernel by this process so far (osqp_amd_shared_batch_launches): one per `SharedBatch.solve`."""
+    return int(lib.osqp_amd_shared_batch_launches())
+
+
+class SharedBatch:
+    """ONE model and `count` right-hand sides on a shared KKT inverse (osqp_amd_shared_batch_setup).
+    Instance i is `setup(P, q0, A, l0, u0)`, `update(q=q[i], l=l[i], u=u[i])`, `solve()` on a fresh model: scaling comes from the
+    base data, rho is fixed (`adaptive_rho` is set to 0 here unless the caller passes it; anything else is refused by the
+    library) and every row of every instance must keep the kind -- loose, equality, inequality -- it has under (l0, u0).
+    After setup every instance holds (q0, l0, u0).  Arrays of `update` / `warm_start` and the `out` of `solve` are numpy arrays
+    or device arrays (`DeviceArray`, torch tensors), as for `ResidentBatch`; there is no `rows=`, polish or derivative here."""
+
+    SETTINGS = ("max_iter", "eps_abs", "eps_rel", "eps_prim_inf", "eps_dual_inf", "alpha", "check_termination",
+                "scaled_termination", "rho")
+
+    def __init__(self, lib, P, A, q0, l0, u0, count, device=0, **settings):
+        P, A, self.n, self.m, _ = _pattern_sizes(P, A)
+        if P.shape != (self.n, self.n):
+            raise ValueError(f"P: expected shape {(self.n, self.n)}, got {P.shape}")
+        self.count = int(count)
+        if self.count <= 0:
+            raise ValueError("count: the batch is empty")
+        q0 = _batch_array("q0", q0, (self.n,))[0]
+        l0 = _batch_array("l0", l0, (self.m,))[0]
+        u0 = _batch_array("u0", u0, (self.m,))[0]
+        settings.setdefault("adaptive_rho", 0)
+        stgs = make_settings(lib, settings)
+        self.lib, self.device, self.handle = lib, int(device), C.c_void_p()
+        Pp, Pi = np.ascontiguousarray(P.indptr, dtype=np.int64), np.ascontiguousarray(P.indices, dtype=np.int64)
+        Ap, Ai = np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int64)
+        Px, Ax = _as_f64(P.data), _as_f64(A.data)
+        rc = lib.osqp_amd_shared_batch_setup(C.byref(self.handle), self.count, self.n, self.m, _iptr(Pp), _iptr(Pi), _fptr(Px), _iptr(Ap),
+                                             _iptr(Ai), _fptr(Ax), _fptr(q0), _fptr(l0), _fptr(u0), C.byref(stgs), self.device)
+        if rc != 0:
+            self.handle = C.c_void_p()
+            raise OSQPError("Error in shared batch setup: " + lib.osqp_amd_last_error().decode())
+
+    def _call(self, what, rc):
+        if rc != 0:
+            raise OSQPError(f"Error in shared batch {what}: " + self.lib.osqp_amd_last_error().decode())
+
+    def update(self, q=None, l=None, u=None):
+        """New q [count x n] and / or bounds l, u [count x m] (both, in one form).  Bounds with l > u, or that change the kind
+        of a row of an instance, raise -- naming the first offending instance and row -- and leave the handle as it was."""
+        qa = None if q is None else _batch_array("q", q, (self.count, self.n))
+        if (l is None) != (u is None):
+            raise ValueError("l and u: a shared batch updates both bounds in one call")
+        ba = None
+        if l is not None:
+            ba = (_batch_array("l", l, (self.count, self.m)), _batch_array("u", u, (self.count, self.m)))
+            if ba[0][2] != ba[1][2]:
+                raise ValueError("l and u must both be host arrays or both device arrays")
+        if qa is not None:
+            self._call("update", self.lib.osqp_amd_shared_batch_update_lin_cost(self.handle, qa[1], qa[2]))
+        if ba is not None:
+            self._call("update", self.lib.osqp_amd_shared_batch_update_bounds(self.handle, ba[0][1], ba[1][1], ba[0][2]))
+
+    def warm_start(self, x=None, y=None):
+        """Start the next solve from x [count x n] and / or y [count x m] (caller's units); a missing one is zero."""
+        got = [None if v is None else _batch_array(nm, v, (self.count, k)) for nm, v, k in (("x", x, self.n), ("y", y, self.m))]
+        forms = {g[2] for g in got if g is not None}
+        if len(forms) > 1:
+            raise ValueError("x and y must both be host arrays or both device arrays")
+        if forms:
+            self._call("warm start", self.lib.osqp_amd_shared_batch_warm_start(self.handle, None if got[0] is None else got[0][1],
+                                                                               None if got[1] is None else got[1][1], forms.pop()))
+
+    def solve(self, out=None):
+        """Solve every instance in one launch -> (x [count x n], y [count x m], info [count x 6]: iter, status_val, pri_res,
+        dua_res, obj_val, 0).  out=None: numpy arrays; out=(x, y, info) of device arrays: written in place and returned."""
+        k = self.count
+        if out is None:
+            x, y, info = np.empty((k, self.n)), np.empty((k, self.m)), np.empty((k, 6))
+            self._call("solve", self.lib.osqp_amd_shared_batch_resolve(self.handle, x.ctypes.data, y.ctypes.data, info.ctypes.data, 0))
+            return x, y, info
+        if len(out) != 3:
+            raise ValueError("out: expected (x, y, info)")
+        ptrs = []
+        for name, a, cols in (("out[0]", out[0], self.n), ("out[1]", out[1], self.m), ("out[2]", out[2], 6)):
+            if a is None and cols == 0:
+                ptrs.append(None)
+                continue
+            if not hasattr(a, "data_ptr"):
+                raise ValueError(f"{name}: expected a device array (DeviceArray, torch tensor); omit `out` for numpy results")
+            ptrs.append(_batch_array(name, a, (k, cols))[1])
+        self._call("solve", self.lib.osqp_amd_shared_batch_resolve(self.handle, ptrs[0], ptrs[1], ptrs[2], 1))
+        return out
+
+    def update_settings(self, **kw):
+        """New values for settings of the following solves (osqp_amd_shared_batch_update_setting): the names of `SETTINGS`.
+        `rho` re-factorises the shared matrix once; the carried iterates stay.  Any other name raises, here or in the library."""
+        for key, value in kw.items():
+            if value is None:
+                continue
+            self._call("settings update", self.lib.osqp_amd_shared_batch_update_setting(self.handle, key.encode(), float(value)))
+
+    def device_bytes(self):
+        return int(self.lib.osqp_amd_shared_batch_device_bytes(self.handle))
+
+    def alloc(self):
+        """Device arrays (x, y, info) for `solve(out=...)`; y is None for a batch without constraints."""
+        return (DeviceArray(self.lib, self.count, self.n, self.device),
+                DeviceArray(self.lib, self.count, self.m, self.device) if self.m else None,
+                DeviceArray(self.lib, self.count, 6, self.device))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.osqp_amd_shared_batch_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def status_names(info):
     return [status_map[int(v)] for v in info[:, 1]]

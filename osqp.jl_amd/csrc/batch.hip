@@ -27,6 +27,9 @@
 //                     ADMM launch of osqp_amd_batch_resolve: normalises the directions that launch left in the records (RES_CERT);
 //   batch_gap.hpp     k_batch_gap -- primal objective, dual objective and duality gap of the resident batch, a launch of its own on
 //                     request (osqp_amd_batch_duality); reads the records, the raw data and the pattern, writes three doubles;
+//   batch_shared.hpp  the shared batch (osqp_amd_shared_batch_*): one model and many right-hand sides on ONE inverse --
+//                     k_shared_factor (setup), k_batch_solve_shared (T instances per workgroup, the dense step on the fp64
+//                     matrix cores) and their small kernels; a handle type of its own (SharedBatch below);
 //   this file         the small kernels (warm start, rho fill, bound check, the row scatter and gather of a selection, MPC generator), the
 //                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
@@ -49,6 +52,7 @@
 #include "batch_sched.hpp"
 #include "batch_solve.hpp"
 #include "batch_large.hpp"
+#include "batch_shared.hpp"
 #include "rng.hpp"
 
 namespace oq {
@@ -565,6 +569,77 @@ void set_polish(BatchPlan &b, c_int polish_new, c_int refine_new) {
 #define OQ_BATCH_CATCH                                                                          \
   catch (const Error &er) { set_last_error(er.what()); return er.code ? er.code : 6; }         \
   catch (const std::exception &ex) { set_last_error(ex.what()); return 6; }
+
+// ---- the shared batch (batch_shared.hpp) ---------------------------------------------------------------
+int g_shared_launches = 0;  // launches of k_batch_solve_shared by this process (osqp_amd_shared_batch_launches)
+// What a shape needs, from the shape alone: T never depends on the number of instances.
+struct SharedPlan { int T; size_t lds_bytes, model_bytes, inst_bytes, factor_lds; };
+SharedPlan shared_plan(long long n, long long m, long long nnzA, long long nnzF) {
+  if (n <= 0 || n > shared::kMaxN || m < 0 || m > 65535 || nnzA < 0 || nnzA > 65535 || nnzF < 0 || nnzF > 65535)
+    throw Error(1, "a shared batch supports 1 <= n <= 256 and fewer than 65536 rows / non-zeros (n = " + std::to_string(n) + ")");
+  const size_t fl = large_lds_bytes((int)n, (int)m, (int)nnzA, (int)nnzF);  // k_shared_factor: the layout of k_batch_solve_large
+  if (fl > 160 * 1024) throw Error(1, "instance too large for the LDS-resident batched path (needs " + std::to_string(fl) + " bytes of LDS)");
+  size_t bytes = 0;
+  for (int T : shared::kTileSizes) {
+    bytes = shared::lds_bytes((int)n, (int)m, (int)nnzA, T);
+    if (bytes <= 160 * 1024)
+      return SharedPlan{T, bytes, shared::model_layout((int)n, (int)m, (int)nnzA, (int)nnzF).total * sizeof(double),
+                        shared::tile_layout((int)n, (int)m, 1).total * sizeof(double), fl};
+  }
+  throw Error(1, "instance too large for the LDS-resident batched path (needs " + std::to_string(bytes) + " bytes of LDS)");
+}
+struct SharedBatch {
+  int device = 0, count = 0, n = 0, m = 0, nnzA = 0, nnzP = 0, nnzF = 0, ntiles = 0;
+  SharedPlan plan{};
+  OSQPSettings st;
+  DevicePattern dp;
+  shared::ModelLayout ML;
+  shared::TileLayout TL;
+  DevBuf<double> Px, Ax, q0, l0, u0;   // the raw base data: k_shared_factor runs on them again after a rho update
+  DevBuf<double> model, scratch, tiles;
+  DevBuf<double> in_a, in_b, x_out, y_out, info_out;  // staging of host-pointer calls
+  DevBuf<unsigned long long> flag;
+  std::vector<double> hdr;  // c, rho, pd of the model block
+  size_t device_bytes() const {
+    return (Px.n + Ax.n + q0.n + l0.n + u0.n + model.n + scratch.n + tiles.n + in_a.n + in_b.n + x_out.n + y_out.n + info_out.n + 1) * sizeof(double);
+  }
+};
+SharedBatch *shared_handle(osqp_amd_shared_batch *h) {
+  if (!h) { set_last_error("null shared batch handle"); return nullptr; }
+  return (SharedBatch *)h;
+}
+// scaling, row kinds, rho per row and the inverse into the model block; a pivot block that is not positive definite is an Error
+void shared_factor(SharedBatch &b, const OSQPSettings &st, hipStream_t s) {
+  HIP_CHECK(hipFuncSetAttribute((const void *)shared::k_shared_factor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b.plan.factor_lds));
+  OQ_LAUNCH(shared::k_shared_factor, dim3(1), dim3(NT), b.plan.factor_lds, s, b.dp.P, st, b.Px.get(), b.Ax.get(), b.q0.get(), b.l0.get(), b.u0.get(),
+            b.scratch.get(), b.model.get());
+  b.hdr.assign(shared::MB_HDR, 0.0);
+  b.model.download(b.hdr.data(), shared::MB_HDR, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (b.hdr[shared::MB_PD] == 0.0) throw Error(7, "problem non convex: the reduced KKT matrix is not positive definite (OSQP_NON_CVX)");
+}
+// one vector of every instance into the tile records (k_shared_put); stride 0: the same base vector for all
+void shared_put(SharedBatch &b, const double *src, int stride, int len, const double *scale, double mult, int clamp, size_t off, hipStream_t s) {
+  if (!len) return;
+  OQ_LAUNCH(shared::k_shared_put, dim3(blocks_for((int64_t)b.count * len, 256)), dim3(256), 0, s, b.count, len, b.plan.T, src, stride, scale, mult, clamp,
+            b.tiles.get(), off, b.TL.total);
+}
+// the check of new bounds (device pointers) against l <= u and the row kinds of the base: false with the message set
+bool shared_bounds_ok(SharedBatch &b, const double *l, const double *u, hipStream_t s) {
+  unsigned long long word = ~0ull;
+  b.flag.upload(&word, 1, s);
+  OQ_LAUNCH(shared::k_shared_check_bounds, dim3(blocks_for((int64_t)b.count * b.m, 256)), dim3(256), 0, s, b.count, b.m, l, u, b.model.get() + b.ML.E,
+            (const int *)(b.model.get() + b.ML.ctype), b.flag.get());
+  b.flag.download(&word, 1, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (word == ~0ull) return true;
+  const unsigned long long g = word >> 2;
+  const std::string at = "instance " + std::to_string(g / b.m) + ", row " + std::to_string(g % b.m);
+  if ((word & 3) == 1) set_last_error("lower bound greater than upper bound (" + at + ")");
+  else set_last_error("the bounds change the kind of a row (loose / equality / inequality) from the one it has under the base bounds, which the shared "
+                      "inverse was built for (" + at + ")");
+  return false;
+}
 
 // osqp_amd_batch_adjoint, _multi (subset false: every instance, rows / k unused) and osqp_amd_batch_adjoint_rows, _multi_rows
 // (subset true: the k instances of rows; every array of the call is compact, row j for instance rows[j]).  ncot pairs
@@ -1339,6 +1414,180 @@ c_int osqp_amd_batch_gap_refusals_rows(osqp_amd_batch *handle, const c_int *rows
 c_int osqp_amd_batch_destroy(osqp_amd_batch *handle) {
   if (!handle) return 0;
   BatchPlan *b = (BatchPlan *)handle;
+  try { DeviceScope on_device(b->device); delete b; } catch (...) { return 1; }
+  return 0;
+}
+
+// ---- the shared batch: one model, many right-hand sides on one inverse (include/osqp_amd.h) ------------
+c_int osqp_amd_shared_batch_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out) {
+  try {
+    const SharedPlan sp = shared_plan(n, m, nnzA, nnzF);
+    if (out) { out[0] = sp.T; out[1] = (c_int)sp.lds_bytes; out[2] = (c_int)sp.model_bytes; out[3] = (c_int)sp.inst_bytes; }
+    return 0;
+  } OQ_BATCH_CATCH
+}
+c_int osqp_amd_shared_batch_launches(void) { return g_shared_launches; }
+
+c_int osqp_amd_shared_batch_setup(osqp_amd_shared_batch **out, c_int count, c_int n, c_int m, const c_int *Pp, const c_int *Pi, const c_float *Px,
+                                  const c_int *Ap, const c_int *Ai, const c_float *Ax, const c_float *q0, const c_float *l0, const c_float *u0,
+                                  const OSQPSettings *settings, c_int device) {
+  if (!out) { set_last_error("invalid batch data"); return 1; }
+  *out = nullptr;
+  try {
+    if (count <= 0 || count > 16777216) { set_last_error("invalid batch data"); return 1; }
+    if (n > shared::kMaxN) { set_last_error("a shared batch supports 1 <= n <= 256 and fewer than 65536 rows / non-zeros (n = " + std::to_string(n) + ")"); return 1; }
+    {
+      const int before = g_batch_large;  // the data checks of the batched path, for ONE instance and with its n <= 256 cap
+      g_batch_large = 1;
+      const BatchProblem one{1, n, m, Pp, Pi, Px, Ap, Ai, Ax, q0, l0, u0, settings};
+      const c_int bad = validate_batch_data(one, true);
+      g_batch_large = before;
+      if (bad) return bad;
+    }
+    if (settings->adaptive_rho) {
+      set_last_error("adaptive_rho must be 0 for a shared batch: all instances share one inverse of the reduced KKT matrix, which is built for one rho "
+                     "(change it with osqp_amd_shared_batch_update_setting(\"rho\"))");
+      return 2;
+    }
+    const BatchProblem prob{1, n, m, Pp, Pi, Px, Ap, Ai, Ax, q0, l0, u0, settings};
+    const HostPattern hp = host_pattern(prob);
+    std::unique_ptr<SharedBatch> b(new SharedBatch());
+    b->plan = shared_plan(n, m, hp.nnzA, hp.nnzF);
+    DeviceScope on_device((int)device);
+    hipStream_t s = nullptr;
+    b->device = (int)device; b->count = (int)count; b->st = *settings;
+    b->n = (int)n; b->m = (int)m; b->nnzA = hp.nnzA; b->nnzP = hp.nnzP; b->nnzF = hp.nnzF;
+    b->ML = shared::model_layout(b->n, b->m, b->nnzA, b->nnzF); b->TL = shared::tile_layout(b->n, b->m, b->plan.T);
+    b->ntiles = (b->count + b->plan.T - 1) / b->plan.T;
+    b->dp.build(hp, s);
+    b->Px.alloc(b->nnzP); b->Ax.alloc(b->nnzA); b->q0.alloc(n); b->l0.alloc(m); b->u0.alloc(m);
+    b->Px.upload(Px, b->nnzP, s); b->Ax.upload(Ax, b->nnzA, s); b->q0.upload(q0, n, s); b->l0.upload(l0, m, s); b->u0.upload(u0, m, s);
+    b->model.alloc(b->ML.total); b->scratch.alloc((size_t)n * n); b->tiles.alloc((size_t)b->ntiles * b->TL.total); b->flag.alloc(1);
+    const size_t cnt = (size_t)count;
+    b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6);
+    shared_factor(*b, b->st, s);
+    // every instance holds (q0, l0, u0) and a zero iterate
+    OQ_LAUNCH(shared::k_shared_zero, dim3(blocks_for((int64_t)b->tiles.n, 256)), dim3(256), 0, s, b->tiles.n, b->tiles.get());
+    shared_put(*b, b->q0.get(), 0, b->n, b->model.get() + b->ML.D, b->hdr[shared::MB_C], 0, b->TL.q, s);
+    shared_put(*b, b->l0.get(), 0, b->m, b->model.get() + b->ML.E, 1.0, -1, b->TL.l, s);
+    shared_put(*b, b->u0.get(), 0, b->m, b->model.get() + b->ML.E, 1.0, 1, b->TL.u, s);
+    HIP_CHECK(hipDeviceSynchronize());
+    *out = (osqp_amd_shared_batch *)b.release();
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_update_lin_cost(osqp_amd_shared_batch *handle, const c_float *q_all, c_int where) {
+  SharedBatch *b = shared_handle(handle);
+  if (!b) return 1;
+  if (!q_all) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const double *qd = device_ptr(q_all, (size_t)b->count * b->n, where, b->in_a, s);
+    shared_put(*b, qd, b->n, b->n, b->model.get() + b->ML.D, b->hdr[shared::MB_C], 0, b->TL.q, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_update_bounds(osqp_amd_shared_batch *handle, const c_float *l_all, const c_float *u_all, c_int where) {
+  SharedBatch *b = shared_handle(handle);
+  if (!b) return 1;
+  if (b->m == 0) return 0;
+  if (!l_all || !u_all) { set_last_error("a shared batch updates both bounds in one call"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const size_t len = (size_t)b->count * b->m;
+    const double *ld = device_ptr(l_all, len, where, b->in_a, s), *ud = device_ptr(u_all, len, where, b->in_b, s);
+    if (!shared_bounds_ok(*b, ld, ud, s)) return 1;  // before anything of the handle is written
+    shared_put(*b, ld, b->m, b->m, b->model.get() + b->ML.E, 1.0, -1, b->TL.l, s);
+    shared_put(*b, ud, b->m, b->m, b->model.get() + b->ML.E, 1.0, 1, b->TL.u, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_warm_start(osqp_amd_shared_batch *handle, const c_float *x_all, const c_float *y_all, c_int where) {
+  SharedBatch *b = shared_handle(handle);
+  if (!b) return 1;
+  if (!x_all && !y_all) return 0;
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const double *xd = x_all ? device_ptr(x_all, (size_t)b->count * b->n, where, b->in_a, s) : nullptr;
+    const double *yd = y_all && b->m ? device_ptr(y_all, (size_t)b->count * b->m, where, b->in_b, s) : nullptr;
+    OQ_LAUNCH(shared::k_shared_warm, dim3(blocks_for((int64_t)b->count * (b->n + b->m), 256)), dim3(256), 0, s, b->dp.P, b->count, b->plan.T, b->Ax.get(),
+              b->model.get(), xd, yd, b->tiles.get());
+    HIP_CHECK(hipStreamSynchronize(s));
+    b->st.warm_start = 1;  // as osqp_warm_start does
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_resolve(osqp_amd_shared_batch *handle, c_float *x_out, c_float *y_out, c_float *info_out, c_int where) {
+  SharedBatch *b = shared_handle(handle);
+  if (!b) return 1;
+  if (!x_out || !info_out || (b->m > 0 && !y_out)) { set_last_error("invalid batch data"); return 1; }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    double *xd = where ? x_out : b->x_out.get(), *yd = where ? y_out : b->y_out.get(), *id = where ? info_out : b->info_out.get();
+    HIP_CHECK(hipFuncSetAttribute((const void *)shared::k_batch_solve_shared, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->plan.lds_bytes));
+    g_batch_last_kernel = shared::kLastKernel;
+    g_shared_launches++;
+    OQ_LAUNCH(shared::k_batch_solve_shared, dim3(b->ntiles), dim3(NT), b->plan.lds_bytes, s, b->dp.P, b->st, b->count, b->plan.T, (int)(b->st.warm_start != 0),
+              (const double *)b->model.get(), b->tiles.get(), xd, yd, id);
+    if (!where) {
+      b->x_out.download(x_out, (size_t)b->count * b->n, s);
+      if (b->m) b->y_out.download(y_out, (size_t)b->count * b->m, s);
+      b->info_out.download(info_out, (size_t)b->count * 6, s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_update_setting(osqp_amd_shared_batch *handle, const char *name, c_float value) {
+  SharedBatch *b = shared_handle(handle);
+  if (!b) return 1;
+  if (!name) { set_last_error("invalid batch data"); return 1; }
+  try {
+    static const char *const kNames[] = {"max_iter", "eps_abs", "eps_rel", "eps_prim_inf", "eps_dual_inf", "alpha", "check_termination", "scaled_termination", "rho"};
+    bool listed = false;
+    for (const char *k : kNames) listed = listed || !strcmp(name, k);
+    if (!listed) { set_last_error(std::string(name) + " cannot be updated on a shared batch or is not recognized"); return 1; }
+    OSQPSettings st = b->st;
+    bool ok = false;
+#define OQ_SHARED_SETTING(field, type, cond)                                                                                            \
+    if (!strcmp(name, #field)) {                                                                                                          \
+      const bool whole = std::is_floating_point<type>::value || (value == std::floor(value) && std::fabs(value) <= 9007199254740992.0); \
+      if (whole && setting_ok_##field((type)value)) { st.field = (type)value; ok = true; }                                                \
+    }
+    OQ_UPDATABLE_SETTINGS(OQ_SHARED_SETTING)
+#undef OQ_SHARED_SETTING
+    if (!ok) { set_last_error(std::string("invalid value for the setting ") + name); return 1; }
+    if (!strcmp(name, "rho")) {  // one re-factorisation; the carried iterates stay, as with osqp_update_rho
+      DeviceScope on_dev(b->device);
+      hipStream_t s = nullptr;
+      st.rho = std::min(std::max(st.rho, (c_float)B_RHO_MIN), (c_float)B_RHO_MAX);
+      try { shared_factor(*b, st, s); }
+      catch (...) { shared_factor(*b, b->st, s); throw; }  // the model block of the rho that stays
+    }
+    b->st = st;
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_device_bytes(osqp_amd_shared_batch *handle) {
+  SharedBatch *b = shared_handle(handle);
+  return b ? (c_int)b->device_bytes() : -1;
+}
+
+c_int osqp_amd_shared_batch_destroy(osqp_amd_shared_batch *handle) {
+  if (!handle) return 0;
+  SharedBatch *b = (SharedBatch *)handle;
   try { DeviceScope on_device(b->device); delete b; } catch (...) { return 1; }
   return 0;
 }

@@ -821,6 +821,104 @@ function batch_large_plan(n::Integer, m::Integer, nnzA::Integer, nnzF::Integer)
     return (lds_bytes = Int(out[1]), scratch_bytes = Int(out[2]), tiles_per_wave = Int(out[3]))
 end
 
+# ---------------------------------------------------------------------------------------------------------
+# The shared batch (include/osqp_amd.h: osqp_amd_shared_batch_*, DESIGN.md section 13.3): ONE model (P, A, q0, l0, u0, settings)
+# and `count` instances that differ in q, l and u only, on one shared inverse of the reduced KKT matrix.  Instance i is
+# `setup!` on the base data, `update!(q = q[:, i], l = l[:, i], u = u[:, i])`, `solve!`.  `adaptive_rho` is set to false unless
+# given; every row of every instance must keep the kind (loose / equality / inequality) it has under (l0, u0).  Arrays are one
+# COLUMN per instance, host `Matrix{Float64}` or device pointers, as for the resident batch.
+# ---------------------------------------------------------------------------------------------------------
+mutable struct SharedBatch
+    handle::Ptr{Cvoid}
+    count::Int
+    n::Int
+    m::Int
+end
+
+"(T, lds_bytes, model_bytes, instance_bytes) for a shape (osqp_amd_shared_batch_plan; host only): T, the instances per workgroup, depends on the shape alone."
+function shared_batch_plan(n::Integer, m::Integer, nnzA::Integer, nnzF::Integer)
+    out = zeros(Cc_int, 4)
+    GC.@preserve out begin
+        flag = ccall((:osqp_amd_shared_batch_plan, lib), Cc_int, (Cc_int, Cc_int, Cc_int, Cc_int, Ptr{Cc_int}), n, m, nnzA, nnzF, pointer(out))
+    end
+    flag == 0 || error("Error in batched plan: $(last_error())")
+    return (T = Int(out[1]), lds_bytes = Int(out[2]), model_bytes = Int(out[3]), instance_bytes = Int(out[4]))
+end
+
+function shared_batch_setup(P::SparseMatrixCSC, A::SparseMatrixCSC, q0::Vector{Float64}, l0::Vector{Float64}, u0::Vector{Float64},
+                            count::Integer; device::Integer = 0, settings...)
+    Pu = triu(P)
+    n, m = size(A, 2), size(A, 1)
+    length(q0) == n && length(l0) == m && length(u0) == m || error("q0, l0, u0: expected lengths $(n), $(m), $(m)")
+    d = Dict{Symbol,Any}(settings)
+    haskey(d, :adaptive_rho) || (d[:adaptive_rho] = false)
+    stgs = OSQP.Settings(d)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    Pp, Pi = Vector{Cc_int}(Pu.colptr .- 1), Vector{Cc_int}(Pu.rowval .- 1)
+    Ap, Ai = Vector{Cc_int}(A.colptr .- 1), Vector{Cc_int}(A.rowval .- 1)
+    flag = ccall((:osqp_amd_shared_batch_setup, lib), Cc_int,
+                 (Ptr{Ptr{Cvoid}}, Cc_int, Cc_int, Cc_int, Ptr{Cc_int}, Ptr{Cc_int}, Ptr{Cdouble}, Ptr{Cc_int}, Ptr{Cc_int}, Ptr{Cdouble},
+                  Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{OSQP.Settings}, Cc_int),
+                 h, count, n, m, Pp, Pi, Vector{Float64}(Pu.nzval), Ap, Ai, Vector{Float64}(A.nzval), q0, l0, u0, Ref(stgs), device)
+    flag == 0 || error("Error in shared batch setup: $(last_error())")
+    b = SharedBatch(h[], count, n, m)
+    finalizer(x -> ccall((:osqp_amd_shared_batch_destroy, lib), Cc_int, (Ptr{Cvoid},), x.handle), b)
+    return b
+end
+
+"New q [n x count] and / or bounds l, u [m x count] (both).  Bounds that cross or change the kind of a row are refused."
+function shared_batch_update!(b::SharedBatch; q::BatchArg = nothing, l::BatchArg = nothing, u::BatchArg = nothing)
+    (l === nothing) == (u === nothing) || error("l and u: a shared batch updates both bounds in one call")
+    GC.@preserve q l u begin
+        if q !== nothing
+            flag = ccall((:osqp_amd_shared_batch_update_lin_cost, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Cc_int), b.handle, _batch_ptr(q), _batch_where(q))
+            flag == 0 || error("Error in shared batch update: $(last_error())")
+        end
+        if l !== nothing
+            flag = ccall((:osqp_amd_shared_batch_update_bounds, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                         b.handle, _batch_ptr(l), _batch_ptr(u), _batch_where(l, u))
+            flag == 0 || error("Error in shared batch update: $(last_error())")
+        end
+    end
+    return nothing
+end
+
+function shared_batch_warm_start!(b::SharedBatch; x::BatchArg = nothing, y::BatchArg = nothing)
+    GC.@preserve x y begin
+        flag = ccall((:osqp_amd_shared_batch_warm_start, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, _batch_ptr(x), _batch_ptr(y), _batch_where(x, y))
+    end
+    flag == 0 || error("Error in shared batch warm start: $(last_error())")
+    return nothing
+end
+
+"Solve every instance in one launch -> (x [n x count], y [m x count], info [6 x count]: iter, status_val, pri_res, dua_res, obj_val, 0)."
+function shared_batch_solve!(b::SharedBatch)
+    x, y, info = Matrix{Float64}(undef, b.n, b.count), Matrix{Float64}(undef, b.m, b.count), Matrix{Float64}(undef, 6, b.count)
+    flag = ccall((:osqp_amd_shared_batch_resolve, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int), b.handle, x, y, info, 0)
+    flag == 0 || error("Error in shared batch solve: $(last_error())")
+    return x, y, info
+end
+
+"The same into device arrays."
+function shared_batch_solve!(b::SharedBatch, x::Ptr{Cdouble}, y::Ptr{Cdouble}, info::Ptr{Cdouble})
+    flag = ccall((:osqp_amd_shared_batch_resolve, lib), Cc_int, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int), b.handle, x, y, info, 1)
+    flag == 0 || error("Error in shared batch solve: $(last_error())")
+    return nothing
+end
+
+"max_iter, eps_abs, eps_rel, eps_prim_inf, eps_dual_inf, alpha, check_termination, scaled_termination, rho (one re-factorisation)."
+function shared_batch_update_settings!(b::SharedBatch; kwargs...)
+    for (key, value) in kwargs
+        flag = ccall((:osqp_amd_shared_batch_update_setting, lib), Cc_int, (Ptr{Cvoid}, Cstring, Cdouble), b.handle, String(key), Float64(value))
+        flag == 0 || error("Error in shared batch settings update: $(last_error())")
+    end
+    return nothing
+end
+
+shared_batch_device_bytes(b::SharedBatch) = Int(ccall((:osqp_amd_shared_batch_device_bytes, lib), Cc_int, (Ptr{Cvoid},), b.handle))
+shared_batch_launches() = Int(ccall((:osqp_amd_shared_batch_launches, lib), Cc_int, ()))
+
 """
     batch_large_factor!(b, on = true) -> Bool
 

@@ -258,6 +258,21 @@ EXT_SYMBOLS = {
     "osqp_amd_batch_jvp": (c_int, [C.c_void_p, c_int] + [C.c_void_p] * 9 + [c_int]),
     "osqp_amd_batch_jvp_launches": (c_int, []),
     "osqp_amd_batch_update_setting": (c_int, [C.c_void_p, C.c_char_p, c_float]),
+    # the shared batch (include/osqp_amd.h: osqp_amd_shared_batch_*): one model, many right-hand sides; a handle type of its own
+    "osqp_amd_shared_batch_plan": (c_int, [c_int, c_int, c_int, c_int, C.c_void_p]),
+    "osqp_amd_shared_batch_setup": (
+        c_int,
+        [C.POINTER(C.c_void_p), c_int, c_int, c_int, c_int_p, c_int_p, c_float_p, c_int_p, c_int_p, c_float_p,
+         c_float_p, c_float_p, c_float_p, C.POINTER(Settings), c_int],
+    ),
+    "osqp_amd_shared_batch_update_lin_cost": (c_int, [C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_shared_batch_update_bounds": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_shared_batch_warm_start": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_shared_batch_resolve": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
+    "osqp_amd_shared_batch_update_setting": (c_int, [C.c_void_p, C.c_char_p, c_float]),
+    "osqp_amd_shared_batch_device_bytes": (c_int, [C.c_void_p]),
+    "osqp_amd_shared_batch_launches": (c_int, []),
+    "osqp_amd_shared_batch_destroy": (c_int, [C.c_void_p]),
     "osqp_amd_batch_certificates": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_batch_cert_launches": (c_int, []),
     # the reading calls for a selection: rows and k after the handle, every array compact ([k x .], [ndir x k x .])
