@@ -311,6 +311,24 @@ def selection(rows, count):
     return arr
 
 
+# The calls of a resident handle that exist for every instance and for a selection, by base name: the symbols are spelled
+# out so that a search for one finds its caller (`ResidentBatch._entry`).
+_CALL_FORMS = {
+    "update_lin_cost": ("osqp_amd_batch_update_lin_cost", "osqp_amd_batch_update_lin_cost_rows"),
+    "update_bounds": ("osqp_amd_batch_update_bounds", "osqp_amd_batch_update_bounds_rows"),
+    "update_matrices": ("osqp_amd_batch_update_matrices", "osqp_amd_batch_update_matrices_rows"),
+    "warm_start": ("osqp_amd_batch_warm_start", "osqp_amd_batch_warm_start_rows"),
+    "resolve": ("osqp_amd_batch_resolve", "osqp_amd_batch_resolve_rows"),
+    "polish_status": ("osqp_amd_batch_polish_status", "osqp_amd_batch_polish_status_rows"),
+    "certificates": ("osqp_amd_batch_certificates", "osqp_amd_batch_certificates_rows"),
+    "duality": ("osqp_amd_batch_duality", "osqp_amd_batch_duality_rows"),
+    "gap_refusals": ("osqp_amd_batch_gap_refusals", "osqp_amd_batch_gap_refusals_rows"),
+    "adjoint": ("osqp_amd_batch_adjoint", "osqp_amd_batch_adjoint_rows"),
+    "adjoint_multi": ("osqp_amd_batch_adjoint_multi", "osqp_amd_batch_adjoint_multi_rows"),
+    "jvp": ("osqp_amd_batch_jvp", "osqp_amd_batch_jvp_rows"),
+}
+
+
 class ResidentBatch:
     """`count` QPs of the caller's own that share one sparsity pattern, resident in HBM (osqp_amd_batch_setup): the life
     cycle of a single model -- setup, `update`, `warm_start`, `solve`, again and again -- instance by instance.  Scaling is
@@ -388,6 +406,35 @@ class ResidentBatch:
         if rc != 0:
             raise OSQPError(f"Error in batched {what}: " + self.lib.osqp_amd_last_error().decode())
 
+    def _served(self, rows):
+        """(sel, k) of a `rows=` argument: the checked selection and its length, or (None, count) for every instance."""
+        if rows is None:
+            return None, self.count
+        sel = selection(rows, self.count)
+        return sel, len(sel)
+
+    def _entry(self, what, name, sel, *args):
+        """One call of the library on the handle (`name`: a key of _CALL_FORMS): osqp_amd_batch_<name>(handle, *args) for every
+        instance (sel None), or osqp_amd_batch_<name>_rows(handle, rows, k, *args) for the selection; a refusal raises as
+        "Error in batched <what>"."""
+        whole, subset = _CALL_FORMS[name]
+        if sel is None:
+            self._call(what, getattr(self.lib, whole)(self.handle, *args))
+        else:
+            self._call(what, getattr(self.lib, subset)(self.handle, _iptr(sel), len(sel), *args))
+
+    def _one_output(self, what, name, sel, out, shape, device_shape=None):
+        """The one output of the entry `name`: out=None -> a new numpy array of `shape`; out = a device array of `device_shape`
+        (None: `shape`) -> filled in place.  Returns the array."""
+        if out is None:
+            res = np.empty(shape)
+            self._entry(what, name, sel, res.ctypes.data, 0)
+            return res
+        if not hasattr(out, "data_ptr"):
+            raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
+        self._entry(what, name, sel, _batch_array("out", out, shape if device_shape is None else device_shape)[1], 1)
+        return out
+
     def _pair(self, names, values, cols, rows=None):
         """The two optional arrays of one library call: both in the same form (host or device); None stays NULL.  `rows`:
         the number of rows they must have (None: count)."""
@@ -403,57 +450,36 @@ class ResidentBatch:
         the stored factors), then the matrices (which re-equilibrate, with the q, l, u just given).  Nothing is changed by a
         call whose arguments fail the checks; `l > u` in any instance raises and leaves the bounds as they were.
         rows: a selection (`selection`); the arrays are then [k x .] and only those instances change and re-equilibrate."""
-        sel = None if rows is None else selection(rows, self.count)
-        k = self.count if sel is None else len(sel)
+        sel, k = self._served(rows)
         qa = None if q is None else _batch_array("q", q, (k, self.n))
         keep_b, bounds, where_b = self._pair(("l", "u"), (l, u), (self.m, self.m), k)
         keep_m, mats, where_m = self._pair(("Px", "Ax"), (Px, Ax), (self.nnzP, self.nnzA), k)
         if keep_b[0] is not None and keep_b[1] is not None and not where_b and np.any(keep_b[0][0] > keep_b[1][0]):
             raise OSQPError("Error in batched update: lower bound greater than upper bound")
-        if sel is not None:
-            lib, h, sp = self.lib, self.handle, _iptr(sel)
-            if qa is not None:
-                self._call("update", lib.osqp_amd_batch_update_lin_cost_rows(h, sp, k, qa[1], qa[2]))
-            if bounds[0] is not None or bounds[1] is not None:
-                self._call("update", lib.osqp_amd_batch_update_bounds_rows(h, sp, k, bounds[0], bounds[1], where_b))
-            if mats[0] is not None or mats[1] is not None:
-                self._call("update", lib.osqp_amd_batch_update_matrices_rows(h, sp, k, mats[0], mats[1], where_m))
-            return
         if qa is not None:
-            self._call("update", self.lib.osqp_amd_batch_update_lin_cost(self.handle, qa[1], qa[2]))
+            self._entry("update", "update_lin_cost", sel, qa[1], qa[2])
         if bounds[0] is not None or bounds[1] is not None:
-            self._call("update", self.lib.osqp_amd_batch_update_bounds(self.handle, bounds[0], bounds[1], where_b))
+            self._entry("update", "update_bounds", sel, bounds[0], bounds[1], where_b)
         if mats[0] is not None or mats[1] is not None:
-            self._call("update", self.lib.osqp_amd_batch_update_matrices(self.handle, mats[0], mats[1], where_m))
+            self._entry("update", "update_matrices", sel, mats[0], mats[1], where_m)
 
     def warm_start(self, x=None, y=None, rows=None):
         """Start the next solve from x and / or y (caller's units, [count x n] / [count x m]); a missing one is zero.
         rows: a selection (`selection`); x / y are then [k x .] and only the iterates of those instances change."""
-        sel = None if rows is None else selection(rows, self.count)
-        keep, ptrs, where = self._pair(("x", "y"), (x, y), (self.n, self.m), None if sel is None else len(sel))
-        if sel is not None:
-            if ptrs[0] is not None or ptrs[1] is not None:
-                self._call("warm start", self.lib.osqp_amd_batch_warm_start_rows(self.handle, _iptr(sel), len(sel), ptrs[0], ptrs[1], where))
-            return
+        sel, k = self._served(rows)
+        keep, ptrs, where = self._pair(("x", "y"), (x, y), (self.n, self.m), k)
         if ptrs[0] is not None or ptrs[1] is not None:
-            self._call("warm start", self.lib.osqp_amd_batch_warm_start(self.handle, ptrs[0], ptrs[1], where))
+            self._entry("warm start", "warm_start", sel, ptrs[0], ptrs[1], where)
 
     def solve(self, out=None, rows=None):
         """Solve every instance -> (x [count x n], y [count x m], info [count x 6]: iter, status_val, pri_res, dua_res,
         obj_val, rho_updates).  out=None: numpy arrays; out=(x, y, info) of device arrays: written in place and returned.
         rows: a selection (`selection`): only those instances are launched, the results are [k x .] (`alloc(k)`), and every
         other instance keeps its iterate, rho, certificates, polish status and info row."""
-        sel = None if rows is None else selection(rows, self.count)
-        k = self.count if sel is None else len(sel)
-
-        def resolve(xp, yp, ip, where):
-            if sel is None:
-                return self.lib.osqp_amd_batch_resolve(self.handle, xp, yp, ip, where)
-            return self.lib.osqp_amd_batch_resolve_rows(self.handle, _iptr(sel), k, xp, yp, ip, where)
-
+        sel, k = self._served(rows)
         if out is None:
             x, y, info = np.empty((k, self.n)), np.empty((k, self.m)), np.empty((k, 6))
-            self._call("solve", resolve(x.ctypes.data, y.ctypes.data, info.ctypes.data, 0))
+            self._entry("solve", "resolve", sel, x.ctypes.data, y.ctypes.data, info.ctypes.data, 0)
             return x, y, info
         if len(out) != 3:
             raise ValueError("out: expected (x, y, info)")
@@ -465,7 +491,7 @@ class ResidentBatch:
             if not hasattr(a, "data_ptr"):
                 raise ValueError(f"{name}: expected a device array (DeviceArray, torch tensor); omit `out` for numpy results")
             ptrs.append(_batch_array(name, a, (k, cols))[1])
-        self._call("solve", resolve(ptrs[0], ptrs[1], ptrs[2], 1))
+        self._entry("solve", "resolve", sel, ptrs[0], ptrs[1], ptrs[2], 1)
         return out
 
     def polish_status(self, out=None, rows=None):
@@ -473,23 +499,9 @@ class ResidentBatch:
         not Solved, or `polish` is off).  out=None: a numpy int array [count]; out = a device array [count x 1] of float64:
         filled in place and returned.  rows: a selection (`selection`); the result is [k] ([k x 1]), entry j for instance
         rows[j], gathered on the device."""
-        sel = None if rows is None else selection(rows, self.count)
-        k = self.count if sel is None else len(sel)
-
-        def status(ptr, where):
-            if sel is None:
-                return self.lib.osqp_amd_batch_polish_status(self.handle, ptr, where)
-            return self.lib.osqp_amd_batch_polish_status_rows(self.handle, _iptr(sel), k, ptr, where)
-
-        if out is None:
-            st = np.empty(k)
-            self._call("polish status", status(st.ctypes.data, 0))
-            return st.astype(np.int64)
-        if not hasattr(out, "data_ptr"):
-            raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
-        ptr = _batch_array("out", out, (k, 1))[1]
-        self._call("polish status", status(ptr, 1))
-        return out
+        sel, k = self._served(rows)
+        st = self._one_output("polish status", "polish_status", sel, out, (k,), (k, 1))
+        return st.astype(np.int64) if out is None else st
 
     def update_polish(self, polish, polish_refine_iter=None):
         """Switch polishing of the following solves on (1 / True) or off (0 / False), as `update_settings(polish=...)` does
@@ -532,18 +544,11 @@ class ResidentBatch:
         solve.  out=None: numpy arrays; out=(p, d) of device arrays, either may be None: filled in place and returned.
         With m = 0 the first element is None.  rows: a selection (`selection`); the arrays are [k x .], row j for instance
         rows[j], gathered on the device."""
-        sel = None if rows is None else selection(rows, self.count)
-        k = self.count if sel is None else len(sel)
-
-        def certs(pp, dp, where):
-            if sel is None:
-                return self.lib.osqp_amd_batch_certificates(self.handle, pp, dp, where)
-            return self.lib.osqp_amd_batch_certificates_rows(self.handle, _iptr(sel), k, pp, dp, where)
-
+        sel, k = self._served(rows)
         if out is None:
             p = np.empty((k, self.m)) if self.m else None
             d = np.empty((k, self.n))
-            self._call("certificates", certs(None if p is None else p.ctypes.data, d.ctypes.data, 0))
+            self._entry("certificates", "certificates", sel, None if p is None else p.ctypes.data, d.ctypes.data, 0)
             return p, d
         if len(out) != 2:
             raise ValueError("out: expected (prim_inf_cert, dual_inf_cert)")
@@ -557,7 +562,7 @@ class ResidentBatch:
             ptrs.append(_batch_array(name, a, (k, cols))[1])
         if ptrs[1] is None and (ptrs[0] is None or self.m == 0):
             raise ValueError("out: no certificate was asked for")
-        self._call("certificates", certs(ptrs[0], ptrs[1], 1))
+        self._entry("certificates", "certificates", sel, ptrs[0], ptrs[1], 1)
         return (None if self.m == 0 else out[0]), out[1]
 
     def duality(self, out=None, rows=None):
@@ -566,23 +571,8 @@ class ResidentBatch:
         solution.  Every instance served must be current (solved after its last update or warm start).  out=None: a numpy
         array; out = a device array [count x 3] of float64: filled in place and returned.  rows: a selection (`selection`);
         the result is [k x 3], row j for instance rows[j], and only these must be current.  Only reads the handle."""
-        sel = None if rows is None else selection(rows, self.count)
-        k = self.count if sel is None else len(sel)
-
-        def dual(ptr, where):
-            if sel is None:
-                return self.lib.osqp_amd_batch_duality(self.handle, ptr, where)
-            return self.lib.osqp_amd_batch_duality_rows(self.handle, _iptr(sel), k, ptr, where)
-
-        if out is None:
-            res = np.empty((k, 3))
-            self._call("duality", dual(res.ctypes.data, 0))
-            return res
-        if not hasattr(out, "data_ptr"):
-            raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
-        ptr = _batch_array("out", out, (k, 3))[1]
-        self._call("duality", dual(ptr, 1))
-        return out
+        sel, k = self._served(rows)
+        return self._one_output("duality", "duality", sel, out, (k, 3))
 
     def duality_gap_check(self, on=True):
         """The duality gap as a third termination test of every later `solve()`, whole or `rows=`
@@ -597,23 +587,8 @@ class ResidentBatch:
         (osqp_amd_batch_gap_refusals); zeros while the rule is off.  out=None: a numpy array of float64; out = a device array
         [count] of float64: filled in place and returned.  rows: a selection (`selection`); the result is [k], entry j for
         instance rows[j].  Only reads the handle."""
-        sel = None if rows is None else selection(rows, self.count)
-        k = self.count if sel is None else len(sel)
-
-        def refusals(ptr, where):
-            if sel is None:
-                return self.lib.osqp_amd_batch_gap_refusals(self.handle, ptr, where)
-            return self.lib.osqp_amd_batch_gap_refusals_rows(self.handle, _iptr(sel), k, ptr, where)
-
-        if out is None:
-            res = np.empty(k)
-            self._call("gap_refusals", refusals(res.ctypes.data, 0))
-            return res
-        if not hasattr(out, "data_ptr"):
-            raise ValueError("out: expected a device array (DeviceArray, torch tensor); omit `out` for a numpy result")
-        ptr = _batch_array("out", out, (k,))[1]
-        self._call("gap_refusals", refusals(ptr, 1))
-        return out
+        sel, k = self._served(rows)
+        return self._one_output("gap_refusals", "gap_refusals", sel, out, (k,))
 
     ADJOINT_WANT = ("q", "l", "u", "Px", "Ax")
 
@@ -639,8 +614,7 @@ class ResidentBatch:
         same number of dimensions and the same ncot (osqp_amd_batch_adjoint_multi) -- one launch, one factorisation per
         instance, one solve per cotangent, and cotangent c has the bits of a call with that pair alone.  The gradients are then
         shaped like the cotangents, [ncot x count x .]; "act" [count x m] and "status" [count] stay per instance."""
-        sel = None if rows is None else selection(rows, self.count)
-        cnt = self.count if sel is None else len(sel)
+        sel, cnt = self._served(rows)
         cols = self._adjoint_cols()
         want = tuple(want)
         for w in want:
@@ -689,14 +663,9 @@ class ResidentBatch:
             res = out
         tail = [ptrs[0], ptrs[1]] + [addr.get(k) for k in self.ADJOINT_WANT] + [addr.get("act"), addr.get("status"), where]
         if many:
-            if sel is None:
-                self._call("adjoint", self.lib.osqp_amd_batch_adjoint_multi(self.handle, ncot, *tail))
-            else:
-                self._call("adjoint", self.lib.osqp_amd_batch_adjoint_multi_rows(self.handle, _iptr(sel), cnt, ncot, *tail))
-        elif sel is None:
-            self._call("adjoint", self.lib.osqp_amd_batch_adjoint(self.handle, *tail))
+            self._entry("adjoint", "adjoint_multi", sel, ncot, *tail)
         else:
-            self._call("adjoint", self.lib.osqp_amd_batch_adjoint_rows(self.handle, _iptr(sel), cnt, *tail))
+            self._entry("adjoint", "adjoint", sel, *tail)
         if not where:
             if "act" in res:
                 res["act"] = res["act"].astype(np.int64)
@@ -720,8 +689,7 @@ class ResidentBatch:
         EVERY instance, as for `adjoint`.  rows: a selection (`selection`): a launch of k workgroups; the tangents and the
         results are [k x .] / [ndir x k x .], "act" [k x m], "status" [k], row j for instance rows[j] with the bits of row rows[j]
         of the whole call, and only the SELECTED instances must hold a current solution."""
-        sel = None if rows is None else selection(rows, self.count)
-        cnt = self.count if sel is None else len(sel)
+        sel, cnt = self._served(rows)
         cols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA)
         given = {k: v for k, v in zip(self.JVP_TANGENTS, (q, l, u, Px, Ax)) if v is not None}
         if not given:
@@ -765,10 +733,7 @@ class ResidentBatch:
             res = out
         tail = [ndir] + [got[k][1] if k in got else None for k in self.JVP_TANGENTS]
         tail += [addr.get("x"), addr.get("y"), addr.get("act"), addr.get("status"), where]
-        if sel is None:
-            self._call("jvp", self.lib.osqp_amd_batch_jvp(self.handle, *tail))
-        else:
-            self._call("jvp", self.lib.osqp_amd_batch_jvp_rows(self.handle, _iptr(sel), cnt, *tail))
+        self._entry("jvp", "jvp", sel, *tail)
         if not where:
             if "act" in res:
                 res["act"] = res["act"].astype(np.int64)
@@ -795,8 +760,7 @@ class ResidentBatch:
         rows: a selection (`selection`): the arrays are [k x . x .], entry j for instance rows[j].  device=False: numpy
         results; device=True: the unit vectors are made and the results returned as torch tensors on the handle's device
         (no host hop).  Nothing is computed on the results: they are transposed and placed."""
-        sel = None if rows is None else selection(rows, self.count)
-        cnt = self.count if sel is None else len(sel)
+        sel, cnt = self._served(rows)
         of, wrt = tuple(of), tuple(wrt)
         wcols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA)
         ocols = dict(x=self.n, y=self.m)

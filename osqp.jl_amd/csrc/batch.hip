@@ -31,7 +31,11 @@
 //                     k_shared_factor (setup), k_batch_solve_shared (T instances per workgroup, the dense step on the fp64
 //                     matrix cores) and their small kernels; a handle type of its own (SharedBatch below);
 //   this file         the small kernels (warm start, rho fill, bound check, the row scatter and gather of a selection, MPC generator), the
-//                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.
+//                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.  A resident call exists for every instance and
+//                     for a selection (osqp_amd_batch_X, osqp_amd_batch_X_rows): ONE static body batch_X(handle, subset, rows, k, ...)
+//                     each, the extern "C" entries forward.  What differs between the two forms is in `Served` (launch size,
+//                     sel), put_rows / give_rows (copy vs. scatter / gather) and OutStage (host-pointer outputs through adj_out);
+//                     launch_factor is the one launcher of the polish, adjoint and JVP kernels.
 // Same algorithm as oracle/osqp_oracle.c with the KKT system in reduced form.
 // Both kernels also run in RESIDENT mode (osqp_amd_batch_setup ... _resolve, "the state record" in batch_common.hpp):
 // scaling, iterate and rho of every instance live in HBM between launches; a branch of the prologue and of the epilogue on
@@ -403,8 +407,9 @@ struct BatchPlan : BatchData {
 
 // The checks osqp_setup makes [REF src/interface.jl:47-100 + the C side's validate_data / validate_settings], shared by the
 // one-shot osqp_amd_batch_solve and osqp_amd_batch_setup.  outputs_ok: what the caller checked of its own output
-// pointers.  0 = fine; otherwise the return code, the message is set.
-c_int validate_batch_data(const BatchProblem &p, bool outputs_ok) {
+// pointers; max_n: the size cap of the caller's path (kPivotW, or 256 for the opt-in large path and the shared batch).
+// 0 = fine; otherwise the return code, the message is set.
+c_int validate_batch_data(const BatchProblem &p, bool outputs_ok, c_int max_n) {
   const c_int count = p.count, n = p.n, m = p.m, *Pp = p.Pp, *Pi = p.Pi, *Ap = p.Ap, *Ai = p.Ai;
   const c_float *Px_all = p.Px_all, *Ax_all = p.Ax_all, *q_all = p.q_all, *l_all = p.l_all, *u_all = p.u_all;
   const OSQPSettings *settings = p.settings;
@@ -412,8 +417,8 @@ c_int validate_batch_data(const BatchProblem &p, bool outputs_ok) {
     set_last_error("invalid batch data"); return 1;
   }
   if (validate_settings(settings)) { set_last_error("invalid settings"); return 2; }
-  if (n > (g_batch_large ? kLargeMaxN : kPivotW) || m > 65535 || Pp[0] != 0 || Ap[0] != 0 || Pp[n] < 0 || Ap[n] < 0 || Pp[n] > 65535 || Ap[n] > 65535) {
-    set_last_error(g_batch_large ? "the batched path supports n <= 256 (osqp_amd_batch_large on) and fewer than 65536 rows / non-zeros"
+  if (n > max_n || m > 65535 || Pp[0] != 0 || Ap[0] != 0 || Pp[n] < 0 || Ap[n] < 0 || Pp[n] > 65535 || Ap[n] > 65535) {
+    set_last_error(max_n > kPivotW ? "the batched path supports n <= 256 (osqp_amd_batch_large on) and fewer than 65536 rows / non-zeros"
                                  : "the batched path supports n <= 128 and fewer than 65536 rows / non-zeros");
     return 1;
   }
@@ -484,6 +489,59 @@ void scatter_rows(const BatchPlan &b, int k, int cols, const double *src, double
 void gather_rows(const BatchPlan &b, int k, int cols, const double *src, double *dst, hipStream_t s) {
   if (cols) OQ_LAUNCH(k_batch_gather_rows, dim3(k), dim3(256), 0, s, b.sel.get(), k, cols, src, dst);
 }
+// Whom a resident call serves: every instance (osqp_amd_batch_X) or the selection of the _rows form of the same call.
+// launch: the workgroups of its launches and the rows of its arrays (count, or k: the arrays are then compact, row j for
+// instance rows[j]); sel: what BatchIO::sel and the small kernels take (nullptr, or the handle's uploaded selection).
+struct Served { bool subset; int launch; const int *sel; };
+// that of the running call; a selection is checked and uploaded here (select_rows): false with the message set when it is bad
+bool serve(BatchPlan &b, bool subset, const c_int *rows, c_int k, hipStream_t s, Served &v) {
+  if (subset && !select_rows(b, rows, k, s)) return false;
+  v = subset ? Served{true, (int)k, b.sel.get()} : Served{false, b.count, nullptr};
+  return true;
+}
+void mark(BatchPlan &b, const Served &v, bool is_current) { if (v.subset) b.mark_rows(is_current); else b.mark(is_current); }
+// The rows of the call (src [v.launch x cols], host or device pointer by `where`) into the handle's array dst [count x cols].
+// Every instance: straight into dst, one upload or one d2d copy; a selection: through `stage` when they are host data, then
+// scattered.
+void put_rows(const BatchPlan &b, const Served &v, int cols, const c_float *src, c_int where, DevBuf<double> &stage, DevBuf<double> &dst, hipStream_t s) {
+  const size_t len = (size_t)v.launch * cols;
+  if (!len) return;
+  if (v.subset) scatter_rows(b, v.launch, cols, device_ptr(src, len, where, stage, s), dst.get(), s);
+  else if (where) copy_d2d(dst.get(), src, len, s);
+  else dst.upload(src, len, s);
+}
+// The other way: the rows of the handle's array src [count x cols] out into dst [v.launch x cols].  Every instance: one
+// download or one d2d copy by `where`; a selection: gathered on the device, so dst is device memory -- the caller's array or
+// its slot of an OutStage.
+void give_rows(const BatchPlan &b, const Served &v, int cols, const DevBuf<double> &src, c_float *dst, c_int where, hipStream_t s) {
+  const size_t len = (size_t)v.launch * cols;
+  if (v.subset) gather_rows(b, v.launch, cols, src.get(), dst, s);
+  else if (where) copy_d2d(dst, src.get(), len, s);
+  else src.download(dst, len, s);
+}
+// The outputs of a call as the device pointers its kernels write (nullptr: not wanted).  Not staged: the caller's own
+// pointers.  Staged (host pointers): the wanted ones share the handle's adj_out at running offsets, in the order given, and
+// download() issues their copies once the launches are on the stream.
+struct OutStage {
+  c_float *host[7];
+  size_t len[7];
+  double *dev[7];
+  int count = 0;
+  bool staged;
+  OutStage(BatchPlan &b, bool staged_, std::initializer_list<c_float *> outs, std::initializer_list<size_t> lens) : staged(staged_) {
+    size_t total = 0, at = 0;
+    for (c_float *h : outs) { host[count] = h; len[count] = lens.begin()[count]; if (h) total += len[count]; count++; }
+    if (staged && b.adj_out.n < total) b.adj_out.alloc(total);
+    for (int j = 0; j < count; j++) {
+      dev[j] = staged && host[j] ? b.adj_out.get() + at : host[j];
+      if (staged && host[j]) at += len[j];
+    }
+  }
+  void download(int j, hipStream_t s) const {
+    if (staged && host[j]) HIP_CHECK(hipMemcpyAsync(host[j], dev[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  void download(hipStream_t s) const { for (int j = 0; j < count; j++) download(j, s); }
+};
 // The rule of the derivative calls: every instance they serve holds the solution of its current data.  rows nullptr: all of
 // the batch (osqp_amd_batch_adjoint, _jvp); otherwise the selection (the *_rows forms), in its order.  false with the message
 // set, naming the first instance that does not.
@@ -532,24 +590,32 @@ double *large_factor_scratch(const DevicePattern &dp, int launch, hipStream_t s)
   if (dp.scratch.n < need) { HIP_CHECK(hipStreamSynchronize(s)); dp.scratch.alloc(need); }
   return dp.scratch.get();
 }
-// polish() of the oracle on every Solved instance of the launch that has just written io.x / io.y / io.info and the records
-// (`count` workgroups, instance by io.sel)
-void launch_polish(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
+// One launch of k_batch_polish, k_batch_adjoint or k_batch_jvp (`lds` / `global`: its instantiation with the factor in LDS and
+// its LARGE one; `a`: its argument block, filled by the caller but for the scratch), `launch` workgroups.  A pattern the
+// kernels cannot serve is refused here; `launches` is the counter of the kernel.
+template <typename A>
+void launch_factor(BatchPlan &b, void (*lds)(Pattern, int, polish::Layout, A), void (*global)(Pattern, int, polish::Layout, A), A &a, int launch,
+                   int &launches, hipStream_t s) {
   const Pattern &P = b.dp.P;
   const bool large = b.large_factor && b.dp.large;
   polish_check_fits(P, large);
   const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, large);
+  if (large) a.scratch = large_factor_scratch(b.dp, launch, s);
+  auto *const kern = large ? global : lds;
+  HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+  launches++;
+  OQ_LAUNCH(kern, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
+}
+// polish() of the oracle on every Solved instance of the launch that has just written io.x / io.y / io.info and the records
+// (`count` workgroups, instance by io.sel)
+void launch_polish(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
   polish::Args a;
   a.Px = io.Px; a.Ax = io.Ax; a.q = io.q; a.l = io.l; a.u = io.u;
   a.x = io.x; a.y = io.y; a.info = io.info; a.rec = io.rec; a.status = b.pstat.get();
   a.x_stride = io.x_stride; a.y_stride = io.y_stride; a.info_stride = io.info_stride; a.rec_stride = io.rec_stride;
   a.refine = (int)b.st.polish_refine_iter; a.unscaled = b.st.scaling && !b.st.scaled_termination;
   a.delta = b.st.delta; a.sel = io.sel;
-  if (large) a.scratch = large_factor_scratch(b.dp, count, s);
-  auto *const kern = large ? polish::k_batch_polish<true> : polish::k_batch_polish<false>;
-  HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-  g_batch_polish_launches++;
-  OQ_LAUNCH(kern, dim3(count), dim3(polish::PT), (size_t)L.total, s, P, count, L, a);
+  launch_factor(b, polish::k_batch_polish<false>, polish::k_batch_polish<true>, a, count, g_batch_polish_launches, s);
 }
 // the certificates of the launch that has just written io.info and, under RES_CERT, left the directions in the records
 void launch_cert(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
@@ -565,6 +631,18 @@ void launch_cert(BatchPlan &b, const BatchIO &io, int count, hipStream_t s) {
 void set_polish(BatchPlan &b, c_int polish_new, c_int refine_new) {
   if (polish_new) polish_check_fits(b.dp.P, b.large_factor);
   b.st.polish = polish_new; b.st.polish_refine_iter = refine_new;
+}
+// `value` for the setting `name` into st, by the rule of the name from the table of the single-model updates (engine.hpp); an
+// integer setting takes integral values.  known: the name is in the table; ok: the value passed its rule and is set
+void parse_setting(const char *name, c_float value, OSQPSettings &st, bool &known, bool &ok) {
+#define OQ_BATCH_SETTING(field, type, cond)                                                                                               \
+  if (!known && !strcmp(name, #field)) {                                                                                                  \
+    known = true;                                                                                                                         \
+    const bool whole = std::is_floating_point<type>::value || (value == std::floor(value) && std::fabs(value) <= 9007199254740992.0);   \
+    if (whole && setting_ok_##field((type)value)) { st.field = (type)value; ok = true; }                                                  \
+  }
+  OQ_UPDATABLE_SETTINGS(OQ_BATCH_SETTING)
+#undef OQ_BATCH_SETTING
 }
 #define OQ_BATCH_CATCH                                                                          \
   catch (const Error &er) { set_last_error(er.what()); return er.code ? er.code : 6; }         \
@@ -653,47 +731,26 @@ c_int batch_adjoint(osqp_amd_batch *handle, bool subset, const c_int *rows, c_in
   if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
   if (!subset && !holds_current(*b, nullptr)) return 1;
   try {
-    const Pattern &P = b->dp.P;
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    if (subset) {  // only the selected instances must be current; nothing is launched when one is not
-      if (!select_rows(*b, rows, k, s)) return 1;
-      if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
-    }
-    const bool large = b->large_factor && b->dp.large;
-    polish_check_fits(P, large);
-    const int launch = subset ? (int)k : b->count;
-    const size_t cnt = (size_t)launch, nc = (size_t)ncot, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    // only the selected instances must be current; nothing is launched when one is not
+    if (v.subset && !holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
+    const size_t cnt = (size_t)v.launch, nc = (size_t)ncot, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
     if (!lm) { dy = nullptr; dl = du = act_out = nullptr; }
     if (!la) dAx = nullptr;
     if (!lp) dPx = nullptr;
-    // host pointers: the wanted outputs share one staging buffer, in this order
-    c_float *const host[7] = {dq, dl, du, dPx, dAx, act_out, status_out};
-    const size_t len[7] = {nc * ln, nc * lm, nc * lm, nc * lp, nc * la, lm, cnt};
-    double *dev[7];
-    size_t total = 0;
-    for (int j = 0; j < 7; j++) if (host[j]) total += len[j];
-    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
-    size_t at = 0;
-    for (int j = 0; j < 7; j++) {
-      dev[j] = !host[j] ? nullptr : (where ? host[j] : b->adj_out.get() + at);
-      if (host[j] && !where) at += len[j];
-    }
+    const OutStage o(*b, !where, {dq, dl, du, dPx, dAx, act_out, status_out}, {nc * ln, nc * lm, nc * lm, nc * lp, nc * la, lm, cnt});
     polish::AdjointArgs a;
     a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
     a.gx = dx ? device_ptr(dx, nc * ln, where, b->in_a, s) : nullptr;
     a.gy = dy ? device_ptr(dy, nc * lm, where, b->in_b, s) : nullptr;
-    a.dq = dev[0]; a.dl = dev[1]; a.du = dev[2]; a.dPx = dev[3]; a.dAx = dev[4]; a.act = dev[5]; a.status = dev[6];
+    a.dq = o.dev[0]; a.dl = o.dev[1]; a.du = o.dev[2]; a.dPx = o.dev[3]; a.dAx = o.dev[4]; a.act = o.dev[5]; a.status = o.dev[6];
     a.ncot = (int)ncot; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
-    a.sel = subset ? b->sel.get() : nullptr;
-    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, large);
-    if (large) a.scratch = large_factor_scratch(b->dp, launch, s);
-    auto *const kern = large ? polish::k_batch_adjoint<true> : polish::k_batch_adjoint<false>;
-    HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    g_batch_adjoint_launches++;
-    OQ_LAUNCH(kern, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
-    if (!where)
-      for (int j = 0; j < 7; j++) if (host[j]) HIP_CHECK(hipMemcpyAsync(host[j], dev[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+    a.sel = v.sel;
+    launch_factor(*b, polish::k_batch_adjoint<false>, polish::k_batch_adjoint<true>, a, v.launch, g_batch_adjoint_launches, s);
+    o.download(s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
@@ -710,32 +767,16 @@ c_int batch_jvp(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k,
   if (!tx_out && !ty_out) { set_last_error("invalid batch data: the sensitivities need tx_out or ty_out"); return 1; }
   if (!subset && !holds_current(*b, nullptr)) return 1;
   try {
-    const Pattern &P = b->dp.P;
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    if (subset) {
-      if (!select_rows(*b, rows, k, s)) return 1;
-      if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
-    }
-    const bool large = b->large_factor && b->dp.large;
-    polish_check_fits(P, large);
-    const int launch = subset ? (int)k : b->count;
-    const size_t cnt = (size_t)launch, nd = (size_t)ndir, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    if (v.subset && !holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
+    const size_t cnt = (size_t)v.launch, nd = (size_t)ndir, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
     if (!lm) { tl = tu = nullptr; ty_out = act_out = nullptr; }
     if (!la) tAx = nullptr;
     if (!lp) tPx = nullptr;
-    // host pointers: the wanted outputs share one staging buffer, in this order
-    c_float *const host[4] = {tx_out, ty_out, act_out, status_out};
-    const size_t len[4] = {nd * ln, nd * lm, lm, cnt};
-    double *dev[4];
-    size_t total = 0;
-    for (int j = 0; j < 4; j++) if (host[j]) total += len[j];
-    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
-    size_t at = 0;
-    for (int j = 0; j < 4; j++) {
-      dev[j] = !host[j] ? nullptr : (where ? host[j] : b->adj_out.get() + at);
-      if (host[j] && !where) at += len[j];
-    }
+    const OutStage o(*b, !where, {tx_out, ty_out, act_out, status_out}, {nd * ln, nd * lm, lm, cnt});
     polish::JvpArgs a;
     a.Px = b->Px.get(); a.Ax = b->Ax.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
     a.tq = tq ? device_ptr(tq, nd * ln, where, b->in_a, s) : nullptr;
@@ -743,17 +784,11 @@ c_int batch_jvp(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k,
     a.tu = tu ? device_ptr(tu, nd * lm, where, b->in_c, s) : nullptr;
     a.tPx = tPx ? device_ptr(tPx, nd * lp, where, b->in_d, s) : nullptr;
     a.tAx = tAx ? device_ptr(tAx, nd * la, where, b->in_e, s) : nullptr;
-    a.tx = dev[0]; a.ty = dev[1]; a.act = dev[2]; a.status = dev[3];
+    a.tx = o.dev[0]; a.ty = o.dev[1]; a.act = o.dev[2]; a.status = o.dev[3];
     a.ndir = (int)ndir; a.info_stride = 6; a.rec_stride = b->rec_stride; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
-    a.sel = subset ? b->sel.get() : nullptr;
-    const polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, large);
-    if (large) a.scratch = large_factor_scratch(b->dp, launch, s);
-    auto *const kern = large ? polish::k_batch_jvp<true> : polish::k_batch_jvp<false>;
-    HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    g_batch_jvp_launches++;
-    OQ_LAUNCH(kern, dim3(launch), dim3(polish::PT), (size_t)L.total, s, P, launch, L, a);
-    if (!where)
-      for (int j = 0; j < 4; j++) if (host[j]) HIP_CHECK(hipMemcpyAsync(host[j], dev[j], len[j] * sizeof(double), hipMemcpyDeviceToHost, s));
+    a.sel = v.sel;
+    launch_factor(*b, polish::k_batch_jvp<false>, polish::k_batch_jvp<true>, a, v.launch, g_batch_jvp_launches, s);
+    o.download(s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
@@ -817,7 +852,7 @@ c_int osqp_amd_batch_solve(c_int count, c_int n, c_int m, const c_int *Pp, const
                            const OSQPSettings *settings, c_float *x_out, c_float *y_out, OSQPInfo *info_out, c_int device) {
   try {
     const BatchProblem prob{count, n, m, Pp, Pi, Px_all, Ap, Ai, Ax_all, q_all, l_all, u_all, settings};
-    if (c_int bad = validate_batch_data(prob, x_out && info_out && (m <= 0 || y_out))) return bad;
+    if (c_int bad = validate_batch_data(prob, x_out && info_out && (m <= 0 || y_out), g_batch_large ? kLargeMaxN : kPivotW)) return bad;
     DeviceScope on_device((int)device);
     hipStream_t s = nullptr;
     DevicePattern dp;
@@ -920,7 +955,7 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, 
   *out = nullptr;
   try {
     const BatchProblem prob{count, n, m, Pp, Pi, Px_all, Ap, Ai, Ax_all, q_all, l_all, u_all, settings};
-    if (c_int bad = validate_batch_data(prob, true)) return bad;
+    if (c_int bad = validate_batch_data(prob, true, g_batch_large ? kLargeMaxN : kPivotW)) return bad;
     DeviceScope on_device((int)device);
     hipStream_t s = nullptr;
     std::unique_ptr<BatchPlan> b(new BatchPlan());
@@ -950,230 +985,179 @@ c_int osqp_amd_batch_setup(osqp_amd_batch **out, c_int count, c_int n, c_int m, 
   } OQ_BATCH_CATCH
 }
 
-c_int osqp_amd_batch_update_lin_cost(osqp_amd_batch *handle, const c_float *q_all, c_int where) {
+// The calls below serve every instance (osqp_amd_batch_X: subset false, rows / k unused, arrays [count x .]) or a selection
+// (osqp_amd_batch_X_rows, include/osqp_amd.h: subset true, arrays compact [k x .], row j for instance rows[j]): one body each,
+// the entries forward.  The handle and the required arrays are checked first; a whole call with nothing to do returns before
+// any device call; a selection is checked and uploaded before anything else (`serve`), so a bad one is refused even when
+// there is nothing to do.
+static c_int batch_update_lin_cost(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, const c_float *q, c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
-  if (!q_all) { set_last_error("invalid batch data"); return 1; }
+  if (!q) { set_last_error("invalid batch data"); return 1; }
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    const size_t len = (size_t)b->count * b->n;
-    b->mark(false);
-    if (where) copy_d2d(b->q.get(), q_all, len, s); else b->q.upload(q_all, len, s);
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    mark(*b, v, false);
+    put_rows(*b, v, b->n, q, where, b->in_a, b->q, s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
 }
+c_int osqp_amd_batch_update_lin_cost(osqp_amd_batch *handle, const c_float *q_all, c_int where) {
+  return batch_update_lin_cost(handle, false, nullptr, 0, q_all, where);
+}
+c_int osqp_amd_batch_update_lin_cost_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *q_rows, c_int where) {
+  return batch_update_lin_cost(handle, true, rows, k, q_rows, where);
+}
 
-c_int osqp_amd_batch_update_bounds(osqp_amd_batch *handle, const c_float *l_all, const c_float *u_all, c_int where) {
+static c_int batch_update_bounds(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, const c_float *l, const c_float *u, c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
-  if (b->m == 0 || (!l_all && !u_all)) return 0;
+  const bool nothing = b->m == 0 || (!l && !u);
+  if (nothing && !subset) return 0;
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    const size_t len = (size_t)b->count * b->m;
-    // checked on the device against the bound that stays, before anything of the handle changes
-    const double *ln = l_all ? device_ptr(l_all, len, where, b->in_a, s) : b->l.get();
-    const double *un = u_all ? device_ptr(u_all, len, where, b->in_b, s) : b->u.get();
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    if (nothing) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
+    const size_t len = (size_t)v.launch * b->m;
+    // checked on the device against the bound that stays (of the same instance), before anything of the handle changes
+    const double *ln = l ? device_ptr(l, len, where, b->in_a, s) : nullptr;
+    const double *un = u ? device_ptr(u, len, where, b->in_b, s) : nullptr;
     int bad = 0;
     HIP_CHECK(hipMemsetAsync(b->bad.get(), 0, sizeof(int), s));
-    OQ_LAUNCH(k_batch_check_bounds, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, len, ln, un, b->bad.get());
+    if (v.subset)
+      OQ_LAUNCH(k_batch_check_bounds_rows, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, v.sel, v.launch, b->m, ln, un, b->l.get(), b->u.get(),
+                b->bad.get());
+    else
+      OQ_LAUNCH(k_batch_check_bounds, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, len, ln ? ln : b->l.get(), un ? un : b->u.get(), b->bad.get());
     b->bad.download(&bad, 1, s);
     HIP_CHECK(hipStreamSynchronize(s));
     if (bad) { set_last_error("lower bound greater than upper bound"); return 1; }
-    b->mark(false);
-    if (l_all) copy_d2d(b->l.get(), ln, len, s);
-    if (u_all) copy_d2d(b->u.get(), un, len, s);
+    mark(*b, v, false);
+    if (ln) put_rows(*b, v, b->m, ln, 1, b->in_a, b->l, s);  // on the device by now
+    if (un) put_rows(*b, v, b->m, un, 1, b->in_b, b->u, s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
 }
-
-c_int osqp_amd_batch_update_matrices(osqp_amd_batch *handle, const c_float *Px_all, const c_float *Ax_all, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (!Px_all && !Ax_all) return 0;
-  try {
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    const size_t lp = (size_t)b->count * b->nnzP, la = (size_t)b->count * b->nnzA;
-    b->mark(false);
-    if (Px_all && lp) { if (where) copy_d2d(b->Px.get(), Px_all, lp, s); else b->Px.upload(Px_all, lp, s); }
-    if (Ax_all && la) { if (where) copy_d2d(b->Ax.get(), Ax_all, la, s); else b->Ax.upload(Ax_all, la, s); }
-    resident_equilibrate(*b, b->count, nullptr, s);  // from scratch on the raw data with the current q, l, u; the scaled iterate stays as it is
-    HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-  } OQ_BATCH_CATCH
+c_int osqp_amd_batch_update_bounds(osqp_amd_batch *handle, const c_float *l_all, const c_float *u_all, c_int where) {
+  return batch_update_bounds(handle, false, nullptr, 0, l_all, u_all, where);
 }
-
-c_int osqp_amd_batch_warm_start(osqp_amd_batch *handle, const c_float *x_all, const c_float *y_all, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (!x_all && !y_all) return 0;
-  try {
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    b->mark(false);
-    const double *xd = x_all ? device_ptr(x_all, (size_t)b->count * b->n, where, b->in_a, s) : nullptr;
-    const double *yd = y_all && b->m ? device_ptr(y_all, (size_t)b->count * b->m, where, b->in_b, s) : nullptr;
-    OQ_LAUNCH(k_batch_warm, dim3(b->count), dim3(256), 0, s, b->dp.P, b->count, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride, (const int *)nullptr);
-    HIP_CHECK(hipStreamSynchronize(s));
-    b->st.warm_start = 1;  // as osqp_warm_start does
-    return 0;
-  } OQ_BATCH_CATCH
-}
-
-c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_out, c_float *info_out, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (!x_out || !info_out || (b->m > 0 && !y_out)) { set_last_error("invalid batch data"); return 1; }
-  try {
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    BatchIO io = b->inputs();
-    io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : b->info_all.get();
-    io.x_stride = b->n; io.y_stride = b->m; io.info_stride = io.info_cols = 6;
-    // (a resolve that failed between its solve launch and k_batch_cert may have left directions where the records of
-    // infeasible instances hold zeros: the next one starts every instance from zero and rewrites every record)
-    io.rec = b->rec.get(); io.rec_stride = b->rec_stride;
-    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0) | (b->gap_rule ? RES_GAP : 0);
-    b->rec_raw = true;
-    launch_batch(b->dp, b->st, b->count, io, s);
-    launch_cert(*b, io, b->count, s);  // before anything else reads the records: it puts them back as a solve without RES_CERT leaves them
-    b->rec_raw = false;
-    b->pstat_live = b->st.polish != 0;
-    if (b->pstat_live) launch_polish(*b, io, b->count, s);
-    if (where) copy_d2d(b->info_all.get(), info_out, (size_t)b->count * 6, s);  // the statuses, for osqp_amd_batch_adjoint
-    if (!where) {
-      b->x_out.download(x_out, (size_t)b->count * b->n, s);
-      if (b->m) b->y_out.download(y_out, (size_t)b->count * b->m, s);
-      b->info_all.download(info_out, (size_t)b->count * 6, s);
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    b->mark(true);
-    return 0;
-  } OQ_BATCH_CATCH
-}
-
-// ---- the same five calls for a selection of the instances (include/osqp_amd.h, "*_rows") -------------------------------------
-c_int osqp_amd_batch_update_lin_cost_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *q_rows, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (!q_rows) { set_last_error("invalid batch data"); return 1; }
-  try {
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    if (!select_rows(*b, rows, k, s)) return 1;
-    b->mark_rows(false);
-    scatter_rows(*b, (int)k, b->n, device_ptr(q_rows, (size_t)k * b->n, where, b->in_a, s), b->q.get(), s);
-    HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-  } OQ_BATCH_CATCH
-}
-
 c_int osqp_amd_batch_update_bounds_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *l_rows, const c_float *u_rows,
                                         c_int where) {
+  return batch_update_bounds(handle, true, rows, k, l_rows, u_rows, where);
+}
+
+static c_int batch_update_matrices(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, const c_float *Px, const c_float *Ax, c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
+  const bool nothing = !Px && !Ax;
+  if (nothing && !subset) return 0;
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    if (!select_rows(*b, rows, k, s)) return 1;
-    if (b->m == 0 || (!l_rows && !u_rows)) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
-    const size_t len = (size_t)k * b->m;
-    // checked on the device against the stored bound of the same instance where one is kept, before anything changes
-    const double *ln = l_rows ? device_ptr(l_rows, len, where, b->in_a, s) : nullptr;
-    const double *un = u_rows ? device_ptr(u_rows, len, where, b->in_b, s) : nullptr;
-    int bad = 0;
-    HIP_CHECK(hipMemsetAsync(b->bad.get(), 0, sizeof(int), s));
-    OQ_LAUNCH(k_batch_check_bounds_rows, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, b->sel.get(), (int)k, b->m, ln, un, b->l.get(),
-              b->u.get(), b->bad.get());
-    b->bad.download(&bad, 1, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (bad) { set_last_error("lower bound greater than upper bound"); return 1; }
-    b->mark_rows(false);
-    if (ln) scatter_rows(*b, (int)k, b->m, ln, b->l.get(), s);
-    if (un) scatter_rows(*b, (int)k, b->m, un, b->u.get(), s);
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    if (nothing) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
+    mark(*b, v, false);
+    if (Px) put_rows(*b, v, b->nnzP, Px, where, b->in_a, b->Px, s);
+    if (Ax) put_rows(*b, v, b->nnzA, Ax, where, b->in_b, b->Ax, s);
+    // from scratch on the raw data with the current q, l, u, the served instances only; the scaled iterate stays as it is
+    resident_equilibrate(*b, v.launch, v.sel, s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
 }
-
+c_int osqp_amd_batch_update_matrices(osqp_amd_batch *handle, const c_float *Px_all, const c_float *Ax_all, c_int where) {
+  return batch_update_matrices(handle, false, nullptr, 0, Px_all, Ax_all, where);
+}
 c_int osqp_amd_batch_update_matrices_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *Px_rows, const c_float *Ax_rows,
                                           c_int where) {
+  return batch_update_matrices(handle, true, rows, k, Px_rows, Ax_rows, where);
+}
+
+static c_int batch_warm_start(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, const c_float *x, const c_float *y, c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
+  const bool nothing = !x && !y;
+  if (nothing && !subset) return 0;
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    if (!select_rows(*b, rows, k, s)) return 1;
-    if (!Px_rows && !Ax_rows) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
-    b->mark_rows(false);
-    if (Px_rows && b->nnzP) scatter_rows(*b, (int)k, b->nnzP, device_ptr(Px_rows, (size_t)k * b->nnzP, where, b->in_a, s), b->Px.get(), s);
-    if (Ax_rows && b->nnzA) scatter_rows(*b, (int)k, b->nnzA, device_ptr(Ax_rows, (size_t)k * b->nnzA, where, b->in_b, s), b->Ax.get(), s);
-    resident_equilibrate(*b, (int)k, b->sel.get(), s);  // the selected instances only: k workgroups
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    if (nothing) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
+    mark(*b, v, false);
+    const double *xd = x ? device_ptr(x, (size_t)v.launch * b->n, where, b->in_a, s) : nullptr;
+    const double *yd = y && b->m ? device_ptr(y, (size_t)v.launch * b->m, where, b->in_b, s) : nullptr;
+    OQ_LAUNCH(k_batch_warm, dim3(v.launch), dim3(256), 0, s, b->dp.P, v.launch, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride, v.sel);
     HIP_CHECK(hipStreamSynchronize(s));
+    b->st.warm_start = 1;  // a setting of the handle, as osqp_warm_start does
     return 0;
   } OQ_BATCH_CATCH
 }
-
+c_int osqp_amd_batch_warm_start(osqp_amd_batch *handle, const c_float *x_all, const c_float *y_all, c_int where) {
+  return batch_warm_start(handle, false, nullptr, 0, x_all, y_all, where);
+}
 c_int osqp_amd_batch_warm_start_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, const c_float *x_rows, const c_float *y_rows,
                                      c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  try {
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    if (!select_rows(*b, rows, k, s)) return 1;
-    if (!x_rows && !y_rows) { HIP_CHECK(hipStreamSynchronize(s)); return 0; }
-    b->mark_rows(false);
-    const double *xd = x_rows ? device_ptr(x_rows, (size_t)k * b->n, where, b->in_a, s) : nullptr;
-    const double *yd = y_rows && b->m ? device_ptr(y_rows, (size_t)k * b->m, where, b->in_b, s) : nullptr;
-    OQ_LAUNCH(k_batch_warm, dim3((unsigned)k), dim3(256), 0, s, b->dp.P, (int)k, b->Ax.get(), xd, yd, b->rec.get(), b->rec_stride,
-              (const int *)b->sel.get());
-    HIP_CHECK(hipStreamSynchronize(s));
-    b->st.warm_start = 1;  // a setting of the handle, as in osqp_amd_batch_warm_start
-    return 0;
-  } OQ_BATCH_CATCH
+  return batch_warm_start(handle, true, rows, k, x_rows, y_rows, where);
 }
 
-c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *x_out, c_float *y_out, c_float *info_out,
-                                  c_int where) {
+static c_int batch_resolve(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, c_float *x_out, c_float *y_out, c_float *info_out,
+                           c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
   if (!x_out || !info_out || (b->m > 0 && !y_out)) { set_last_error("invalid batch data"); return 1; }
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    if (!select_rows(*b, rows, k, s)) return 1;
-    const int cnt = (int)k;
-    // compact outputs: row j of x / y / info is of instance rows[j] (host pointers: through the first k rows of the staging)
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    // host pointers: through the first v.launch rows of the staging.  The info rows of every instance go straight into
+    // info_all; those of a selection are compact (info_out) and scattered into it below
+    DevBuf<double> &info_stage = v.subset ? b->info_out : b->info_all;
     BatchIO io = b->inputs();
-    io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : b->info_out.get();
+    io.x = where ? x_out : b->x_out.get(); io.y = where ? y_out : b->y_out.get(); io.info = where ? info_out : info_stage.get();
     io.x_stride = b->n; io.y_stride = b->m; io.info_stride = io.info_cols = 6;
-    io.rec = b->rec.get(); io.rec_stride = b->rec_stride; io.sel = b->sel.get();
-    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0) | (b->gap_rule ? RES_GAP : 0);  // rec_raw: as osqp_amd_batch_resolve
+    // (a resolve that failed between its solve launch and k_batch_cert may have left directions where the records of
+    // infeasible instances hold zeros: the next one starts every instance it serves from zero and rewrites their records)
+    io.rec = b->rec.get(); io.rec_stride = b->rec_stride; io.sel = v.sel;
+    io.res_mode = RES_SOLVE | RES_CERT | (b->st.warm_start && !b->rec_raw ? RES_WARM : 0) | (b->gap_rule ? RES_GAP : 0);
     b->rec_raw = true;
-    launch_batch(b->dp, b->st, cnt, io, s);
-    launch_cert(*b, io, cnt, s);
+    launch_batch(b->dp, b->st, v.launch, io, s);
+    launch_cert(*b, io, v.launch, s);  // before anything else reads the records: it puts them back as a solve without RES_CERT leaves them
     b->rec_raw = false;
-    // the polish status is of every instance's own last resolve: the others keep theirs (all 0 while the buffer is not live)
+    // the polish status is of every instance's own last resolve: after a selection the others keep theirs (all 0 while the
+    // buffer is not live), and the selected ones read 0 when polish is off
     const bool was_live = b->pstat_live;
-    if (!was_live) b->pstat.zero(s);
-    b->pstat_live = true;
-    if (b->st.polish) launch_polish(*b, io, cnt, s);
-    else if (was_live) OQ_LAUNCH(k_batch_fill_rows, dim3(blocks_for(cnt, 256)), dim3(256), 0, s, b->sel.get(), cnt, 0.0, b->pstat.get());
-    scatter_rows(*b, cnt, 6, io.info, b->info_all.get(), s);  // after the polish launch, which rewrites the residuals
+    if (v.subset && !was_live) b->pstat.zero(s);
+    b->pstat_live = v.subset || b->st.polish != 0;
+    if (b->st.polish) launch_polish(*b, io, v.launch, s);
+    else if (v.subset && was_live) OQ_LAUNCH(k_batch_fill_rows, dim3(blocks_for(v.launch, 256)), dim3(256), 0, s, v.sel, v.launch, 0.0, b->pstat.get());
+    // the statuses, for osqp_amd_batch_adjoint: after the polish launch, which rewrites the residuals
+    if (v.subset) scatter_rows(*b, v.launch, 6, io.info, b->info_all.get(), s);
+    else if (where) copy_d2d(b->info_all.get(), info_out, (size_t)v.launch * 6, s);
     if (!where) {
-      b->x_out.download(x_out, (size_t)cnt * b->n, s);
-      if (b->m) b->y_out.download(y_out, (size_t)cnt * b->m, s);
-      b->info_out.download(info_out, (size_t)cnt * 6, s);
+      b->x_out.download(x_out, (size_t)v.launch * b->n, s);
+      if (b->m) b->y_out.download(y_out, (size_t)v.launch * b->m, s);
+      info_stage.download(info_out, (size_t)v.launch * 6, s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
-    b->mark_rows(true);
+    mark(*b, v, true);
     return 0;
   } OQ_BATCH_CATCH
+}
+c_int osqp_amd_batch_resolve(osqp_amd_batch *handle, c_float *x_out, c_float *y_out, c_float *info_out, c_int where) {
+  return batch_resolve(handle, false, nullptr, 0, x_out, y_out, info_out, where);
+}
+c_int osqp_amd_batch_resolve_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *x_out, c_float *y_out, c_float *info_out,
+                                  c_int where) {
+  return batch_resolve(handle, true, rows, k, x_out, y_out, info_out, where);
 }
 
 c_int osqp_amd_batch_adjoint(osqp_amd_batch *handle, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl, c_float *du,
@@ -1204,45 +1188,33 @@ c_int osqp_amd_batch_jvp_rows(osqp_amd_batch *handle, const c_int *rows, c_int k
   return batch_jvp(handle, true, rows, k, ndir, tq, tl, tu, tPx, tAx, tx_out, ty_out, act_out, status_out, where);
 }
 
-c_int osqp_amd_batch_polish_status(osqp_amd_batch *handle, c_float *status_out, c_int where) {
+static c_int batch_polish_status(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, c_float *status_out, c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
   if (!status_out) { set_last_error("invalid batch data"); return 1; }
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    const size_t len = (size_t)b->count;
-    if (!b->pstat_live) {  // no resolve yet, or the last one did not polish: all 0
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    const size_t len = (size_t)v.launch;
+    if (!b->pstat_live) {  // no resolve yet, or the last one did not polish: all 0, whatever the buffer holds
       if (where) HIP_CHECK(hipMemsetAsync(status_out, 0, len * sizeof(double), s));
       else std::fill(status_out, status_out + len, 0.0);
-    } else if (where) copy_d2d(status_out, b->pstat.get(), len, s);
-    else b->pstat.download(status_out, len, s);
-    HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-  } OQ_BATCH_CATCH
-}
-
-c_int osqp_amd_batch_polish_status_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *status_out, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (!status_out) { set_last_error("invalid batch data"); return 1; }
-  try {
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    if (!select_rows(*b, rows, k, s)) return 1;
-    const size_t len = (size_t)k;
-    if (!b->pstat_live) {  // as osqp_amd_batch_polish_status: all 0
-      if (where) HIP_CHECK(hipMemsetAsync(status_out, 0, len * sizeof(double), s));
-      else std::fill(status_out, status_out + len, 0.0);
-    } else if (where) gather_rows(*b, (int)k, 1, b->pstat.get(), status_out, s);
-    else {  // host pointer: gathered into the staging of the derivative calls, then down
-      if (b->adj_out.n < len) b->adj_out.alloc(len);
-      gather_rows(*b, (int)k, 1, b->pstat.get(), b->adj_out.get(), s);
-      b->adj_out.download(status_out, len, s);
+    } else {  // a selection with a host pointer: gathered into the staging, then down
+      const OutStage o(*b, v.subset && !where, {status_out}, {len});
+      give_rows(*b, v, 1, b->pstat, o.dev[0], where, s);
+      o.download(s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
+}
+c_int osqp_amd_batch_polish_status(osqp_amd_batch *handle, c_float *status_out, c_int where) {
+  return batch_polish_status(handle, false, nullptr, 0, status_out, where);
+}
+c_int osqp_amd_batch_polish_status_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *status_out, c_int where) {
+  return batch_polish_status(handle, true, rows, k, status_out, where);
 }
 
 c_int osqp_amd_batch_update_polish(osqp_amd_batch *handle, c_int polish_new, c_int polish_refine_iter_new) {
@@ -1261,17 +1233,9 @@ c_int osqp_amd_batch_update_setting(osqp_amd_batch *handle, const char *name, c_
   if (!b) return 1;
   if (!name) { set_last_error("invalid batch data"); return 1; }
   try {
-    // the rule of the name from the table of the single-model updates (engine.hpp); an integer setting takes integral values
     OSQPSettings st = b->st;
     bool known = false, ok = false;
-#define OQ_BATCH_SETTING(field, type, cond)                                                                       \
-    if (!known && !strcmp(name, #field)) {                                                                          \
-      known = true;                                                                                                 \
-      const bool whole = std::is_floating_point<type>::value || (value == std::floor(value) && std::fabs(value) <= 9007199254740992.0); \
-      if (whole && setting_ok_##field((type)value)) { st.field = (type)value; ok = true; }                          \
-    }
-    OQ_UPDATABLE_SETTINGS(OQ_BATCH_SETTING)
-#undef OQ_BATCH_SETTING
+    parse_setting(name, value, st, known, ok);
     if (!known) { set_last_error(std::string(name) + " cannot be updated or is not recognized"); return 1; }
     if (!ok) { set_last_error(std::string("invalid value for the setting ") + name); return 1; }
     if (!strcmp(name, "polish") || !strcmp(name, "polish_refine_iter")) { set_polish(*b, st.polish, st.polish_refine_iter); return 0; }
@@ -1287,7 +1251,8 @@ c_int osqp_amd_batch_update_setting(osqp_amd_batch *handle, const char *name, c_
   } OQ_BATCH_CATCH
 }
 
-c_int osqp_amd_batch_certificates(osqp_amd_batch *handle, c_float *prim_inf_cert_out, c_float *dual_inf_cert_out, c_int where) {
+static c_int batch_certificates(osqp_amd_batch *handle, bool subset, const c_int *rows, c_int k, c_float *prim_inf_cert_out,
+                                c_float *dual_inf_cert_out, c_int where) {
   BatchPlan *b = resident_plan(handle);
   if (!b) return 1;
   if (b->m == 0) prim_inf_cert_out = nullptr;
@@ -1295,46 +1260,27 @@ c_int osqp_amd_batch_certificates(osqp_amd_batch *handle, c_float *prim_inf_cert
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    c_float *const out[2] = {prim_inf_cert_out, dual_inf_cert_out};
-    DevBuf<double> *const src[2] = {&b->pcert, &b->dcert};
-    const size_t len[2] = {(size_t)b->count * b->m, (size_t)b->count * b->n};
-    for (int k = 0; k < 2; k++) {
-      if (!out[k]) continue;
-      if (where) copy_d2d(out[k], src[k]->get(), len[k], s); else src[k]->download(out[k], len[k], s);
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    const DevBuf<double> *const src[2] = {&b->pcert, &b->dcert};
+    const int cols[2] = {b->m, b->n};
+    // a selection with host pointers: the two are gathered into the shared staging, in this order
+    const OutStage o(*b, v.subset && !where, {prim_inf_cert_out, dual_inf_cert_out}, {(size_t)v.launch * b->m, (size_t)v.launch * b->n});
+    for (int j = 0; j < 2; j++) {
+      if (!o.host[j]) continue;
+      give_rows(*b, v, cols[j], *src[j], o.dev[j], where, s);
+      o.download(j, s);  // each behind its own gather, as the copies always were issued
     }
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
 }
-
+c_int osqp_amd_batch_certificates(osqp_amd_batch *handle, c_float *prim_inf_cert_out, c_float *dual_inf_cert_out, c_int where) {
+  return batch_certificates(handle, false, nullptr, 0, prim_inf_cert_out, dual_inf_cert_out, where);
+}
 c_int osqp_amd_batch_certificates_rows(osqp_amd_batch *handle, const c_int *rows, c_int k, c_float *prim_inf_cert_out,
                                        c_float *dual_inf_cert_out, c_int where) {
-  BatchPlan *b = resident_plan(handle);
-  if (!b) return 1;
-  if (b->m == 0) prim_inf_cert_out = nullptr;
-  if (!prim_inf_cert_out && !dual_inf_cert_out) { set_last_error("invalid batch data: no certificate was asked for"); return 1; }
-  try {
-    DeviceScope on_dev(b->device);
-    hipStream_t s = nullptr;
-    if (!select_rows(*b, rows, k, s)) return 1;
-    c_float *const out[2] = {prim_inf_cert_out, dual_inf_cert_out};
-    const double *const src[2] = {b->pcert.get(), b->dcert.get()};
-    const int cols[2] = {b->m, b->n};
-    // host pointers: the two share the staging of the derivative calls, in this order
-    size_t total = 0;
-    for (int j = 0; j < 2; j++) if (out[j]) total += (size_t)k * cols[j];
-    if (!where && b->adj_out.n < total) b->adj_out.alloc(total);
-    size_t at = 0;
-    for (int j = 0; j < 2; j++) {
-      if (!out[j]) continue;
-      const size_t len = (size_t)k * cols[j];
-      double *const dev = where ? out[j] : b->adj_out.get() + at;
-      gather_rows(*b, (int)k, cols[j], src[j], dev, s);
-      if (!where) { HIP_CHECK(hipMemcpyAsync(out[j], dev, len * sizeof(double), hipMemcpyDeviceToHost, s)); at += len; }
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    return 0;
-  } OQ_BATCH_CATCH
+  return batch_certificates(handle, true, rows, k, prim_inf_cert_out, dual_inf_cert_out, where);
 }
 
 // osqp_amd_batch_duality (subset false) and osqp_amd_batch_duality_rows: one launch of k_batch_gap (batch_gap.hpp), one
@@ -1348,19 +1294,17 @@ static c_int batch_duality(osqp_amd_batch *handle, bool subset, const c_int *row
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    if (subset) {  // only the selected instances must be current; nothing is launched when one is not
-      if (!select_rows(*b, rows, k, s)) return 1;
-      if (!holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
-    }
-    const int launch = subset ? (int)k : b->count;
-    const size_t len = (size_t)launch * 3;
-    if (!where && b->adj_out.n < len) b->adj_out.alloc(len);
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    // only the selected instances must be current; nothing is launched when one is not
+    if (v.subset && !holds_current(*b, &b->sel_host)) { HIP_CHECK(hipStreamSynchronize(s)); return 1; }
+    const OutStage o(*b, !where, {out}, {(size_t)v.launch * 3});
     gap::Args a;
     a.Px = b->Px.get(); a.q = b->q.get(); a.l = b->l.get(); a.u = b->u.get(); a.info = b->info_all.get(); a.rec = b->rec.get();
-    a.out = where ? out : b->adj_out.get();
-    a.info_stride = 6; a.rec_stride = b->rec_stride; a.sel = subset ? b->sel.get() : nullptr;
-    OQ_LAUNCH(gap::k_batch_gap, dim3(launch), dim3(gap::GT), 0, s, b->dp.P, launch, a);
-    if (!where) HIP_CHECK(hipMemcpyAsync(out, a.out, len * sizeof(double), hipMemcpyDeviceToHost, s));
+    a.out = o.dev[0];
+    a.info_stride = 6; a.rec_stride = b->rec_stride; a.sel = v.sel;
+    OQ_LAUNCH(gap::k_batch_gap, dim3(v.launch), dim3(gap::GT), 0, s, b->dp.P, v.launch, a);
+    o.download(s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
@@ -1395,13 +1339,12 @@ static c_int batch_gap_refusals(osqp_amd_batch *handle, bool subset, const c_int
   try {
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
-    if (subset && !select_rows(*b, rows, k, s)) return 1;
-    const int launch = subset ? (int)k : b->count;
-    if (!where && b->adj_out.n < (size_t)launch) b->adj_out.alloc((size_t)launch);
-    double *const dev = where ? out : b->adj_out.get();
-    OQ_LAUNCH(k_batch_gap_refusals, dim3(blocks_for(launch, 256)), dim3(256), 0, s, subset ? (const int *)b->sel.get() : (const int *)nullptr, launch,
-              (int)b->gap_rule, (const double *)b->rec.get(), b->rec_stride, dev);
-    if (!where) HIP_CHECK(hipMemcpyAsync(out, dev, (size_t)launch * sizeof(double), hipMemcpyDeviceToHost, s));
+    Served v;
+    if (!serve(*b, subset, rows, k, s, v)) return 1;
+    const OutStage o(*b, !where, {out}, {(size_t)v.launch});
+    OQ_LAUNCH(k_batch_gap_refusals, dim3(blocks_for(v.launch, 256)), dim3(256), 0, s, v.sel, v.launch, (int)b->gap_rule, (const double *)b->rec.get(),
+              b->rec_stride, o.dev[0]);
+    o.download(s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
@@ -1436,20 +1379,14 @@ c_int osqp_amd_shared_batch_setup(osqp_amd_shared_batch **out, c_int count, c_in
   try {
     if (count <= 0 || count > 16777216) { set_last_error("invalid batch data"); return 1; }
     if (n > shared::kMaxN) { set_last_error("a shared batch supports 1 <= n <= 256 and fewer than 65536 rows / non-zeros (n = " + std::to_string(n) + ")"); return 1; }
-    {
-      const int before = g_batch_large;  // the data checks of the batched path, for ONE instance and with its n <= 256 cap
-      g_batch_large = 1;
-      const BatchProblem one{1, n, m, Pp, Pi, Px, Ap, Ai, Ax, q0, l0, u0, settings};
-      const c_int bad = validate_batch_data(one, true);
-      g_batch_large = before;
-      if (bad) return bad;
-    }
+    // the data checks of the batched path, for ONE instance and with the cap of this path
+    const BatchProblem prob{1, n, m, Pp, Pi, Px, Ap, Ai, Ax, q0, l0, u0, settings};
+    if (c_int bad = validate_batch_data(prob, true, shared::kMaxN)) return bad;
     if (settings->adaptive_rho) {
       set_last_error("adaptive_rho must be 0 for a shared batch: all instances share one inverse of the reduced KKT matrix, which is built for one rho "
                      "(change it with osqp_amd_shared_batch_update_setting(\"rho\"))");
       return 2;
     }
-    const BatchProblem prob{1, n, m, Pp, Pi, Px, Ap, Ai, Ax, q0, l0, u0, settings};
     const HostPattern hp = host_pattern(prob);
     std::unique_ptr<SharedBatch> b(new SharedBatch());
     b->plan = shared_plan(n, m, hp.nnzA, hp.nnzF);
@@ -1559,14 +1496,8 @@ c_int osqp_amd_shared_batch_update_setting(osqp_amd_shared_batch *handle, const 
     for (const char *k : kNames) listed = listed || !strcmp(name, k);
     if (!listed) { set_last_error(std::string(name) + " cannot be updated on a shared batch or is not recognized"); return 1; }
     OSQPSettings st = b->st;
-    bool ok = false;
-#define OQ_SHARED_SETTING(field, type, cond)                                                                                            \
-    if (!strcmp(name, #field)) {                                                                                                          \
-      const bool whole = std::is_floating_point<type>::value || (value == std::floor(value) && std::fabs(value) <= 9007199254740992.0); \
-      if (whole && setting_ok_##field((type)value)) { st.field = (type)value; ok = true; }                                                \
-    }
-    OQ_UPDATABLE_SETTINGS(OQ_SHARED_SETTING)
-#undef OQ_SHARED_SETTING
+    bool known = false, ok = false;  // known: every listed name is in the table
+    parse_setting(name, value, st, known, ok);
     if (!ok) { set_last_error(std::string("invalid value for the setting ") + name); return 1; }
     if (!strcmp(name, "rho")) {  // one re-factorisation; the carried iterates stay, as with osqp_update_rho
       DeviceScope on_dev(b->device);
