@@ -1026,8 +1026,31 @@ c_int osqp_amd_duality(OSQPWorkspace *work, c_float *out, c_int count);
  *            (one k_shared_factor launch; the carried iterates stay, as with osqp_update_rho).  Any other name is refused.
  * device_bytes()  the device memory the handle holds, staging included.
  * where: 0 host pointers, 1 device pointers on the handle's device.  Every call blocks until done; 0 = success, otherwise
- * osqp_amd_last_error has the reason.  The handle has no polish, derivatives, certificates or `rows` entries, and its
- * matrices cannot be updated: a new model is a new handle. */
+ * osqp_amd_last_error has the reason.
+ * adjoint()  gradients of a scalar loss with respect to the data through the solutions of the last resolve (DESIGN.md section
+ *            13.4): the mathematics and the five-gradient table of osqp_amd_batch_adjoint, the rules of
+ *            osqp_amd_batch_adjoint_multi -- `ncot` pairs (dx, dy) per instance in cotangent-major arrays [ncot x count x n],
+ *            [ncot x count x m], NULL = zeros (not both); dq, dl, du, dPx, dAx [ncot x count x cols], NULL = not wanted; act_out
+ *            [count x m] (-1 lower, 1 upper, 0 inactive; a row with l == u is active and lower) and status_out [count] once per
+ *            instance.  Status 1: differentiated; 0: the instance's last status is not OSQP_SOLVED; -1: the factorisation
+ *            failed; rows with status != 1 are zeros.  Instance i is differentiated as the shared instance it is: the scaling
+ *            is that of the base data.
+ *            dPx_sum [ncot x nnzP], dAx_sum [ncot x nnzA] (NULL = not wanted): the gradients of the SHARED values, the sums
+ *            over the instances of the per-instance rows r_i, formed on the device in a fixed order that depends on count alone:
+ *              s_b = ((r_16b + r_16b+1) + ...) + r_16b+15   over each block of 16 consecutive instances (the last one shorter),
+ *              sum = ((s_0 + s_1) + s_2) + ...,
+ *            plain IEEE additions, no atomics -- a loop in that order reproduces the bits, and they are the same whether or not
+ *            dPx / dAx were asked for (then the rows go through a bounded scratch of the handle).  The gradients of
+ *            (instance, cotangent) have the same bits whatever count, ncot, the position, the neighbours or the outputs wanted.
+ *            The form of the kernel follows from the shape: the factor in LDS where that layout fits 160 KB (n <= 128),
+ *            otherwise in a fixed number of n x n blocks of global scratch, allocated at the first such call and counted by
+ *            device_bytes() -- never count x n x n.  A shape neither form serves is refused ("instance too large ...").
+ *            CURRENCY: the call is refused (1, a message, nothing launched) before the first resolve and after any
+ *            update_lin_cost, update_bounds, warm_start or update_setting("rho") that followed the last resolve.  It only
+ *            reads the handle: a resolve after it has the bits of one without it.  One call counts once in
+ *            osqp_amd_shared_batch_adjoint_launches, whatever ncot is; a refused call does not count.
+ * The handle has no polish, forward sensitivities, certificates, duality or `rows` entries, and its matrices cannot be
+ * updated: a new model is a new handle. */
 typedef struct osqp_amd_shared_batch osqp_amd_shared_batch;
 c_int osqp_amd_shared_batch_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out /* [4] */);
 c_int osqp_amd_shared_batch_setup(osqp_amd_shared_batch **out, c_int count, c_int n, c_int m,
@@ -1040,6 +1063,11 @@ c_int osqp_amd_shared_batch_update_bounds(osqp_amd_shared_batch *batch, const c_
 c_int osqp_amd_shared_batch_warm_start(osqp_amd_shared_batch *batch, const c_float *x_all, const c_float *y_all, c_int where);
 c_int osqp_amd_shared_batch_resolve(osqp_amd_shared_batch *batch, c_float *x_out, c_float *y_out, c_float *info_out, c_int where);
 c_int osqp_amd_shared_batch_update_setting(osqp_amd_shared_batch *batch, const char *name, c_float value);
+c_int osqp_amd_shared_batch_adjoint(osqp_amd_shared_batch *batch, c_int ncot, const c_float *dx, const c_float *dy,
+                                    c_float *dq, c_float *dl, c_float *du, c_float *dPx, c_float *dAx, /* [ncot x count x cols] or NULL */
+                                    c_float *dPx_sum, c_float *dAx_sum,                                /* [ncot x nnzP], [ncot x nnzA] or NULL */
+                                    c_float *act_out, c_float *status_out, c_int where);
+c_int osqp_amd_shared_batch_adjoint_launches(void);
 c_int osqp_amd_shared_batch_device_bytes(osqp_amd_shared_batch *batch);
 c_int osqp_amd_shared_batch_launches(void);
 c_int osqp_amd_shared_batch_destroy(osqp_amd_shared_batch *batch);

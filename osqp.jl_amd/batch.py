@@ -922,13 +922,21 @@ def shared_launches(lib):
     return int(lib.osqp_amd_shared_batch_launches())
 
 
+def shared_adjoint_launches(lib):
+    """Accepted `SharedBatch.adjoint` calls of this process so far (osqp_amd_shared_batch_adjoint_launches): one per call, whatever
+    the number of cotangents; a refused call does not count."""
+    return int(lib.osqp_amd_shared_batch_adjoint_launches())
+
+
 class SharedBatch:
     """ONE model and `count` right-hand sides on a shared KKT inverse (osqp_amd_shared_batch_setup).
     Instance i is `setup(P, q0, A, l0, u0)`, `update(q=q[i], l=l[i], u=u[i])`, `solve()` on a fresh model: scaling comes from the
     base data, rho is fixed (`adaptive_rho` is set to 0 here unless the caller passes it; anything else is refused by the
     library) and every row of every instance must keep the kind -- loose, equality, inequality -- it has under (l0, u0).
     After setup every instance holds (q0, l0, u0).  Arrays of `update` / `warm_start` and the `out` of `solve` are numpy arrays
-    or device arrays (`DeviceArray`, torch tensors), as for `ResidentBatch`; there is no `rows=`, polish or derivative here."""
+    or device arrays (`DeviceArray`, torch tensors), as for `ResidentBatch`.  `adjoint` differentiates the solutions of the last
+    `solve()`, per instance and -- for the shared values of P and A -- summed over the instances; there is no `rows=`, polish,
+    `jvp`, certificate or duality call here, and the matrices cannot be updated: a new model is a new handle."""
 
     SETTINGS = ("max_iter", "eps_abs", "eps_rel", "eps_prim_inf", "eps_dual_inf", "alpha", "check_termination",
                 "scaled_termination", "rho")
@@ -949,6 +957,8 @@ class SharedBatch:
         Pp, Pi = np.ascontiguousarray(P.indptr, dtype=np.int64), np.ascontiguousarray(P.indices, dtype=np.int64)
         Ap, Ai = np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int64)
         Px, Ax = _as_f64(P.data), _as_f64(A.data)
+        self.nnzP, self.nnzA = P.nnz, A.nnz
+        self.Px, self.Ax = Px.copy(), Ax.copy()  # the shared values, in the order of the gradients "Px_sum" / "Ax_sum"
         rc = lib.osqp_amd_shared_batch_setup(C.byref(self.handle), self.count, self.n, self.m, _iptr(Pp), _iptr(Pi), _fptr(Px), _iptr(Ap),
                                              _iptr(Ai), _fptr(Ax), _fptr(q0), _fptr(l0), _fptr(u0), C.byref(stgs), self.device)
         if rc != 0:
@@ -1013,6 +1023,87 @@ class SharedBatch:
             if value is None:
                 continue
             self._call("settings update", self.lib.osqp_amd_shared_batch_update_setting(self.handle, key.encode(), float(value)))
+
+    ADJOINT_WANT = ("q", "l", "u", "Px", "Ax")
+    ADJOINT_SUMS = ("Px", "Ax")
+
+    def adjoint(self, dx=None, dy=None, want=ADJOINT_WANT, sums=(), out=None):
+        """Gradients of a scalar loss with respect to the data, through the solutions of the last `solve()`
+        (osqp_amd_shared_batch_adjoint): dx [count x n], dy [count x m] are the loss's gradients with respect to x and y (None:
+        zero; not both), or both with a leading axis [ncot x count x .] for several cotangents in one call.  Returns a dict with
+        the entries of `want` -- "q", "l", "u", "Px", "Ax", per instance, shaped like the cotangents -- the entries of `sums`
+        (a subset of ("Px", "Ax")) under "Px_sum" [nnz(P upper)] and "Ax_sum" [nnz(A)] ([ncot x .] with a leading axis): the
+        gradients of the SHARED values, summed over the instances on the device in blocks of 16 (include/osqp_amd.h has the
+        order; the bits do not depend on `want`) -- plus "act" [count x m] and "status" [count] (1 differentiated, 0 no
+        solution, -1 factorisation failed; such rows are zeros).  Entries of width 0 are left out.  Host form: numpy dx / dy,
+        out=None, numpy results.  Device form: dx / dy device arrays and `out` a dict of float64 device arrays for the wanted
+        entries (the sums as [1 x cols] or [cols] without a leading axis) and, optionally, "act" and "status" ([count x 1]).  The handle
+        must hold the solutions of its current data: a `solve()` since the last `update`, `warm_start` or rho update."""
+        cnt = self.count
+        cols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA, Px_sum=self.nnzP, Ax_sum=self.nnzA, act=self.m, status=1)
+        want, sums = tuple(want), tuple(sums)
+        for w in want:
+            if w not in self.ADJOINT_WANT:
+                raise ValueError(f"want: unknown gradient {w!r}; expected a subset of {self.ADJOINT_WANT}")
+        for w in sums:
+            if w not in self.ADJOINT_SUMS:
+                raise ValueError(f"sums: unknown sum {w!r}; expected a subset of {self.ADJOINT_SUMS}")
+        if dx is None and dy is None:
+            raise ValueError("dx and dy: at least one incoming gradient is needed")
+        shapes = {k: tuple(v.shape) if hasattr(v, "data_ptr") else np.asarray(v).shape for k, v in (("dx", dx), ("dy", dy)) if v is not None}
+        dims = {k: len(s) for k, s in shapes.items()}
+        if len(set(dims.values())) > 1 or next(iter(dims.values())) not in (2, 3):
+            raise ValueError(f"dx and dy: expected both [count x cols] or both [ncot x count x cols], got dimensions {dims}")
+        many = next(iter(dims.values())) == 3
+        ncot = 1
+        if many:
+            ncots = {k: int(s[0]) for k, s in shapes.items()}
+            if len(set(ncots.values())) > 1:
+                raise ValueError(f"dx and dy: they must carry the same number of cotangents, got {ncots}")
+            ncot = next(iter(ncots.values()))
+            if ncot < 1:
+                raise ValueError("dx and dy: ncot must be at least 1")
+        lead = (ncot, cnt) if many else (cnt,)
+        got = [None if v is None else _batch_array(nm, v, lead + (k,)) for nm, v, k in (("dx", dx, self.n), ("dy", dy, self.m))]
+        forms = {g[2] for g in got if g is not None}
+        if len(forms) > 1:
+            raise ValueError("dx and dy must both be host arrays or both device arrays")
+        ptrs, where = [None if g is None else g[1] for g in got], forms.pop()
+        wanted = want + tuple(w + "_sum" for w in sums)
+        oshape = {k: (cnt, cols[k]) if k in ("act", "status") else
+                  ((ncot if many else 1, cols[k]) if k.endswith("_sum") else lead + (cols[k],)) for k in cols}
+        order = self.ADJOINT_WANT + ("Px_sum", "Ax_sum", "act", "status")
+        names = [k for k in order if cols[k] > 0]
+        if not where:
+            if out is not None:
+                raise ValueError("out: host gradients (numpy dx / dy) return numpy arrays; pass device arrays for dx / dy to fill `out`")
+            res = {k: np.empty(oshape[k]) for k in names if k in wanted or k in ("act", "status")}
+            addr = {k: v.ctypes.data for k, v in res.items()}
+        else:
+            if not isinstance(out, dict):
+                raise ValueError("out: device gradients need a dict of device arrays to fill, one per entry of `want` and `sums`")
+            for k in out:
+                if k not in cols:
+                    raise ValueError(f"out: unknown entry {k!r}")
+            addr = {}
+            for k in names:
+                if k in out and (k in wanted or k in ("act", "status")):
+                    if not hasattr(out[k], "data_ptr"):
+                        raise ValueError(f"out[{k!r}]: expected a device array (DeviceArray, torch tensor)")
+                    flat = k.endswith("_sum") and not many and len(tuple(out[k].shape)) == 1  # a torch vector [cols]
+                    addr[k] = _batch_array(f"out[{k!r}]", out[k], (cols[k],) if flat else oshape[k])[1]
+                elif k in wanted:
+                    raise ValueError(f"out: no array for the wanted gradient {k!r}")
+            res = out
+        self._call("adjoint", self.lib.osqp_amd_shared_batch_adjoint(self.handle, ncot, ptrs[0], ptrs[1], *[addr.get(k) for k in order], where))
+        if not where:
+            for k in ("Px_sum", "Ax_sum"):
+                if k in res and not many:
+                    res[k] = res[k][0]
+            if "act" in res:
+                res["act"] = res["act"].astype(np.int64)
+            res["status"] = res["status"].ravel().astype(np.int64)
+        return res
 
     def device_bytes(self):
         return int(self.lib.osqp_amd_shared_batch_device_bytes(self.handle))

@@ -30,6 +30,8 @@
 //   batch_shared.hpp  the shared batch (osqp_amd_shared_batch_*): one model and many right-hand sides on ONE inverse --
 //                     k_shared_factor (setup), k_batch_solve_shared (T instances per workgroup, the dense step on the fp64
 //                     matrix cores) and their small kernels; a handle type of its own (SharedBatch below);
+//   batch_shared_adjoint.hpp  k_shared_adjoint -- the adjoint of the shared batch from the model block and the tile records
+//                     (osqp_amd_shared_batch_adjoint), and k_shared_reduce_rows, the summed matrix gradients in a fixed order;
 //   this file         the small kernels (warm start, rho fill, bound check, the row scatter and gather of a selection, MPC generator), the
 //                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.  A resident call exists for every instance and
 //                     for a selection (osqp_amd_batch_X, osqp_amd_batch_X_rows): ONE static body batch_X(handle, subset, rows, k, ...)
@@ -57,6 +59,7 @@
 #include "batch_solve.hpp"
 #include "batch_large.hpp"
 #include "batch_shared.hpp"
+#include "batch_shared_adjoint.hpp"
 #include "rng.hpp"
 
 namespace oq {
@@ -523,12 +526,13 @@ void give_rows(const BatchPlan &b, const Served &v, int cols, const DevBuf<doubl
 // pointers.  Staged (host pointers): the wanted ones share the handle's adj_out at running offsets, in the order given, and
 // download() issues their copies once the launches are on the stream.
 struct OutStage {
-  c_float *host[7];
-  size_t len[7];
-  double *dev[7];
+  c_float *host[9];
+  size_t len[9];
+  double *dev[9];
   int count = 0;
   bool staged;
-  OutStage(BatchPlan &b, bool staged_, std::initializer_list<c_float *> outs, std::initializer_list<size_t> lens) : staged(staged_) {
+  template <typename Handle>  // BatchPlan or SharedBatch: whoever owns an adj_out
+  OutStage(Handle &b, bool staged_, std::initializer_list<c_float *> outs, std::initializer_list<size_t> lens) : staged(staged_) {
     size_t total = 0, at = 0;
     for (c_float *h : outs) { host[count] = h; len[count] = lens.begin()[count]; if (h) total += len[count]; count++; }
     if (staged && b.adj_out.n < total) b.adj_out.alloc(total);
@@ -675,11 +679,17 @@ struct SharedBatch {
   shared::TileLayout TL;
   DevBuf<double> Px, Ax, q0, l0, u0;   // the raw base data: k_shared_factor runs on them again after a rho update
   DevBuf<double> model, scratch, tiles;
-  DevBuf<double> in_a, in_b, x_out, y_out, info_out;  // staging of host-pointer calls
+  DevBuf<double> in_a, in_b, x_out, y_out, info_out, adj_out;  // staging of host-pointer calls
   DevBuf<unsigned long long> flag;
   std::vector<double> hdr;  // c, rho, pd of the model block
+  // the adjoint (osqp_amd_shared_batch_adjoint): status [count], the status_val of the last resolve; current: the tile records
+  // hold the solutions of the current data; adj_factor: the W factor blocks of the form with the factor in global scratch,
+  // adj_rows: the bounded row scratch of the summed matrix gradients -- both allocated at first use
+  DevBuf<double> status, adj_factor, adj_rows;
+  bool current = false;
   size_t device_bytes() const {
-    return (Px.n + Ax.n + q0.n + l0.n + u0.n + model.n + scratch.n + tiles.n + in_a.n + in_b.n + x_out.n + y_out.n + info_out.n + 1) * sizeof(double);
+    return (Px.n + Ax.n + q0.n + l0.n + u0.n + model.n + scratch.n + tiles.n + in_a.n + in_b.n + x_out.n + y_out.n + info_out.n + adj_out.n + status.n +
+            adj_factor.n + adj_rows.n + 1) * sizeof(double);
   }
 };
 SharedBatch *shared_handle(osqp_amd_shared_batch *h) {
@@ -717,6 +727,35 @@ bool shared_bounds_ok(SharedBatch &b, const double *l, const double *u, hipStrea
   else set_last_error("the bounds change the kind of a row (loose / equality / inequality) from the one it has under the base bounds, which the shared "
                       "inverse was built for (" + at + ")");
   return false;
+}
+
+// ---- the adjoint of the shared batch (batch_shared_adjoint.hpp) ----------------------------------------
+int g_shared_adjoint_launches = 0;  // accepted calls of osqp_amd_shared_batch_adjoint by this process (_adjoint_launches)
+constexpr size_t kSharedRowScratch = (size_t)64 << 20;  // bytes of the row scratch of the summed matrix gradients (at least one block of 16)
+// The form of k_shared_adjoint a shape takes, from the shape alone: M as a packed triangle in LDS whenever that layout fits
+// (n <= 128: factor_solve holds two entries per lane), otherwise the factor in global scratch; a shape neither serves is an Error.
+// blocks: W, the factor blocks of the form with the factor in global scratch = the workgroups of its launches: one per compute
+// unit, two where the LDS of the layout lets two workgroups share a compute unit (185 VGPRs allow no third) -- 0 for the LDS form
+struct SharedAdjointPlan { bool large; polish::Layout L; int blocks; };
+SharedAdjointPlan shared_adjoint_plan(const Pattern &P) {
+  polish::Layout L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, false);
+  if (P.n <= kPivotW && L.total <= polish::kLdsLimit) return SharedAdjointPlan{false, L, 0};
+  L = polish::make_layout(P.n, P.m, P.nnzA, P.nnzF, true);
+  if (P.n > polish::lf::kMaxN || L.total > polish::kLdsLimit)
+    throw Error(1, "instance too large to differentiate on the LDS-resident batched path (needs " + std::to_string(L.total) + " bytes of LDS, " +
+                       std::to_string(polish::kLdsLimit) + " available, with the factor in global scratch)");
+  return SharedAdjointPlan{true, L, shared::kAdjointBlocks * std::min(2, polish::kLdsLimit / L.total)};
+}
+// One launch of k_shared_adjoint over the instances a.first .. a.first + a.cnt - 1: a workgroup per instance, or at most W of them
+// where each needs its factor block
+void launch_shared_adjoint(SharedBatch &b, const SharedAdjointPlan &ap, shared::SharedAdjointArgs &a, hipStream_t s) {
+  auto *const kern = ap.large ? shared::k_shared_adjoint<true> : shared::k_shared_adjoint<false>;
+  const int grid = ap.large ? std::min(a.cnt, ap.blocks) : a.cnt;
+  HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, ap.L.total));
+  OQ_LAUNCH(kern, dim3(grid), dim3(polish::PT), (size_t)ap.L.total, s, b.dp.P, ap.L, a);
+}
+void launch_shared_reduce(int ncot, int cnt, int rcount, int cols, bool cont, const double *rows, double *out, hipStream_t s) {
+  OQ_LAUNCH(shared::k_shared_reduce_rows, dim3(blocks_for((int64_t)ncot * cols, 256)), dim3(256), 0, s, ncot, cnt, rcount, cols, (int)cont, rows, out);
 }
 
 // osqp_amd_batch_adjoint, _multi (subset false: every instance, rows / k unused) and osqp_amd_batch_adjoint_rows, _multi_rows
@@ -1401,7 +1440,7 @@ c_int osqp_amd_shared_batch_setup(osqp_amd_shared_batch **out, c_int count, c_in
     b->Px.upload(Px, b->nnzP, s); b->Ax.upload(Ax, b->nnzA, s); b->q0.upload(q0, n, s); b->l0.upload(l0, m, s); b->u0.upload(u0, m, s);
     b->model.alloc(b->ML.total); b->scratch.alloc((size_t)n * n); b->tiles.alloc((size_t)b->ntiles * b->TL.total); b->flag.alloc(1);
     const size_t cnt = (size_t)count;
-    b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6);
+    b->x_out.alloc(cnt * n); b->y_out.alloc(cnt * m); b->info_out.alloc(cnt * 6); b->status.alloc(cnt);
     shared_factor(*b, b->st, s);
     // every instance holds (q0, l0, u0) and a zero iterate
     OQ_LAUNCH(shared::k_shared_zero, dim3(blocks_for((int64_t)b->tiles.n, 256)), dim3(256), 0, s, b->tiles.n, b->tiles.get());
@@ -1422,6 +1461,7 @@ c_int osqp_amd_shared_batch_update_lin_cost(osqp_amd_shared_batch *handle, const
     DeviceScope on_dev(b->device);
     hipStream_t s = nullptr;
     const double *qd = device_ptr(q_all, (size_t)b->count * b->n, where, b->in_a, s);
+    b->current = false;
     shared_put(*b, qd, b->n, b->n, b->model.get() + b->ML.D, b->hdr[shared::MB_C], 0, b->TL.q, s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;
@@ -1439,6 +1479,7 @@ c_int osqp_amd_shared_batch_update_bounds(osqp_amd_shared_batch *handle, const c
     const size_t len = (size_t)b->count * b->m;
     const double *ld = device_ptr(l_all, len, where, b->in_a, s), *ud = device_ptr(u_all, len, where, b->in_b, s);
     if (!shared_bounds_ok(*b, ld, ud, s)) return 1;  // before anything of the handle is written
+    b->current = false;
     shared_put(*b, ld, b->m, b->m, b->model.get() + b->ML.E, 1.0, -1, b->TL.l, s);
     shared_put(*b, ud, b->m, b->m, b->model.get() + b->ML.E, 1.0, 1, b->TL.u, s);
     HIP_CHECK(hipStreamSynchronize(s));
@@ -1455,6 +1496,7 @@ c_int osqp_amd_shared_batch_warm_start(osqp_amd_shared_batch *handle, const c_fl
     hipStream_t s = nullptr;
     const double *xd = x_all ? device_ptr(x_all, (size_t)b->count * b->n, where, b->in_a, s) : nullptr;
     const double *yd = y_all && b->m ? device_ptr(y_all, (size_t)b->count * b->m, where, b->in_b, s) : nullptr;
+    b->current = false;
     OQ_LAUNCH(shared::k_shared_warm, dim3(blocks_for((int64_t)b->count * (b->n + b->m), 256)), dim3(256), 0, s, b->dp.P, b->count, b->plan.T, b->Ax.get(),
               b->model.get(), xd, yd, b->tiles.get());
     HIP_CHECK(hipStreamSynchronize(s));
@@ -1476,12 +1518,15 @@ c_int osqp_amd_shared_batch_resolve(osqp_amd_shared_batch *handle, c_float *x_ou
     g_shared_launches++;
     OQ_LAUNCH(shared::k_batch_solve_shared, dim3(b->ntiles), dim3(NT), b->plan.lds_bytes, s, b->dp.P, b->st, b->count, b->plan.T, (int)(b->st.warm_start != 0),
               (const double *)b->model.get(), b->tiles.get(), xd, yd, id);
+    // the statuses, for osqp_amd_shared_batch_adjoint: a copy of the handle's own, whoever owns the info rows
+    OQ_LAUNCH(shared::k_shared_status, dim3(blocks_for((int64_t)b->count, 256)), dim3(256), 0, s, b->count, (const double *)id, b->status.get());
     if (!where) {
       b->x_out.download(x_out, (size_t)b->count * b->n, s);
       if (b->m) b->y_out.download(y_out, (size_t)b->count * b->m, s);
       b->info_out.download(info_out, (size_t)b->count * 6, s);
     }
     HIP_CHECK(hipStreamSynchronize(s));
+    b->current = true;
     return 0;
   } OQ_BATCH_CATCH
 }
@@ -1503,10 +1548,80 @@ c_int osqp_amd_shared_batch_update_setting(osqp_amd_shared_batch *handle, const 
       DeviceScope on_dev(b->device);
       hipStream_t s = nullptr;
       st.rho = std::min(std::max(st.rho, (c_float)B_RHO_MIN), (c_float)B_RHO_MAX);
+      b->current = false;  // the carried iterates are those of the old rho: a resolve comes first
       try { shared_factor(*b, st, s); }
       catch (...) { shared_factor(*b, b->st, s); throw; }  // the model block of the rho that stays
     }
     b->st = st;
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_adjoint_launches(void) { return g_shared_adjoint_launches; }
+
+c_int osqp_amd_shared_batch_adjoint(osqp_amd_shared_batch *handle, c_int ncot, const c_float *dx, const c_float *dy, c_float *dq, c_float *dl,
+                                    c_float *du, c_float *dPx, c_float *dAx, c_float *dPx_sum, c_float *dAx_sum, c_float *act_out,
+                                    c_float *status_out, c_int where) {
+  SharedBatch *b = shared_handle(handle);
+  if (!b) return 1;
+  if (ncot < 1) { set_last_error("invalid batch data: the adjoint needs ncot >= 1"); return 1; }
+  if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
+  if (!b->current) {
+    set_last_error("the shared batch holds no current solution: call osqp_amd_shared_batch_resolve after the last update, warm start or rho update");
+    return 1;
+  }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const Pattern &P = b->dp.P;
+    const SharedAdjointPlan ap = shared_adjoint_plan(P);  // a refusal comes before anything is allocated or launched
+    const int count = b->count;
+    const size_t cnt = (size_t)count, nc = (size_t)ncot, ln = cnt * b->n, lm = cnt * b->m, lp = cnt * b->nnzP, la = cnt * b->nnzA;
+    if (!lm) { dy = nullptr; dl = du = act_out = nullptr; }
+    if (!la) dAx = dAx_sum = nullptr;
+    if (!lp) dPx = dPx_sum = nullptr;
+    if (!dx && !dy) { set_last_error("invalid batch data: the adjoint needs dx or dy"); return 1; }
+    const OutStage o(*b, !where, {dq, dl, du, dPx, dAx, dPx_sum, dAx_sum, act_out, status_out},
+                     {nc * ln, nc * lm, nc * lm, nc * lp, nc * la, nc * (size_t)b->nnzP, nc * (size_t)b->nnzA, lm, cnt});
+    shared::SharedAdjointArgs a;
+    a.model = b->model.get(); a.tiles = b->tiles.get(); a.status_in = b->status.get();
+    a.gx = dx ? device_ptr(dx, nc * ln, where, b->in_a, s) : nullptr;
+    a.gy = dy ? device_ptr(dy, nc * lm, where, b->in_b, s) : nullptr;
+    a.dq = o.dev[0]; a.dl = o.dev[1]; a.du = o.dev[2]; a.act = o.dev[7]; a.status = o.dev[8];
+    a.count = count; a.T = b->plan.T; a.ncot = (int)ncot; a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
+    a.scratch = nullptr;
+    if (ap.large) {
+      const size_t need = (size_t)ap.blocks * b->n * b->n;
+      if (b->adj_factor.n < need) b->adj_factor.alloc(need);
+      a.scratch = b->adj_factor.get();
+    }
+    // a sum whose rows the caller does not take: the rows of one launch go to the handle's scratch, `chunk` instances (a multiple
+    // of 16, or all of them) at a time, and are added to the running sum in the order of the contract
+    const bool psum = dPx_sum && !dPx, asum = dAx_sum && !dAx;
+    const size_t per_inst = nc * ((psum ? (size_t)b->nnzP : 0) + (asum ? (size_t)b->nnzA : 0));
+    int chunk = count;
+    if (per_inst) {
+      const size_t fit = std::max<size_t>(shared::kSumBlock, (kSharedRowScratch / sizeof(double) / per_inst) & ~(size_t)(shared::kSumBlock - 1));
+      if (fit < cnt) chunk = (int)fit;
+      if (ap.large && chunk < count && chunk > ap.blocks) chunk -= chunk % ap.blocks;  // whole rounds of the W workgroups: no short last round per chunk
+      if (b->adj_rows.n < per_inst * chunk) { HIP_CHECK(hipStreamSynchronize(s)); b->adj_rows.alloc(per_inst * chunk); }
+    }
+    g_shared_adjoint_launches++;
+    for (int first = 0; first < count; first += chunk) {
+      const int now = std::min(chunk, count - first);
+      double *const rowsP = psum ? b->adj_rows.get() : nullptr;
+      double *const rowsA = asum ? b->adj_rows.get() + (psum ? nc * (size_t)now * b->nnzP : 0) : nullptr;
+      a.first = first; a.cnt = now;
+      a.dPx = psum ? rowsP : o.dev[3]; a.pcount = psum ? now : count; a.pfirst = psum ? first : 0;
+      a.dAx = asum ? rowsA : o.dev[4]; a.acount = asum ? now : count; a.afirst = asum ? first : 0;
+      launch_shared_adjoint(*b, ap, a, s);
+      if (psum) launch_shared_reduce((int)ncot, now, now, b->nnzP, first > 0, rowsP, o.dev[5], s);
+      if (asum) launch_shared_reduce((int)ncot, now, now, b->nnzA, first > 0, rowsA, o.dev[6], s);
+    }
+    if (dPx_sum && dPx) launch_shared_reduce((int)ncot, count, count, b->nnzP, false, o.dev[3], o.dev[5], s);
+    if (dAx_sum && dAx) launch_shared_reduce((int)ncot, count, count, b->nnzA, false, o.dev[4], o.dev[6], s);
+    o.download(s);
+    HIP_CHECK(hipStreamSynchronize(s));
     return 0;
   } OQ_BATCH_CATCH
 }

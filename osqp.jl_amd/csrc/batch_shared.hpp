@@ -10,6 +10,8 @@
 //                          of k_batch_solve_large, the per-instance vectors as [. x T] arrays (entry idx of column c at
 //                          idx T + c), the dense step v_mfma_f64_16x16x4_f64 on 16-row tiles of M^-1 read from the model block;
 //   k_shared_put / _warm / _check_bounds   the small kernels of the updates.
+// The adjoint of the handle (k_shared_adjoint, k_shared_reduce_rows) reads the model block and the tile records laid out here:
+// batch_shared_adjoint.hpp, DESIGN.md section 13.4.
 // WHERE THE VECTORS LIVE.  LDS holds what an iteration reads more than once or with scattered addresses: the scaled values
 // of A, rho and 1 / rho (shared), and per tile b (padded to a multiple of 16 rows, the padding zero), x~, x, z, y and
 // zt = rho z - y.  q, l and u are read once per iteration, entry idx T + c by the thread that owns it: they stay in the TILE

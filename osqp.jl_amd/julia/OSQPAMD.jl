@@ -833,6 +833,8 @@ mutable struct SharedBatch
     count::Int
     n::Int
     m::Int
+    nnzP::Int
+    nnzA::Int
 end
 
 "(T, lds_bytes, model_bytes, instance_bytes) for a shape (osqp_amd_shared_batch_plan; host only): T, the instances per workgroup, depends on the shape alone."
@@ -861,7 +863,7 @@ function shared_batch_setup(P::SparseMatrixCSC, A::SparseMatrixCSC, q0::Vector{F
                   Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{OSQP.Settings}, Cc_int),
                  h, count, n, m, Pp, Pi, Vector{Float64}(Pu.nzval), Ap, Ai, Vector{Float64}(A.nzval), q0, l0, u0, Ref(stgs), device)
     flag == 0 || error("Error in shared batch setup: $(last_error())")
-    b = SharedBatch(h[], count, n, m)
+    b = SharedBatch(h[], count, n, m, length(Pu.nzval), length(A.nzval))
     finalizer(x -> ccall((:osqp_amd_shared_batch_destroy, lib), Cc_int, (Ptr{Cvoid},), x.handle), b)
     return b
 end
@@ -918,6 +920,47 @@ end
 
 shared_batch_device_bytes(b::SharedBatch) = Int(ccall((:osqp_amd_shared_batch_device_bytes, lib), Cc_int, (Ptr{Cvoid},), b.handle))
 shared_batch_launches() = Int(ccall((:osqp_amd_shared_batch_launches, lib), Cc_int, ()))
+
+"""
+    shared_batch_adjoint(b; dx = nothing, dy = nothing, want = (:q, :l, :u, :Px, :Ax), sums = ()) -> NamedTuple
+
+Gradients of a scalar loss through the solutions of the last `shared_batch_solve!` (osqp_amd_shared_batch_adjoint, DESIGN.md
+section 13.4).  dx [n x count] / dy [m x count] (or [n x count x ncot] / [m x count x ncot] for several cotangents; `nothing` =
+zeros, not both).  Returns the entries of `want` per instance ([cols x count] or [cols x count x ncot]), the entries of `sums`
+(a subset of (:Px, :Ax)) as `Px_sum` / `Ax_sum` ([nnz] or [nnz x ncot]: the gradients of the SHARED values, summed over the
+instances on the device in blocks of 16 -- the order is in include/osqp_amd.h), plus `act` [m x count] and `status` [count].
+Refused before the first solve and after any update, warm start or rho update that followed the last one.
+"""
+function shared_batch_adjoint(b::SharedBatch; dx::Union{Nothing,Array{Float64}} = nothing, dy::Union{Nothing,Array{Float64}} = nothing,
+                              want = (:q, :l, :u, :Px, :Ax), sums = ())
+    all(w -> w in (:q, :l, :u, :Px, :Ax), want) || error("want: expected a subset of (:q, :l, :u, :Px, :Ax)")
+    all(w -> w in (:Px, :Ax), sums) || error("sums: expected a subset of (:Px, :Ax)")
+    dx === nothing && dy === nothing && error("dx and dy: at least one incoming gradient is needed")
+    ref = dx === nothing ? dy : dx
+    many = ndims(ref) == 3
+    ncot = many ? size(ref, 3) : 1
+    for (name, v, k) in (("dx", dx, b.n), ("dy", dy, b.m))
+        v === nothing || size(v) == (many ? (k, b.count, ncot) : (k, b.count)) || error("$(name): expected [$(k) x $(b.count)] or [$(k) x $(b.count) x ncot]")
+    end
+    cols = (q = b.n, l = b.m, u = b.m, Px = b.nnzP, Ax = b.nnzA)
+    per = Dict(k => (k in want && cols[k] > 0 ? (many ? zeros(cols[k], b.count, ncot) : zeros(cols[k], b.count)) : nothing) for k in keys(cols))
+    tot = Dict(k => (k in sums && cols[k] > 0 ? (many ? zeros(cols[k], ncot) : zeros(cols[k])) : nothing) for k in (:Px, :Ax))
+    act, status = zeros(b.m, b.count), zeros(b.count)
+    p(a) = a === nothing ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve dx dy per tot act status begin
+        flag = ccall((:osqp_amd_shared_batch_adjoint, lib), Cc_int,
+                     (Ptr{Cvoid}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                      Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, ncot, p(dx), p(dy), p(per[:q]), p(per[:l]), p(per[:u]), p(per[:Px]), p(per[:Ax]), p(tot[:Px]), p(tot[:Ax]),
+                     b.m > 0 ? pointer(act) : Ptr{Cdouble}(C_NULL), pointer(status), 0)
+    end
+    flag == 0 || error("Error in shared batch adjoint: $(last_error())")
+    return (q = per[:q], l = per[:l], u = per[:u], Px = per[:Px], Ax = per[:Ax], Px_sum = tot[:Px], Ax_sum = tot[:Ax],
+            act = Matrix{Int}(act), status = Vector{Int}(status))
+end
+
+"Accepted `shared_batch_adjoint` calls of this process: one per call whatever ncot; a refused call does not count."
+shared_batch_adjoint_launches() = Int(ccall((:osqp_amd_shared_batch_adjoint_launches, lib), Cc_int, ()))
 
 """
     batch_large_factor!(b, on = true) -> Bool

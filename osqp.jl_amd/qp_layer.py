@@ -33,6 +33,16 @@ disjoint selections can both run their backward (the forward-mode rule runs with
 an instance's active constraints are dependent the derivative does not exist and the regularised answer is returned
 (include/osqp_amd.h, osqp_amd_batch_adjoint); the same holds for the tangents (osqp_amd_batch_jvp).
 
+A shared batch (`batch.SharedBatch`: ONE model, many right-hand sides) as a layer: `SharedBatchQPFunction` /
+`SharedBatchQPLayer(sb)`, after the two classes above.  q, l, u [count x .] update the handle and get per-instance gradients;
+Px [nnzP] and Ax [nnzA] are the shared values -- they must be the handle's own and get the gradients SUMMED over the instances
+(`SharedBatch.adjoint(sums=...)`: one launch of k_shared_adjoint plus the fixed-order reduction, no host hop).
+
+    sb = batch.SharedBatch(lib, P, A, q0, l0, u0, count)
+    layer = SharedBatchQPLayer(sb)
+    Px = torch.nn.Parameter(layer.Px.clone())
+    x, y = layer(q=q_t, l=l_t, u=u_t, Px=Px)    # Px.grad [nnzP]: the sum over the instances
+
 A single model (`interface.Model`: one large sparse QP, any n) as a layer: `QPFunction` / `QPLayer(model)`, at the end of this
 file.  The forward is `update` + `solve`, the backward one `interface.adjoint` call on the kept factor, and under
 `torch.autograd.forward_ad` the tangents of (x, y) come from one `interface.jvp` call on the same factor.  Two routes, by
@@ -225,6 +235,137 @@ class BatchQPLayer(torch.nn.Module):
         if not stamp_holds(self.rb, stamp, sel):
             raise RuntimeError("BatchQPLayer.jacobian: the batch has been solved again since the last forward of this layer")
         return self.rb.jacobian(of=of, wrt=wrt, mode=mode, rows=sel, out_rows=out_rows, chunk=chunk, device=True)
+
+
+def shared_values(sb, device):
+    """The values of P (upper triangle) and A of the shared batch `sb` as tensors on `device`, uploaded once per handle: what
+    a Px / Ax input of `SharedBatchQPFunction` is compared with."""
+    own = getattr(sb, "_qp_layer_values", None)
+    if own is None or own["Px"].device != device:
+        own = sb._qp_layer_values = dict(Px=torch.tensor(sb.Px, device=device), Ax=torch.tensor(sb.Ax, device=device))
+    return own
+
+
+class SharedBatchQPAdjoint(torch.autograd.Function):
+    """The pull-back of `SharedBatchQPFunction` as a Function of its own with a `vmap` rule, after `BatchQPAdjoint`: (gx, gy) ->
+    the gradients `want` (per instance) and `sums` (of the shared values) through ONE `SharedBatch.adjoint` call; under
+    `torch.func.vmap` the cotangents go to the library with a leading axis [ncot x count x .]."""
+
+    @staticmethod
+    def forward(sb, stamp, want, sums, gx, gy):
+        return SharedBatchQPAdjoint._pull(sb, stamp, want, sums, gx, gy, ())
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError("SharedBatchQPAdjoint: the adjoint of the batch is not differentiable a second time")
+
+    @staticmethod
+    def vmap(info, in_dims, sb, stamp, want, sums, gx, gy):
+        ncot = info.batch_size
+
+        def front(g, dim):  # the batch axis to the front; a cotangent that arrives unbatched is the same for every one
+            if g is None:
+                return None
+            return g.unsqueeze(0).expand((ncot,) + tuple(g.shape)) if dim is None else g.movedim(dim, 0)
+
+        out = SharedBatchQPAdjoint._pull(sb, stamp, want, sums, front(gx, in_dims[4]), front(gy, in_dims[5]), (ncot,))
+        return out, tuple(0 for _ in out)
+
+    @staticmethod
+    def _pull(sb, stamp, want, sums, gx, gy, lead):
+        if not stamp_holds(sb, stamp, None):
+            raise RuntimeError("SharedBatchQPFunction: the batch has been solved again since this forward; its handle holds one "
+                               "solution, so backward must run before the next forward")
+        cols = dict(q=sb.n, l=sb.m, u=sb.m, Px=sb.nnzP, Ax=sb.nnzA)
+        ref = gx if gx is not None else gy
+        out = {w: torch.empty(lead + (sb.count, cols[w]), dtype=torch.float64, device=ref.device) for w in want}
+        out.update({w + "_sum": torch.empty(lead + (cols[w],), dtype=torch.float64, device=ref.device) for w in sums})
+        _sync(ref)
+        sb.adjoint(dx=None if gx is None else gx.contiguous(), dy=None if gy is None or sb.m == 0 else gy.contiguous(), want=want, sums=sums,
+                   out=out)
+        return tuple(out[w] for w in want) + tuple(out[w + "_sum"] for w in sums)
+
+
+class SharedBatchQPFunction(torch.autograd.Function):
+    """(x, y) of every instance of a shared batch as a function of q, l, u [count x .] -- which update the handle and receive
+    per-instance gradients -- and of the SHARED values Px [nnzP], Ax [nnzA], which must be the handle's own (they are not
+    updated: a new model is a new handle) and receive the gradients summed over the instances."""
+
+    @staticmethod
+    def forward(sb, q, l, u, Px, Ax):
+        given = dict(zip(NAMES, (q, l, u, Px, Ax)))
+        tensors = [t for t in given.values() if t is not None]
+        if not tensors:
+            raise ValueError("SharedBatchQPFunction: at least one of q, l, u, Px, Ax must be a tensor")
+        _check_inputs(given)
+        if (l is None) != (u is None):
+            raise ValueError("l and u: a shared batch updates both bounds in one call")
+        ref = tensors[0]
+        for name in ("Px", "Ax"):  # compared on the device: no host hop
+            t, own = given[name], shared_values(sb, ref.device)[name]
+            if t is not None and (tuple(t.shape) != tuple(own.shape) or not torch.equal(t.detach(), own)):
+                raise ValueError(f"{name}: the values differ from those of the handle; a shared batch cannot update its matrices "
+                                 "(a new model is a new handle)")
+        _sync(ref)
+        sb.update(**{name: given[name].detach().contiguous() for name in ("q", "l", "u") if given[name] is not None})
+        x = torch.empty((sb.count, sb.n), dtype=torch.float64, device=ref.device)
+        y = torch.empty((sb.count, sb.m), dtype=torch.float64, device=ref.device)
+        info = torch.empty((sb.count, 6), dtype=torch.float64, device=ref.device)
+        sb.solve(out=(x, y if sb.m else None, info))
+        sb._qp_layer_info = info
+        sb._qp_layer_served = stamp_forward(sb, None)  # for setup_context, which runs next
+        return x, y
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.sb = inputs[0]
+        ctx.stamp = ctx.sb._qp_layer_served
+
+    @staticmethod
+    def backward(ctx, gx, gy):
+        sb = ctx.sb
+        if not stamp_holds(sb, ctx.stamp, None):
+            raise RuntimeError("SharedBatchQPFunction: the batch has been solved again since this forward; its handle holds one "
+                               "solution, so backward must run before the next forward")
+        need = dict(zip(NAMES, ctx.needs_input_grad[1:6]))
+        cols = dict(q=sb.n, l=sb.m, u=sb.m, Px=sb.nnzP, Ax=sb.nnzA)
+        want = tuple(k for k in ("q", "l", "u") if need[k] and cols[k] > 0)
+        sums = tuple(k for k in ("Px", "Ax") if need[k] and cols[k] > 0)
+        if gx is None and gy is None:
+            return (None,) * 6
+        ref = gx if gx is not None else gy
+        out = dict(zip(want + sums, SharedBatchQPAdjoint.apply(sb, ctx.stamp, want, sums, gx, gy))) if want or sums else {}
+        # a wanted gradient of width zero: zeros (`ref` carries the batch axis of a vmapped pull-back)
+        lead = tuple(ref.shape[:-2])
+        zeros = {k: ref.new_zeros(lead + ((sb.count, 0) if k in ("q", "l", "u") else (0,))) for k in NAMES}
+        grads = {k: (out[k] if k in out else (zeros[k] if need[k] else None)) for k in NAMES}
+        return (None,) + tuple(grads[k] for k in NAMES)
+
+
+class SharedBatchQPLayer(torch.nn.Module):
+    """`layer(q=None, l=None, u=None, Px=None, Ax=None) -> (x, y)` on the shared batch `sb` (`batch.SharedBatch`: one model, many
+    right-hand sides); `layer.info` is the info array [count x 6] of the last forward.  q, l, u: float64 CUDA tensors
+    [count x .] (None keeps the handle's data; l and u come together); they update the handle and get per-instance gradients
+    from `SharedBatch.adjoint`.  Px [nnz(P upper)], Ax [nnz(A)]: the SHARED values as float64 CUDA tensors -- they must equal
+    the handle's values bit for bit (ValueError otherwise: a new model is a new handle) and get the gradients summed over the
+    instances, "Px_sum" / "Ax_sum" of the same adjoint call.  `layer.Px` / `layer.Ax` are the handle's values on its device,
+    ready to be cloned into parameters.  The stamp rule of `BatchQPLayer` holds: backward after a later forward raises.
+    `torch.func.vmap` / `jacrev` over the pull-back is one adjoint call with a leading axis.  Forward mode is not offered."""
+
+    def __init__(self, sb):
+        super().__init__()
+        self.sb, self.info = sb, None
+        own = shared_values(sb, torch.device("cuda", sb.device))
+        self.Px, self.Ax = own["Px"], own["Ax"]
+
+    def forward(self, q=None, l=None, u=None, Px=None, Ax=None):
+        x, y = SharedBatchQPFunction.apply(self.sb, q, l, u, Px, Ax)
+        self.info = self.sb._qp_layer_info
+        return x, y
 
 
 def stamp_model_forward(model):

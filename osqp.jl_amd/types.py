@@ -270,6 +270,9 @@ EXT_SYMBOLS = {
     "osqp_amd_shared_batch_warm_start": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_shared_batch_resolve": (c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_int]),
     "osqp_amd_shared_batch_update_setting": (c_int, [C.c_void_p, C.c_char_p, c_float]),
+    # handle, ncot, dx, dy, dq, dl, du, dPx, dAx, dPx_sum, dAx_sum, act, status, where
+    "osqp_amd_shared_batch_adjoint": (c_int, [C.c_void_p, c_int] + [C.c_void_p] * 11 + [c_int]),
+    "osqp_amd_shared_batch_adjoint_launches": (c_int, []),
     "osqp_amd_shared_batch_device_bytes": (c_int, [C.c_void_p]),
     "osqp_amd_shared_batch_launches": (c_int, []),
     "osqp_amd_shared_batch_destroy": (c_int, [C.c_void_p]),
