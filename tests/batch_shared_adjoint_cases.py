@@ -24,6 +24,7 @@ CASES = {
     "banded-128": ("banded", (128, 192, 4), 18, 0, 16),     # last n of the LDS form
     "random-129-eq": ("random", (129, 160, 5), 17, 12, 16),  # first n of the scratch form, equalities, n no multiple of 32
     "banded-256": ("banded", (256, 512, 6), 14, 0, 4),      # the cap; T = 4
+    "banded-240": ("banded", (240, 360, 5), 281, 0, 8),     # T = 8: the stride of the tile records; ldm = 240, 15 tiles of 16
 }
 COND_MAX = 1e8
 BLOCK = 16

@@ -25,6 +25,23 @@ BOXED = {
     "banded-129-eq": ("banded", (129, 193, 4), 15, 20, 7),
     "banded-33-eq": ("banded", (33, 40, 3), 16, 5, 7),
 }
+# The edges of the dense step (tests/test_batch_shared_steps_*.py): id -> (kind, shape, seed, neq, T, ldm, ntile).  T is the
+# number of instances per workgroup that batch.shared_plan gives the shape, ldm = 16 ceil(n / 16) and ntile = ldm / 16 what the
+# matrix-core product branches on; each batch has 2 T + 3 instances: two full tiles and a partial one.
+EDGES = {
+    "banded-2": ("banded", (2, 2, 1), 51, 0, 16, 16, 1),             # smallest; 14 padding rows (the seed: max E <= 2 c, see
+                                                                     # test_batch_shared_steps_host.py)
+    "banded-15": ("banded", (15, 20, 3), 55, 0, 16, 16, 1),          # the tail chunk only; one padding row
+    "banded-16": ("banded", (16, 24, 3), 56, 0, 16, 16, 1),          # one exact tile, no padding
+    "banded-32-eq": ("banded", (32, 48, 3), 72, 4, 16, 32, 2),       # one full 32-column chunk, no tail; equalities
+    "banded-128": ("banded", (128, 192, 4), 168, 0, 16, 128, 8),     # ntile = the number of wavefronts: no second tile
+    "banded-130-m400": ("banded", (130, 400, 5), 170, 0, 8, 144, 9),  # T = 8; only wavefront 0 holds two tiles
+    "banded-176-eq": ("banded", (176, 300, 5), 216, 8, 8, 176, 11),  # T = 8; a tail chunk with two tiles; equalities
+    "banded-240": ("banded", (240, 360, 5), 280, 0, 8, 240, 15),     # T = 8; odd tile count
+    "banded-241-eq": ("banded", (241, 400, 5), 281, 6, 8, 256, 16),  # T = 8; 15 padding rows in the last tile; LDS nearly full
+    "banded-200-m460": ("banded", (200, 460, 5), 240, 0, 4, 208, 13),  # T = 4 away from n = 256; ldm an odd multiple of 16
+}
+BOXED.update({name: (kind, shape, seed, neq, 2 * T + 3) for name, (kind, shape, seed, neq, T, _, _) in EDGES.items()})
 CHAINS = [(17, 5), (130, 20), (256, 40)]
 CHAIN_STATUS = [1, -3, -4] * 3
 CHAIN_STATUS_30 = [2, -3, -4, -2, -3, -4, 2, -3, -4]  # max_iter = 30, rho = 1.0
@@ -120,8 +137,13 @@ class OracleShared:
             oq.warm_start(mdl, x=None if x is None else x[i], y=None if y is None or not self.m else y[i])
 
     def update_settings(self, **kw):
+        """`oq.update_settings`; scaled_termination, which that function does not list, goes to the oracle's own symbol."""
+        kw = dict(kw)
+        scaled = kw.pop("scaled_termination", None)
         for mdl in self.models:
             oq.update_settings(mdl, **kw)
+            if scaled is not None:
+                assert mdl.lib.osqp_update_scaled_termination(mdl.workspace, int(scaled)) == 0
 
     def solve(self):
         return [oq.solve(mdl) for mdl in self.models]

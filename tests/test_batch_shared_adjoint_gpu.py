@@ -11,6 +11,7 @@ FIGURES of the first test on an MI355X (kernel vs exact, instances compared; bou
   banded-128     6.0e-14   35 of 35   (6.1e-11)
   random-129-eq  5.7e-14   35 of 35   (5.4e-11)
   banded-256     2.2e-13   10 of 11   (2.1e-10; instance 1 has cond K 1.3e14 and is filtered)
+  banded-240     8.4e-14   19 of 19   (9.0e-11; T = 8)
 Everything else here is an equality of bits: instance i of a batch against the batch of one, a permutation, cotangent c of an
 ncot = 3 call against a call of its own, host against device form, any `want` / `sums` against any other, the sums against the
 numpy loop in the order of the contract, a resolve after an adjoint against one without."""
@@ -78,7 +79,7 @@ def test_kernel_agrees_with_the_exact_adjoint(product_lib, name):
 
 
 # ---- 2. bits -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["banded-17", "random-129-eq", "banded-256"])
+@pytest.mark.parametrize("name", ["banded-17", "random-129-eq", "banded-256", "banded-240"])
 def test_bits_do_not_depend_on_the_batch_the_call_or_the_outputs(product_lib, name):
     lib = product_lib
     r = _run(lib, name)
