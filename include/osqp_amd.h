@@ -1049,7 +1049,22 @@ c_int osqp_amd_duality(OSQPWorkspace *work, c_float *out, c_int count);
  *            update_lin_cost, update_bounds, warm_start or update_setting("rho") that followed the last resolve.  It only
  *            reads the handle: a resolve after it has the bits of one without it.  One call counts once in
  *            osqp_amd_shared_batch_adjoint_launches, whatever ncot is; a refused call does not count.
- * The handle has no polish, forward sensitivities, certificates, duality or `rows` entries, and its matrices cannot be
+ * jvp()      forward sensitivities of the solutions of the last resolve along `ndir` directions of the data (DESIGN.md section
+ *            13.5): the mathematics of osqp_amd_batch_jvp -- per instance i with solution (x_i, y_i) and active rows a_i, ONE
+ *            solve per direction with [P, Aa'; Aa, 0] [tx; ty_a] = [-(tq_i + tP x_i + tA' y_i); (tb_i - tA x_i)_a], tb = tl on the
+ *            lower rows, tu on the upper ones, ty zero on the inactive rows.  tq, tl, tu are PER INSTANCE, direction-major
+ *            [ndir x count x n], [ndir x count x m].  tPx [ndir x nnzP] and tAx [ndir x nnzA] are ONE tangent per direction
+ *            for the whole batch, as P and A are shared: tPx on the stored upper triangle (an off-diagonal entry stands for
+ *            both halves), tAx in the order of the Ax given at setup -- the index spaces of dPx_sum / dAx_sum.  A NULL tangent
+ *            is zero and gives the bits of an explicit zero array; not all five may be NULL (arrays of width 0 are dropped
+ *            first).  On a row with l == u (scaled, as the handle stores it) only tl is read.  tx [ndir x count x n], ty
+ *            [ndir x count x m], NULL = not wanted (not both); act_out [count x m] and status_out [count] as the adjoint's,
+ *            with the same values.  The sensitivities of (instance, direction) have the same bits whatever count, ndir, the
+ *            position, the neighbours or the outputs wanted.  The form of the kernel and its factor blocks are the adjoint's:
+ *            the same blocks, allocated by whichever call comes first.  ndir < 1 is refused.  CURRENCY and reading only: as
+ *            the adjoint.  One call counts once in osqp_amd_shared_batch_jvp_launches, whatever ndir is; a refused call does
+ *            not count.
+ * The handle has no polish, certificates, duality or `rows` entries, and its matrices cannot be
  * updated: a new model is a new handle. */
 typedef struct osqp_amd_shared_batch osqp_amd_shared_batch;
 c_int osqp_amd_shared_batch_plan(c_int n, c_int m, c_int nnzA, c_int nnzF, c_int *out /* [4] */);
@@ -1068,6 +1083,12 @@ c_int osqp_amd_shared_batch_adjoint(osqp_amd_shared_batch *batch, c_int ncot, co
                                     c_float *dPx_sum, c_float *dAx_sum,                                /* [ncot x nnzP], [ncot x nnzA] or NULL */
                                     c_float *act_out, c_float *status_out, c_int where);
 c_int osqp_amd_shared_batch_adjoint_launches(void);
+c_int osqp_amd_shared_batch_jvp(osqp_amd_shared_batch *batch, c_int ndir,
+                                const c_float *tq, const c_float *tl, const c_float *tu,   /* [ndir x count x n | m | m] or NULL */
+                                const c_float *tPx, const c_float *tAx,                    /* [ndir x nnzP], [ndir x nnzA] or NULL: shared */
+                                c_float *tx, c_float *ty,                                  /* [ndir x count x n | m] or NULL */
+                                c_float *act_out, c_float *status_out, c_int where);       /* [count x m], [count] or NULL */
+c_int osqp_amd_shared_batch_jvp_launches(void);
 c_int osqp_amd_shared_batch_device_bytes(osqp_amd_shared_batch *batch);
 c_int osqp_amd_shared_batch_launches(void);
 c_int osqp_amd_shared_batch_destroy(osqp_amd_shared_batch *batch);

@@ -928,6 +928,12 @@ def shared_adjoint_launches(lib):
     return int(lib.osqp_amd_shared_batch_adjoint_launches())
 
 
+def shared_jvp_launches(lib):
+    """Accepted `SharedBatch.jvp` calls of this process so far (osqp_amd_shared_batch_jvp_launches): one per call, whatever the
+    number of directions; a refused call does not count."""
+    return int(lib.osqp_amd_shared_batch_jvp_launches())
+
+
 class SharedBatch:
     """ONE model and `count` right-hand sides on a shared KKT inverse (osqp_amd_shared_batch_setup).
     Instance i is `setup(P, q0, A, l0, u0)`, `update(q=q[i], l=l[i], u=u[i])`, `solve()` on a fresh model: scaling comes from the
@@ -935,8 +941,10 @@ class SharedBatch:
     library) and every row of every instance must keep the kind -- loose, equality, inequality -- it has under (l0, u0).
     After setup every instance holds (q0, l0, u0).  Arrays of `update` / `warm_start` and the `out` of `solve` are numpy arrays
     or device arrays (`DeviceArray`, torch tensors), as for `ResidentBatch`.  `adjoint` differentiates the solutions of the last
-    `solve()`, per instance and -- for the shared values of P and A -- summed over the instances; there is no `rows=`, polish,
-    `jvp`, certificate or duality call here, and the matrices cannot be updated: a new model is a new handle."""
+    `solve()`, per instance and -- for the shared values of P and A -- summed over the instances; `jvp` moves them along
+    directions of the data, with ONE tangent of the shared values of P and A for the whole batch; `jacobian` builds Jacobians
+    from either.  There is no `rows=`, polish, certificate or duality call here, and the matrices cannot be updated: a new
+    model is a new handle."""
 
     SETTINGS = ("max_iter", "eps_abs", "eps_rel", "eps_prim_inf", "eps_dual_inf", "alpha", "check_termination",
                 "scaled_termination", "rho")
@@ -1104,6 +1112,161 @@ class SharedBatch:
                 res["act"] = res["act"].astype(np.int64)
             res["status"] = res["status"].ravel().astype(np.int64)
         return res
+
+    JVP_TANGENTS = ("q", "l", "u", "Px", "Ax")
+    JVP_SHARED = ("Px", "Ax")
+
+    def jvp(self, q=None, l=None, u=None, Px=None, Ax=None, out=None):
+        """Forward sensitivities of the solutions of the last `solve()` along directions of the data (osqp_amd_shared_batch_jvp,
+        DESIGN.md section 13.5).  The tangents q [count x n], l, u [count x m] are PER INSTANCE; Px [nnz(P upper)] and Ax [nnz(A)]
+        are ONE tangent of the SHARED values for the whole batch, in the index spaces of "Px_sum" / "Ax_sum" (None: zero; not
+        all).  Or all of them with a leading axis, [ndir x count x .] and [ndir x nnz], for several directions in one call: one
+        factorisation per instance, one solve per direction, and direction d has the bits of a call with that direction alone.
+        Mixed ranks raise.  Returns a dict: "x" (tangent of the solutions) and "y" (of the multipliers; zero on inactive rows),
+        [count x .] or [ndir x count x .], "act" [count x m] (-1 lower, 1 upper, 0 inactive) and "status" (1 differentiated, 0 no
+        solution, -1 factorisation failed; such rows are zeros), as `adjoint` returns them.  Entries of width 0 are left out,
+        and a tangent of width 0 is ignored.  On a row with l == u only the tangent `l` is read.  Host form: numpy tangents,
+        out=None, numpy results.  Device form: device arrays and `out` a dict of float64 device arrays -- "x" and / or "y",
+        optionally "act" [count x m] and "status" [count x 1] -- filled in place and returned.  The handle must hold the
+        solutions of its current data, as for `adjoint`."""
+        cnt = self.count
+        cols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA)
+        given = {k: v for k, v in zip(self.JVP_TANGENTS, (q, l, u, Px, Ax)) if v is not None}
+        if not given:
+            raise ValueError("q, l, u, Px, Ax: at least one tangent is needed")
+        shapes = {k: tuple(v.shape) if hasattr(v, "data_ptr") else np.asarray(v).shape for k, v in given.items()}
+        # the rank of a direction-less call: 2 for the per-instance tangents, 1 for the shared ones
+        extra = {k: len(s) - (1 if k in self.JVP_SHARED else 2) for k, s in shapes.items()}
+        if len(set(extra.values())) > 1 or next(iter(extra.values())) not in (0, 1):
+            raise ValueError("tangents: expected q, l, u [count x cols] with Px, Ax [nnz], or all with a leading axis [ndir x ...], got shapes "
+                             f"{shapes}")
+        many = next(iter(extra.values())) == 1
+        ndir = 1
+        if many:
+            ndirs = {k: int(s[0]) for k, s in shapes.items()}
+            if len(set(ndirs.values())) > 1:
+                raise ValueError(f"tangents: they must carry the same number of directions, got {ndirs}")
+            ndir = next(iter(ndirs.values()))
+            if ndir < 1:
+                raise ValueError("tangents: ndir must be at least 1")
+        lead = (ndir,) if many else ()
+        got = {k: _batch_array(k, v, lead + (() if k in self.JVP_SHARED else (cnt,)) + (cols[k],)) for k, v in given.items()}
+        forms = {g[2] for g in got.values()}
+        if len(forms) > 1:
+            raise ValueError("tangents: they must all be host arrays or all device arrays")
+        where = forms.pop()
+        got = {k: g for k, g in got.items() if cols[k] > 0}
+        if not got:
+            raise ValueError("q, l, u, Px, Ax: every tangent given has width 0")
+        ocols = dict(x=self.n, y=self.m, act=self.m, status=1)
+        oshape = dict(x=lead + (cnt, self.n), y=lead + (cnt, self.m), act=(cnt, self.m), status=(cnt, 1))
+        names = [k for k in ("x", "y", "act", "status") if ocols[k] > 0]
+        if not where:
+            if out is not None:
+                raise ValueError("out: host tangents (numpy) return numpy arrays; pass device arrays for the tangents to fill `out`")
+            res = {k: np.empty(oshape[k]) for k in names}
+            addr = {k: v.ctypes.data for k, v in res.items()}
+        else:
+            if not isinstance(out, dict):
+                raise ValueError("out: device tangents need a dict of device arrays to fill: x, y")
+            for k in out:
+                if k not in ocols:
+                    raise ValueError(f"out: unknown entry {k!r}")
+            addr = {}
+            for k in names:
+                if k in out:
+                    if not hasattr(out[k], "data_ptr"):
+                        raise ValueError(f"out[{k!r}]: expected a device array (DeviceArray, torch tensor)")
+                    addr[k] = _batch_array(f"out[{k!r}]", out[k], oshape[k])[1]
+            if "x" not in addr and "y" not in addr:
+                raise ValueError("out: no array for 'x' or 'y'")
+            res = out
+        tail = [got[k][1] if k in got else None for k in self.JVP_TANGENTS]
+        tail += [addr.get("x"), addr.get("y"), addr.get("act"), addr.get("status"), where]
+        self._call("jvp", self.lib.osqp_amd_shared_batch_jvp(self.handle, ndir, *tail))
+        if not where:
+            if "act" in res:
+                res["act"] = res["act"].astype(np.int64)
+            res["status"] = res["status"].ravel().astype(np.int64)
+        return res
+
+    JACOBIAN_OF = ("x", "y")
+    JACOBIAN_BUDGET = 256 << 20  # bytes: the unit vectors and the largest output of one call of `jacobian` (default chunk)
+
+    def jacobian(self, of=("x",), wrt=("q",), mode="auto", chunk=None):
+        """Jacobians of the solutions of the last `solve()` with respect to the data: a dict {(o, w): array} for o in `of` (a
+        subset of "x", "y") and w in `wrt` (a subset of "q", "l", "u", "Px", "Ax"), plus "act" and "status" as `adjoint` / `jvp`
+        return them (an instance with status != 1 has zeros).  w in q, l, u: [count x cols(o) x cols(w)], entry [i, a, b] the
+        derivative of component a of o of instance i with respect to entry b of ITS OWN w.  w in Px, Ax: [count x cols(o) x nnz],
+        the derivative with respect to entry b of the SHARED values.  mode="forward": unit directions through `jvp`, one solve
+        per column of the `wrt` arrays -- one unit direction is applied to every instance at once; mode="reverse": unit
+        cotangents through `adjoint` with the per-instance rows, one solve per output component; "auto": the one with fewer
+        solves per instance (reverse on a tie).  chunk: the most directions / cotangents per call; the chunks are independent
+        calls whose results are concatenated.  Default: as many as keep the unit vectors and the largest output of one call
+        under 256 MiB together, at least 1.  Host arrays only.  Nothing is computed on the results: they are transposed and
+        placed."""
+        of, wrt = tuple(of), tuple(wrt)
+        cnt = self.count
+        wcols = dict(q=self.n, l=self.m, u=self.m, Px=self.nnzP, Ax=self.nnzA)
+        ocols = dict(x=self.n, y=self.m)
+        if not of or len(set(of)) != len(of) or any(o not in self.JACOBIAN_OF for o in of):
+            raise ValueError(f"of: expected a non-empty subset of {self.JACOBIAN_OF} without repeats, got {of!r}")
+        if not wrt or len(set(wrt)) != len(wrt) or any(w not in self.ADJOINT_WANT for w in wrt):
+            raise ValueError(f"wrt: expected a non-empty subset of {self.ADJOINT_WANT} without repeats, got {wrt!r}")
+        if mode not in ("auto", "reverse", "forward"):
+            raise ValueError(f"mode: expected 'auto', 'reverse' or 'forward', got {mode!r}")
+        n_rev, n_fwd = sum(ocols[o] for o in of), sum(wcols[w] for w in wrt)
+        if n_rev == 0 or n_fwd == 0:
+            raise ValueError("jacobian: no output component or no data column is asked for")
+        if mode == "auto":
+            mode = "reverse" if n_rev <= n_fwd else "forward"
+        total = n_rev if mode == "reverse" else n_fwd
+        if chunk is not None and (not isinstance(chunk, (int, np.integer)) or isinstance(chunk, bool) or chunk < 1):
+            raise ValueError(f"chunk: expected a positive integer, got {chunk!r}")
+        reverse = mode == "reverse"
+        if chunk is None:
+            unit = sum(ocols[o] for o in of) if reverse else sum(wcols[w] for w in wrt if w not in self.JVP_SHARED)
+            largest = max(wcols[w] for w in wrt) if reverse else max(ocols[o] for o in of)
+            chunk = max(1, self.JACOBIAN_BUDGET // (8 * cnt * (unit + largest)))
+        chunk = int(min(chunk, total))
+        # the solves of the call in order: segment (name, first solve, number) -- the components of each o (reverse), the
+        # columns of each w (forward)
+        segs, at = [], 0
+        for name, width in ([(o, ocols[o]) for o in of] if reverse else [(w, wcols[w]) for w in wrt]):
+            segs.append((name, at, width))
+            at += width
+        J = {(o, w): np.zeros((cnt, ocols[o], wcols[w])) for o in of for w in wrt}
+        res = {}
+        for c0 in range(0, total, chunk):
+            c1 = min(c0 + chunk, total)
+            nc = c1 - c0
+            # the part [a, b) of each segment that falls into this chunk, as positions of the chunk and of the segment
+            parts = [(name, max(s0, c0) - c0, min(s0 + w, c1) - c0, max(s0, c0) - s0) for name, s0, w in segs if max(s0, c0) < min(s0 + w, c1)]
+            if reverse:
+                cot = {o: np.zeros((nc, cnt, ocols[o])) for o in of if ocols[o] > 0}
+                for o, a, b, p0 in parts:
+                    cot[o][np.arange(a, b), :, np.arange(p0, p0 + b - a)] = 1.0
+                want = tuple(w for w in wrt if wcols[w] > 0)
+                res = self.adjoint(dx=cot.get("x"), dy=cot.get("y"), want=want)
+                for o, a, b, p0 in parts:
+                    for w in want:
+                        J[(o, w)][:, p0:p0 + b - a, :] = np.transpose(res[w][a:b], (1, 0, 2))
+            else:
+                tan = {w: np.zeros((nc, wcols[w]) if w in self.JVP_SHARED else (nc, cnt, wcols[w])) for w in wrt if wcols[w] > 0}
+                for w, a, b, p0 in parts:
+                    if w in self.JVP_SHARED:
+                        tan[w][np.arange(a, b), np.arange(p0, p0 + b - a)] = 1.0
+                    else:
+                        tan[w][np.arange(a, b), :, np.arange(p0, p0 + b - a)] = 1.0
+                res = self.jvp(**tan)
+                for w, a, b, p0 in parts:
+                    for o in of:
+                        if ocols[o] > 0:
+                            J[(o, w)][:, :, p0:p0 + b - a] = np.transpose(res[o][a:b], (1, 2, 0))
+        if "act" in res:
+            J["act"] = res["act"]
+        J["status"] = res["status"]
+        return J
 
     def device_bytes(self):
         return int(self.lib.osqp_amd_shared_batch_device_bytes(self.handle))

@@ -32,6 +32,8 @@
 //                     matrix cores) and their small kernels; a handle type of its own (SharedBatch below);
 //   batch_shared_adjoint.hpp  k_shared_adjoint -- the adjoint of the shared batch from the model block and the tile records
 //                     (osqp_amd_shared_batch_adjoint), and k_shared_reduce_rows, the summed matrix gradients in a fixed order;
+//   batch_shared_jvp.hpp  k_shared_jvp -- the forward sensitivities of the shared batch on the same data path, with matrix
+//                     tangents shared by the instances (osqp_amd_shared_batch_jvp);
 //   this file         the small kernels (warm start, rho fill, bound check, the row scatter and gather of a selection, MPC generator), the
 //                     launcher (launch_batch), the handle (BatchPlan) and the C ABI.  A resident call exists for every instance and
 //                     for a selection (osqp_amd_batch_X, osqp_amd_batch_X_rows): ONE static body batch_X(handle, subset, rows, k, ...)
@@ -60,6 +62,7 @@
 #include "batch_large.hpp"
 #include "batch_shared.hpp"
 #include "batch_shared_adjoint.hpp"
+#include "batch_shared_jvp.hpp"
 #include "rng.hpp"
 
 namespace oq {
@@ -686,10 +689,13 @@ struct SharedBatch {
   // hold the solutions of the current data; adj_factor: the W factor blocks of the form with the factor in global scratch,
   // adj_rows: the bounded row scratch of the summed matrix gradients -- both allocated at first use
   DevBuf<double> status, adj_factor, adj_rows;
+  // forward sensitivities (osqp_amd_shared_batch_jvp): the staging of host-pointer calls -- the five tangents come in through
+  // in_a, in_b and these three, the outputs leave through adj_out; the factor blocks are adj_factor, whichever call came first
+  DevBuf<double> in_c, in_d, in_e;
   bool current = false;
   size_t device_bytes() const {
     return (Px.n + Ax.n + q0.n + l0.n + u0.n + model.n + scratch.n + tiles.n + in_a.n + in_b.n + x_out.n + y_out.n + info_out.n + adj_out.n + status.n +
-            adj_factor.n + adj_rows.n + 1) * sizeof(double);
+            adj_factor.n + adj_rows.n + in_c.n + in_d.n + in_e.n + 1) * sizeof(double);
   }
 };
 SharedBatch *shared_handle(osqp_amd_shared_batch *h) {
@@ -750,6 +756,14 @@ SharedAdjointPlan shared_adjoint_plan(const Pattern &P) {
 // where each needs its factor block
 void launch_shared_adjoint(SharedBatch &b, const SharedAdjointPlan &ap, shared::SharedAdjointArgs &a, hipStream_t s) {
   auto *const kern = ap.large ? shared::k_shared_adjoint<true> : shared::k_shared_adjoint<false>;
+  const int grid = ap.large ? std::min(a.cnt, ap.blocks) : a.cnt;
+  HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, ap.L.total));
+  OQ_LAUNCH(kern, dim3(grid), dim3(polish::PT), (size_t)ap.L.total, s, b.dp.P, ap.L, a);
+}
+// The same for k_shared_jvp (batch_shared_jvp.hpp): the plan, the grid and the factor blocks of the adjoint
+int g_shared_jvp_launches = 0;  // accepted calls of osqp_amd_shared_batch_jvp by this process (_jvp_launches)
+void launch_shared_jvp(SharedBatch &b, const SharedAdjointPlan &ap, shared::SharedJvpArgs &a, hipStream_t s) {
+  auto *const kern = ap.large ? shared::k_shared_jvp<true> : shared::k_shared_jvp<false>;
   const int grid = ap.large ? std::min(a.cnt, ap.blocks) : a.cnt;
   HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, ap.L.total));
   OQ_LAUNCH(kern, dim3(grid), dim3(polish::PT), (size_t)ap.L.total, s, b.dp.P, ap.L, a);
@@ -1620,6 +1634,54 @@ c_int osqp_amd_shared_batch_adjoint(osqp_amd_shared_batch *handle, c_int ncot, c
     }
     if (dPx_sum && dPx) launch_shared_reduce((int)ncot, count, count, b->nnzP, false, o.dev[3], o.dev[5], s);
     if (dAx_sum && dAx) launch_shared_reduce((int)ncot, count, count, b->nnzA, false, o.dev[4], o.dev[6], s);
+    o.download(s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  } OQ_BATCH_CATCH
+}
+
+c_int osqp_amd_shared_batch_jvp_launches(void) { return g_shared_jvp_launches; }
+
+c_int osqp_amd_shared_batch_jvp(osqp_amd_shared_batch *handle, c_int ndir, const c_float *tq, const c_float *tl, const c_float *tu,
+                                const c_float *tPx, const c_float *tAx, c_float *tx_out, c_float *ty_out, c_float *act_out, c_float *status_out,
+                                c_int where) {
+  SharedBatch *b = shared_handle(handle);
+  if (!b) return 1;
+  if (ndir < 1) { set_last_error("invalid batch data: the sensitivities need ndir >= 1"); return 1; }
+  const size_t cnt = (size_t)b->count, nd = (size_t)ndir, ln = cnt * b->n, lm = cnt * b->m;
+  if (!lm) { tl = tu = nullptr; ty_out = act_out = nullptr; }  // arrays of width 0 are dropped first
+  if (!b->nnzA) tAx = nullptr;
+  if (!b->nnzP) tPx = nullptr;
+  if (!tq && !tl && !tu && !tPx && !tAx) { set_last_error("invalid batch data: the sensitivities need a tangent"); return 1; }
+  if (!tx_out && !ty_out) { set_last_error("invalid batch data: the sensitivities need tx_out or ty_out"); return 1; }
+  if (!b->current) {
+    set_last_error("the shared batch holds no current solution: call osqp_amd_shared_batch_resolve after the last update, warm start or rho update");
+    return 1;
+  }
+  try {
+    DeviceScope on_dev(b->device);
+    hipStream_t s = nullptr;
+    const Pattern &P = b->dp.P;
+    const SharedAdjointPlan ap = shared_adjoint_plan(P);  // a refusal comes before anything is allocated or launched
+    const OutStage o(*b, !where, {tx_out, ty_out, act_out, status_out}, {nd * ln, nd * lm, lm, cnt});
+    shared::SharedJvpArgs a;
+    a.model = b->model.get(); a.tiles = b->tiles.get(); a.status_in = b->status.get();
+    a.tq = tq ? device_ptr(tq, nd * ln, where, b->in_a, s) : nullptr;
+    a.tl = tl ? device_ptr(tl, nd * lm, where, b->in_b, s) : nullptr;
+    a.tu = tu ? device_ptr(tu, nd * lm, where, b->in_c, s) : nullptr;
+    a.tPx = tPx ? device_ptr(tPx, nd * b->nnzP, where, b->in_d, s) : nullptr;  // one row per direction: shared by the instances
+    a.tAx = tAx ? device_ptr(tAx, nd * b->nnzA, where, b->in_e, s) : nullptr;
+    a.tx = o.dev[0]; a.ty = o.dev[1]; a.act = o.dev[2]; a.status = o.dev[3];
+    a.count = b->count; a.first = 0; a.cnt = b->count; a.T = b->plan.T; a.ndir = (int)ndir;
+    a.refine = (int)b->st.polish_refine_iter; a.delta = b->st.delta;
+    a.scratch = nullptr;
+    if (ap.large) {  // the factor blocks of the adjoint: allocated by whichever call comes first
+      const size_t need = (size_t)ap.blocks * b->n * b->n;
+      if (b->adj_factor.n < need) b->adj_factor.alloc(need);
+      a.scratch = b->adj_factor.get();
+    }
+    g_shared_jvp_launches++;
+    launch_shared_jvp(*b, ap, a, s);
     o.download(s);
     HIP_CHECK(hipStreamSynchronize(s));
     return 0;

@@ -963,6 +963,53 @@ end
 shared_batch_adjoint_launches() = Int(ccall((:osqp_amd_shared_batch_adjoint_launches, lib), Cc_int, ()))
 
 """
+    shared_batch_jvp(b; tq = nothing, tl = nothing, tu = nothing, tPx = nothing, tAx = nothing) -> NamedTuple
+
+Forward sensitivities of the solutions of the last `shared_batch_solve!` along directions of the data
+(osqp_amd_shared_batch_jvp, DESIGN.md section 13.5).  tq [n x count], tl, tu [m x count] are PER INSTANCE; tPx [nnzP] and tAx [nnzA]
+are ONE tangent of the SHARED values for the whole batch, in the index spaces of `Px_sum` / `Ax_sum` (`nothing` = zeros, not
+all).  Or all with a trailing axis, [. x count x ndir] and [nnz x ndir], for several directions in one call.  Returns `x`
+[n x count (x ndir)], `y` [m x count (x ndir)], `act` [m x count] and `status` [count], as `shared_batch_adjoint` returns them.  On a
+row with l == u only `tl` is read.  Refused before the first solve and after any update, warm start or rho update that followed
+the last one.
+"""
+function shared_batch_jvp(b::SharedBatch; tq::Union{Nothing,Array{Float64}} = nothing, tl::Union{Nothing,Array{Float64}} = nothing,
+                          tu::Union{Nothing,Array{Float64}} = nothing, tPx::Union{Nothing,Array{Float64}} = nothing,
+                          tAx::Union{Nothing,Array{Float64}} = nothing)
+    per = (("tq", tq, b.n), ("tl", tl, b.m), ("tu", tu, b.m))
+    shared = (("tPx", tPx, b.nnzP), ("tAx", tAx, b.nnzA))
+    extra = vcat([ndims(v) - 2 for (_, v, _) in per if v !== nothing], [ndims(v) - 1 for (_, v, _) in shared if v !== nothing])
+    isempty(extra) && error("tq, tl, tu, tPx, tAx: at least one tangent is needed")
+    (all(==(extra[1]), extra) && extra[1] in (0, 1)) ||
+        error("tangents: expected tq, tl, tu [cols x count] with tPx, tAx [nnz], or all with a trailing axis [... x ndir]")
+    many = extra[1] == 1
+    given = [v for (_, v, _) in (per..., shared...) if v !== nothing]
+    ndir = many ? size(given[1], ndims(given[1])) : 1
+    ndir >= 1 || error("tangents: ndir must be at least 1")
+    for (name, v, k) in per
+        v === nothing || size(v) == (many ? (k, b.count, ndir) : (k, b.count)) || error("$(name): expected [$(k) x $(b.count)] or [$(k) x $(b.count) x ndir]")
+    end
+    for (name, v, k) in shared
+        v === nothing || size(v) == (many ? (k, ndir) : (k,)) || error("$(name): expected [$(k)] or [$(k) x ndir]")
+    end
+    tx = many ? zeros(b.n, b.count, ndir) : zeros(b.n, b.count)
+    ty = many ? zeros(b.m, b.count, ndir) : zeros(b.m, b.count)
+    act, status = zeros(b.m, b.count), zeros(b.count)
+    p(a) = (a === nothing || isempty(a)) ? Ptr{Cdouble}(C_NULL) : pointer(a)
+    GC.@preserve tq tl tu tPx tAx tx ty act status begin
+        flag = ccall((:osqp_amd_shared_batch_jvp, lib), Cc_int,
+                     (Ptr{Cvoid}, Cc_int, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+                      Ptr{Cdouble}, Ptr{Cdouble}, Cc_int),
+                     b.handle, ndir, p(tq), p(tl), p(tu), p(tPx), p(tAx), pointer(tx), p(ty), p(act), pointer(status), 0)
+    end
+    flag == 0 || error("Error in shared batch jvp: $(last_error())")
+    return (x = tx, y = ty, act = Matrix{Int}(act), status = Vector{Int}(status))
+end
+
+"Accepted `shared_batch_jvp` calls of this process: one per call whatever ndir; a refused call does not count."
+shared_batch_jvp_launches() = Int(ccall((:osqp_amd_shared_batch_jvp_launches, lib), Cc_int, ()))
+
+"""
     batch_large_factor!(b, on = true) -> Bool
 
 Polish, adjoint and JVP on a resident batch with 128 < n <= 256 (osqp_amd_batch_large_factor, DESIGN.md section 13.2): a switch

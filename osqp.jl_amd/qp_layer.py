@@ -324,6 +324,26 @@ class SharedBatchQPFunction(torch.autograd.Function):
     def setup_context(ctx, inputs, output):
         ctx.sb = inputs[0]
         ctx.stamp = ctx.sb._qp_layer_served
+        ctx.given = tuple(name for name, t in zip(NAMES, inputs[1:6]) if t is not None)  # for jvp: the inputs that have a tangent
+
+    @staticmethod
+    def jvp(ctx, t_sb, tq, tl, tu, tPx, tAx):
+        """Forward mode: the tangents of (x, y) of every instance along the tangents of the tensor inputs (an input without a
+        tangent arrives as zeros, a None input as None) through ONE `SharedBatch.jvp` call on the device.  The tangents of Px /
+        Ax are the shared [nnz] vectors: one direction of the model's values moves every instance.  The stamp rule of
+        `backward` holds."""
+        sb = ctx.sb
+        if not stamp_holds(sb, ctx.stamp, None):
+            raise RuntimeError("SharedBatchQPFunction: the batch has been solved again since this forward; its handle holds one "
+                               "solution, so jvp must run before the next forward")
+        cols = dict(q=sb.n, l=sb.m, u=sb.m, Px=sb.nnzP, Ax=sb.nnzA)
+        tang = {k: t.contiguous() for k, t in zip(NAMES, (tq, tl, tu, tPx, tAx)) if k in ctx.given and t is not None and cols[k] > 0}
+        ref = next(iter(tang.values()))
+        tx = torch.empty((sb.count, sb.n), dtype=torch.float64, device=ref.device)
+        ty = torch.empty((sb.count, sb.m), dtype=torch.float64, device=ref.device)
+        _sync(ref)
+        sb.jvp(**tang, out=dict(x=tx, y=ty) if sb.m else dict(x=tx))
+        return tx, ty
 
     @staticmethod
     def backward(ctx, gx, gy):
@@ -354,7 +374,8 @@ class SharedBatchQPLayer(torch.nn.Module):
     the handle's values bit for bit (ValueError otherwise: a new model is a new handle) and get the gradients summed over the
     instances, "Px_sum" / "Ax_sum" of the same adjoint call.  `layer.Px` / `layer.Ax` are the handle's values on its device,
     ready to be cloned into parameters.  The stamp rule of `BatchQPLayer` holds: backward after a later forward raises.
-    `torch.func.vmap` / `jacrev` over the pull-back is one adjoint call with a leading axis.  Forward mode is not offered."""
+    `torch.func.vmap` / `jacrev` over the pull-back is one adjoint call with a leading axis.  Forward mode (`torch.autograd.forward_ad`, `torch.func.jvp`) is one
+    `SharedBatch.jvp` call: the tangents of q, l, u are per instance, those of Px / Ax are the shared [nnz] vectors."""
 
     def __init__(self, sb):
         super().__init__()

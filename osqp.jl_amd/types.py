@@ -273,6 +273,9 @@ EXT_SYMBOLS = {
     # handle, ncot, dx, dy, dq, dl, du, dPx, dAx, dPx_sum, dAx_sum, act, status, where
     "osqp_amd_shared_batch_adjoint": (c_int, [C.c_void_p, c_int] + [C.c_void_p] * 11 + [c_int]),
     "osqp_amd_shared_batch_adjoint_launches": (c_int, []),
+    # handle, ndir, tq, tl, tu, tPx, tAx, tx, ty, act, status, where
+    "osqp_amd_shared_batch_jvp": (c_int, [C.c_void_p, c_int] + [C.c_void_p] * 9 + [c_int]),
+    "osqp_amd_shared_batch_jvp_launches": (c_int, []),
     "osqp_amd_shared_batch_device_bytes": (c_int, [C.c_void_p]),
     "osqp_amd_shared_batch_launches": (c_int, []),
     "osqp_amd_shared_batch_destroy": (c_int, [C.c_void_p]),
